@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- MaxSim (query, doc) pairs scored per second on MI355X.
 
-Contract (driver): `python bench.py --gpus N --steps K --warmup W`.  Rank 0 prints ONE JSON line.
+Contract (driver): `python bench.py --gpus N --steps K --warmup W`.  Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes
+the last timed step's scores and top-k to DIR/*.npy (float32 / float64, seeded inputs) so two builds can be compared output for output.
 N > 1: one process per GPU over RCCL.  Either the caller launches the ranks (torch.distributed.run: WORLD_SIZE
 / RANK / LOCAL_RANK in the environment) or -- when `--gpus N` is given without a launcher -- this file re-executes
 itself under `python -m torch.distributed.run --nproc-per-node N` (launch_ranks below).  It refuses to run N ranks
@@ -82,7 +83,13 @@ def parse_args():
     ap.add_argument("--topk", type=int, default=10)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step (scores, top-k) as DIR/<name>.npy (rank 0), "
+                         "e.g. bench_outputs/")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: the result line reports the time of the timed steps")
+    return args
 
 
 def _free_port():
@@ -119,6 +126,30 @@ def launch_ranks(n_gpus):
         return 2
     cmd, env = rank_launch_command(n_gpus, sys.argv[1:], _free_port(), os.environ)
     return subprocess.call(cmd, env=env)
+
+
+DUMP_SCORES_BYTES = 48 << 20       # the score matrix is dumped whole up to this size, else as a fixed sample of its columns
+
+
+def dump_outputs(out_dir, scores, top):
+    """The last timed step's results, as a caller of that path receives them: the [n_queries, n_docs] fp32 score matrix of this shard
+    and the merged top-k (scores, global doc ids).  The inputs are seeded, so two builds can be compared file by file.  A score matrix
+    above DUMP_SCORES_BYTES is written as the same seeded sample of document columns every run, with the sampled ids beside it."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    s = scores.float().cpu().numpy()
+    if s.nbytes > DUMP_SCORES_BYTES:
+        n_cols = DUMP_SCORES_BYTES // (4 * s.shape[0])
+        cols = np.sort(np.random.default_rng(0).choice(s.shape[1], size=n_cols, replace=False))
+        np.save(os.path.join(out_dir, "scores_sample_doc_ids.npy"), cols.astype(np.float64))
+        np.save(os.path.join(out_dir, "scores_sample.npy"), np.ascontiguousarray(s[:, cols]))
+    else:
+        np.save(os.path.join(out_dir, "scores.npy"), s)
+    top_scores, top_ids = top
+    np.save(os.path.join(out_dir, "topk_scores.npy"), top_scores.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "topk_ids.npy"), top_ids.cpu().numpy().astype(np.float64))     # ids < 2**53: exact in float64
 
 
 # N > 1: the regimes every rank runs after the headline.  Eight ranks each re-score their parity sample on the cores torchrun
@@ -185,6 +216,8 @@ def main():
     torch.cuda.synchronize()
 
     dt, kern_ms, scores, top = run_regime(amd, q, corpus, args.steps, args.warmup, args.topk, world, rank, dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, scores, top)
     kern_avg = sum(kern_ms) / len(kern_ms)
     pairs_per_step = args.nq * args.docs * world
     out = {

@@ -13,10 +13,8 @@ from .common import HBM_PEAK_GBS, MFMA_PEAK_TFLOPS, ROOT, make_queries, make_que
 def cpu_baseline(q_len, doc_len):
     """The reference's CPU scorer on the slice SURVEY 8(d) names: 128 queries x 1024 docs (131 072 pairs, one 128 x 128 block row of the
     reference's blocking x 8), bf16 and fp32 inputs, best of 2.  kind = "reference": the VERBATIM
-    colpali_engine/utils/processing_utils.py (BaseVisualRetrieverProcessor.score_multi_vector, :132-187) -- the live checkout where it
-    exists, else the byte-for-byte git-ignored copy oracle/fetch_reference_tests.py leaves under tests/_reference_pkg/ (it travels to the
-    GPU box with the working tree); kind = "port": oracle/torch_port.py, the restatement with the same torch calls, only where neither
-    file is present."""
+    colpali_engine/utils/processing_utils.py (BaseVisualRetrieverProcessor.score_multi_vector, :132-187) -- where the live checkout
+    exists; kind = "port": oracle/torch_port.py, the restatement with the same torch calls, everywhere else."""
     from oracle import refimport, torch_port
 
     try:

@@ -60,7 +60,7 @@ def loss_step_numbers(amd, dev):
     stay on PyTorch-ROCm), bf16.  Per loss class: eager and one-hipGraph time of the forward direction and of BOTH directions captured as
     one graph, device time of a replay (HIP events), peak MiB, the fraction of the roof
         max(2 * B * C * Lq * Ld * 128 FLOP / 2.5 PFLOP/s, (Q + D read, dQ + dD written) / 8 TB/s)     per direction,
-    the reference's own module (the verbatim late_interaction_losses.py where the fetched copy exists, else its restatement) on the same
+    the reference's own module (the live late_interaction_losses.py where the reference checkout exists, else its restatement) on the same
     GPU, and loss / gradient error against the float64 oracle (oracle/li_loss_oracle.py: the checker, not the thing measured)."""
     from oracle import li_loss_oracle, refimport
 

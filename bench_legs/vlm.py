@@ -69,8 +69,8 @@ def vlm_in_the_loop_numbers(amd, dev, family="colpali"):
     """BASELINE configs 2 / 3 AS WRITTEN -- "embed + score 1k synthetic pages" -- with the VLM in the loop: a random-init model of the
     named geometry (no checkpoint exists offline) embeds 1000 synthetic pages and 100 ragged queries on PyTorch-ROCm, its forward patched by
     colpali_amd.patch_colpali_engine(models=True) so that the tail is the fused head; the page embeddings go to the resident packed
-    corpus, the queries are scored against it.  The class is the REFERENCE's own (oracle/refimport.py: the fetched, git-ignored copy
-    under tests/_reference_pkg/); when it is not there the leg is skipped.  Context key: the VLM forward dominates by construction
+    corpus, the queries are scored against it.  The class is the REFERENCE's own (oracle/refimport.py: the live reference checkout);
+    when it is not there the leg is skipped.  Context key: the VLM forward dominates by construction
     and is not ours -- `head_and_scorer_share` says how much of the wall time the path this repository owns takes."""
     try:
         model, page_batch, S, vocab, what = _vlm_family(family, dev)

@@ -15,9 +15,6 @@ import sys
 import types
 
 REFERENCE_ROOT = os.environ.get("COLPALI_REFERENCE_ROOT", "/root/reference")
-# where oracle/fetch_reference_tests.py leaves verbatim, git-ignored copies of the reference's model files (they travel to the
-# GPU box with the working tree, like the reference's own tests under tests/_reference_tests/)
-FETCHED_ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), "..", "tests", "_reference_pkg"))
 
 
 def available() -> bool:
@@ -39,27 +36,11 @@ def load():
     return BaseVisualRetrieverProcessor, late_interaction_losses
 
 
-def load_hot_path(allow_fetched: bool = True):
-    """(BaseVisualRetrieverProcessor, late_interaction_losses module, "live" | "fetched") from the reference checkout where it exists,
-    else from the verbatim git-ignored copies oracle/fetch_reference_tests.py leaves under tests/_reference_pkg/ (the GPU box).
+def load_hot_path():
+    """(BaseVisualRetrieverProcessor, late_interaction_losses module, "live") from the reference checkout; raises where it is absent.
     bench.py times THESE as `cpu_baseline.kind = "reference"` and as the reference loss module on the same GPU."""
-    if available():
-        proc, losses = load()
-        return proc, losses, "live"
-    have = all(os.path.exists(os.path.join(FETCHED_ROOT, "colpali_engine", rel)) for rel in
-               ("loss/late_interaction_losses.py", "utils/processing_utils.py", "utils/torch_utils.py"))
-    if not (allow_fetched and have):
-        raise RuntimeError("no reference hot-path files: neither the checkout nor tests/_reference_pkg/ (oracle/fetch_reference_tests.py)")
-    sys.dont_write_bytecode = True
-    for name, sub in (("colpali_engine", ""), ("colpali_engine.loss", "loss"), ("colpali_engine.utils", "utils")):
-        if name not in sys.modules:
-            pkg = types.ModuleType(name)
-            pkg.__path__ = [os.path.join(FETCHED_ROOT, "colpali_engine", sub)]
-            sys.modules[name] = pkg
-    from colpali_engine.loss import late_interaction_losses  # noqa: E402
-    from colpali_engine.utils.processing_utils import BaseVisualRetrieverProcessor  # noqa: E402
-
-    return BaseVisualRetrieverProcessor, late_interaction_losses, "fetched"
+    proc, losses = load()
+    return proc, losses, "live"
 
 
 def load_colpali_class():
@@ -81,16 +62,14 @@ def load_colpali_class():
 
 
 def model_root() -> str:
-    """The directory holding `colpali_engine/models/...`: the reference checkout here, the fetched copy on the GPU box."""
+    """The directory holding `colpali_engine/models/...`: the reference checkout; raises where it is absent."""
     if available():
         return REFERENCE_ROOT
-    if os.path.isdir(os.path.join(FETCHED_ROOT, "colpali_engine", "models")):
-        return FETCHED_ROOT
-    raise RuntimeError("no reference model files: neither the checkout nor tests/_reference_pkg/ (oracle/fetch_reference_tests.py)")
+    raise RuntimeError(f"no reference model files: reference checkout not found at {REFERENCE_ROOT}")
 
 
 def load_model_class(rel_module: str, cls_name: str):
-    """A Col* model class of the (live or fetched) reference, e.g. ("models/qwen2/colqwen2/modeling_colqwen2", "ColQwen2").
+    """A Col* model class of the live reference, e.g. ("models/qwen2/colqwen2/modeling_colqwen2", "ColQwen2").
     Random-init use only.  Every package on the way is a stub (the real __init__ files import every family and, through
     them, dependencies that are not installed)."""
     root = model_root()

@@ -1,6 +1,10 @@
 """Shared helpers for the parity tests (CPU side only; no product imports)."""
 from __future__ import annotations
 
+import os
+import subprocess
+import sys
+
 import numpy as np
 
 from oracle import maxsim_oracle as mo
@@ -110,3 +114,18 @@ def ranking_tolerance(got_scores, truth_scores, cap=2e-6):
     e = float(np.max(np.abs(got - truth) / np.maximum(np.abs(truth), 1.0)))     # same error measure as every score test
     assert 2 * e <= cap, f"score error {e:.3e} too large for a meaningful ranking comparison"
     return 2 * e + 1e-9
+
+
+_REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+_SUITE = os.path.join(_REPO, "tests", "reference_suite")
+
+
+def run_contract_checks(group, device, **env_extra):
+    """tests/reference_suite/contract_checks.py <group> in a subprocess whose `colpali_engine` is the stub package (colpali_amd's scorers
+    and loss classes); `device` is the default device of new tensors there.  Asserts a zero exit status and returns stdout."""
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(_SUITE, "stub"), _REPO]), REFSUITE_DEVICE=device,
+               PYTHONDONTWRITEBYTECODE="1", **env_extra)
+    res = subprocess.run([sys.executable, os.path.join(_SUITE, "contract_checks.py"), group],
+                         capture_output=True, text=True, env=env, cwd=_SUITE, timeout=600)
+    assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
+    return res.stdout

@@ -1,14 +1,13 @@
-"""Tiny random-init instances of the REFERENCE's Col* model classes (oracle/refimport.py: the live checkout in the build container,
-the fetched git-ignored copy under tests/_reference_pkg/ on the GPU box).  Test infrastructure; no weights exist offline."""
+"""Tiny random-init instances of the test suite's Col* model classes (tests/model_classes.py: transformers backbones with the Col*
+embedding tail).  Test infrastructure; no weights exist offline."""
 import torch
 
-from oracle import refimport
+from tests.model_classes import ColPali, ColQwen2
 
 
 def tiny_colpali(mask_non_image_embeddings=False, seed=0):
     from transformers import PaliGemmaConfig
 
-    ColPali = refimport.load_model_class("models/paligemma/colpali/modeling_colpali", "ColPali")
     cfg = PaliGemmaConfig(
         vision_config=dict(model_type="siglip_vision_model", hidden_size=32, intermediate_size=64, num_hidden_layers=1,
                            num_attention_heads=2, image_size=28, patch_size=14, projection_dim=128, vocab_size=300),
@@ -22,7 +21,6 @@ def tiny_colpali(mask_non_image_embeddings=False, seed=0):
 def tiny_colqwen2(seed=0):
     from transformers import Qwen2VLConfig
 
-    ColQwen2 = refimport.load_model_class("models/qwen2/colqwen2/modeling_colqwen2", "ColQwen2")
     cfg = Qwen2VLConfig(
         text_config=dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
                          vocab_size=300, rope_scaling={"type": "mrope", "mrope_section": [8, 12, 12]}, max_position_embeddings=512,

@@ -1,6 +1,6 @@
-"""patch_colpali_engine(models=True) on the GPU: the REAL reference model classes (random-init tiny configs) with the fused
-embedding head installed, against the same instances unpatched -- i.e. against the reference's own lines
-(modeling_colpali.py:65-78, modeling_colqwen2.py:59-75) executed by torch on the same GPU.
+"""patch_colpali_engine(models=True) on the GPU: Col* model classes with real transformers backbones (tests/model_classes.py,
+random-init tiny configs) with the fused embedding head installed, against the same instances unpatched -- i.e. against the
+Col* embedding tail (projection, norm, masks) executed by torch on the same GPU.
 
 Tolerances: bf16 / fp16 outputs within one ulp of the reference's output element-wise and > 90 % bit-equal (the reference rounds the
 Linear output, the norm and the quotient to the model dtype: one rounding each, reproduced by the kernel; the library GEMM's
@@ -11,16 +11,9 @@ import torch
 
 import colpali_amd
 from colpali_amd import models as M
-from oracle import refimport
+from tests.model_fixtures import colpali_page_batch, colqwen2_page_batch, text_batch, tiny_colpali, tiny_colqwen2
 
 pytestmark = pytest.mark.gpu
-
-try:
-    refimport.model_root()
-except RuntimeError:
-    pytest.skip("no reference model files (tests/_reference_pkg/ is fetched by __graft_entry__.build())", allow_module_level=True)
-
-from tests.model_fixtures import colpali_page_batch, colqwen2_page_batch, text_batch, tiny_colpali, tiny_colqwen2  # noqa: E402
 
 DEV = "cuda:0"
 

@@ -5,8 +5,6 @@ CPU request must WORK -- BASELINE config 1 reads "score_multi_vector on CPU".  R
 
 Tolerance: |got - truth| <= 1e-5 * max(|truth|, 1); literal tier within one bf16 ulp of the live reference's bf16 CPU output."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,7 +13,7 @@ import torch
 import colpali_amd as amd
 from oracle import maxsim_oracle as mo
 from tests.conftest import load_golden
-from tests.helpers import config1_inputs, ragged_from_golden
+from tests.helpers import config1_inputs, ragged_from_golden, run_contract_checks
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 RTOL = 1e-5
@@ -156,18 +154,10 @@ def test_concurrent_callers_share_the_thread_pool_without_deadlock():
 
 
 def test_the_reference_scorer_tests_pass_on_a_host_without_a_gpu():
-    """/root/reference/tests/utils/test_processing_utils.py, unmodified, in a subprocess that sees NO GPU: `device` defaults to
+    """tests/reference_suite/contract_checks.py's scorer checks in a subprocess that sees NO GPU: `device` defaults to
     get_torch_device("auto") = "cpu" there, and both scorers must work (round-3 review: the patched package used to raise)."""
-    suite = os.path.join(ROOT, "tests", "_reference_tests")
-    if not os.path.isdir(suite):
-        pytest.skip("tests/_reference_tests/ is absent (oracle/fetch_reference_tests.py copies it where /root/reference exists)")
-    stub = os.path.join(ROOT, "tests", "reference_suite", "stub")
-    env = dict(os.environ, PYTHONPATH=os.pathsep.join([stub, ROOT]), REFSUITE_DEVICE="cpu", PYTHONDONTWRITEBYTECODE="1",
-               HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
-    res = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "-p", "refsuite_plugin", "--rootdir", suite,
-                          "-c", os.devnull, os.path.join(suite, "test_processing_utils.py")],
-                         capture_output=True, text=True, env=env, cwd=suite, timeout=600)
-    assert res.returncode == 0 and "2 passed" in res.stdout, (res.stdout + res.stderr)[-3000:]
+    out = run_contract_checks("scorer", "cpu", HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
+    assert "2 passed" in out, out
 
 
 def test_host_gather_range_copies_any_byte_range_of_the_virtual_concatenation():

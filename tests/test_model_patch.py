@@ -1,18 +1,11 @@
-"""patch_colpali_engine(models=True) on the REAL reference classes (CPU side: the wrapper's control flow; the fused kernel itself is
-checked on the GPU in tests/test_gpu_models.py).  Skipped where neither the reference checkout nor its fetched copy exists."""
+"""patch_colpali_engine(models=True) on Col* model classes with real transformers backbones (tests/model_classes.py; CPU side: the
+wrapper's control flow; the fused kernel itself is checked on the GPU in tests/test_gpu_models.py)."""
 import pytest
 import torch
 
 import colpali_amd
 from colpali_amd import models as M
-from oracle import refimport
-
-try:
-    refimport.model_root()
-except RuntimeError:
-    pytest.skip("no reference model files here", allow_module_level=True)
-
-from tests.model_fixtures import text_batch, tiny_colpali, tiny_colqwen2  # noqa: E402
+from tests.model_fixtures import text_batch, tiny_colpali, tiny_colqwen2
 
 
 def test_patch_installs_and_restores_the_forward():
