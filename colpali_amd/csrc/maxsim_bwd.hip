@@ -605,7 +605,9 @@ __global__ __launch_bounds__(kRowsThreads) void maxsim_bwd_dd_rows_kernel(const 
     }
     __syncthreads();
     ROWS_STAMP(3);
-    // ---- exclusive scan of the counts: thread t owns rows 2t, 2t + 1 (kRowsMaxRows = 2 * kRowsThreads)
+    // ---- exclusive scan of the counts: thread t owns rows 2t, 2t + 1 (kRowsMaxRows = 2 * kRowsThreads).  The total start[n_rows] comes
+    // from the last thread, whose inclusive sum covers every row (counts past n_rows are 0): with n_rows = kRowsMaxRows no thread owns
+    // row n_rows, and a write keyed on "2t or 2t + 1 == n_rows" left it unset
     {
         const int c0 = 2 * t < n_rows ? cnt[2 * t] : 0, c1 = 2 * t + 1 < n_rows ? cnt[2 * t + 1] : 0;
         int v = c0 + c1;
@@ -622,7 +624,7 @@ __global__ __launch_bounds__(kRowsThreads) void maxsim_bwd_dd_rows_kernel(const 
         const int excl = base + incl - v;
         if (2 * t < n_rows) { start[2 * t] = (uint16_t)excl; cnt[2 * t] = excl; }
         if (2 * t + 1 < n_rows) { start[2 * t + 1] = (uint16_t)(excl + c0); cnt[2 * t + 1] = excl + c0; }
-        if (2 * t == n_rows || 2 * t + 1 == n_rows) start[n_rows] = (uint16_t)(2 * t == n_rows ? excl : excl + c0);
+        if (t == kRowsThreads - 1) start[n_rows] = (uint16_t)(excl + v);
     }
     __syncthreads();
     ROWS_STAMP(4);

@@ -129,3 +129,29 @@ def run_contract_checks(group, device, **env_extra):
                          capture_output=True, text=True, env=env, cwd=_SUITE, timeout=600)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
     return res.stdout
+
+
+def pairs_bwd_truth(Q, D, d_off, pairs, g, argmax, chunk=1 << 15):
+    """float64 (dQ [n_q, Lq, dim], dD [total_rows, dim]) of msim_pairs_bwd's contract (include/maxsim.h):
+        dQ[b_p, i]                 += g[p] * D[d_off[c_p] + argmax[p, i]]
+        dD[d_off[c_p] + argmax[p, i]] += g[p] * Q[b_p, i]
+    for every (pair p, token i) whose routing is not -1 (-1: the zero padding row won the max).  Only the rows that carry entries
+    are gathered, `chunk` entries at a time."""
+    import torch
+
+    Q, D = torch.as_tensor(Q).double(), torch.as_tensor(D).double()
+    n_q, Lq, dim = Q.shape
+    am, pr, off, gg = (torch.as_tensor(x).cpu() for x in (argmax, pairs, d_off, g))
+    am, pr, off, gg = am.long().view(-1, Lq), pr.long().view(-1, 2), off.long(), gg.double()
+    p, i = (am >= 0).nonzero(as_tuple=True)
+    b, c = pr[p, 0], pr[p, 1]
+    assert bool((am[p, i] < off[c + 1] - off[c]).all()), "routing beyond the document's rows"
+    row = off[c] + am[p, i]
+    dQ = torch.zeros(n_q * Lq, dim, dtype=torch.float64)
+    dD = torch.zeros(D.shape[0], dim, dtype=torch.float64)
+    for s in range(0, p.numel(), chunk):
+        sl = slice(s, s + chunk)
+        w = gg[p[sl]].unsqueeze(1)
+        dQ.index_add_(0, b[sl] * Lq + i[sl], w * D[row[sl]])
+        dD.index_add_(0, row[sl], w * Q[b[sl], i[sl]])
+    return dQ.view(n_q, Lq, dim), dD
