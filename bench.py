@@ -3,6 +3,11 @@
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`.  Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes
 the last timed step's scores and top-k to DIR/*.npy (float32 / float64, seeded inputs) so two builds can be compared output for output.
+Such a plain run does only what the headline needs: it builds the shard and the queries, warms up, times the K steps and prints the
+line (its roofline comes from the timed steps' own events).  `--full` runs every other leg after the timed steps: the machine's
+ceilings, the top-k parity checks, power samples, the 1-rank RCCL merge, the CPU baseline and the other workloads (drop-in, embedding
+head, other corpus geometries, the loss step, the VLM in the loop), and the other query batches (`--regimes`).  `--no-cpu-baseline`
+and `--no-parity` narrow a `--full` run.
 N > 1: one process per GPU over RCCL.  Either the caller launches the ranks (torch.distributed.run: WORLD_SIZE
 / RANK / LOCAL_RANK in the environment) or -- when `--gpus N` is given without a launcher -- this file re-executes
 itself under `python -m torch.distributed.run --nproc-per-node N` (launch_ranks below).  It refuses to run N ranks
@@ -17,7 +22,7 @@ batch against the whole shard with the fused gfx950 MaxSim kernel, selects the p
 and (N>1) merges the shards' top-k with one RCCL all-gather.  Weak scaling: the shard per GPU is
 fixed, the corpus grows with N.
 
-stdout is ONE compact strict-JSON line (bench_legs/line.py: the contract keys, `roofline`, `cpu_baseline`, `topk_parity` and a flat
+stdout is ONE compact strict-JSON line (bench_legs/line.py: the contract keys, `roofline`, with --full `cpu_baseline`, `topk_parity` and a flat
 dict of scalar summaries, <= 8 KiB, no NaN tokens); the full report of every leg is written to bench_detail.json next to this file
 (and to gpurun_out/ when that directory exists).  Nothing else is printed to stdout; stderr carries library banners only.
 
@@ -25,7 +30,7 @@ The JSON line carries
   roofline     -- of the dominant kernel (the fused MaxSim kernel), from HIP events recorded on the
                   launch stream inside the timed region; algorithmic bytes = docs streamed once
                   per query block (262144/Bq + 4 B per pair)
-  cpu_baseline -- the reference's CPU scorer (oracle/torch_port.py restates
+  cpu_baseline -- (--full) the reference's CPU scorer (oracle/torch_port.py restates
                   processing_utils.py:163-186 with the same torch calls) timed on this box's
                   host cores on a bounded sample of the same workload, rank 0, N=1 only
 """
@@ -74,21 +79,25 @@ def parse_args():
                          "BASELINE config 4 over 8 GPUs")
     ap.add_argument("--doc-len", type=int, default=1024)
     ap.add_argument("--nq", type=int, default=4, help="queries per step (32 tokens each); 4 = BASELINE config 1's query batch")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (ceilings, parity, baselines, other workloads and query batches)")
     ap.add_argument("--regimes", type=str, default=None,
-                    help="other query batches measured after the headline and reported under 'regimes' ('' = none; default: REGIMES_SINGLE "
+                    help="with --full: other query batches measured after the headline and reported under 'regimes' ('' = none; default: REGIMES_SINGLE "
                          "at --gpus 1, the shorter REGIMES_MULTI above): N = N queries of "
                          "--q-len tokens; NxL = N queries of L tokens; NxrA-B = N queries of ragged lengths U{A..B} (real query lengths: "
                          "processing_utils.py:86 appends 10 augmentation tokens, SURVEY: Lq ~ 20-40)")
     ap.add_argument("--q-len", type=int, default=32)
     ap.add_argument("--topk", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the legs run beside it")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the top-k parity checks")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path returned in its last step (scores, top-k) as DIR/<name>.npy (rank 0), "
                          "e.g. bench_outputs/")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1: the result line reports the time of the timed steps")
+    if args.regimes is not None and not args.full:
+        ap.error("--regimes needs --full: a plain run measures the headline batch only")
     return args
 
 
@@ -170,7 +179,7 @@ def main():
     os.dup2(2, 1)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.regimes is None:
-        args.regimes = REGIMES_SINGLE if world == 1 else REGIMES_MULTI
+        args.regimes = "" if not args.full else REGIMES_SINGLE if world == 1 else REGIMES_MULTI
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
@@ -258,18 +267,18 @@ def main():
         out["launched_by"] = "bench.py (self-spawned torch.distributed.run)" if os.environ.get("BENCH_SELF_LAUNCHED") else "external launcher"
         if out["rccl_ranks"] != args.gpus:
             raise SystemExit(f"process group spans {out['rccl_ranks']} ranks, --gpus {args.gpus} requested")
-    ceil_ = stream_ceiling(amd, corpus) if corpus.blob.shape[1] == 128 else None
+    ceil_ = stream_ceiling(amd, corpus) if args.full and corpus.blob.shape[1] == 128 else None
     if ceil_:
         out["roofline"]["stream_ceiling_gbs"] = ceil_["gbs"]
         out["roofline"]["stream_ceiling_what"] = ceil_["what"]
         if out["roofline"]["bound"] == "hbm":
             out["roofline"]["frac_of_stream_ceiling"] = out["roofline"]["achieved"] / ceil_["gbs"]
-    ceil_m = mfma_ceiling(amd, corpus) if corpus.blob.shape[1] == 128 else None
+    ceil_m = mfma_ceiling(amd, corpus) if args.full and corpus.blob.shape[1] == 128 else None
     if ceil_m:
         out["mfma_ceiling"] = ceil_m
         if out["roofline"]["bound"] == "mfma":
             out["roofline"]["ratio_to_registers_only_probe"] = out["roofline"]["achieved"] / ceil_m["registers_only_tflops"]
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         # every rank checks its own shard (the CPU oracle as the checker); the verdicts are combined below
         local_top = amd.topk(scores, args.topk, corpus.id_base)
         n_rand = 1000 if world == 1 else 300       # N > 1: every rank runs the oracle on the cores torchrun leaves it (often one)
@@ -326,13 +335,13 @@ def main():
         if rank == 0:
             out["topk_parity"] = par
             out["parity_max_rel_err_vs_oracle_sample"] = par["max_rel_err"]
-    if world == 1 and os.environ.get("BENCH_POWER_SAMPLE", "1") != "0":
+    if args.full and world == 1 and os.environ.get("BENCH_POWER_SAMPLE", "1") != "0":
         ps = power_sample(amd, q, corpus)
         if ps:
             out["roofline"]["power"] = ps
-    if world == 1 and os.environ.get("BENCH_FORCE_COLLECTIVE", "1") != "0":
+    if args.full and world == 1 and os.environ.get("BENCH_FORCE_COLLECTIVE", "1") != "0":
         out["forced_collective_1rank"] = forced_collective_numbers(amd, q, corpus, args.topk, dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from bench_legs.baselines import cpu_baseline, torch_gpu_reference
         from bench_legs.dropin import dropin_numbers, embed_and_score_numbers
         from bench_legs.head import embed_head_numbers
@@ -352,7 +361,7 @@ def main():
     # other regimes of the same step on the same resident shard (every rank takes part: collectives inside)
     regimes = []
     zero_corpus = None
-    if world == 1 and os.environ.get("BENCH_ZERO_SHARD", "1") != "0":
+    if args.full and world == 1 and os.environ.get("BENCH_ZERO_SHARD", "1") != "0":
         from colpali_amd.corpus import PackedCorpus
 
         zero_corpus = PackedCorpus(blob=torch.zeros_like(corpus.blob), offsets=corpus.offsets, clamp0=None, lengths=corpus.lengths)
@@ -393,14 +402,14 @@ def main():
         del zero_corpus
     out["regimes"] = regimes
     out["host_threads"] = {"torch_num_threads": torch.get_num_threads(), "cpus_the_container_grants": granted, "host_cpus": os.cpu_count()}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and os.environ.get("BENCH_LOSS", "1") != "0":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and os.environ.get("BENCH_LOSS", "1") != "0":
         try:
             from bench_legs.loss_step import loss_step_numbers
 
             out["loss_step_config5"] = loss_step_numbers(amd, dev)                 # BASELINE config 5 (after the timed regimes: its float64
         except Exception as e:                                                     # oracle is a minute of CPU work)
             out["loss_step_config5"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and os.environ.get("BENCH_VLM", "1") != "0":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and os.environ.get("BENCH_VLM", "1") != "0":
         for key, family in (("embed_and_score_1k_pages_vlm_in_the_loop", "colpali"),              # BASELINE config 2
                             ("embed_and_score_1k_pages_vlm_in_the_loop_colqwen2", "colqwen2")):     # BASELINE config 3
             try:    # context only, and last: a multi-billion-parameter random-init VLM must never take the bench line down

@@ -310,6 +310,27 @@ def test_bench_self_launch_builds_one_rank_per_gpu_on_the_loopback():
         assert n == len(lens) and min(lens) >= 1
 
 
+def test_bench_plain_run_is_the_default_and_regimes_need_full(monkeypatch):
+    """A plain `bench.py` run measures the headline alone; the other query batches (`--regimes`) belong to `--full` and are refused
+    without it rather than silently not measured."""
+    import importlib.util
+    import sys
+
+    spec = importlib.util.spec_from_file_location("bench_under_test3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse_args()
+    assert not a.full and a.regimes is None and (a.steps, a.warmup) == (5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--regimes", "1000"])
+    with pytest.raises(SystemExit) as e:
+        bench.parse_args()
+    assert e.value.code == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--regimes", "1000", "--no-parity"])
+    a = bench.parse_args()
+    assert a.full and a.regimes == "1000" and a.no_parity
+
+
 def test_native_host_packing_drops_exactly_the_all_zero_rows():
     """msim_host_count_nonzero_rows / msim_host_gather_nonzero_rows (the host side of the flat query layout: include/maxsim.h): rows
     whose bytes are all zero are dropped, everything else -- a row with one non-zero element, with -0.0 -- keeps its order."""

@@ -1,6 +1,8 @@
 #!/bin/bash
-# What the driver runs at round end, in one gpurun call:  gpurun --timeout 1500 -- 'bash tools/gpu_validate.sh'
+# End-of-work validation on the GPU machine, from the repository root: the GPU tests, smoke() and the benchmark with every leg.
+# Usage: bash tools/gpu_validate.sh [out_dir]      (the bench line and its stderr go to out_dir, default bench_outputs/)
 python -m pytest tests -x -q -m gpu 2>&1 | grep -E "passed|failed|error" | tail -3
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-mkdir -p gpurun_out
-python bench.py > gpurun_out/bench_validate.json 2> gpurun_out/bench_validate.err; tail -c 3500 gpurun_out/bench_validate.json
+OUT=${1:-bench_outputs}
+mkdir -p "$OUT"
+python bench.py --full > "$OUT/bench_validate.json" 2> "$OUT/bench_validate.err"; tail -c 3500 "$OUT/bench_validate.json"

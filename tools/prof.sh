@@ -4,10 +4,11 @@
 #        PROF_CMD="python tools/prof_head.py" tools/prof.sh <tag>   -> profiles another workload
 set -u
 TAG=$1; shift
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-if [ -n "${PROF_CMD:-}" ]; then B="$PROF_CMD"; cd $GRAFT_REPO_ROOT; else B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-parity $*"; fi
+if [ -n "${PROF_CMD:-}" ]; then B="$PROF_CMD"; cd "$REPO"; else B="python $REPO/bench.py --full --no-cpu-baseline --no-parity $*"; fi
 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o trace -- $B > $OUT/bench_trace.json 2> $OUT/trace.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/pmc_fetch -o pmc -- $B > $OUT/bench_pmc_fetch.json 2> $OUT/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -f csv -d $OUT/pmc_write -o pmc -- $B > $OUT/bench_pmc_write.json 2> $OUT/pmc_write.err

@@ -3,10 +3,11 @@
 # the MSIM_* knobs exist in the measurement build only: `make -C colpali_amd/csrc ab` first
 export COLPALI_AMD_LIB=${COLPALI_AMD_LIB:-tools/_ab/libmaxsim_ab.so}
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_convoy
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-parity --regimes 1000 --steps 3 --warmup 1"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-parity --regimes 1000 --steps 3 --warmup 1"
 for mode in 1 0; do
   MSIM_BATCH_CONVOY=$mode rocprofv3 --kernel-trace --pmc FETCH_SIZE -f csv -d $OUT/convoy$mode -o pmc -- $B > $OUT/bench_convoy$mode.json 2> $OUT/convoy$mode.err
   python - <<PY
