@@ -6,6 +6,7 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
   * ColbertPairwiseCELoss (+ ColbertLoss, ColbertSigmoidLoss, ColbertModule)
                                   <- colpali_engine/loss/late_interaction_losses.py:255-313 (:110-164, :401-465, :6-107)
   * ShardedRetriever / topk       -- sharded-corpus top-k with an RCCL all-gather merge (no reference equivalent)
+  * rerank                        -- exact MaxSim of per-query candidate lists; two-stage search (ShardedRetriever.search(prefilter=))
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
@@ -18,7 +19,7 @@ from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPai
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
 from .patch import patch_colpali_engine, unpatch_colpali_engine
-from .retrieval import (ExactMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered, shard_range,
+from .retrieval import (ExactMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered, rerank, shard_range,
                         shard_topk, topk)
 from .scoring import (get_similarity_maps_from_embeddings, get_torch_device, maxsim_scores, score_multi_vector,
                       score_single_vector, similarity_matrix)
@@ -43,6 +44,7 @@ __all__ = [
     "create_plaid_index",
     "get_topk_plaid",
     "merge_gathered",
+    "rerank",
     "shard_range",
     "shard_topk",
     "topk",

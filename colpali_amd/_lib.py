@@ -29,7 +29,7 @@ def _lib_path() -> str:
 LIB_PATH = _lib_path()
 
 MSIM_FLAG_REF_ROUNDING = 0x1
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 def dtype_code(dtype) -> int:
@@ -157,6 +157,10 @@ def lib() -> ctypes.CDLL:
     L.msim_loss_epilogue.restype = i32
     L.msim_host_gather.argtypes = [vp, vp, vp, vp, i64, i32]
     L.msim_host_gather.restype = i32
+    L.msim_fwd_candidates_workspace_bytes.argtypes = [i32, i32, i32]
+    L.msim_fwd_candidates_workspace_bytes.restype = sz
+    L.msim_fwd_candidates.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i64, i64, vp, i64, vp, u32, vp, vp]
+    L.msim_fwd_candidates.restype = i32
     L.msim_topk_workspace_bytes.argtypes = [i32, i64, i32]
     L.msim_topk_workspace_bytes.restype = sz
     L.msim_topk_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]

@@ -30,6 +30,7 @@
 #include "token_pooling.hip"
 #include "loss_epilogue.hip"
 #include "topk_select.hip"
+#include "maxsim_candidates.hip"
 
 namespace {
 
@@ -2461,6 +2462,115 @@ int msim_topk_f32(const float *scores, const int64_t *ids, int n_q, int64_t n, i
         which ^= 1;
         seg = seg1;
     }
+    return MSIM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- candidate reranking (K1c, maxsim_candidates.hip)
+namespace {
+
+struct CandLayout {        // msim_fwd_candidates' workspace, every piece 16-byte aligned
+    size_t status, cnt, bsum, estart, istart, rank, entries, items, total;
+};
+
+CandLayout cand_layout(int n_q, int m, int n_d) {
+    auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+    const size_t E = (size_t)n_q * (size_t)m;
+    const size_t nb = ((size_t)n_d + msim::kCandScanDocs - 1) / msim::kCandScanDocs;
+    CandLayout L;
+    size_t w = 0;
+    L.status = w;   w += 16;                                             // zeroed together with the counts
+    L.cnt = w;      w += a16((size_t)n_d * msim::kCandClasses * 4);
+    L.bsum = w;     w += a16((2 * nb + 2) * 4);
+    L.estart = w;   w += a16(((size_t)n_d + 1) * 4);
+    L.istart = w;   w += a16(((size_t)n_d + 1) * 4);
+    L.rank = w;     w += a16(E * 4);
+    L.entries = w;  w += a16(E * sizeof(int2));
+    L.items = w;    w += a16(E * sizeof(msim::CandItem));
+    L.total = w;
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t msim_fwd_candidates_workspace_bytes(int n_q, int m, int n_d) {
+    if (n_q <= 0 || m <= 0 || n_d < 0) return 0;
+    return cand_layout(n_q, m, n_d).total;
+}
+
+int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+                        const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, const int64_t *cand, int m, int64_t ld_cand,
+                        int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids, unsigned flags, void *workspace,
+                        void *stream) {
+    if (n_q < 0 || m < 0 || n_d < 0) return fail(MSIM_EINVAL, "negative size (n_q=%d m=%d n_d=%d)", n_q, m, n_d);
+    if (n_q == 0 || m == 0) return MSIM_OK;
+    if (!Qt || !q_off || !q_off_host || (!D && n_d > 0) || !d_off || !cand || !out_scores || !workspace)
+        return fail(MSIM_EINVAL, "null pointer argument");
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || dim != msim::kDim)
+        return fail(MSIM_EUNSUPPORTED, "msim_fwd_candidates takes bfloat16 / float16 embeddings of width %d (dtype code %d, dim %d)",
+                    msim::kDim, dtype, dim);
+    if ((reinterpret_cast<uintptr_t>(Qt) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(workspace)) & 15)
+        return fail(MSIM_EINVAL, "Qt, D and workspace must be 16-byte aligned");
+    if (ld_cand < m) return fail(MSIM_EINVAL, "ld_cand=%lld < m=%d", (long long)ld_cand, m);
+    if (ld_scores < m) return fail(MSIM_EINVAL, "ld_scores=%lld < m=%d", (long long)ld_scores, m);
+    if (flags & ~(MSIM_FLAG_REF_ROUNDING)) return fail(MSIM_EINVAL, "unknown flags 0x%x", flags);
+    if ((long long)n_q * m > 0x7fffffff) return fail(MSIM_EUNSUPPORTED, "more than 2^31 - 1 entries (n_q=%d x m=%d)", n_q, m);
+    if (q_off_host[0] != 0) return fail(MSIM_EINVAL, "q_off[0] must be 0");
+    for (int i = 0; i < n_q; ++i) {
+        const int len = q_off_host[i + 1] - q_off_host[i];
+        if (len < 0) return fail(MSIM_EINVAL, "q_off must be non-decreasing (query %d)", i);
+        if (len > msim::kStreamMaxUnits * msim::kUnitTok)
+            return fail(MSIM_EUNSUPPORTED, "query %d has %d tokens: msim_fwd_candidates takes queries of at most %d", i, len,
+                        msim::kStreamMaxUnits * msim::kUnitTok);
+    }
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const CandLayout lay = cand_layout(n_q, m, n_d);
+    char *ws = static_cast<char *>(workspace);
+    int32_t *status = reinterpret_cast<int32_t *>(ws + lay.status);
+    int32_t *cnt = reinterpret_cast<int32_t *>(ws + lay.cnt), *bsum = reinterpret_cast<int32_t *>(ws + lay.bsum);
+    int32_t *estart = reinterpret_cast<int32_t *>(ws + lay.estart), *istart = reinterpret_cast<int32_t *>(ws + lay.istart);
+    int32_t *rank = reinterpret_cast<int32_t *>(ws + lay.rank);
+    int2 *entries = reinterpret_cast<int2 *>(ws + lay.entries);
+    msim::CandItem *items = reinterpret_cast<msim::CandItem *>(ws + lay.items);
+    const long long E = (long long)n_q * m;
+    const unsigned eblocks = (unsigned)((E + 255) / 256);
+    {
+        const long long n16 = (long long)(lay.bsum - lay.status) / 16;     // status word + counters, a multiple of 16 bytes
+        const long long blocks = (n16 + 255) / 256;
+        hipLaunchKernelGGL(msim::cand_zero_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st,
+                           reinterpret_cast<msim::i32x4 *>(status), n16);
+    }
+    hipLaunchKernelGGL(msim::cand_count_kernel, dim3(eblocks), dim3(256), 0, st, cand, (long long)ld_cand, n_q, m, (long long)id_base, n_d,
+                       q_off, cnt, rank, out_scores, (long long)ld_scores, out_ids, status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "cand_count_kernel launch: %s", hipGetErrorString(e));
+    if (n_d == 0) return MSIM_OK;                  // every entry was out of range
+    const int nb = (n_d + msim::kCandScanDocs - 1) / msim::kCandScanDocs;
+    hipLaunchKernelGGL(msim::cand_block_sums_kernel, dim3(nb), dim3(256), 0, st, cnt, n_d, bsum);
+    hipLaunchKernelGGL(msim::cand_scan_sums_kernel, dim3(1), dim3(256), 0, st, bsum, nb);
+    hipLaunchKernelGGL(msim::cand_block_starts_kernel, dim3(nb), dim3(256), 0, st, cnt, n_d, bsum, nb, estart, istart);
+    hipLaunchKernelGGL(msim::cand_place_kernel, dim3(eblocks), dim3(256), 0, st, cand, (long long)ld_cand, n_q, m, (long long)id_base, q_off,
+                       cnt, rank, estart, istart, n_d, entries, items, status);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "candidate list kernels launch: %s", hipGetErrorString(e));
+    // a persistent grid sized from what the host knows: at most one item per entry, two workgroups per CU
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = f16 ? msim::maxsim_candidates_kernel<true, 0> : msim::maxsim_candidates_kernel<false, 0>;
+    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
+    if (int rc = allow_lds(kern, msim::kCandLdsBytes, f16 ? configured_f16 : configured_bf16)) return rc;
+    const long long wg_needed = (E + 3) / 4;
+    const long long wg_cap = (long long)di->cus * (di->lds_per_cu / msim::kCandLdsBytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(wg_needed < wg_cap ? wg_needed : wg_cap)), dim3(256), msim::kCandLdsBytes, st,
+                       static_cast<const uint16_t *>(Qt), q_off, static_cast<const uint16_t *>(D), d_off, d_clamp0, entries, items,
+                       istart + n_d, (int)E, n_q, m, n_d, out_scores, (long long)ld_scores, flags, status);
+    hipLaunchKernelGGL(msim::cand_poison_kernel, dim3(eblocks), dim3(256), 0, st, status, n_q, m, out_scores, (long long)ld_scores);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_candidates_kernel launch: %s", hipGetErrorString(e));
     return MSIM_OK;
 }
 

@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from .corpus import PackedCorpus
 from .corpus import PackedQueries, pack_queries
-from .scoring import maxsim_scores
+from .scoring import _require_gpu, maxsim_scores
 
 
 def shard_range(n_total: int, world: int, rank: int) -> Tuple[int, int]:
@@ -79,16 +79,18 @@ def merge_gathered(all_s: torch.Tensor, all_i: torch.Tensor, k: int,
 
 
 def shard_topk(scores: torch.Tensor, k: int, id_base: int, world: int = 1, dist=None, group=None,
-               select: Callable = topk, force_collective: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+               select: Callable = topk, force_collective: bool = False,
+               ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-shard top-k of a local score matrix, then (world > 1) all-gather + merge.
 
-    `scores` [n_q, n_local]: column j is document id_base + j.  Returns the same global
+    `scores` [n_q, n_local]: column j is document id_base + j, or ids[q, j] when `ids` is given (int64 [n_q, n_local], -1 = no
+    document: reranked candidate lists).  Returns the same global
     (scores [n_q, k], ids [n_q, k]) on every rank.  `force_collective=True` sends a single rank through the
     message packing, the all-gather (RCCL under the `nccl` backend) and the strided-view merge as well: the
     multi-GPU code path, exercised on the one GPU a test box has (the result is the same by construction).
     """
     if world <= 1 and not force_collective:
-        return select(scores, k, id_base, None)
+        return select(scores, k, id_base, ids)
     world = max(world, 1)
     if dist is None:
         import torch.distributed as dist  # noqa: PLW0642 - the default collective library
@@ -101,9 +103,9 @@ def shard_topk(scores: torch.Tensor, k: int, id_base: int, world: int = 1, dist=
     my_s = mine[:sb].view(torch.float32).view(n_q, k)
     my_i = mine[sbp:].view(torch.int64).view(n_q, k)
     if select is topk:
-        topk(scores, k, id_base, None, out=(my_s, my_i))                    # the selection kernel writes the message in place
+        topk(scores, k, id_base, ids, out=(my_s, my_i))                     # the selection kernel writes the message in place
     else:
-        loc_s, loc_i = select(scores, k, id_base, None)
+        loc_s, loc_i = select(scores, k, id_base, ids)
         my_s.copy_(loc_s)
         my_i.copy_(loc_i)
     flat = torch.empty((world * nbytes,), dtype=torch.uint8, device=scores.device)     # rank-major concatenation
@@ -114,33 +116,143 @@ def shard_topk(scores: torch.Tensor, k: int, id_base: int, world: int = 1, dist=
     return merge_gathered(all_s, all_i, k, select)
 
 
+def _query_format(queries) -> Tuple[torch.dtype, int]:
+    if isinstance(queries, PackedQueries):
+        return queries.dtype, int(queries.tokens.shape[1])
+    if isinstance(queries, torch.Tensor):
+        return queries.dtype, int(queries.shape[-1])
+    if len(queries) == 0:
+        raise ValueError("No queries provided")
+    return queries[0].dtype, int(queries[0].shape[-1])
+
+
+def rerank_scores(queries, corpus: PackedCorpus, candidates: torch.Tensor, *, ref_rounding: bool = False,
+                  out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MaxSim of listed candidates (include/maxsim.h: msim_fwd_candidates): (scores fp32 [n_q, m], ids int64 [n_q, m]).
+
+    Entry (q, j) is scored against document candidates[q, j] (a GLOBAL id) of `corpus`; an id of -1 or outside
+    [id_base, id_base + len(corpus)) comes back as (-inf, -1).  `rerank` is the public form; this one is what
+    `ShardedRetriever` calls per shard (its `rerank_fn`)."""
+    dev = _require_gpu(corpus.device)
+    q_dtype, dim = _query_format(queries)
+    if q_dtype != corpus.blob.dtype:        # as maxsim_scores: torch.einsum raises on mixed dtypes too
+        raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {corpus.blob.dtype}")
+    if q_dtype not in (torch.bfloat16, torch.float16) or dim != 128 or corpus.blob.shape[1] != 128:
+        raise NotImplementedError(f"rerank takes bfloat16 / float16 embeddings of width 128 (got {q_dtype}, width {dim})")
+    if not isinstance(queries, PackedQueries):
+        dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+        queries = pack_queries(queries, dev, layout="flat", compact=not dense_on_device)
+    if queries.device != dev:
+        raise ValueError("queries and corpus live on different devices")
+    n_q = len(queries)
+    if (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2
+            or candidates.shape[0] != n_q or candidates.device != dev):
+        raise ValueError(f"candidates must be an int64 [n_q={n_q}, m] tensor on {dev}")
+    if (candidates.shape[1] > 1 and candidates.stride(1) != 1) or (n_q > 1 and candidates.stride(0) < candidates.shape[1]):
+        candidates = candidates.contiguous()          # e.g. one shared list broadcast to every query (row stride 0)
+    m = int(candidates.shape[1])
+    ld_cand = candidates.stride(0) if n_q > 1 else max(m, 1)
+    if out is None:
+        out = torch.empty((n_q, m), dtype=torch.float32, device=dev)
+    elif out.shape != (n_q, m) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous fp32 [n_q, m] tensor on the corpus' device")
+    ids = torch.empty((n_q, m), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    n = len(corpus)
+    with torch.cuda.device(dev):
+        nbytes = L.msim_fwd_candidates_workspace_bytes(n_q, m, n)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        rc = L.msim_fwd_candidates(_lib.dtype_code(q_dtype), _lib.ptr(queries.tokens), _lib.ptr(queries.offsets),
+                                   queries.offsets_host.data_ptr(), n_q, _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets),
+                                   _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(candidates), m, ld_cand, int(corpus.id_base),
+                                   _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.MSIM_FLAG_REF_ROUNDING if ref_rounding else 0,
+                                   _lib.ptr(ws), _lib.current_stream_handle(dev))
+    _lib.check(rc, "msim_fwd_candidates")
+    return out, ids
+
+
+def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[int] = None, *, ref_rounding: bool = False,
+           out=None):
+    """Exact MaxSim of each query against ITS candidate documents only -- the second stage of a two-stage search.
+
+    queries: a `PackedQueries`, a host list of [len_i, 128] tensors or a [n_q, Lq, 128] tensor (packed as
+    `ShardedRetriever.search` does); candidates: int64 [n_q, m] GLOBAL ids on the corpus' device (-1 = none).
+    k=None: fp32 [n_q, m] scores aligned with `candidates`; scores[q, j] has the bits of
+    `maxsim_scores(queries, corpus)[q, candidates[q, j] - corpus.id_base]`, and an empty or out-of-corpus entry is -inf.
+    k set: (scores [n_q, k], ids [n_q, k]) of `topk` over the listed documents -- (score desc, id asc), padded with
+    (-inf, -1); an id listed twice in a row is scored twice and may appear twice.
+    out: the fp32 [n_q, m] score tensor (k=None) or the (scores, ids) pair `topk` writes (k set).
+    Asynchronous on torch's current stream; with a `PackedQueries` the call is hipGraph-capturable (no host synchronisation, no
+    allocation inside the library call)."""
+    if k is None:
+        return rerank_scores(queries, corpus, candidates, ref_rounding=ref_rounding, out=out)[0]
+    scores, ids = rerank_scores(queries, corpus, candidates, ref_rounding=ref_rounding)
+    return topk(scores, k, 0, ids, out=out)
+
+
 class ShardedRetriever:
     """One instance per process/GPU; holds this rank's resident shard of the corpus."""
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
-                 score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False):
+                 score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
+                 rerank_fn: Callable = rerank_scores):
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
+        self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
         self.force_collective = force_collective
         if world > 1 and dist is None:
             import torch.distributed as dist_mod
 
             self.dist = dist_mod
 
-    def search(self, queries, k: int = 10, compact: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None,
+               prefilter: Optional[PackedCorpus] = None, n_candidates: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """queries (replicated on every rank): a `PackedQueries`, a list of [len_i, 128] tensors, or a [n_q, Lq, 128] tensor.
         A host list is packed into the flat layout (ragged lengths, zero rows dropped on the way into the staging buffer).  A dense
         DEVICE tensor is scored as it stands unless `compact=True`: dropping its zero padding rows needs the per-query counts on the
         host (one small D2H + a synchronisation), which would make a call that is otherwise fully asynchronous and hipGraph-capturable
         block the host (round-4 advisor finding).  Callers with heavily padded query boxes pass `compact=True`, or pack once with
-        `pack_queries` and hand the `PackedQueries` over; the scores are the same either way (a zero row adds exactly 0)."""
+        `pack_queries` and hand the `PackedQueries` over; the scores are the same either way (a zero row adds exactly 0).
+
+        Reranking (`rerank`): `candidates` -- int64 [n_q, m] GLOBAL ids, the same on every rank -- scores each query against its listed
+        documents only: every rank reranks the ids it holds, then the same all-gather and merge run.  `prefilter` -- a `PackedCorpus`
+        over the same documents as the shard (same count, same id_base; any rows per document, e.g. pooled pages) -- makes the list
+        here: stage 1 scores the prefilter and keeps the GLOBAL top `n_candidates` (one all-gather: the list is the same on every rank,
+        so the answer does not depend on the number of shards), stage 2 reranks that list exactly on the full-resolution shard."""
+        if n_candidates is not None and prefilter is None:
+            raise ValueError("n_candidates goes with prefilter=")
+        if candidates is not None or prefilter is not None:
+            return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates)
         if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
         scores = self._score(queries, self.shard)
         return shard_topk(scores, k, self.shard.id_base, self.world, self.dist, self.group, self._select,
                           force_collective=self.force_collective)
+
+    def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates):
+        if candidates is not None and prefilter is not None:
+            raise ValueError("pass either candidates= or prefilter=, not both")
+        if prefilter is not None:
+            if not isinstance(prefilter, PackedCorpus):
+                raise ValueError("prefilter must be a PackedCorpus")
+            if len(prefilter) != len(self.shard) or prefilter.id_base != self.shard.id_base:
+                raise ValueError(f"prefilter holds {len(prefilter)} documents from id {prefilter.id_base}; the shard holds "
+                                 f"{len(self.shard)} from id {self.shard.id_base}: it must cover the same documents")
+            if n_candidates is None or int(n_candidates) < 1:
+                raise ValueError("prefilter= needs n_candidates >= 1")
+        uses_kernels = self._rerank is rerank_scores or (prefilter is not None and self._score is maxsim_scores)
+        if uses_kernels and not isinstance(queries, PackedQueries):
+            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+            queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
+        if prefilter is not None:
+            coarse = self._score(queries, prefilter)                     # stage 1: the cheap corpus
+            _, candidates = shard_topk(coarse, int(n_candidates), prefilter.id_base, self.world, self.dist, self.group, self._select,
+                                       force_collective=self.force_collective)
+        scores, ids = self._rerank(queries, self.shard, candidates)      # stage 2: exact, this shard's candidates only
+        return shard_topk(scores, k, 0, self.world, self.dist, self.group, self._select, force_collective=self.force_collective,
+                          ids=ids)
 
 
 class ExactMaxSimIndex:

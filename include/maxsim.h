@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MSIM_ABI_VERSION 20
+#define MSIM_ABI_VERSION 21
 
 /* error codes */
 #define MSIM_OK 0
@@ -163,6 +163,32 @@ int msim_fwd_ragged(int dtype, const void *Qt, const int32_t *q_off, const int32
                     int n_d, int dim,
                     float *scores, int64_t ld_scores,
                     uint32_t flags, void *workspace, void *stream);
+
+/*
+ * RERANKING: the same scores for a LIST of candidate documents per query -- the exact second stage behind a cheap first one (pooled
+ * pages, BM25, a bi-encoder, a metadata filter, hard-negative mining).  For every entry (q, j) of cand [n_q, m] (row stride
+ * ld_cand >= m, int64 GLOBAL ids; the shard's document c has id id_base + c):
+ *     out_scores[q, j] = scores[q, cand[q, j] - id_base]   of msim_fwd_ragged on the same queries, corpus and flags -- bit for bit
+ *     out_ids[q, j]    = cand[q, j]                        (out_ids: int64 [n_q, ld_scores], or NULL)
+ * An entry whose id is -1, or outside [id_base, id_base + n_d), is written as (-inf, -1) and reads no document; a query of 0 tokens
+ * scores 0.  A duplicate id is scored once per occurrence (identical bits).  out_scores fp32 [n_q, ld_scores], ld_scores >= m.
+ * Queries in the flat layout (q_off on the device, q_off_host the same n_q + 1 numbers on the host, read during the call only), bf16 /
+ * f16, width 128, 0 .. 128 tokens per query (MSIM_EUNSUPPORTED otherwise); d_clamp0 and MSIM_FLAG_REF_ROUNDING as msim_fwd (no other
+ * flag).  The candidate matrix is inverted ON THE DEVICE into work items -- one document and up to eight 16-token units of the
+ * queries that listed it -- so a document is read once per group of queries that listed it, not once per entry (kernel K1c,
+ * maxsim_candidates.hip); the host never reads the list, so the call is asynchronous and hipGraph-capturable like the others.
+ * Every index the device derives is checked before it becomes an address; a broken invariant (a device q_off that disagrees with
+ * q_off_host, or a library bug) makes every score of the call NaN instead of leaving one unwritten.
+ * workspace: msim_fwd_candidates_workspace_bytes(n_q, m, n_d) bytes (0 when there is no entry), 16-byte aligned, contents
+ * irrelevant; one per call in flight.  After the call its first int32 is 0, or the bits of the broken invariant.
+ * ld_cand >= m: a list shared by every query is passed once per row (the binding copies a broadcast view).
+ */
+size_t msim_fwd_candidates_workspace_bytes(int n_q, int m, int n_d);
+int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q,
+                        const void *D, const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim,
+                        const int64_t *cand, int m, int64_t ld_cand, int64_t id_base,
+                        float *out_scores, int64_t ld_scores, int64_t *out_ids /* or NULL */,
+                        unsigned flags, void *workspace, void *stream);
 
 /*
  * The same scores for two DENSE BOXES when the queries are long and the documents short -- the symmetric direction of the reference
