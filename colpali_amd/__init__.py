@@ -7,6 +7,7 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                   <- colpali_engine/loss/late_interaction_losses.py:255-313 (:110-164, :401-465, :6-107)
   * ShardedRetriever / topk       -- sharded-corpus top-k with an RCCL all-gather merge (no reference equivalent)
   * rerank                        -- exact MaxSim of per-query candidate lists; two-stage search (ShardedRetriever.search(prefilter=))
+  * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
@@ -15,6 +16,7 @@ colpali_amd/csrc/); this package is the thin host-side mirror of the reference i
 from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pack_queries
 from . import loss
 from .embed import CorpusWriter, embedding_head
+from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPairwiseCELoss,
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
@@ -29,6 +31,10 @@ __all__ = [
     "HierarchicalTokenPooler",
     "TokenPoolingOutput",
     "embedding_head",
+    "FdeConfig",
+    "FdeIndex",
+    "encode_queries",
+    "fde_scores",
     "ColbertLoss",
     "ColbertModule",
     "ColbertNegativeCELoss",

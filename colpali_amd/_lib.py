@@ -29,7 +29,7 @@ def _lib_path() -> str:
 LIB_PATH = _lib_path()
 
 MSIM_FLAG_REF_ROUNDING = 0x1
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 def dtype_code(dtype) -> int:
@@ -161,6 +161,12 @@ def lib() -> ctypes.CDLL:
     L.msim_fwd_candidates_workspace_bytes.restype = sz
     L.msim_fwd_candidates.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i64, i64, vp, i64, vp, u32, vp, vp]
     L.msim_fwd_candidates.restype = i32
+    L.msim_fde_encode_docs.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.msim_fde_encode_docs.restype = i32
+    L.msim_fde_encode_queries.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.msim_fde_encode_queries.restype = i32
+    L.msim_fde_scores.argtypes = [i32, vp, i32, vp, i32, i32, vp, i64, vp]
+    L.msim_fde_scores.restype = i32
     L.msim_topk_workspace_bytes.argtypes = [i32, i64, i32]
     L.msim_topk_workspace_bytes.restype = sz
     L.msim_topk_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]

@@ -31,6 +31,7 @@
 #include "loss_epilogue.hip"
 #include "topk_select.hip"
 #include "maxsim_candidates.hip"
+#include "fde.hip"
 
 namespace {
 
@@ -2572,6 +2573,104 @@ int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const i
     e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_candidates_kernel launch: %s", hipGetErrorString(e));
     return MSIM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- fixed dimensional encodings (fde.hip)
+namespace {
+
+// the encoding's configuration: what the kernels implement, or MSIM_EUNSUPPORTED / MSIM_EINVAL
+int fde_check_config(const char *who, int dtype, int dim, int reps, int ksim, int dproj, long long *F_out) {
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || dim != msim::kDim)
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 embeddings of width %d (dtype code %d, dim %d)", who, msim::kDim,
+                    dtype, dim);
+    if (reps < 1) return fail(MSIM_EINVAL, "%s: reps=%d < 1", who, reps);
+    if (ksim < 1 || ksim > msim::kFdeMaxKsim) return fail(MSIM_EUNSUPPORTED, "%s: k_sim=%d outside 1..%d", who, ksim, msim::kFdeMaxKsim);
+    if (!(dproj == 8 || dproj == 16 || dproj == 32 || dproj == 64))
+        return fail(MSIM_EUNSUPPORTED, "%s: d_proj=%d is not 8, 16, 32 or 64", who, dproj);
+    const long long F = (long long)reps * (1LL << ksim) * dproj;
+    if (F % 256 != 0 || F > 65536)
+        return fail(MSIM_EUNSUPPORTED, "%s: F = reps x 2^k_sim x d_proj = %lld must be a multiple of 256 and at most 65536", who, F);
+    *F_out = F;
+    return MSIM_OK;
+}
+
+int fde_encode(const char *who, int dtype, const void *X, const int32_t *off, int n, int64_t n_rows, int dim, const float *G,
+               const float *S, int reps, int ksim, int dproj, int is_doc, int fill_empty, void *out, uint8_t *codes, void *stream) {
+    if (n < 0 || n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (n=%d rows=%lld)", who, n, (long long)n_rows);
+    long long F = 0;
+    if (int rc = fde_check_config(who, dtype, dim, reps, ksim, dproj, &F)) return rc;
+    if (n == 0) return MSIM_OK;
+    if ((!X && n_rows > 0) || !off || !G || !S || !out) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(out) & 1))
+        return fail(MSIM_EINVAL, "%s: the rows must be 16-byte aligned and the output 2-byte aligned", who);
+    if (fill_empty != 0 && fill_empty != 1) return fail(MSIM_EINVAL, "%s: fill_empty=%d is not 0 or 1", who, fill_empty);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = f16 ? msim::fde_encode_kernel<true> : msim::fde_encode_kernel<false>;
+    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
+    constexpr int kMaxLds = msim::fde_encode_lds_bytes(msim::kFdeMaxKsim, 64);
+    if (int rc = allow_lds(kern, kMaxLds, f16 ? configured_f16 : configured_bf16)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(256), msim::fde_encode_lds_bytes(ksim, dproj), st, static_cast<const uint16_t *>(X),
+                       off, n, (long long)n_rows, G, S, reps, ksim, dproj, is_doc, fill_empty, static_cast<uint16_t *>(out), codes);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "fde_encode_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+template <int QB, int DB, int NBUF>
+int fde_scores_launch(bool f16, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld, hipStream_t st) {
+    auto kern = f16 ? msim::fde_scores_kernel<QB, DB, NBUF, true> : msim::fde_scores_kernel<QB, DB, NBUF, false>;
+    constexpr int lds = msim::fde_scores_lds_bytes<QB, DB, NBUF>();
+    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
+    if (int rc = allow_lds(kern, lds, f16 ? configured_f16 : configured_bf16)) return rc;
+    const long long n_qt = (n_q + QB - 1) / QB, n_dt = ((long long)n_d + DB - 1) / DB;
+    if (n_qt * n_dt > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "msim_fde_scores: %lld tiles exceed one launch", n_qt * n_dt);
+    const int vec = (reinterpret_cast<uintptr_t>(scores) & 15) == 0 && (ld & 3) == 0;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(n_qt * n_dt)), dim3(256), lds, st, static_cast<const uint16_t *>(Fq), n_q,
+                       static_cast<const uint16_t *>(Fd), n_d, F, scores, (long long)ld, (int)n_qt, vec);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "fde_scores_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_fde_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, const float *G, const float *S,
+                         int reps, int ksim, int dproj, int fill_empty, void *out, uint8_t *codes, void *stream) {
+    return fde_encode("msim_fde_encode_docs", dtype, D, d_off, n_d, n_rows, dim, G, S, reps, ksim, dproj, 1, fill_empty, out, codes,
+                      stream);
+}
+
+int msim_fde_encode_queries(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t n_rows, int dim, const float *G,
+                            const float *S, int reps, int ksim, int dproj, void *out, uint8_t *codes, void *stream) {
+    return fde_encode("msim_fde_encode_queries", dtype, Qt, q_off, n_q, n_rows, dim, G, S, reps, ksim, dproj, 0, 0, out, codes, stream);
+}
+
+int msim_fde_scores(int dtype, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld_scores, void *stream) {
+    if (n_q < 0 || n_d < 0 || F < 0) return fail(MSIM_EINVAL, "msim_fde_scores: negative size (n_q=%d n_d=%d F=%d)", n_q, n_d, F);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
+        return fail(MSIM_EUNSUPPORTED, "msim_fde_scores takes bfloat16 / float16 encodings (dtype code %d)", dtype);
+    if (F % 256 != 0 || F == 0 || F > 65536)
+        return fail(MSIM_EUNSUPPORTED, "msim_fde_scores: F=%d must be a positive multiple of 256, at most 65536", F);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if (!Fq || !Fd || !scores) return fail(MSIM_EINVAL, "msim_fde_scores: null pointer argument");
+    if ((reinterpret_cast<uintptr_t>(Fq) | reinterpret_cast<uintptr_t>(Fd)) & 15)
+        return fail(MSIM_EINVAL, "msim_fde_scores: Fq and Fd must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(scores) & 3)) return fail(MSIM_EINVAL, "msim_fde_scores: scores must be 4-byte aligned");
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "msim_fde_scores: ld_scores=%lld < n_d=%d", (long long)ld_scores, n_d);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    // a few queries: a narrow query tile and a 4-deep ring (HBM-bound: Fd streams once); many: 128 x 128 tiles (MFMA-bound)
+    if (n_q <= 64) return fde_scores_launch<32, 128, 4>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
+    return fde_scores_launch<128, 128, 2>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
 }
 
 }  // extern "C"

@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from .corpus import PackedCorpus
 from .corpus import PackedQueries, pack_queries
+from .fde import FdeIndex, fde_scores
 from .scoring import _require_gpu, maxsim_scores
 
 
@@ -195,11 +196,12 @@ class ShardedRetriever:
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
-                 rerank_fn: Callable = rerank_scores):
+                 rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores):
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
         self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
+        self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
         self.force_collective = force_collective
         if world > 1 and dist is None:
             import torch.distributed as dist_mod
@@ -207,7 +209,7 @@ class ShardedRetriever:
             self.dist = dist_mod
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None,
-               prefilter: Optional[PackedCorpus] = None, n_candidates: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               prefilter=None, n_candidates: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """queries (replicated on every rank): a `PackedQueries`, a list of [len_i, 128] tensors, or a [n_q, Lq, 128] tensor.
         A host list is packed into the flat layout (ragged lengths, zero rows dropped on the way into the staging buffer).  A dense
         DEVICE tensor is scored as it stands unless `compact=True`: dropping its zero padding rows needs the per-query counts on the
@@ -219,7 +221,9 @@ class ShardedRetriever:
         documents only: every rank reranks the ids it holds, then the same all-gather and merge run.  `prefilter` -- a `PackedCorpus`
         over the same documents as the shard (same count, same id_base; any rows per document, e.g. pooled pages) -- makes the list
         here: stage 1 scores the prefilter and keeps the GLOBAL top `n_candidates` (one all-gather: the list is the same on every rank,
-        so the answer does not depend on the number of shards), stage 2 reranks that list exactly on the full-resolution shard."""
+        so the answer does not depend on the number of shards), stage 2 reranks that list exactly on the full-resolution shard.
+        `prefilter` may also be an `FdeIndex` of the shard (same count, same id_base): stage 1 is then the fixed-dimensional-encoding
+        GEMM (`fde_scores`), under the same rules."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
         if candidates is not None or prefilter is not None:
@@ -235,19 +239,21 @@ class ShardedRetriever:
         if candidates is not None and prefilter is not None:
             raise ValueError("pass either candidates= or prefilter=, not both")
         if prefilter is not None:
-            if not isinstance(prefilter, PackedCorpus):
-                raise ValueError("prefilter must be a PackedCorpus")
+            if not isinstance(prefilter, (PackedCorpus, FdeIndex)):
+                raise ValueError("prefilter must be a PackedCorpus or an FdeIndex")
             if len(prefilter) != len(self.shard) or prefilter.id_base != self.shard.id_base:
                 raise ValueError(f"prefilter holds {len(prefilter)} documents from id {prefilter.id_base}; the shard holds "
                                  f"{len(self.shard)} from id {self.shard.id_base}: it must cover the same documents")
             if n_candidates is None or int(n_candidates) < 1:
                 raise ValueError("prefilter= needs n_candidates >= 1")
-        uses_kernels = self._rerank is rerank_scores or (prefilter is not None and self._score is maxsim_scores)
+        fde = isinstance(prefilter, FdeIndex)
+        stage1 = self._fde_score if fde else self._score
+        uses_kernels = self._rerank is rerank_scores or (prefilter is not None and stage1 in (maxsim_scores, fde_scores))
         if uses_kernels and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
         if prefilter is not None:
-            coarse = self._score(queries, prefilter)                     # stage 1: the cheap corpus
+            coarse = stage1(queries, prefilter)                          # stage 1: the cheap corpus, or the encodings
             _, candidates = shard_topk(coarse, int(n_candidates), prefilter.id_base, self.world, self.dist, self.group, self._select,
                                        force_collective=self.force_collective)
         scores, ids = self._rerank(queries, self.shard, candidates)      # stage 2: exact, this shard's candidates only

@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MSIM_ABI_VERSION 21
+#define MSIM_ABI_VERSION 22
 
 /* error codes */
 #define MSIM_OK 0
@@ -504,6 +504,37 @@ size_t msim_topk_workspace_bytes(int n_q, int64_t n, int k);
 int msim_topk_f32(const float *scores, const int64_t *ids, int n_q, int64_t n, int64_t ld,
                   int k, int64_t id_base,
                   float *out_scores, int64_t *out_ids, void *workspace, void *stream);
+
+/*
+ * FIXED DIMENSIONAL ENCODINGS (FDE; Dhulipala et al., "MUVERA", NeurIPS 2024): one vector of F values per page and per query whose
+ * inner product approximates MaxSim -- a first stage that is one dense GEMM, reranked exactly by msim_fwd_candidates (fde.hip).
+ * Configuration: reps R >= 1, k_sim in 1..6 (B = 2^k_sim buckets), d_proj in {8, 16, 32, 64}; F = R * B * d_proj must be a multiple
+ * of 256 and at most 65536; bf16 / f16 rows of width 128 (MSIM_EUNSUPPORTED otherwise).  G fp32 [R, k_sim, 128] and S fp32
+ * [R, d_proj, 128] (entries +-1) on the device, drawn by the caller.  For rep r:
+ *     phi_r(x) = sum_i 2^i [<G[r, i], x> > 0]        psi_r(x) = S[r] x / sqrt(d_proj)
+ * Entry (r * B + b) * d_proj + j of an encoding is psi_r(v)[j], where v is
+ *     msim_fde_encode_queries: the SUM of the query's tokens with phi_r = b (zeros if none);
+ *     msim_fde_encode_docs:    the MEAN of the page's rows with phi_r = b.  An empty bucket with fill_empty = 1 takes the row p whose
+ *                              phi_r(p) has the smallest Hamming distance to b (the lowest row index on a tie); with fill_empty = 0,
+ *                              and for a page of 0 rows, zeros.
+ * Inputs in the packed layout: rows X [n_rows, 128], item i = rows off[i] .. off[i + 1] - 1 (off int32 [n + 1] on the device; an item
+ * whose offsets fall outside 0 .. n_rows is written as NaN).  out [n, F] in the input dtype, computed in fp32 and rounded once;
+ * deterministic (no float atomics: reruns are bit-identical).  codes: uint8 [n_rows, R] = phi_r of every row, or NULL.
+ * Asynchronous on `stream`, no allocation, no host synchronisation: hipGraph-capturable.
+ */
+int msim_fde_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim,
+                         const float *G, const float *S, int reps, int ksim, int dproj, int fill_empty,
+                         void *out, uint8_t *codes /* or NULL */, void *stream);
+int msim_fde_encode_queries(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t n_rows, int dim,
+                            const float *G, const float *S, int reps, int ksim, int dproj,
+                            void *out, uint8_t *codes /* or NULL */, void *stream);
+/*
+ * scores[q, c] = sum_f Fq[q, f] * Fd[c, f] in fp32 (Fq [n_q, F], Fd [n_d, F] contiguous, bf16 | f16, 16-byte aligned; scores fp32
+ * [n_q, ld_scores], ld_scores >= n_d).  A streamed MFMA GEMM; a query's scores have the same bits whatever other queries share the
+ * call (the summation order depends on F only).  F: a positive multiple of 256, at most 65536.  No workspace.
+ */
+int msim_fde_scores(int dtype, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld_scores,
+                    void *stream);
 
 #ifdef __cplusplus
 }
