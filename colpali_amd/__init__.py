@@ -8,6 +8,7 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
   * ShardedRetriever / topk       -- sharded-corpus top-k with an RCCL all-gather merge (no reference equivalent)
   * rerank                        -- exact MaxSim of per-query candidate lists; two-stage search (ShardedRetriever.search(prefilter=))
   * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
+  * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
@@ -17,6 +18,7 @@ from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pa
 from . import loss
 from .embed import CorpusWriter, embedding_head
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
+from .int8_index import Int8Index, int8_scores, quantize_queries
 from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPairwiseCELoss,
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
@@ -35,6 +37,9 @@ __all__ = [
     "FdeIndex",
     "encode_queries",
     "fde_scores",
+    "Int8Index",
+    "int8_scores",
+    "quantize_queries",
     "ColbertLoss",
     "ColbertModule",
     "ColbertNegativeCELoss",

@@ -167,6 +167,12 @@ def lib() -> ctypes.CDLL:
     L.msim_fde_encode_queries.restype = i32
     L.msim_fde_scores.argtypes = [i32, vp, i32, vp, i32, i32, vp, i64, vp]
     L.msim_fde_scores.restype = i32
+    L.msim_i8_encode_docs.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, vp]
+    L.msim_i8_encode_docs.restype = i32
+    L.msim_i8_encode_queries.argtypes = [i32, vp, i64, i32, vp, vp, vp]
+    L.msim_i8_encode_queries.restype = i32
+    L.msim_i8_scores.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp]
+    L.msim_i8_scores.restype = i32
     L.msim_topk_workspace_bytes.argtypes = [i32, i64, i32]
     L.msim_topk_workspace_bytes.restype = sz
     L.msim_topk_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]

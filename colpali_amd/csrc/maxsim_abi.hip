@@ -32,6 +32,7 @@
 #include "topk_select.hip"
 #include "maxsim_candidates.hip"
 #include "fde.hip"
+#include "int8_index.hip"
 
 namespace {
 
@@ -2671,6 +2672,125 @@ int msim_fde_scores(int dtype, const void *Fq, int n_q, const void *Fd, int n_d,
     // a few queries: a narrow query tile and a 4-deep ring (HBM-bound: Fd streams once); many: 128 x 128 tiles (MFMA-bound)
     if (n_q <= 64) return fde_scores_launch<32, 128, 4>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
     return fde_scores_launch<128, 128, 2>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the int8 token-level index (int8_index.hip)
+namespace {
+
+int i8_check_rows(const char *who, int dtype, int dim) {
+    if (dim != msim::kDim) return fail(MSIM_EINVAL, "%s: rows of width %d; the int8 index takes width %d", who, dim, msim::kDim);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 rows (dtype code %d)", who, dtype);
+    return MSIM_OK;
+}
+
+bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+template <int NT, int GW, int D>
+int i8_scores_launch(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int QG, int TPQ, int passes,
+                     const int8_t *d8, const float *sd, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int ppw,
+                     int n_groups, float *scores, int64_t ld, hipStream_t st) {
+    const long long n_gb = (n_groups + GW - 1) / GW;
+    const long long n_ranges = ((long long)n_d + ppw - 1) / ppw, n_pb = (n_ranges + 4 / GW - 1) / (4 / GW);
+    if (n_gb * n_pb > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "msim_i8_scores: %lld workgroups exceed one launch", n_gb * n_pb);
+    hipLaunchKernelGGL((msim::i8_scores_kernel<NT, GW, D>), dim3((unsigned)(n_gb * n_pb)), dim3(256), 0, st, q8, sq, q_off, n_q,
+                       (long long)q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, (long long)d_rows, ppw, n_groups, (int)n_gb,
+                       scores, (long long)ld);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "i8_scores_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_i8_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int8_t *codes, float *scales,
+                        void *stream) {
+    const char *who = "msim_i8_encode_docs";
+    if (n_d < 0 || n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (n_d=%d rows=%lld)", who, n_d, (long long)n_rows);
+    if (int rc = i8_check_rows(who, dtype, dim)) return rc;
+    if (n_d == 0) return MSIM_OK;
+    if ((!D && n_rows > 0) || !d_off || (!codes && n_rows > 0) || !scales) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(D, 16) || misaligned(codes, 16) || misaligned(d_off, 4) || misaligned(scales, 4))
+        return fail(MSIM_EINVAL, "%s: rows and codes must be 16-byte aligned, offsets and scales 4-byte aligned", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::i8_encode_docs_kernel<true> : msim::i8_encode_docs_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_d), dim3(256), 0, st, static_cast<const uint16_t *>(D), d_off, n_d, (long long)n_rows, codes,
+                       scales);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "i8_encode_docs_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_i8_encode_queries(int dtype, const void *Qt, int64_t n_rows, int dim, int8_t *codes, float *scales, void *stream) {
+    const char *who = "msim_i8_encode_queries";
+    if (n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (rows=%lld)", who, (long long)n_rows);
+    if (int rc = i8_check_rows(who, dtype, dim)) return rc;
+    if (n_rows == 0) return MSIM_OK;
+    if (!Qt || !codes || !scales) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(codes, 16) || misaligned(scales, 4))
+        return fail(MSIM_EINVAL, "%s: rows and codes must be 16-byte aligned, scales 4-byte aligned", who);
+    if ((n_rows + 15) / 16 > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld rows exceed one launch", who, (long long)n_rows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::i8_encode_rows_kernel<true> : msim::i8_encode_rows_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n_rows + 15) / 16)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), (long long)n_rows,
+                       codes, scales);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "i8_encode_rows_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, const int8_t *d8,
+                   const float *sd, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int dim, float *scores,
+                   int64_t ld_scores, void *stream) {
+    const char *who = "msim_i8_scores";
+    if (n_q < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d,
+                    (long long)q_rows, (long long)d_rows, max_q_tokens);
+    if (dim != msim::kDim) return fail(MSIM_EINVAL, "%s: rows of width %d; the int8 index takes width %d", who, dim, msim::kDim);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if ((!q8 && q_rows > 0) || (!sq && q_rows > 0) || !q_off || (!d8 && d_rows > 0) || !sd || !d_off || !scores)
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(q8, 16) || misaligned(d8, 16) || misaligned(sq, 4) || misaligned(sd, 4) || misaligned(q_off, 4) ||
+        misaligned(d_off, 4) || misaligned(scores, 4))
+        return fail(MSIM_EINVAL, "%s: codes must be 16-byte aligned; scales, offsets and scores 4-byte aligned", who);
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
+    if (max_q_tokens > (1 << 20)) return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, 1 << 20);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the query plan: every query gets TPQ 16-token tiles, QG queries fill one wave's NT tiles; a longer query takes several passes
+    constexpr int NT = 8;
+    const int tiles = max_q_tokens ? (max_q_tokens + msim::kI8Tile - 1) / msim::kI8Tile : 1;
+    int QG = 1, TPQ = NT, passes = 1;
+    if (tiles <= NT) {
+        TPQ = tiles;
+        QG = NT / tiles;
+    } else {
+        passes = (tiles + NT - 1) / NT;
+    }
+    const long long n_groups = ((long long)n_q + QG - 1) / QG;
+    // page ranges: enough waves to fill the chip (8 per CU, ~4 rounds); at most 16 pages a range when several query groups re-read it
+    const long long want = (long long)di->cus * 32;
+    const long long work = n_groups * n_d;
+    const int cap = n_groups == 1 ? msim::kI8MaxRange : 16;
+    long long ppw = (work + want - 1) / want;
+    ppw = ppw < 1 ? 1 : ppw > cap ? cap : ppw;
+    if (n_groups == 1)
+        return i8_scores_launch<NT, 1, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw, 1,
+                                          scores, ld_scores, st);
+    if (n_groups == 2)
+        return i8_scores_launch<NT, 2, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw, 2,
+                                          scores, ld_scores, st);
+    return i8_scores_launch<NT, 4, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw,
+                                      (int)n_groups, scores, ld_scores, st);
 }
 
 }  // extern "C"

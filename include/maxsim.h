@@ -536,6 +536,37 @@ int msim_fde_encode_queries(int dtype, const void *Qt, const int32_t *q_off, int
 int msim_fde_scores(int dtype, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld_scores,
                     void *stream);
 
+/*
+ * INT8 TOKEN-LEVEL INDEX (int8_index.hip): an int8 copy of a packed corpus, scored token by token on int8 MFMAs -- a first stage
+ * for two-stage search that keeps MaxSim's structure, reranked exactly by msim_fwd_candidates.  All arithmetic is IEEE fp32 on the
+ * bf16 / f16 values; division is correctly rounded; rint rounds half to even.
+ *   Pages (msim_i8_encode_docs): page c with a_c = max |x| over its rows and columns, inv = 127.0f / a_c, per element
+ *     d8 = (x == 0) ? 0 : clamp(rint(x * inv), -127, 127), scale sd_c = a_c / 127.0f.  A page with a_c = 0 gets codes 0 and scale
+ *     0 (the x == 0 rule is the formula wherever inv is finite; it also fixes the codes of a page whose a_c is so small that inv
+ *     overflows to +inf: zeros stay 0, everything else becomes +-127).  Codes int8 [n_rows, 128] at the rows of the input (row r
+ *     of the corpus is row r of the codes); scales fp32 [n_d].  A page whose offsets fall outside 0 .. n_rows gets a NaN scale and
+ *     no codes.
+ *   Queries (msim_i8_encode_queries): every token row i of the flat layout is quantized the same way with its own row max:
+ *     codes q8 [n_rows, 128], scales sq [n_rows].
+ *   Score (msim_i8_scores): I_ij = sum_k q8_ik d8_jk (exact int32); M_ic = max_j I_ij, then max(M_ic, 0) where clamp0[c] is set;
+ *     scores[q, c] = fl32(sd_c * T), T = the SEQUENTIAL fp32 sum in token order of fl32(float(M_ic) * sq_i) (no fused multiply-add).
+ *     A page of 0 rows scores -inf; a query of 0 tokens scores 0 against every other page.  A score's bits depend on its query and
+ *     page only (not on the batch, the tiling or a rerun).  max_q_tokens: the caller's upper bound on every query's token
+ *     count, from which the launch plan gives each query Q = 16 * ceil(max_q_tokens / 16) token slots (rounded up to a multiple of
+ *     128 above 128).  A query longer than Q, or with offsets outside 0 .. q_rows, scores NaN; a query within Q but above
+ *     max_q_tokens is scored normally.  When a page's offsets fall outside 0 .. d_rows, every page scored by the same wave (a range
+ *     of at most 63 consecutive pages) scores NaN.  clamp0: uint8 [n_d] or NULL.  scores fp32 [n_q, ld_scores], ld_scores >= n_d.  No workspace.
+ * Width 128 only (MSIM_EINVAL otherwise); bf16 / f16 inputs (MSIM_EUNSUPPORTED otherwise).  Codes 16-byte aligned, offsets,
+ * scales and scores 4-byte aligned.  A call with nothing to do returns 0 before it looks at a pointer.  Asynchronous on `stream`,
+ * no allocation, no host synchronisation: hipGraph-capturable.
+ */
+int msim_i8_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim,
+                        int8_t *codes, float *scales, void *stream);
+int msim_i8_encode_queries(int dtype, const void *Qt, int64_t n_rows, int dim, int8_t *codes, float *scales, void *stream);
+int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                   const int8_t *d8, const float *sd, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                   int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
