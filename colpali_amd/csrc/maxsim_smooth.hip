@@ -365,6 +365,28 @@ __device__ __forceinline__ float round_finite(float x) {
     }
 }
 
+// fp16 weights only.  w = g[p] * exp(..) is split into an fp16 head and remainder, and fp16 has 5 exponent bits: |w| below 2^-14 loses
+// mantissa, below 2^-25 everything, above 65504 it is inf.  So the owner's pair list is normalised by the power of two at its largest
+// |g| (exact), the weights are formed and split in [0, 2), and the power of two is put back in fp32 at the store (exact): the result
+// is linear in the scale of g.  bf16 (fp32's exponent range) and fp32 do not need it and do not pay for it.
+__device__ __forceinline__ void g_pow2_scale(float gmax, float &norm, float &denorm) {
+    uint32_t e = (__float_as_uint(gmax) >> 23) & 0xffu;
+    norm = denorm = 1.0f;                                   // all g zero / subnormal / not finite: leave them alone
+    if (e >= 1 && e <= 254) {
+        e = e > 253 ? 253 : e;                              // keep 2^(127 - e) a normal number
+        norm = __uint_as_float((254u - e) << 23);
+        denorm = __uint_as_float(e << 23);
+    }
+}
+// the largest |g| of the list range [lo, hi) (through `order` for the by-document list), the same value in every lane of every wave
+__device__ __forceinline__ float g_range_max(const float *__restrict__ g, const int32_t *__restrict__ order, int lo, int hi, int lane) {
+    float gm = 0.0f;
+    for (int k = lo + lane; k < hi; k += 64) gm = fmaxf(gm, fabsf(g[order ? order[k] : k]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gm = fmaxf(gm, __shfl_xor(gm, o));
+    return gm;
+}
+
 typedef __attribute__((ext_vector_type(2))) int i32x2;
 template <int ES> struct BVec;
 template <> struct BVec<4> { typedef i32x4 type; };
@@ -443,6 +465,9 @@ __global__ __launch_bounds__(DQ ? kSmoothWavesDQ * 64 : kSmoothWavesDD * 64) voi
         p_hi = lower_bound_idx(a.n_pairs, own + 1, doc_of);
     }
 
+    float g_norm = 1.0f, g_denorm = 1.0f;
+    if constexpr (DT == kDtypeF16) g_pow2_scale(g_range_max(g, DQ ? nullptr : order_by_doc, p_lo, p_hi, lane), g_norm, g_denorm);
+
     f32x16 acc2[kSmoothCB];
 #pragma unroll
     for (int cb = 0; cb < kSmoothCB; ++cb) acc2[cb] = f32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -450,7 +475,7 @@ __global__ __launch_bounds__(DQ ? kSmoothWavesDQ * 64 : kSmoothWavesDD * 64) voi
     for (int k = p_lo + split; k < p_hi; k += (DQ ? a.n_split : 1)) {
         const int p = DQ ? k : order_by_doc[k];
         const int oth = DQ ? pairs[2 * p + 1] : pairs[2 * p];      // the other entity: document (DQ) or query (DD)
-        const float gp = g[p];
+        const float gp = DT == kDtypeF16 ? g[p] * g_norm : g[p];
         int oth_len;
         const char *oth_base;
         if constexpr (DQ) {
@@ -570,6 +595,7 @@ __global__ __launch_bounds__(DQ ? kSmoothWavesDQ * 64 : kSmoothWavesDD * 64) voi
                 float x = acc2[cb][r];
 #pragma unroll
                 for (int w2 = 0; w2 < NW - 1; ++w2) x += red[w2][cb][r][lane];
+                if constexpr (DT == kDtypeF16) x *= g_denorm;
                 v[cb] = x;
             }
             const int orow_out = acc_row(r, lane);
@@ -634,6 +660,9 @@ __global__ __launch_bounds__(DQ ? kSmoothWavesDQ * 64 : kSmoothWavesDD * 64) voi
         p_hi = lower_bound_idx(a.n_pairs, own + 1, doc_of);
     }
 
+    float g_norm = 1.0f, g_denorm = 1.0f;
+    if constexpr (DT == kDtypeF16) g_pow2_scale(g_range_max(g, DQ ? nullptr : order_by_doc, p_lo, p_hi, lane), g_norm, g_denorm);
+
     // ---- LDS addressing (K1s slab image: logical 16-byte chunk c of row r at chunk c ^ (r & 15))
     const int l16 = lane & 15, l4 = lane >> 4;
     int src_off[4];
@@ -661,7 +690,7 @@ __global__ __launch_bounds__(DQ ? kSmoothWavesDQ * 64 : kSmoothWavesDD * 64) voi
                 if (it_k >= p_hi) return Item{nullptr, nullptr, 0.0f, 0, 0, false};
                 const int p = DQ ? it_k : order_by_doc[it_k];
                 const int oth = DQ ? pairs[2 * p + 1] : pairs[2 * p];
-                info.gp = g[p];
+                info.gp = F16 ? g[p] * g_norm : g[p];
                 info.lse_p = lse + (size_t)p * a.Lq;
                 if constexpr (DQ) {
                     info.len = d_off[oth + 1] - d_off[oth];
@@ -798,6 +827,7 @@ __global__ __launch_bounds__(DQ ? kSmoothWavesDQ * 64 : kSmoothWavesDD * 64) voi
                 float x = acc2[cb][r];
 #pragma unroll
                 for (int w2 = 0; w2 < NW - 1; ++w2) x += red[w2][cb][r][lane];
+                if constexpr (DT == kDtypeF16) x *= g_denorm;
                 v[cb] = x;
             }
             const int orow_out = acc_row(r, lane);

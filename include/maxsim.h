@@ -329,6 +329,18 @@ int msim_pairs_bwd(int dtype, const void *Q, int n_q, int Lq,
  * Same conventions as msim_pairs_bwd (pairs sorted by query, order_by_doc, full overwrite, deterministic, no atomics).
  * The dQ pass splits a query's pair list over several workgroups and sums their partial results in a fixed order: it
  * needs msim_smooth_bwd_workspace_bytes(n_q, Lq, dim) bytes of scratch (16-byte aligned; 0 = none needed).
+ *
+ * A document without rows (d_off[c + 1] == d_off[c]): its score and every lse[p, i] of its pairs are -inf (the logsumexp over
+ * nothing, as torch.logsumexp gives it).  msim_smooth_pairs_bwd accepts such pairs with that lse: they contribute nothing, and the
+ * gradients of every other pair in the list are finite and unchanged.
+ * A pair with an index out of range (q outside [0, n_q) or c outside [0, n_d)) is a caller error: msim_smooth_pairs skips it and
+ * leaves out_scores[p] and out_lse[p, :] untouched, every other pair is computed as usual.  msim_smooth_pairs_bwd does NOT check:
+ * every pair handed to it must be in range.
+ * Range of g: any finite fp32 values, for every dtype.  The result is linear in the scale of g up to fp32 rounding: for fp16
+ * embeddings the weights g[p] * w are normalised by the power of two at the largest |g| of each query's (dQ) / document's (dD) pair
+ * list before they are split into fp16 pieces, so neither a tiny g (loss weights, gradient accumulation) nor a large one (an fp16
+ * GradScaler) leaves fp16's exponent range; within one such list a weight more than 2^-24 below the largest |g| is lost, as it is
+ * against fp32 accumulation anyway.  bf16 and fp32 embeddings use g as it is.
  */
 int msim_smooth_fwd(int dtype, const void *Q, int n_q, int Lq,
                     const void *D, const int32_t *d_off, int n_d, int dim, float tau,

@@ -155,3 +155,72 @@ def pairs_bwd_truth(Q, D, d_off, pairs, g, argmax, chunk=1 << 15):
         dQ.index_add_(0, b[sl] * Lq + i[sl], w * D[row[sl]])
         dD.index_add_(0, row[sl], w * Q[b[sl], i[sl]])
     return dQ.view(n_q, Lq, dim), dD
+
+
+def _smooth_operands(Q, D, d_off, pairs):
+    import torch
+
+    Q, D = torch.as_tensor(Q).double(), torch.as_tensor(D).double()
+    off = torch.as_tensor(d_off).cpu().long().tolist()
+    pr = torch.as_tensor(pairs).cpu().long().view(-1, 2).tolist()
+    return Q, D, off, pr
+
+
+def _pair_chunks(pr, off, Lq, budget):
+    """Runs of consecutive pairs whose documents have one length (one batched product each), at most `budget` similarities per run."""
+    s = 0
+    while s < len(pr):
+        n = off[pr[s][1] + 1] - off[pr[s][1]]
+        e = s + 1
+        while e < len(pr) and off[pr[e][1] + 1] - off[pr[e][1]] == n and (e - s + 1) * Lq * max(n, 1) <= budget:
+            e += 1
+        yield s, e, n
+        s = e
+
+
+def smooth_truth(Q, D, d_off, pairs, tau, budget=1 << 22):
+    """float64 (scores [n_pairs], lse [n_pairs, Lq]) of msim_smooth_pairs' contract (include/maxsim.h):
+        lse[p, i] = log sum_{j < len(c_p)} exp(<Q[q_p, i], D[d_off[c_p] + j]> / tau),    scores[p] = sum_i tau * lse[p, i]
+    on a ragged packed corpus; a document without rows gives -inf (torch.logsumexp over nothing).  Runs on the device of Q."""
+    import torch
+
+    Q, D, off, pr = _smooth_operands(Q, D, d_off, pairs)
+    Lq = Q.shape[1]
+    lse = torch.empty(len(pr), Lq, dtype=torch.float64, device=Q.device)
+    for s, e, n in _pair_chunks(pr, off, Lq, budget):
+        qi = torch.tensor([p[0] for p in pr[s:e]], device=Q.device)
+        rows = torch.tensor([off[p[1]] for p in pr[s:e]], device=Q.device).unsqueeze(1) + torch.arange(n, device=Q.device)
+        S = torch.einsum("pid,pjd->pij", Q[qi], D[rows]) / tau
+        lse[s:e] = torch.logsumexp(S, dim=2)
+    return tau * lse.sum(1), lse
+
+
+def smooth_bwd_truth(Q, D, d_off, pairs, g, tau, budget=1 << 22):
+    """float64 (dQ [n_q, Lq, dim], dD [rows, dim], AQ, AD) of msim_smooth_pairs_bwd's contract (include/maxsim.h):
+        w[p, i, j] = exp(<Q[q_p, i], D[j]> / tau - lse[p, i])
+        dQ[q, i]          = sum_{p: q_p = q} g[p] sum_j w[p, i, j] D[d_off[c_p] + j]
+        dD[d_off[c] + j]  = sum_{p: c_p = c} g[p] sum_i w[p, i, j] Q[q_p, i]
+    AQ / AD are the same sums over absolute values (sum |g| w |x|): the scale a rounding error of the weights is measured against.
+    Runs on the device of Q."""
+    import torch
+
+    Q, D, off, pr = _smooth_operands(Q, D, d_off, pairs)
+    gg = torch.as_tensor(g).double().to(Q.device)
+    n_q, Lq, dim = Q.shape
+    dev = Q.device
+    out = [torch.zeros(n_q, Lq, dim, dtype=torch.float64, device=dev), torch.zeros(D.shape[0], dim, dtype=torch.float64, device=dev),
+           torch.zeros(n_q, Lq, dim, dtype=torch.float64, device=dev), torch.zeros(D.shape[0], dim, dtype=torch.float64, device=dev)]
+    for s, e, n in _pair_chunks(pr, off, Lq, budget):
+        if n == 0:
+            continue
+        qi = torch.tensor([p[0] for p in pr[s:e]], device=dev)
+        rows = torch.tensor([off[p[1]] for p in pr[s:e]], device=dev).unsqueeze(1) + torch.arange(n, device=dev)
+        q, d = Q[qi], D[rows]
+        S = torch.einsum("pid,pjd->pij", q, d) / tau
+        w = torch.exp(S - torch.logsumexp(S, dim=2, keepdim=True))
+        gw, aw = gg[s:e].view(-1, 1, 1) * w, gg[s:e].abs().view(-1, 1, 1) * w
+        out[0].index_add_(0, qi, torch.einsum("pij,pjd->pid", gw, d))
+        out[2].index_add_(0, qi, torch.einsum("pij,pjd->pid", aw, d.abs()))
+        out[1].index_add_(0, rows.reshape(-1), torch.einsum("pij,pid->pjd", gw, q).reshape(-1, dim))
+        out[3].index_add_(0, rows.reshape(-1), torch.einsum("pij,pid->pjd", aw, q.abs()).reshape(-1, dim))
+    return tuple(out)

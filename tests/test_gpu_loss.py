@@ -490,6 +490,32 @@ def test_config5_full_shape_loss_and_grads(amd, offset, cls, kind, dtype):
         assert (d.grad.float().abs().sum(dim=(1, 2)) > 0).sum().item() <= 2 * Q.shape[0]
 
 
+@pytest.mark.parametrize("cls,kind", [("ColbertPairwiseCELoss", "pairwise"), ("ColbertLoss", "infonce")])
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_config5_full_shape_smooth_max_loss_and_grads(amd, cls, kind, dtype):
+    """The smooth-max twin of test_config5_full_shape_loss_and_grads (same inputs, same tolerances): use_smooth_max=True at
+    32 x 256 x 32 x 780, where the dQ pass splits every query's 256-pair list and the pair forward strides its grid."""
+    offset = 96
+    Q, D = _config5_inputs(offset)
+    Qx, Dx = Q.to(dtype), D.to(dtype)
+    kw = dict(normalize_scores=False) if kind == "pairwise" else dict()
+    want_loss, want_dq, want_dd = lo.loss_and_grads(kind, Qx.float(), Dx.float(), offset=offset, use_smooth_max=True, tau=0.1, **kw)
+    q, d = Qx.cuda().requires_grad_(True), Dx.cuda().requires_grad_(True)
+    loss = getattr(amd, cls)(use_smooth_max=True, tau=0.1, **kw)(query_embeddings=q, doc_embeddings=d, offset=offset)
+    assert loss.dtype == dtype and loss.dim() == 0
+    loss.backward()
+    # every row takes part in a logsumexp (zero padding rows contribute exp(0)): no mask
+    if dtype == torch.float32:
+        assert abs(float(loss.detach()) - float(want_loss)) <= 1e-5 * abs(float(want_loss)) + 1e-6
+        for got, want in ((q.grad, want_dq), (d.grad, want_dd)):
+            bad = (got.cpu().double() - want).abs() > 1e-4 * want.abs() + 1e-6
+            assert int(bad.sum()) == 0
+    else:
+        assert abs(float(loss.detach()) - float(want_loss)) <= 2.0**-8 * abs(float(want_loss)) + 1e-6
+        assert grads_close(q.grad, want_dq)
+        assert grads_close(d.grad, want_dd)
+
+
 def test_positional_three_argument_call_of_the_evaluation_path(amd):
     """trainer/contrastive_trainer.py:221-224: prediction_step calls loss_func(query, doc, neg_doc) / loss_func(query, doc)
     positionally, without `offset`."""
