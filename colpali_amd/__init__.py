@@ -19,6 +19,7 @@ from . import loss
 from .embed import CorpusWriter, embedding_head
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .int8_index import Int8Index, int8_scores, quantize_queries
+from .live import LiveCorpus
 from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPairwiseCELoss,
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
@@ -40,6 +41,7 @@ __all__ = [
     "Int8Index",
     "int8_scores",
     "quantize_queries",
+    "LiveCorpus",
     "ColbertLoss",
     "ColbertModule",
     "ColbertNegativeCELoss",

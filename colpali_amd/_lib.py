@@ -173,6 +173,12 @@ def lib() -> ctypes.CDLL:
     L.msim_i8_encode_queries.restype = i32
     L.msim_i8_scores.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp]
     L.msim_i8_scores.restype = i32
+    L.msim_live_compact_workspace_bytes.argtypes = [i32, i64]
+    L.msim_live_compact_workspace_bytes.restype = sz
+    L.msim_live_compact.argtypes = [vp, i64, i64, vp, vp, i32, vp, vp, vp, i64, vp]
+    L.msim_live_compact.restype = i32
+    L.msim_live_mask_scores.argtypes = [vp, i64, i32, i64, vp, vp]
+    L.msim_live_mask_scores.restype = i32
     L.msim_topk_workspace_bytes.argtypes = [i32, i64, i32]
     L.msim_topk_workspace_bytes.restype = sz
     L.msim_topk_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]

@@ -33,6 +33,7 @@
 #include "maxsim_candidates.hip"
 #include "fde.hip"
 #include "int8_index.hip"
+#include "live_corpus.hip"
 
 namespace {
 
@@ -2791,6 +2792,120 @@ int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int 
                                           scores, ld_scores, st);
     return i8_scores_launch<NT, 4, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw,
                                       (int)n_groups, scores, ld_scores, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the live corpus (live_corpus.hip)
+namespace {
+
+constexpr int64_t kLiveMaxRowBytes = 65536;
+constexpr int64_t kLiveMaxChunks = 1 << 16;          // two launches per chunk: a bounce buffer of a few rows is for small corpora
+
+struct LiveWorkspace {
+    size_t old_off, tile_sum, tile_base, total;
+    int n_tiles;
+};
+
+LiveWorkspace live_workspace(int n_slots) {
+    LiveWorkspace w;
+    w.n_tiles = (n_slots + msim::kLiveTile - 1) / msim::kLiveTile;
+    w.old_off = up16(msim::kLiveHeaderWords * sizeof(int32_t));
+    w.tile_sum = w.old_off + up16(((size_t)n_slots + 1) * sizeof(int32_t));
+    w.tile_base = w.tile_sum + up16((size_t)w.n_tiles * sizeof(long long));
+    w.total = w.tile_base + up16((size_t)w.n_tiles * sizeof(long long));
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t msim_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes) {
+    (void)bounce_bytes;                                // the bounce buffer is the caller's; the workspace holds the slot tables only
+    if (n_slots <= 0) return 0;
+    return live_workspace(n_slots).total;
+}
+
+int msim_live_compact(void *rows, int64_t row_bytes, int64_t rows_bound, int32_t *off, const uint8_t *alive, int n_slots,
+                      int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream) {
+    const char *who = "msim_live_compact";
+    if (n_slots < 0 || rows_bound < 0 || bounce_bytes < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_slots=%d rows_bound=%lld bounce_bytes=%lld)", who, n_slots, (long long)rows_bound,
+                    (long long)bounce_bytes);
+    if (row_bytes <= 0 || row_bytes % 16 != 0)
+        return fail(MSIM_EINVAL, "%s: row_bytes=%lld must be a positive multiple of 16", who, (long long)row_bytes);
+    if (row_bytes > kLiveMaxRowBytes)
+        return fail(MSIM_EUNSUPPORTED, "%s: rows of %lld bytes (at most %lld)", who, (long long)row_bytes, (long long)kLiveMaxRowBytes);
+    if (rows_bound > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: rows_bound=%lld above 2^31 - 1", who, (long long)rows_bound);
+    if (n_slots == 0) return MSIM_OK;
+    if (!off || !alive || !rows_used_out || !workspace || (!rows && rows_bound > 0) || (!bounce && rows_bound > 0))
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(rows, 16) || misaligned(bounce, 16) || misaligned(workspace, 16) || misaligned(off, 4) || misaligned(rows_used_out, 8))
+        return fail(MSIM_EINVAL, "%s: rows, bounce and workspace must be 16-byte aligned, off 4-byte and rows_used_out 8-byte aligned", who);
+    if (rows_bound > 0 && bounce_bytes < row_bytes)
+        return fail(MSIM_EINVAL, "%s: a bounce buffer of %lld bytes holds no row of %lld bytes", who, (long long)bounce_bytes,
+                    (long long)row_bytes);
+    int64_t chunk_rows = rows_bound > 0 ? bounce_bytes / row_bytes : 1;
+    if (chunk_rows > (1 << 30)) chunk_rows = 1 << 30;
+    const int64_t n_chunks = (rows_bound + chunk_rows - 1) / chunk_rows;
+    if (n_chunks > kLiveMaxChunks)
+        return fail(MSIM_EUNSUPPORTED, "%s: %lld rows through a bounce buffer of %lld rows are %lld chunks (at most %lld)", who,
+                    (long long)rows_bound, (long long)chunk_rows, (long long)n_chunks, (long long)kLiveMaxChunks);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LiveWorkspace w = live_workspace(n_slots);
+    char *ws = static_cast<char *>(workspace);
+    int32_t *hdr = reinterpret_cast<int32_t *>(ws);
+    int32_t *old_off = reinterpret_cast<int32_t *>(ws + w.old_off);
+    long long *tile_sum = reinterpret_cast<long long *>(ws + w.tile_sum);
+    long long *tile_base = reinterpret_cast<long long *>(ws + w.tile_base);
+    hipLaunchKernelGGL(msim::live_reset_kernel, dim3(1), dim3(64), 0, st, hdr);
+    hipLaunchKernelGGL(msim::live_lens_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots,
+                       (long long)rows_bound, hdr, old_off, tile_sum);
+    hipLaunchKernelGGL(msim::live_scan_kernel, dim3(1), dim3(msim::kLiveTile), 0, st, w.n_tiles, n_slots, (long long)rows_bound, hdr,
+                       old_off, tile_sum, tile_base, reinterpret_cast<long long *>(rows_used_out));
+    hipLaunchKernelGGL(msim::live_apply_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots, hdr, old_off,
+                       tile_base);
+    int block_rows = (int)(msim::kLiveBlockBytes / row_bytes);
+    block_rows = block_rows < 1 ? 1 : block_rows > msim::kLiveMaxBlockRows ? msim::kLiveMaxBlockRows : block_rows;
+    const int lpr = (int)(row_bytes / 16);
+    for (int64_t k = 0; k < n_chunks; ++k) {
+        const long long chunk0 = k * chunk_rows;
+        const int rows_here = (int)(rows_bound - chunk0 < chunk_rows ? rows_bound - chunk0 : chunk_rows);
+        const unsigned blocks = (unsigned)((rows_here + block_rows - 1) / block_rows);
+        hipLaunchKernelGGL(msim::live_move_kernel<true>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, static_cast<uint8_t *>(rows),
+                           lpr, (long long)rows_bound, off, old_off, n_slots, hdr, static_cast<uint8_t *>(bounce), chunk0, rows_here,
+                           block_rows);
+        hipLaunchKernelGGL(msim::live_move_kernel<false>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, static_cast<uint8_t *>(rows),
+                           lpr, (long long)rows_bound, off, old_off, n_slots, hdr, static_cast<uint8_t *>(bounce), chunk0, rows_here,
+                           block_rows);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "live compaction launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const uint8_t *alive, void *stream) {
+    const char *who = "msim_live_mask_scores";
+    if (n_q < 0 || n < 0) return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld)", who, n_q, (long long)n);
+    if (n_q == 0 || n == 0) return MSIM_OK;
+    if (!scores || !alive) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(scores, 4)) return fail(MSIM_EINVAL, "%s: scores must be 4-byte aligned", who);
+    if (ld < n) return fail(MSIM_EINVAL, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
+    const int64_t tiles = (n + 1023) / 1024;
+    if (tiles > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)n);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int vec_ok = !misaligned(scores, 16) && ld % 4 == 0;
+    const unsigned row_groups = (unsigned)(n_q < 64 ? n_q : 64);
+    hipLaunchKernelGGL(msim::live_mask_kernel, dim3((unsigned)tiles, row_groups), dim3(256), 0, st, scores, (long long)ld, n_q, (long long)n,
+                       alive, vec_ok);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "live_mask_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
 }
 
 }  // extern "C"

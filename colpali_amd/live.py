@@ -1,0 +1,339 @@
+"""A live resident shard: pages are added, deleted and compacted in place, and every search sees the change at once.
+
+`LiveCorpus` owns one row blob with spare capacity, the page offsets, a tombstone mask (`alive`) and, on request, an int8 index
+kept in step.  No scoring kernel changes: every scorer reads page c through `offsets[c] .. offsets[c + 1]`, so
+
+  * `add` appends rows at the tail of the blob and slots at the tail of the offsets (no reallocation, ever);
+  * `delete` clears `alive`; the scores of deleted slots are overwritten with -inf behind the full scan and the int8 stage 1
+    (msim_live_mask_scores), and deleted candidate ids become -1 before the rerank;
+  * `compact` moves the rows of live pages down over the deleted ones (msim_live_compact, colpali_amd/csrc/live_corpus.hip) and turns
+    every deleted slot into an empty page.
+
+A page's id is its slot: `id_base + slot`, assigned in order of arrival, never reused, never renumbered -- the rule every kernel
+and `shard_topk` already follow.  After any history, `search` returns the scores (bit for bit) of a `ShardedRetriever` over
+`pack_passages(surviving pages in slot order, batch_size=None)`, with that corpus' positions mapped back to slots.
+"""
+from __future__ import annotations
+
+from typing import Callable, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .corpus import PackedCorpus, PackedQueries, _staging, _widen, host_list_image, pack_queries
+from .int8_index import DIM as I8_DIM
+from .int8_index import Int8Index, int8_scores
+from .retrieval import ShardedRetriever, rerank_scores, topk
+from .scoring import maxsim_scores
+
+DEFAULT_BOUNCE_BYTES = 256 << 20     # rows a compaction moves per pair of launches (tools/bench_live.py --bounce-mb)
+
+
+def mask_scores(scores: torch.Tensor, alive: torch.Tensor) -> torch.Tensor:
+    """-inf into column c of every row of `scores` (fp32 [n_q, n], on the GPU) where `alive[c] == 0` (uint8 [n]); in place.
+    Asynchronous on torch's current stream, hipGraph-capturable."""
+    if scores.dim() != 2 or scores.dtype != torch.float32 or scores.device.type != "cuda":
+        raise ValueError("scores must be a 2-D fp32 tensor on the GPU (the mask is a gfx950 kernel; there is no CPU fallback)")
+    n_q, n = scores.shape
+    if alive.dtype != torch.uint8 or alive.dim() != 1 or alive.shape[0] < n or alive.device != scores.device or not alive.is_contiguous():
+        raise ValueError(f"alive must be a contiguous uint8 [>= {n}] tensor on {scores.device}")
+    if n > 1 and scores.stride(1) != 1:
+        raise ValueError("scores must have unit inner stride")
+    ld = scores.stride(0) if n_q > 1 else max(n, 1)
+    with torch.cuda.device(scores.device):
+        rc = _lib.lib().msim_live_mask_scores(_lib.ptr(scores), ld, n_q, n, _lib.ptr(alive), _lib.current_stream_handle(scores.device))
+    _lib.check(rc, "msim_live_mask_scores")
+    return scores
+
+
+class LiveCorpus:
+    """One mutable resident shard (see the module docstring).  `capacity_rows` and `capacity_docs` are fixed at construction.
+
+    `score_fn`, `rerank_fn`, `int8_score_fn`, `select` and `mask_fn` are the hooks of `ShardedRetriever` plus the tombstone mask
+    (`mask_fn(scores, alive) -> scores`); the defaults are the gfx950 kernels.  Host-logic tests inject reference scorers and run on the CPU."""
+
+    def __init__(self, capacity_rows: int, capacity_docs: int, device, dtype: torch.dtype = torch.bfloat16, width: int = 128,
+                 id_base: int = 0, *, bounce_bytes: Optional[int] = None, score_fn: Callable = maxsim_scores,
+                 rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, select: Callable = topk,
+                 mask_fn: Callable = mask_scores):
+        capacity_rows, capacity_docs = int(capacity_rows), int(capacity_docs)
+        if capacity_rows < 1 or capacity_docs < 1:
+            raise ValueError("capacity_rows and capacity_docs must be positive")
+        if capacity_rows >= 2**31:
+            raise NotImplementedError("more than 2^31 patch rows in one shard")
+        _lib.dtype_code(dtype)                                   # raises for anything but bf16 / f16 / f32
+        self.device = torch.device(device)
+        self.dtype, self.dim, self.id_base = dtype, int(width), int(id_base)
+        self.width = _lib.kernel_width(self.dim, dtype)          # physical row width (zero columns appended, as pack_passages)
+        self.capacity_rows, self.capacity_docs = capacity_rows, capacity_docs
+        self.blob = torch.zeros((capacity_rows, self.width), dtype=dtype, device=self.device)
+        self.offsets = torch.zeros((capacity_docs + 1,), dtype=torch.int32, device=self.device)
+        self.alive = torch.zeros((capacity_docs + 1,), dtype=torch.uint8, device=self.device)   # [capacity_docs]: where ids outside the corpus land
+        self._lengths = np.zeros((capacity_docs,), dtype=np.int64)   # host: rows each slot owns now (0 once compacted away)
+        self._alive_h = np.zeros((capacity_docs,), dtype=bool)       # host mirror of `alive` (stale while _dirty)
+        self._dirty = False                                          # a device-side delete has not been read back yet
+        self.n_slots = 0
+        self._rows_used = 0
+        self._score_fn, self._rerank_fn, self._int8_score_fn = score_fn, rerank_fn, int8_score_fn
+        self._select, self._mask_fn = select, mask_fn
+        self._i8_codes: Optional[torch.Tensor] = None
+        self._i8_scales: Optional[torch.Tensor] = None
+        self._compactions = 0
+        self._rows_compacted = 0                                     # rows in use right after the last compaction (check())
+        row_bytes = self.width * self.blob.element_size()
+        want = DEFAULT_BOUNCE_BYTES if bounce_bytes is None else int(bounce_bytes)
+        if want < row_bytes:
+            raise ValueError(f"bounce_bytes={want} holds no row of {row_bytes} bytes")
+        self.bounce_bytes = min(want, capacity_rows * row_bytes) // 16 * 16
+        if self.device.type == "cuda":                   # everything a compaction needs exists up front: no allocation later
+            ws_bytes = _lib.lib().msim_live_compact_workspace_bytes(capacity_docs, self.bounce_bytes)
+            self._bounce = torch.empty((self.bounce_bytes,), dtype=torch.uint8, device=self.device)
+            self._ws = [torch.zeros((ws_bytes,), dtype=torch.uint8, device=self.device) for _ in range(2)]   # rows, int8 codes
+            self._rows_used_dev = torch.zeros((2,), dtype=torch.int64, device=self.device)
+            self._off_tmp = torch.zeros((capacity_docs + 1,), dtype=torch.int32, device=self.device)
+
+    # ------------------------------------------------------------------------------------------------------------ construction
+    @classmethod
+    def from_packed(cls, corpus: PackedCorpus, spare_rows: int, spare_docs: int, **kw) -> "LiveCorpus":
+        """A live corpus holding the pages of `corpus` (one device copy) plus room for `spare_rows` rows and `spare_docs` pages."""
+        if corpus.clamp0 is not None:
+            raise ValueError("a live corpus has no block zero-padding semantics: pack with batch_size=None (clamp0 must be None)")
+        lens = corpus.lengths.numpy().astype(np.int64)
+        if (lens <= 0).any():
+            raise ValueError("a live corpus holds no page of 0 rows: -inf means 'not there'")
+        n, rows = int(lens.size), int(lens.sum())
+        live = cls(rows + int(spare_rows), n + int(spare_docs), corpus.device, corpus.blob.dtype, int(corpus.blob.shape[1]),
+                   corpus.id_base, **kw)
+        live.blob[:rows].copy_(corpus.blob[:rows])
+        live.offsets[:n + 1].copy_(corpus.offsets)
+        live.alive[:n].fill_(1)
+        live._lengths[:n] = lens
+        live._alive_h[:n] = True
+        live.n_slots, live._rows_used = n, rows
+        return live
+
+    # ------------------------------------------------------------------------------------------------------------------ state
+    def __len__(self) -> int:
+        """Slots handed out so far (live or deleted): the number of documents every view and score matrix has."""
+        return self.n_slots
+
+    @property
+    def rows_used(self) -> int:
+        return self._rows_used
+
+    @property
+    def n_live(self) -> int:
+        self._sync_host()
+        return int(self._alive_h[:self.n_slots].sum())
+
+    def _sync_host(self) -> None:
+        """Read the mask back after a device-side delete (one small D2H and a synchronisation)."""
+        if not self._dirty:
+            return
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a device-side delete is pending: call compact() / add() once outside the capture first")
+        n = self.n_slots
+        self._alive_h[:n] = self.alive[:n].cpu().numpy().astype(bool)
+        self._dirty = False
+
+    def check(self) -> None:
+        """Host-side check of what the device found (synchronises): raises if a compaction met broken offsets, or if its row
+        count differs from the host's."""
+        if self.device.type != "cuda" or not self._compactions:
+            return
+        self._sync_host()
+        status = [int(w[:4].view(torch.int32)[0].item()) for w in self._ws]
+        if any(status):
+            raise _lib.MaxSimLibraryError(f"msim_live_compact found broken offsets (status words {status}): nothing further was moved")
+        got = int(self._rows_used_dev[0].item())
+        if got != self._rows_compacted:
+            raise _lib.MaxSimLibraryError(f"msim_live_compact left {got} rows in use, the host expected {self._rows_compacted}")
+
+    def view(self) -> PackedCorpus:
+        """The used prefix as a `PackedCorpus` (zero-copy slices), valid until the next `add` / `compact`.  Every slot is a
+        document: a deleted one keeps its rows until `compact()` and is an empty document afterwards."""
+        n = self.n_slots
+        return PackedCorpus(blob=self.blob[:max(self._rows_used, 1)], offsets=self.offsets[:n + 1], clamp0=None,
+                            lengths=torch.from_numpy(self._lengths[:n].copy()), id_base=self.id_base)
+
+    # -------------------------------------------------------------------------------------------------------------------- add
+    def add(self, pages: Union[torch.Tensor, Sequence[torch.Tensor]]) -> torch.Tensor:
+        """Append pages; returns their ids (int64, host).  `pages`: a list of [rows_i, width] tensors (host tensors go through
+        the pinned staging upload) or one [n, rows, width] tensor (on the device: rows and offsets are written there, nothing
+        synchronises).  Running out of rows or slots raises RuntimeError and leaves the corpus as it was."""
+        if isinstance(pages, torch.Tensor):
+            if pages.dim() != 3:
+                raise ValueError("a page tensor must be 3-D (n_pages, rows, width)")
+            n, per, dim = (int(s) for s in pages.shape)
+            if n and per == 0:
+                raise ValueError("a page of 0 rows cannot be added: in a live corpus -inf means 'not there'")
+            lens = np.full((n,), per, dtype=np.int64)
+            first = pages
+        else:
+            pages = list(pages)
+            n = len(pages)
+            for p in pages:
+                if p.dim() != 2:
+                    raise ValueError("each page must be 2-D (rows, width)")
+                if p.shape[0] == 0:
+                    raise ValueError("a page of 0 rows cannot be added: in a live corpus -inf means 'not there'")
+            lens = np.fromiter((p.shape[0] for p in pages), dtype=np.int64, count=n)
+            first = pages[0] if n else None
+            dim = int(first.shape[1]) if n else self.dim
+            for p in pages:
+                if p.dtype != first.dtype or p.shape[1] != dim:
+                    raise RuntimeError("expected pages of one dtype and one embedding width")
+        if n == 0:
+            return torch.empty((0,), dtype=torch.int64)
+        if first.dtype != self.dtype or dim not in (self.dim, self.width):
+            raise RuntimeError(f"this corpus holds {self.dtype} pages of width {self.dim}, got {first.dtype} of width {dim}")
+        self._sync_host()
+        total, n0, r0 = int(lens.sum()), self.n_slots, self._rows_used
+        if n0 + n > self.capacity_docs:
+            raise RuntimeError(f"live corpus is full: {n0} of capacity_docs={self.capacity_docs} slots are taken, {n} more were asked for")
+        if r0 + total > self.capacity_rows:
+            raise RuntimeError(f"live corpus is full: {r0} of capacity_rows={self.capacity_rows} rows are in use, {total} more were "
+                               "asked for (compact() hands back the rows of deleted pages)")
+        dst = self.blob[r0:r0 + total]
+        if isinstance(pages, torch.Tensor):
+            src = pages.reshape(total, dim).to(self.device, non_blocking=True)
+            dst[:, :dim].copy_(src)
+            if dim < self.width:
+                dst[:, dim:].zero_()
+            ends = torch.arange(1, n + 1, dtype=torch.int32, device=self.device) * int(lens[0]) + self.offsets[n0]
+            self.offsets[n0 + 1:n0 + n + 1].copy_(ends)
+        else:
+            image = host_list_image(pages, "pages") if self.device.type == "cuda" and dim == self.width else None
+            if image is not None:
+                keep, srcs, rows, _, _ = image
+                prefix = np.zeros(n + 1, dtype=np.int64)
+                np.cumsum(rows * (dim * first.element_size()), out=prefix[1:])
+                _staging.of(self.device).upload_image(srcs, prefix, n, dst.view(torch.uint8).view(-1),
+                                                      torch.cuda.current_stream(self.device))
+                del keep
+            else:
+                dst.copy_(_widen(torch.cat([p.to(self.device) for p in pages], dim=0)))
+            ends = torch.from_numpy((r0 + np.cumsum(lens)).astype(np.int32))
+            self.offsets[n0 + 1:n0 + n + 1].copy_(ends)
+        self.alive[n0:n0 + n].fill_(1)
+        self._lengths[n0:n0 + n] = lens
+        self._alive_h[n0:n0 + n] = True
+        self.n_slots, self._rows_used = n0 + n, r0 + total
+        if self._i8_codes is not None:
+            self._encode_i8(n0, n0 + n)
+        return torch.arange(self.id_base + n0, self.id_base + n0 + n, dtype=torch.int64)
+
+    # ----------------------------------------------------------------------------------------------------------------- delete
+    def delete(self, ids) -> None:
+        """Clear `alive` for `ids`; every search sees it at once, the rows stay until `compact()`.  A host list (or host tensor):
+        unknown, out-of-range or already-deleted ids raise KeyError and nothing is deleted.  An int64 tensor on the device is
+        applied without a synchronisation and ids outside the corpus are ignored."""
+        if isinstance(ids, torch.Tensor) and ids.device.type != "cpu":
+            if ids.dtype != torch.int64 or ids.device != self.device:
+                raise ValueError(f"device ids must be an int64 tensor on {self.device}")
+            idx = ids.reshape(-1) - self.id_base
+            idx = torch.where((idx >= 0) & (idx < self.n_slots), idx, torch.full_like(idx, self.capacity_docs))
+            self.alive.index_fill_(0, idx, 0)
+            self._dirty = True
+            return
+        slots = [int(i) - self.id_base for i in (ids.tolist() if isinstance(ids, torch.Tensor) else ids)]
+        self._sync_host()
+        seen = set()
+        for s in slots:
+            if not (0 <= s < self.n_slots) or not self._alive_h[s] or s in seen:
+                raise KeyError(s + self.id_base)
+            seen.add(s)
+        if not slots:
+            return
+        self._alive_h[slots] = False
+        self.alive.index_fill_(0, torch.tensor(slots, dtype=torch.int64).to(self.device), 0)
+
+    # ---------------------------------------------------------------------------------------------------------------- compact
+    def compact(self) -> None:
+        """Move the rows of live pages down over the rows of deleted ones, in place and in slot order; a deleted slot becomes an
+        empty document; slots (ids) do not move.  Asynchronous on torch's current stream, no allocation in the library call.
+        (After a device-side `delete` the mask is read back first: one small D2H and a synchronisation.)"""
+        self._sync_host()
+        n = self.n_slots
+        dead = ~self._alive_h[:n] & (self._lengths[:n] > 0)
+        if not dead.any():
+            return
+        if self.device.type != "cuda":
+            raise RuntimeError("compaction is a gfx950 kernel (msim_live_compact): this corpus lives on " + str(self.device))
+        bound = self._rows_used
+        if self._i8_codes is not None:                   # the same moves on the code rows, against a copy of the old offsets
+            self._off_tmp[:n + 1].copy_(self.offsets[:n + 1])
+            self._compact_rows(self._i8_codes, I8_DIM, bound, self._off_tmp, 1)
+            self._i8_scales[:n].masked_fill_(self.alive[:n] == 0, 0.0)      # an empty page has scale 0 (msim_i8_encode_docs)
+        self._compact_rows(self.blob, self.width * self.blob.element_size(), bound, self.offsets, 0)
+        self._lengths[:n][dead] = 0
+        self._rows_used = self._rows_compacted = int(self._lengths[:n].sum())
+        self._compactions += 1
+
+    def _compact_rows(self, rows: torch.Tensor, row_bytes: int, bound: int, offsets: torch.Tensor, which: int) -> None:
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().msim_live_compact(_lib.ptr(rows), row_bytes, bound, _lib.ptr(offsets), _lib.ptr(self.alive), self.n_slots,
+                                              _lib.ptr(self._rows_used_dev[which:]), _lib.ptr(self._ws[which]), _lib.ptr(self._bounce),
+                                              self.bounce_bytes, _lib.current_stream_handle(self.device))
+        _lib.check(rc, "msim_live_compact")
+
+    # ------------------------------------------------------------------------------------------------------------- int8 index
+    def _encode_i8(self, lo: int, hi: int, chunk_docs: int = 65536) -> None:
+        L = _lib.lib()
+        with torch.cuda.device(self.device):
+            for a in range(lo, hi, chunk_docs):
+                b = min(hi, a + chunk_docs)
+                rc = L.msim_i8_encode_docs(_lib.dtype_code(self.dtype), _lib.ptr(self.blob), _lib.ptr(self.offsets[a:]), b - a,
+                                           self._rows_used, I8_DIM, _lib.ptr(self._i8_codes), _lib.ptr(self._i8_scales[a:]),
+                                           _lib.current_stream_handle(self.device))
+                _lib.check(rc, "msim_i8_encode_docs")
+
+    def int8_index(self) -> Int8Index:
+        """The int8 token-level index of this corpus, kept in step from the first call on: `add` encodes the new pages only,
+        `compact` moves the code rows as it moves the embedding rows.  Its bits equal `Int8Index.build(self.view())`.  Like
+        `view()`, the returned object is valid until the next `add` / `compact`."""
+        if self._i8_codes is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("the int8 index is built by gfx950 kernels: this corpus lives on " + str(self.device))
+            if self.dtype not in (torch.bfloat16, torch.float16) or self.width != I8_DIM:
+                raise NotImplementedError(f"the int8 index takes bfloat16 / float16 pages of width {I8_DIM} "
+                                          f"(got {self.dtype}, width {self.width})")
+            self._i8_codes = torch.zeros((self.capacity_rows, I8_DIM), dtype=torch.int8, device=self.device)
+            self._i8_scales = torch.zeros((self.capacity_docs,), dtype=torch.float32, device=self.device)
+            self._encode_i8(0, self.n_slots)
+        n = self.n_slots
+        return Int8Index(self._i8_codes[:max(self._rows_used, 1)], self._i8_scales[:n], self.offsets[:n + 1], None,
+                         torch.from_numpy(self._lengths[:n].copy()), self.id_base)
+
+    # ----------------------------------------------------------------------------------------------------------------- search
+    def _masked(self, scores: torch.Tensor) -> torch.Tensor:
+        return self._mask_fn(scores, self.alive[:self.n_slots])
+
+    def _score(self, queries, corpus):
+        return self._masked(self._score_fn(queries, corpus))
+
+    def _int8_score(self, queries, index):
+        return self._masked(self._int8_score_fn(queries, index))
+
+    def _rerank(self, queries, corpus, candidates):
+        n = self.n_slots
+        idx = candidates - self.id_base
+        inside = (idx >= 0) & (idx < n)
+        live = self.alive[:max(n, 1)][idx.clamp(0, max(n - 1, 0))] != 0
+        return self._rerank_fn(queries, corpus, torch.where(inside & live, candidates, torch.full_like(candidates, -1)))
+
+    def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None, prefilter=None,
+               n_candidates: Optional[int] = None, world: int = 1, rank: int = 0, dist=None,
+               group=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`ShardedRetriever.search` over the live pages: the same arguments, rules and return value; a deleted page is never
+        returned, and where fewer than `k` live pages exist the tail is (-inf, -1).  `prefilter` is `self.int8_index()`, or a
+        `PackedCorpus` over the same slots (e.g. pooled pages; its deleted slots are masked too)."""
+        shard = self.view()
+        if self.device.type == "cuda" and not isinstance(queries, PackedQueries):     # an injected hook packs host queries itself
+            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+            queries = pack_queries(queries, self.device, compact=compact or not dense_on_device)
+        r = ShardedRetriever(shard, world, rank, dist, group, score_fn=self._score, select=self._select, rerank_fn=self._rerank,
+                             int8_score_fn=self._int8_score)
+        scores, ids = r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates)
+        return scores, torch.where(scores == float("-inf"), torch.full_like(ids, -1), ids)   # a deleted slot that filled a short row

@@ -579,6 +579,36 @@ int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int 
                    const int8_t *d8, const float *sd, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
                    int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
+/*
+ * LIVE CORPUS (live_corpus.hip; additions to ABI 22): a packed corpus whose pages can be deleted and whose rows can be handed
+ * back, without a change to any scorer.  A page's slot c never moves (its id stays id_base + c); `alive` uint8 [n_slots] is the
+ * tombstone mask (0 = deleted).
+ *
+ * msim_live_compact moves the rows of live pages down over the rows of deleted ones, in place and in slot order, and rewrites
+ * off int32 [n_slots + 1] so that a deleted slot becomes an empty page (off[c + 1] == off[c]): new off[c] = the sum of
+ * off[j + 1] - off[j] over the live slots j < c.  Afterwards *rows_used_out (int64, device) = new off[n_slots].  Calling it again
+ * changes nothing.  rows [rows_bound, row_bytes bytes each]: row_bytes a positive multiple of 16 (MSIM_EINVAL otherwise), at most
+ * 65536 (MSIM_EUNSUPPORTED); one call moves rows of any element type (bf16 / f32 embedding rows, int8 code rows).  rows_bound:
+ * rows the array holds at least, off[n_slots] <= rows_bound <= 2^31 - 1; every row index the device derives is checked against it
+ * before it becomes an address.  The rows go through `bounce` (bounce_bytes >= row_bytes, 16-byte aligned, caller-owned) in
+ * chunks of floor(bounce_bytes / row_bytes) destination rows, two stream-ordered launches per chunk (rows -> bounce, bounce ->
+ * rows): a parallel in-place move could overwrite rows another workgroup has not read yet.  Rows below the first deleted page
+ * are neither read nor written.  ceil(rows_bound / chunk rows) must not exceed 65536 (MSIM_EUNSUPPORTED).
+ * workspace: msim_live_compact_workspace_bytes(n_slots, bounce_bytes) bytes, 16-byte aligned; the call initialises it (by a
+ * kernel).  Its first int32 is a status word, valid once the call's work is done: 0 = done; otherwise an invariant was broken
+ * (bit 0: off not non-decreasing from 0 or above rows_bound; bit 1: a derived row outside the array), nothing further was moved
+ * and *rows_used_out = the old off[n_slots].  n_slots == 0 returns 0 before it looks at a pointer.
+ *
+ * msim_live_mask_scores writes -inf into scores[q, c] (fp32 [n_q, ld], ld >= n, 4-byte aligned) for every q where alive[c] == 0,
+ * c < n, and touches nothing else: the mask is read once per column, only columns of deleted slots are written.
+ *
+ * Both are asynchronous on `stream`, allocate nothing, never synchronise with the host and are hipGraph-capturable.
+ */
+size_t msim_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes);
+int msim_live_compact(void *rows, int64_t row_bytes, int64_t rows_bound, int32_t *off, const uint8_t *alive, int n_slots,
+                      int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream);
+int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const uint8_t *alive, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
