@@ -161,6 +161,10 @@ def lib() -> ctypes.CDLL:
     L.msim_fwd_candidates_workspace_bytes.restype = sz
     L.msim_fwd_candidates.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, i64, i64, vp, i64, vp, u32, vp, vp]
     L.msim_fwd_candidates.restype = i32
+    L.msim_fwd_candidates_wide_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.msim_fwd_candidates_wide_workspace_bytes.restype = sz
+    L.msim_fwd_candidates_wide.argtypes = L.msim_fwd_candidates.argtypes
+    L.msim_fwd_candidates_wide.restype = i32
     L.msim_fde_encode_docs.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.msim_fde_encode_docs.restype = i32
     L.msim_fde_encode_queries.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, i32, i32, i32, vp, vp, vp]

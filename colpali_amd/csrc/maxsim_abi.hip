@@ -31,6 +31,7 @@
 #include "loss_epilogue.hip"
 #include "topk_select.hip"
 #include "maxsim_candidates.hip"
+#include "maxsim_candidates_panels.hip"
 #include "fde.hip"
 #include "int8_index.hip"
 #include "live_corpus.hip"
@@ -2495,26 +2496,20 @@ CandLayout cand_layout(int n_q, int m, int n_d) {
     return L;
 }
 
-}  // namespace
+constexpr int kCandWideDim = 320;      // the width msim_fwd_candidates_wide takes: 3 panels, 4 k-steps of 16 in the last
 
-extern "C" {
-
-size_t msim_fwd_candidates_workspace_bytes(int n_q, int m, int n_d) {
-    if (n_q <= 0 || m <= 0 || n_d < 0) return 0;
-    return cand_layout(n_q, m, n_d).total;
-}
-
-int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
-                        const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, const int64_t *cand, int m, int64_t ld_cand,
-                        int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids, unsigned flags, void *workspace,
-                        void *stream) {
+// both entries: `width` = the one row width the entry takes (128: K1c, 320: its panel form K1cP)
+int fwd_candidates(const char *who, int width, int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q,
+                   const void *D, const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, const int64_t *cand, int m,
+                   int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids, unsigned flags,
+                   void *workspace, void *stream) {
     if (n_q < 0 || m < 0 || n_d < 0) return fail(MSIM_EINVAL, "negative size (n_q=%d m=%d n_d=%d)", n_q, m, n_d);
     if (n_q == 0 || m == 0) return MSIM_OK;
     if (!Qt || !q_off || !q_off_host || (!D && n_d > 0) || !d_off || !cand || !out_scores || !workspace)
         return fail(MSIM_EINVAL, "null pointer argument");
-    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || dim != msim::kDim)
-        return fail(MSIM_EUNSUPPORTED, "msim_fwd_candidates takes bfloat16 / float16 embeddings of width %d (dtype code %d, dim %d)",
-                    msim::kDim, dtype, dim);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || dim != width)
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 embeddings of width %d (dtype code %d, dim %d)", who, width, dtype,
+                    dim);
     if ((reinterpret_cast<uintptr_t>(Qt) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(workspace)) & 15)
         return fail(MSIM_EINVAL, "Qt, D and workspace must be 16-byte aligned");
     if (ld_cand < m) return fail(MSIM_EINVAL, "ld_cand=%lld < m=%d", (long long)ld_cand, m);
@@ -2526,7 +2521,7 @@ int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const i
         const int len = q_off_host[i + 1] - q_off_host[i];
         if (len < 0) return fail(MSIM_EINVAL, "q_off must be non-decreasing (query %d)", i);
         if (len > msim::kStreamMaxUnits * msim::kUnitTok)
-            return fail(MSIM_EUNSUPPORTED, "query %d has %d tokens: msim_fwd_candidates takes queries of at most %d", i, len,
+            return fail(MSIM_EUNSUPPORTED, "query %d has %d tokens: %s takes queries of at most %d", i, len, who,
                         msim::kStreamMaxUnits * msim::kUnitTok);
     }
     const DeviceInfo *di = nullptr;
@@ -2561,20 +2556,56 @@ int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const i
                        cnt, rank, estart, istart, n_d, entries, items, status);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "candidate list kernels launch: %s", hipGetErrorString(e));
-    // a persistent grid sized from what the host knows: at most one item per entry, two workgroups per CU
+    // a persistent grid sized from what the host knows: at most one item per entry, as many workgroups per CU as its LDS holds
+    // (K1c: two of 72 KiB; K1cP: one of 136 KiB)
     const bool f16 = dtype == MSIM_DTYPE_F16;
-    auto kern = f16 ? msim::maxsim_candidates_kernel<true, 0> : msim::maxsim_candidates_kernel<false, 0>;
-    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
-    if (int rc = allow_lds(kern, msim::kCandLdsBytes, f16 ? configured_f16 : configured_bf16)) return rc;
+    const bool wide = width != msim::kDim;
+    auto kern = wide ? (f16 ? msim::maxsim_candidates_panels_kernel<3, 4, true, 0> : msim::maxsim_candidates_panels_kernel<3, 4, false, 0>)
+                     : (f16 ? msim::maxsim_candidates_kernel<true, 0> : msim::maxsim_candidates_kernel<false, 0>);
+    const int lds_bytes = wide ? msim::kCandPanelLdsBytes : msim::kCandLdsBytes;
+    static std::atomic<int> configured[2][2][kMaxDevices];
+    if (int rc = allow_lds(kern, lds_bytes, configured[wide][f16])) return rc;
     const long long wg_needed = (E + 3) / 4;
-    const long long wg_cap = (long long)di->cus * (di->lds_per_cu / msim::kCandLdsBytes);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(wg_needed < wg_cap ? wg_needed : wg_cap)), dim3(256), msim::kCandLdsBytes, st,
+    const long long wg_cap = (long long)di->cus * (di->lds_per_cu / lds_bytes);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(wg_needed < wg_cap ? wg_needed : wg_cap)), dim3(256), lds_bytes, st,
                        static_cast<const uint16_t *>(Qt), q_off, static_cast<const uint16_t *>(D), d_off, d_clamp0, entries, items,
                        istart + n_d, (int)E, n_q, m, n_d, out_scores, (long long)ld_scores, flags, status);
     hipLaunchKernelGGL(msim::cand_poison_kernel, dim3(eblocks), dim3(256), 0, st, status, n_q, m, out_scores, (long long)ld_scores);
     e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_candidates_kernel launch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "%s: scoring kernel launch: %s", who, hipGetErrorString(e));
     return MSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t msim_fwd_candidates_workspace_bytes(int n_q, int m, int n_d) {
+    if (n_q <= 0 || m <= 0 || n_d < 0) return 0;
+    return cand_layout(n_q, m, n_d).total;
+}
+
+int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+                        const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, const int64_t *cand, int m, int64_t ld_cand,
+                        int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids, unsigned flags, void *workspace,
+                        void *stream) {
+    return fwd_candidates("msim_fwd_candidates", msim::kDim, dtype, Qt, q_off, q_off_host, n_q, D, d_off, d_clamp0, n_d, dim, cand, m,
+                          ld_cand, id_base, out_scores, ld_scores, out_ids, flags, workspace, stream);
+}
+
+// width 320 (ColQwen3): the inversion into work items does not depend on the row width, so neither does the workspace
+size_t msim_fwd_candidates_wide_workspace_bytes(int n_q, int m, int n_d, int dim) {
+    (void)dim;
+    if (n_q <= 0 || m <= 0 || n_d < 0) return 0;
+    return cand_layout(n_q, m, n_d).total;
+}
+
+int msim_fwd_candidates_wide(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+                             const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, const int64_t *cand, int m,
+                             int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids, unsigned flags,
+                             void *workspace, void *stream) {
+    return fwd_candidates("msim_fwd_candidates_wide", kCandWideDim, dtype, Qt, q_off, q_off_host, n_q, D, d_off, d_clamp0, n_d, dim, cand,
+                          m, ld_cand, id_base, out_scores, ld_scores, out_ids, flags, workspace, stream);
 }
 
 }  // extern "C"

@@ -130,17 +130,20 @@ def _query_format(queries) -> Tuple[torch.dtype, int]:
 
 def rerank_scores(queries, corpus: PackedCorpus, candidates: torch.Tensor, *, ref_rounding: bool = False,
                   out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """MaxSim of listed candidates (include/maxsim.h: msim_fwd_candidates): (scores fp32 [n_q, m], ids int64 [n_q, m]).
+    """MaxSim of listed candidates (include/maxsim.h: msim_fwd_candidates at width 128, msim_fwd_candidates_wide at width 320):
+    (scores fp32 [n_q, m], ids int64 [n_q, m]).
 
     Entry (q, j) is scored against document candidates[q, j] (a GLOBAL id) of `corpus`; an id of -1 or outside
     [id_base, id_base + len(corpus)) comes back as (-inf, -1).  `rerank` is the public form; this one is what
-    `ShardedRetriever` calls per shard (its `rerank_fn`)."""
+    `ShardedRetriever` calls per shard (its `rerank_fn`).  bfloat16 / float16, width 128 or 320 (ColQwen3), queries of at most
+    128 tokens; anything else raises NotImplementedError."""
     dev = _require_gpu(corpus.device)
     q_dtype, dim = _query_format(queries)
     if q_dtype != corpus.blob.dtype:        # as maxsim_scores: torch.einsum raises on mixed dtypes too
         raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {corpus.blob.dtype}")
-    if q_dtype not in (torch.bfloat16, torch.float16) or dim != 128 or corpus.blob.shape[1] != 128:
-        raise NotImplementedError(f"rerank takes bfloat16 / float16 embeddings of width 128 (got {q_dtype}, width {dim})")
+    if q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or corpus.blob.shape[1] != dim:
+        raise NotImplementedError(f"rerank takes bfloat16 / float16 embeddings of width 128 or 320 (got {q_dtype}, width {dim}, "
+                                  f"corpus width {corpus.blob.shape[1]})")
     if not isinstance(queries, PackedQueries):
         dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
         queries = pack_queries(queries, dev, layout="flat", compact=not dense_on_device)
@@ -162,14 +165,16 @@ def rerank_scores(queries, corpus: PackedCorpus, candidates: torch.Tensor, *, re
     L = _lib.lib()
     n = len(corpus)
     with torch.cuda.device(dev):
-        nbytes = L.msim_fwd_candidates_workspace_bytes(n_q, m, n)
+        nbytes = (L.msim_fwd_candidates_workspace_bytes(n_q, m, n) if dim == 128
+                  else L.msim_fwd_candidates_wide_workspace_bytes(n_q, m, n, dim))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-        rc = L.msim_fwd_candidates(_lib.dtype_code(q_dtype), _lib.ptr(queries.tokens), _lib.ptr(queries.offsets),
-                                   queries.offsets_host.data_ptr(), n_q, _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets),
-                                   _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(candidates), m, ld_cand, int(corpus.id_base),
-                                   _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.MSIM_FLAG_REF_ROUNDING if ref_rounding else 0,
-                                   _lib.ptr(ws), _lib.current_stream_handle(dev))
-    _lib.check(rc, "msim_fwd_candidates")
+        entry = L.msim_fwd_candidates if dim == 128 else L.msim_fwd_candidates_wide
+        rc = entry(_lib.dtype_code(q_dtype), _lib.ptr(queries.tokens), _lib.ptr(queries.offsets),
+                   queries.offsets_host.data_ptr(), n_q, _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets),
+                   _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(candidates), m, ld_cand, int(corpus.id_base),
+                   _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.MSIM_FLAG_REF_ROUNDING if ref_rounding else 0,
+                   _lib.ptr(ws), _lib.current_stream_handle(dev))
+    _lib.check(rc, "msim_fwd_candidates" if dim == 128 else "msim_fwd_candidates_wide")
     return out, ids
 
 
@@ -177,8 +182,9 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
            out=None):
     """Exact MaxSim of each query against ITS candidate documents only -- the second stage of a two-stage search.
 
-    queries: a `PackedQueries`, a host list of [len_i, 128] tensors or a [n_q, Lq, 128] tensor (packed as
-    `ShardedRetriever.search` does); candidates: int64 [n_q, m] GLOBAL ids on the corpus' device (-1 = none).
+    queries: a `PackedQueries`, a host list of [len_i, dim] tensors or a [n_q, Lq, dim] tensor (packed as
+    `ShardedRetriever.search` does), dim = 128 or 320 (ColQwen3), bfloat16 / float16, at most 128 tokens per query;
+    candidates: int64 [n_q, m] GLOBAL ids on the corpus' device (-1 = none).
     k=None: fp32 [n_q, m] scores aligned with `candidates`; scores[q, j] has the bits of
     `maxsim_scores(queries, corpus)[q, candidates[q, j] - corpus.id_base]`, and an empty or out-of-corpus entry is -inf.
     k set: (scores [n_q, k], ids [n_q, k]) of `topk` over the listed documents -- (score desc, id asc), padded with

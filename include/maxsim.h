@@ -191,6 +191,39 @@ int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const i
                         unsigned flags, void *workspace, void *stream);
 
 /*
+ * RERANKING at width 320 (ColQwen3, models/qwen3/colqwen3/modeling_colqwen3.py:48) -- an addition to ABI 22; msim_fwd_candidates
+ * itself keeps refusing every width but 128.  The contract is msim_fwd_candidates' with "width 128" replaced by "width 320": for
+ * every entry (q, j) of cand [n_q, m] (row stride ld_cand >= m, int64 GLOBAL ids; the shard's document c has id id_base + c)
+ *     out_scores[q, j] = scores[q, cand[q, j] - id_base]   of msim_fwd_ragged on the same queries, corpus and flags
+ *     out_ids[q, j]    = cand[q, j]                        (out_ids: int64 [n_q, ld_scores], or NULL)
+ * An entry whose id is -1, or outside [id_base, id_base + n_d), is written as (-inf, -1) and reads no document; a query of 0 tokens
+ * scores 0; a duplicate id is scored once per occurrence (identical bits).  bf16 / f16, dim == 320 ONLY (this entry does not serve
+ * width 128: call msim_fwd_candidates), 0 .. 128 tokens per query; MSIM_EUNSUPPORTED for other dtypes, widths and longer queries;
+ * MSIM_EINVAL for a null or misaligned pointer, ld < m, an unknown flag, a non-monotone q_off_host.  Nothing to do (n_q == 0 or
+ * m == 0) returns 0 before any pointer is looked at.  d_clamp0 and MSIM_FLAG_REF_ROUNDING as msim_fwd (no other flag).
+ * BITS: out_scores[q, j] carries the bits msim_fwd_ragged gives the same query and document WHEN THE FLAT PANEL KERNEL K1bPF
+ * COMPUTES IT -- the MFMA chain across the column panels in K1bPF's order and the token sum in the order fixed by the query's
+ * length alone -- so a reranked score does not depend on the batch, the list, the grouping into work items or a rerun.  The one
+ * exception is the scan side's (see msim_fwd_ragged above): a width-320 msim_fwd_ragged call of ONE query length and at most four
+ * 32-token tiles in all runs K1sP, whose token sum is a butterfly.  Against such a call the per-token maxima are identical and the
+ * scores agree to fp32 summation order: |difference| <= 2 * g(L - 1) * sum_i |M_i|, g(n) = n 2^-24 / (1 - n 2^-24), L the query's
+ * token count, M_i its per-token maxima.
+ * The candidate matrix is inverted on the device exactly as in msim_fwd_candidates (the same kernels; work items of one document
+ * and up to eight 16-token units); the item scorer is the panel form K1cP (maxsim_candidates_panels.hip).  Asynchronous on `stream`,
+ * no allocation, no host synchronisation, hipGraph-capturable (the counters are zeroed by a kernel node).  Every index the device
+ * derives is checked before it becomes an address; a broken invariant makes every score of the call NaN.
+ * workspace: msim_fwd_candidates_wide_workspace_bytes(n_q, m, n_d, dim) bytes (0 when there is no entry), 16-byte aligned, contents
+ * irrelevant; one per call in flight.  After the call its first int32 is 0, or the bits of the broken invariant.
+ * NOT served at width 320: the int8 and FDE first stages (msim_i8_*, msim_fde_*: width 128 only), fp32.
+ */
+size_t msim_fwd_candidates_wide_workspace_bytes(int n_q, int m, int n_d, int dim);
+int msim_fwd_candidates_wide(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q,
+                             const void *D, const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim,
+                             const int64_t *cand, int m, int64_t ld_cand, int64_t id_base,
+                             float *out_scores, int64_t ld_scores, int64_t *out_ids /* or NULL */,
+                             unsigned flags, void *workspace, void *stream);
+
+/*
  * The same scores for two DENSE BOXES when the queries are long and the documents short -- the symmetric direction of the reference
  * trainer (trainer/contrastive_trainer.py:202-206, compute_symetric_loss: the pages as query_embeddings [B, 780, 128], the gathered
  * queries as doc_embeddings [C, 32, 128]; late_interaction_losses.py:297-298):
