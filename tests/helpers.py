@@ -224,3 +224,118 @@ def smooth_bwd_truth(Q, D, d_off, pairs, g, tau, budget=1 << 22):
         out[1].index_add_(0, rows.reshape(-1), torch.einsum("pij,pid->pjd", gw, q).reshape(-1, dim))
         out[3].index_add_(0, rows.reshape(-1), torch.einsum("pij,pid->pjd", aw, q.abs()).reshape(-1, dim))
     return tuple(out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Far-side inputs (the sign tier: tests/test_gpu_sign_edges.py, tests/test_host_sign_edges.py).  Queries sit at +0.7 u, document rows
+# at -0.7 u, both with unit noise orthogonal to u scaled by sqrt(0.51): unit rows whose similarities are -0.49 + 0.51 <n, n'>, i.e.
+# negative for every (token, row) pair (largest measured: -0.085 at width 32, -0.24 at 128, -0.33 at 320).  A zero that leaks into a
+# per-token max -- a row past the document's end that was not masked, a clamp applied to the wrong document -- then moves a score by
+# at least the margin the tests assert on their own float64 truth (0.05), where random unit rows would hide it bit for bit.
+
+# every tail class of the 32-row slab, the 128-row chunk and the 16-row int8 chunk
+SIGN_EDGE_LENS = [1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 96, 127, 128, 129, 160, 255, 256, 257, 1023, 1024, 1030]
+SIGN_MARGIN = 0.05
+
+
+def far_side_axis(dim, g):
+    """the fixed unit vector u (float64)"""
+    import torch
+
+    u = torch.randn(dim, generator=g, dtype=torch.float64)
+    return u / u.norm()
+
+
+def far_side_rows(n, u, side, g, dtype):
+    """n rows  side * 0.7 u + sqrt(0.51) noise  (noise: unit, orthogonal to u), cast to dtype; side = +1 queries, -1 document rows"""
+    import torch
+
+    noise = torch.randn(n, u.numel(), generator=g, dtype=torch.float64)
+    noise = noise - (noise @ u).unsqueeze(1) * u
+    noise = noise / noise.norm(dim=1, keepdim=True).clamp_min(1e-300)
+    return (side * 0.7 * u + 0.51**0.5 * noise).to(dtype)
+
+
+def planted_positions(n):
+    """where the planted winner may sit in a document of n rows: row 0, the last row, the first row of the last 32-row slab and the
+    rows on either side of the first slab and chunk boundaries, where they exist"""
+    want = [0, n - 1, (n - 1) // 32 * 32, 31, 32, 127, 128]
+    out = []
+    for p in want:
+        if 0 <= p < n and p not in out:
+            out.append(p)
+    return out
+
+
+def far_side_doc_lens(g, lens=SIGN_EDGE_LENS, copies=2, n_empty=4, max_len=None):
+    """`copies` of every edge length (at most max_len) plus n_empty documents without rows, shuffled: short documents follow long ones
+    and the other way round"""
+    import torch
+
+    lens = [n for n in lens if max_len is None or n <= max_len] * copies + [0] * n_empty
+    return [lens[i] for i in torch.randperm(len(lens), generator=g).tolist()]
+
+
+def far_side_case(seed, q_lens, d_lens, dim, dtype, planted=False):
+    """(queries, documents, planted row per document or -1): lists of [n, dim] CPU tensors of `dtype`.  planted=True replaces one row
+    of every non-empty document by a row on the queries' side (+0.7 u): the position cycles through planted_positions(n) with the
+    document's index, so every position is taken by some document of every length class that has it."""
+    import torch
+
+    g = torch.Generator().manual_seed(seed)
+    u = far_side_axis(dim, g)
+    q_all = far_side_rows(sum(q_lens), u, +1, g, dtype)
+    d_all = far_side_rows(max(sum(d_lens), 1), u, -1, g, dtype)[: sum(d_lens)]
+    qs = [t.clone() for t in q_all.split(list(q_lens))]
+    ps = [t.clone() for t in d_all.split(list(d_lens))]
+    rows = [-1] * len(ps)
+    if planted:
+        for c, p in enumerate(ps):
+            if p.shape[0]:
+                pos = planted_positions(p.shape[0])
+                rows[c] = pos[c % len(pos)]
+                p[rows[c]] = far_side_rows(1, u, +1, g, dtype)[0]
+    return qs, ps, rows
+
+
+def maxsim_truth(q_tokens, D, d_off, device="cpu"):
+    """float64 per-token truth of include/maxsim.h's contract on a packed corpus: for every token row i of q_tokens [T, dim] and every
+    document c (rows d_off[c] .. d_off[c+1]-1 of D): M[i, c] = max_j <q_i, D_j> (-inf for a document without rows), A[i, c] = the first
+    row (relative to the document) that attains it (-1 without rows), G[i, c] = M minus the second largest similarity (+inf for
+    documents of fewer than two rows).  One product per document, on `device`; the results come back on the CPU."""
+    import torch
+
+    Q = torch.as_tensor(q_tokens).to(device).double()
+    Dd = torch.as_tensor(D).to(device).double()
+    off = [int(x) for x in d_off]
+    T, n = Q.shape[0], len(off) - 1
+    M = torch.full((T, n), float("-inf"), dtype=torch.float64, device=device)
+    A = torch.full((T, n), -1, dtype=torch.int64, device=device)
+    G = torch.full((T, n), float("inf"), dtype=torch.float64, device=device)
+    for c in range(n):
+        a, b = off[c], off[c + 1]
+        if b == a:
+            continue
+        S = Q @ Dd[a:b].T
+        top = torch.topk(S, min(2, b - a), dim=1).values
+        M[:, c] = top[:, 0]
+        A[:, c] = (S == top[:, :1]).to(torch.int8).argmax(dim=1)            # argmax of a 0/1 matrix: the first maximal row
+        if b - a > 1:
+            G[:, c] = top[:, 0] - top[:, 1]
+    return M.cpu(), A.cpu(), G.cpu()
+
+
+def token_sums(M, q_lens, clamp0=None):
+    """scores float64 [n_q, n_d]: the sum over every query's tokens of M[i, c], after max(M, 0) on the documents clamp0 flags (the
+    reference's zero padding row: include/maxsim.h, d_clamp0).  An empty document scores -inf, 0 when flagged."""
+    import torch
+
+    M = M.clone()
+    if clamp0 is not None:
+        f = torch.as_tensor(clamp0).bool()
+        M[:, f] = M[:, f].clamp_min(0.0)
+    out, o = [], 0
+    for n in q_lens:
+        out.append(M[o : o + int(n)].sum(dim=0))
+        o += int(n)
+    return torch.stack(out)
