@@ -7,6 +7,7 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                   <- colpali_engine/loss/late_interaction_losses.py:255-313 (:110-164, :401-465, :6-107)
   * ShardedRetriever / topk       -- sharded-corpus top-k with an RCCL all-gather merge (no reference equivalent)
   * rerank                        -- exact MaxSim of per-query candidate lists; two-stage search (ShardedRetriever.search(prefilter=))
+  * align / Alignment             -- which page row matched each query token of a search hit, and its similarity maps
   * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
@@ -14,6 +15,7 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
 colpali_amd/csrc/); this package is the thin host-side mirror of the reference interface.
 """
+from .align import Alignment, align
 from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pack_queries
 from . import loss
 from .embed import CorpusWriter, embedding_head
@@ -30,6 +32,8 @@ from .scoring import (get_similarity_maps_from_embeddings, get_torch_device, max
                       score_single_vector, similarity_matrix)
 
 __all__ = [
+    "Alignment",
+    "align",
     "CorpusWriter",
     "HierarchicalTokenPooler",
     "TokenPoolingOutput",

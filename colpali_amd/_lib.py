@@ -183,6 +183,8 @@ def lib() -> ctypes.CDLL:
     L.msim_live_compact.restype = i32
     L.msim_live_mask_scores.argtypes = [vp, i64, i32, i64, vp, vp]
     L.msim_live_mask_scores.restype = i32
+    L.msim_align_candidates.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, vp, i32, i64, i32, vp, i32, i64, i64, vp, vp, vp, i32, vp]
+    L.msim_align_candidates.restype = i32
     L.msim_topk_workspace_bytes.argtypes = [i32, i64, i32]
     L.msim_topk_workspace_bytes.restype = sz
     L.msim_topk_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]

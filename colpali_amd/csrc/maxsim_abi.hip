@@ -35,6 +35,7 @@
 #include "fde.hip"
 #include "int8_index.hip"
 #include "live_corpus.hip"
+#include "maxsim_align.hip"
 
 namespace {
 
@@ -2937,6 +2938,69 @@ int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const u
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "live_mask_kernel launch: %s", hipGetErrorString(e));
     return MSIM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- token-to-patch alignment of listed entries (K1a, maxsim_align.hip)
+namespace {
+
+template <int DIM>
+int align_launch(bool f16, const void *Qt, const int32_t *q_off, const void *D, const int32_t *d_off, const uint8_t *clamp0,
+                 const int64_t *cand, float *best_sim, int32_t *best_row, float *sims, const msim::AlignArgs &a, hipStream_t st) {
+    auto kern = f16 ? msim::maxsim_align_kernel<DIM, true> : msim::maxsim_align_kernel<DIM, false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)a.n_q * a.m)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), q_off,
+                       static_cast<const uint16_t *>(D), d_off, clamp0, cand, best_sim, best_row, sims, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_align_kernel<%d> launch: %s", DIM, hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_align_candidates(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, const void *D,
+                          const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int64_t d_rows, int dim, const int64_t *cand, int m,
+                          int64_t ld_cand, int64_t id_base, float *best_sim, int32_t *best_row, float *sims, int max_rows,
+                          void *stream) {
+    const char *who = "msim_align_candidates";
+    if (n_q < 0 || m < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0 || max_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d m=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d max_rows=%d)", who, n_q,
+                    m, n_d, (long long)q_rows, (long long)d_rows, max_q_tokens, max_rows);
+    if (n_q == 0 || m == 0) return MSIM_OK;
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || !(dim == msim::kDim || dim == kCandWideDim))
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 embeddings of width %d or %d (dtype code %d, dim %d)", who,
+                    msim::kDim, kCandWideDim, dtype, dim);
+    if (max_q_tokens > msim::kAlignMaxTokens)
+        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d: queries of at most %d tokens", who, max_q_tokens, msim::kAlignMaxTokens);
+    if ((!Qt && q_rows > 0) || !q_off || (!D && d_rows > 0) || !d_off || !cand || ((!best_sim || !best_row) && max_q_tokens > 0))
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(D, 16)) return fail(MSIM_EINVAL, "%s: Qt and D must be 16-byte aligned", who);
+    if (misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(cand, 8) || misaligned(best_sim, 4) || misaligned(best_row, 4) ||
+        misaligned(sims, 4))
+        return fail(MSIM_EINVAL, "%s: offsets and outputs must be 4-byte aligned, cand 8-byte aligned", who);
+    if (ld_cand < m) return fail(MSIM_EINVAL, "%s: ld_cand=%lld < m=%d", who, (long long)ld_cand, m);
+    if ((long long)n_q * m > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: more than 2^31 - 1 entries (n_q=%d x m=%d)", who, n_q, m);
+    if (max_q_tokens == 0) return MSIM_OK;                       // no token slot: nothing to write
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    msim::AlignArgs a;
+    a.ld_cand = ld_cand;
+    a.id_base = id_base;
+    a.q_rows = q_rows;
+    a.d_rows = d_rows;
+    a.n_q = n_q;
+    a.m = m;
+    a.n_d = n_d;
+    a.T = max_q_tokens;
+    a.R = max_rows;
+    a.vec = sims && !misaligned(sims, 16) && max_rows % 4 == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    if (dim == msim::kDim)
+        return align_launch<msim::kDim>(f16, Qt, q_off, D, d_off, d_clamp0, cand, best_sim, best_row, sims, a, st);
+    return align_launch<kCandWideDim>(f16, Qt, q_off, D, d_off, d_clamp0, cand, best_sim, best_row, sims, a, st);
 }
 
 }  // extern "C"

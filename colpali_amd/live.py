@@ -24,6 +24,7 @@ from . import _lib
 from .corpus import PackedCorpus, PackedQueries, _staging, _widen, host_list_image, pack_queries
 from .int8_index import DIM as I8_DIM
 from .int8_index import Int8Index, int8_scores
+from .align import Alignment, align
 from .retrieval import ShardedRetriever, rerank_scores, topk
 from .scoring import maxsim_scores
 
@@ -56,7 +57,7 @@ class LiveCorpus:
     def __init__(self, capacity_rows: int, capacity_docs: int, device, dtype: torch.dtype = torch.bfloat16, width: int = 128,
                  id_base: int = 0, *, bounce_bytes: Optional[int] = None, score_fn: Callable = maxsim_scores,
                  rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, select: Callable = topk,
-                 mask_fn: Callable = mask_scores):
+                 mask_fn: Callable = mask_scores, align_fn: Callable = align):
         capacity_rows, capacity_docs = int(capacity_rows), int(capacity_docs)
         if capacity_rows < 1 or capacity_docs < 1:
             raise ValueError("capacity_rows and capacity_docs must be positive")
@@ -77,6 +78,7 @@ class LiveCorpus:
         self._rows_used = 0
         self._score_fn, self._rerank_fn, self._int8_score_fn = score_fn, rerank_fn, int8_score_fn
         self._select, self._mask_fn = select, mask_fn
+        self._align_fn = align_fn
         self._i8_codes: Optional[torch.Tensor] = None
         self._i8_scales: Optional[torch.Tensor] = None
         self._compactions = 0
@@ -316,12 +318,21 @@ class LiveCorpus:
     def _int8_score(self, queries, index):
         return self._masked(self._int8_score_fn(queries, index))
 
-    def _rerank(self, queries, corpus, candidates):
+    def _live_ids(self, candidates: torch.Tensor) -> torch.Tensor:
+        """`candidates` with every id that is outside the corpus or deleted replaced by -1 (on the device, no synchronisation)"""
         n = self.n_slots
         idx = candidates - self.id_base
         inside = (idx >= 0) & (idx < n)
         live = self.alive[:max(n, 1)][idx.clamp(0, max(n - 1, 0))] != 0
-        return self._rerank_fn(queries, corpus, torch.where(inside & live, candidates, torch.full_like(candidates, -1)))
+        return torch.where(inside & live, candidates, torch.full_like(candidates, -1))
+
+    def _rerank(self, queries, corpus, candidates):
+        return self._rerank_fn(queries, corpus, self._live_ids(candidates))
+
+    def align(self, queries, ids: torch.Tensor, maps: bool = False) -> Alignment:
+        """`align` over the live pages: a deleted id is treated as -1 (no page: (-inf, -1)), as `search(candidates=)` treats it; a
+        surviving page's result has the bits of `align(queries, self.view(), ids)`."""
+        return self._align_fn(queries, self.view(), self._live_ids(ids), maps=maps)
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None, prefilter=None,
                n_candidates: Optional[int] = None, world: int = 1, rank: int = 0, dist=None,

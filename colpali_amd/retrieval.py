@@ -16,6 +16,7 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from . import _lib
+from .align import Alignment, align
 from .corpus import PackedCorpus
 from .corpus import PackedQueries, pack_queries
 from .fde import FdeIndex, fde_scores
@@ -204,13 +205,14 @@ class ShardedRetriever:
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
                  rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores,
-                 int8_score_fn: Callable = int8_scores):
+                 int8_score_fn: Callable = int8_scores, align_fn: Callable = align):
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
         self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
         self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
         self._int8_score = int8_score_fn  # (queries, Int8Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Int8Index>
+        self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
         self.force_collective = force_collective
         if world > 1 and dist is None:
             import torch.distributed as dist_mod
@@ -244,6 +246,25 @@ class ShardedRetriever:
         scores = self._score(queries, self.shard)
         return shard_topk(scores, k, self.shard.id_base, self.world, self.dist, self.group, self._select,
                           force_collective=self.force_collective)
+
+    def align(self, queries, ids: torch.Tensor, maps: bool = False) -> Alignment:
+        """Explain hits (`align`): for every entry of `ids` -- int64 [n_q, m] GLOBAL ids, the same on every rank, e.g. what `search`
+        returned -- the best-matching page row of every query token and its similarity.  Every rank aligns the ids it holds; with
+        world > 1 one element-wise MAX all-reduce of (best_sim, best_row, ids) follows: a rank that does not hold an id contributes
+        (-inf, -1, -1), so every rank ends up with the holder's result (best_row is relative to the page, whichever rank holds it).
+        `maps=True` is for a single shard: the maps of a sharded corpus stay on the rank that holds the page (ValueError)."""
+        if maps and self.world > 1:
+            raise ValueError("maps=True with world > 1: similarity maps are made by the rank that holds the page; call align() on "
+                             "its shard")
+        if self._align is align and not isinstance(queries, PackedQueries):
+            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+            queries = pack_queries(queries, self.shard.device, layout="flat", compact=not dense_on_device)
+        out = self._align(queries, self.shard, ids, maps=maps)
+        if self.world > 1:
+            for t in (out.best_sim, out.best_row, out.ids):
+                self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
+            out.page_lengths = None        # this shard's page lengths do not describe the other ranks' pages
+        return out
 
     def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates):
         if candidates is not None and prefilter is not None:

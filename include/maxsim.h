@@ -224,6 +224,40 @@ int msim_fwd_candidates_wide(int dtype, const void *Qt, const int32_t *q_off, co
                              unsigned flags, void *workspace, void *stream);
 
 /*
+ * TOKEN-TO-PATCH ALIGNMENT of listed entries -- an addition to ABI 22: which rows of a hit page matched each query token, and the
+ * similarity map behind it (colpali_engine/interpretability/similarity_map_utils.py:9-55: einsum("bnk,bijk->bnij") of one query
+ * with one image's patch grid), for pages that live in the packed corpus.  Entry (q, j) of cand [n_q, m] (row stride ld_cand >= m,
+ * int64 GLOBAL ids) is resolved as msim_fwd_candidates resolves it: an id of -1, or outside [id_base, id_base + n_d), is no page.
+ * For every token slot i < max_q_tokens (the caller's host bound on tokens per query, at most 128) of every entry:
+ *     best_sim[q, j, i] = max_{r < len(page)} <Qt[q_off[q] + i], D[d_off[c] + r]>      fp32 accumulation
+ *     best_row[q, j, i] = the FIRST r that attains it (relative to the page)
+ *     sims[q, j, i, r]  = <Qt[q_off[q] + i], D[d_off[c] + r]>                           (sims != NULL: the similarity map)
+ * best_sim fp32 and best_row int32 are [n_q, m, max_q_tokens]; sims fp32 is [n_q, m, max_q_tokens, max_rows] or NULL, max_rows the
+ * caller's host bound on the rows of a listed page.  In sims the columns r >= len(page) and the token slots i >= len(query) hold
+ * -inf.  The conventions are those of msim_pairs_argmax:
+ *   - under d_clamp0[c] a token whose maximum is negative reports (0.0, -1) (the reference's zero padding row wins), and so does
+ *     a flagged page of 0 rows; sims is not clamped;
+ *   - an unflagged page of 0 rows, or an entry without a page, reports (-inf, -1) for the query's tokens;
+ *   - a token slot past the query's end reports (0.0, -1);
+ *   - an entry whose page has more than max_rows rows (whether or not sims is passed), or whose offsets break an invariant --
+ *     q_off not within [0, q_rows] and non-decreasing, a query of more than max_q_tokens tokens, d_off not within [0, d_rows] --
+ *     is written as NaN / -1 in full; its neighbours are untouched.  Every offset is checked on the device before it becomes an
+ *     address: nothing is read or written out of bounds, and the host reads neither the list nor the offsets.
+ * BITS: one fp32 accumulator chain per similarity, k ascending (v_mfma_f32_16x16x32, dim / 32 steps): the bits of a similarity
+ * depend on its token row and its page row alone -- the same at any list position, in any batch, under any m, with or without sims;
+ * best_sim is the maximum of its row of sims bit for bit (before the clamp).
+ * bf16 / f16, dim 128 or 320 (MSIM_EUNSUPPORTED otherwise, and for max_q_tokens > 128); Qt [q_rows, dim], D [d_rows, dim] 16-byte
+ * aligned.  n_q == 0 or m == 0 returns 0 before any pointer is looked at.  One 4-wave workgroup per entry (kernel K1a,
+ * maxsim_align.hip); no workspace, no allocation, no synchronisation: asynchronous on `stream`, hipGraph-capturable.
+ */
+int msim_align_candidates(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                          const void *D, const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int64_t d_rows, int dim,
+                          const int64_t *cand, int m, int64_t ld_cand, int64_t id_base,
+                          float *best_sim, int32_t *best_row,            /* [n_q, m, max_q_tokens] */
+                          float *sims /* or NULL */, int max_rows,       /* [n_q, m, max_q_tokens, max_rows] */
+                          void *stream);
+
+/*
  * The same scores for two DENSE BOXES when the queries are long and the documents short -- the symmetric direction of the reference
  * trainer (trainer/contrastive_trainer.py:202-206, compute_symetric_loss: the pages as query_embeddings [B, 780, 128], the gathered
  * queries as doc_embeddings [C, 32, 128]; late_interaction_losses.py:297-298):
