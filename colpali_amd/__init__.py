@@ -8,6 +8,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
   * ShardedRetriever / topk       -- sharded-corpus top-k with an RCCL all-gather merge (no reference equivalent)
   * rerank                        -- exact MaxSim of per-query candidate lists; two-stage search (ShardedRetriever.search(prefilter=))
   * align / Alignment             -- which page row matched each query token of a search hit, and its similarity maps
+  * mine_hard_negatives / gather_pages -- hard negatives by the model's own MaxSim score over the resident corpus, and the padded
+                                     box of the chosen pages for ColbertNegativeCELoss / ColbertPairwiseNegativeCELoss
   * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
@@ -22,6 +24,7 @@ from .embed import CorpusWriter, embedding_head
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .int8_index import Int8Index, int8_scores, quantize_queries
 from .live import LiveCorpus
+from .mine import gather_pages, mine_hard_negatives
 from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPairwiseCELoss,
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
@@ -46,6 +49,8 @@ __all__ = [
     "int8_scores",
     "quantize_queries",
     "LiveCorpus",
+    "mine_hard_negatives",
+    "gather_pages",
     "ColbertLoss",
     "ColbertModule",
     "ColbertNegativeCELoss",

@@ -36,6 +36,7 @@
 #include "int8_index.hip"
 #include "live_corpus.hip"
 #include "maxsim_align.hip"
+#include "mine.hip"
 
 namespace {
 
@@ -2937,6 +2938,97 @@ int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const u
                        alive, vec_ok);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "live_mask_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- hard-negative mining and the page gather (mine.hip)
+namespace {
+
+// what msim_mine_bounds and msim_mine_mask share: the score matrix and the positives list
+int mine_check(const char *who, const float *scores, int64_t ld, int n_q, int64_t n, const int64_t *pos_ids, const int32_t *pos_off,
+               int64_t nnz) {
+    if (n_q < 0 || n < 0 || nnz < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld nnz=%lld)", who, n_q, (long long)n, (long long)nnz);
+    if (n_q == 0) return MSIM_OK;
+    if (!pos_off || (nnz > 0 && !pos_ids) || (n > 0 && !scores)) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(scores, 4) || misaligned(pos_off, 4) || misaligned(pos_ids, 8))
+        return fail(MSIM_EINVAL, "%s: scores and pos_off must be 4-byte aligned, pos_ids 8-byte aligned", who);
+    if (ld < n) return fail(MSIM_EINVAL, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
+    return MSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_mine_bounds(const float *scores, int64_t ld, int n_q, int64_t n, const int64_t *pos_ids, const int32_t *pos_off, int64_t nnz,
+                     int64_t id_base, const uint8_t *alive, int local, float *bounds, void *stream) {
+    const char *who = "msim_mine_bounds";
+    if (int rc = mine_check(who, scores, ld, n_q, n, pos_ids, pos_off, nnz)) return rc;
+    if (n_q == 0) return MSIM_OK;
+    if (!bounds || misaligned(bounds, 4)) return fail(MSIM_EINVAL, "%s: bounds must be a 4-byte aligned pointer", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned blocks = (unsigned)((n_q + 3) / 4);
+    hipLaunchKernelGGL(msim::mine_bounds_kernel, dim3(blocks), dim3(msim::kMineThreads), 0, st, scores, (long long)ld, n_q, (long long)n,
+                       pos_ids, pos_off, (long long)nnz, (long long)id_base, alive, local != 0, bounds);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "mine_bounds_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_mine_mask(float *scores, int64_t ld, int n_q, int64_t n, const float *bounds, float max_ratio, const uint8_t *alive,
+                   const int64_t *pos_ids, const int32_t *pos_off, int64_t nnz, int64_t id_base, void *stream) {
+    const char *who = "msim_mine_mask";
+    if (int rc = mine_check(who, scores, ld, n_q, n, pos_ids, pos_off, nnz)) return rc;
+    if (n_q == 0 || n == 0) return MSIM_OK;
+    if (misaligned(bounds, 4)) return fail(MSIM_EINVAL, "%s: bounds must be 4-byte aligned", who);
+    if (bounds && max_ratio != max_ratio) return fail(MSIM_EINVAL, "%s: max_ratio is NaN", who);
+    const int64_t all_tiles = (n + msim::kMineTileCols - 1) / msim::kMineTileCols;
+    if (all_tiles >= 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)n);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned tiles = (bounds || alive) ? (unsigned)all_tiles : 0u;     // neither: only the positives' columns change
+    const int vec_ok = !misaligned(scores, 16) && ld % 4 == 0;
+    const unsigned row_groups = (unsigned)(n_q < msim::kMineRowGroups ? n_q : msim::kMineRowGroups);
+    auto kern = bounds ? msim::mine_mask_kernel<true> : msim::mine_mask_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(tiles + 1, row_groups), dim3(msim::kMineThreads), 0, st, scores, (long long)ld, n_q, (long long)n, bounds,
+                       max_ratio, alive, pos_ids, pos_off, (long long)nnz, (long long)id_base, tiles, vec_ok);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "mine_mask_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_gather_pages(const void *rows, int64_t row_bytes, int64_t d_rows, const int32_t *d_off, int n_d, int64_t id_base,
+                      const int64_t *ids, int64_t n_slots, int64_t pad_rows, void *out, int32_t *lengths, void *stream) {
+    const char *who = "msim_gather_pages";
+    if (n_slots < 0 || n_d < 0 || d_rows < 0 || pad_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_slots=%lld n_d=%d d_rows=%lld pad_rows=%lld)", who, (long long)n_slots, n_d,
+                    (long long)d_rows, (long long)pad_rows);
+    if (row_bytes <= 0 || row_bytes % 16 != 0)
+        return fail(MSIM_EINVAL, "%s: row_bytes=%lld must be a positive multiple of 16", who, (long long)row_bytes);
+    if (row_bytes > kLiveMaxRowBytes)
+        return fail(MSIM_EUNSUPPORTED, "%s: rows of %lld bytes (at most %lld)", who, (long long)row_bytes, (long long)kLiveMaxRowBytes);
+    if (d_rows > 0x7fffffffLL || pad_rows > 0x7fffffffLL || n_slots > 0x7fffffffLL)
+        return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld, pad_rows=%lld or n_slots=%lld above 2^31 - 1", who, (long long)d_rows,
+                    (long long)pad_rows, (long long)n_slots);
+    if (n_slots == 0) return MSIM_OK;
+    if (!ids || !lengths || !d_off || (!rows && d_rows > 0) || (!out && pad_rows > 0))
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(rows, 16) || misaligned(out, 16) || misaligned(ids, 8) || misaligned(d_off, 4) || misaligned(lengths, 4))
+        return fail(MSIM_EINVAL, "%s: rows and out must be 16-byte aligned, ids 8-byte, d_off and lengths 4-byte aligned", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(msim::gather_pages_kernel, dim3((unsigned)n_slots), dim3(msim::kMineThreads), 0, st,
+                       static_cast<const uint8_t *>(rows), (int)(row_bytes / 16), (long long)d_rows, d_off, n_d, (long long)id_base, ids,
+                       (long long)pad_rows, static_cast<uint8_t *>(out), lengths);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "gather_pages_kernel launch: %s", hipGetErrorString(e));
     return MSIM_OK;
 }
 

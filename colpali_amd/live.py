@@ -25,6 +25,7 @@ from .corpus import PackedCorpus, PackedQueries, _staging, _widen, host_list_ima
 from .int8_index import DIM as I8_DIM
 from .int8_index import Int8Index, int8_scores
 from .align import Alignment, align
+from .mine import mine_bounds, mine_mask
 from .retrieval import ShardedRetriever, rerank_scores, topk
 from .scoring import maxsim_scores
 
@@ -57,7 +58,8 @@ class LiveCorpus:
     def __init__(self, capacity_rows: int, capacity_docs: int, device, dtype: torch.dtype = torch.bfloat16, width: int = 128,
                  id_base: int = 0, *, bounce_bytes: Optional[int] = None, score_fn: Callable = maxsim_scores,
                  rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, select: Callable = topk,
-                 mask_fn: Callable = mask_scores, align_fn: Callable = align):
+                 mask_fn: Callable = mask_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
+                 mine_mask_fn: Callable = mine_mask):
         capacity_rows, capacity_docs = int(capacity_rows), int(capacity_docs)
         if capacity_rows < 1 or capacity_docs < 1:
             raise ValueError("capacity_rows and capacity_docs must be positive")
@@ -79,6 +81,7 @@ class LiveCorpus:
         self._score_fn, self._rerank_fn, self._int8_score_fn = score_fn, rerank_fn, int8_score_fn
         self._select, self._mask_fn = select, mask_fn
         self._align_fn = align_fn
+        self._mine_bounds_fn, self._mine_mask_fn = mine_bounds_fn, mine_mask_fn
         self._i8_codes: Optional[torch.Tensor] = None
         self._i8_scales: Optional[torch.Tensor] = None
         self._compactions = 0
@@ -333,6 +336,15 @@ class LiveCorpus:
         """`align` over the live pages: a deleted id is treated as -1 (no page: (-inf, -1)), as `search(candidates=)` treats it; a
         surviving page's result has the bits of `align(queries, self.view(), ids)`."""
         return self._align_fn(queries, self.view(), self._live_ids(ids), maps=maps)
+
+    def mine(self, queries, positives, n_neg: int, *, max_ratio: Optional[float] = None, skip_top: int = 0, compact: bool = False,
+             world: int = 1, rank: int = 0, dist=None, group=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`ShardedRetriever.mine` (`mine_hard_negatives`) over the live pages: the tombstone mask goes into the mining mask, so a
+        deleted page is never mined and a deleted positive bounds nothing (it is not there).  The result has the bits of
+        `mine_hard_negatives` over a fresh pack of the surviving pages, positions mapped back to slots."""
+        r = ShardedRetriever(self.view(), world, rank, dist, group, score_fn=self._score_fn, select=self._select,
+                             mine_bounds_fn=self._mine_bounds_fn, mine_mask_fn=self._mine_mask_fn)
+        return r.mine(queries, positives, n_neg, max_ratio=max_ratio, skip_top=skip_top, alive=self.alive[:self.n_slots], compact=compact)
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None, prefilter=None,
                n_candidates: Optional[int] = None, world: int = 1, rank: int = 0, dist=None,

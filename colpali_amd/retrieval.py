@@ -21,6 +21,7 @@ from .corpus import PackedCorpus
 from .corpus import PackedQueries, pack_queries
 from .fde import FdeIndex, fde_scores
 from .int8_index import Int8Index, int8_scores
+from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
 from .scoring import _require_gpu, maxsim_scores
 
 
@@ -205,7 +206,8 @@ class ShardedRetriever:
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
                  rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores,
-                 int8_score_fn: Callable = int8_scores, align_fn: Callable = align):
+                 int8_score_fn: Callable = int8_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
+                 mine_mask_fn: Callable = mine_mask):
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
@@ -213,6 +215,8 @@ class ShardedRetriever:
         self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
         self._int8_score = int8_score_fn  # (queries, Int8Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Int8Index>
         self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
+        self._mine_bounds = mine_bounds_fn    # (scores, csr, id_base, local=, alive=) -> fp32 [n_q]: the best in-shard positive of each query
+        self._mine_mask = mine_mask_fn        # (scores, csr, id_base, bounds, max_ratio, alive) -> scores, -inf where ineligible
         self.force_collective = force_collective
         if world > 1 and dist is None:
             import torch.distributed as dist_mod
@@ -265,6 +269,31 @@ class ShardedRetriever:
                 self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
             out.page_lengths = None        # this shard's page lengths do not describe the other ranks' pages
         return out
+
+    def mine(self, queries, positives, n_neg: int, *, max_ratio: Optional[float] = None, skip_top: int = 0,
+             alive: Optional[torch.Tensor] = None, compact: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Hard negatives over the whole sharded corpus (`mine_hard_negatives`: same rule, same arguments, the same result on every
+        rank): (neg_scores fp32 [n_q, n_neg], neg_ids int64 [n_q, n_neg]).  `positives` (replicated, GLOBAL ids) may live on any
+        shard: each rank takes the maximum over the positives it holds (-inf where it holds none), ONE all-reduce MAX of fp32 [n_q]
+        makes that the global bound of the `max_ratio` rule, each rank masks and selects its best `skip_top + n_neg` locally, and the
+        all-gather + merge of `search` runs over those; the `skip_top` window is cut after the merge, so the answer does not depend
+        on the number of shards.  `alive`: this shard's uint8 tombstones.  Queries are packed as `search` packs them."""
+        n_neg, skip_top, max_ratio = check_mine_args(n_neg, skip_top, max_ratio)
+        if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
+            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+            queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
+        scores = self._score(queries, self.shard)
+        if alive is not None and alive.device != scores.device:
+            raise ValueError("alive and the shard live on different devices")
+        reduce_max = None
+        if self.world > 1:
+            def reduce_max(t):
+                self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
+        masked = mine_masked(scores, positives, int(self.shard.id_base), max_ratio, alive, self._mine_bounds, self._mine_mask, reduce_max)
+
+        def shard_select(s, k, id_base):
+            return shard_topk(s, k, id_base, self.world, self.dist, self.group, self._select, force_collective=self.force_collective)
+        return select_window(masked, int(self.shard.id_base), n_neg, skip_top, shard_select)
 
     def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates):
         if candidates is not None and prefilter is not None:

@@ -676,6 +676,45 @@ int msim_live_compact(void *rows, int64_t row_bytes, int64_t rows_bound, int32_t
                       int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream);
 int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const uint8_t *alive, void *stream);
 
+/*
+ * HARD-NEGATIVE MINING AND THE PAGE GATHER (mine.hip; additions to ABI 22).  Mining is "mask the score matrix of the full scan, then
+ * msim_topk_f32": no scorer and no selection kernel changes.
+ *
+ * scores fp32 [n_q, ld], ld >= n, 4-byte aligned: column c is page id_base + c.  The positives of query q are
+ * pos_ids[pos_off[q] .. pos_off[q + 1]) (int64 GLOBAL ids; pos_off int32 [n_q + 1], read on the device and clipped to [0, nnz], so
+ * a broken pair yields an empty list, never an address).  An id that is negative or outside [id_base, id_base + n) is ignored;
+ * duplicates are allowed.
+ *
+ * msim_mine_bounds: bounds[q] (fp32 [n_q]) = max over the in-shard positives of scores[q, id - id_base] (alive != NULL: those with
+ * alive[id - id_base] != 0 only: a deleted page is not there), or +inf where the query has none (local != 0: -inf instead -- what a rank that holds no positive contributes to an all-reduce MAX).
+ *
+ * msim_mine_mask writes -inf, in place, into scores[q, c] (c < n) where
+ *     c is an in-shard positive of q,  or  alive != NULL and alive[c] == 0 (uint8 [n]),  or
+ *     bounds != NULL and scores[q, c] > max_ratio * bounds[q]   (ONE fp32 multiply, then the reference's own comparison,
+ *     loss/bi_encoder_losses.py:58-59; with bounds[q] < 0 the threshold therefore lies ABOVE the positive's score, as there;
+ *     a NaN threshold (0 x inf) drops nothing)
+ * and touches nothing else: only changing columns are stored.  bounds is what msim_mine_bounds wrote earlier on the same stream
+ * (or the all-reduced maximum of several shards); NULL skips the comparison (max_ratio is then ignored; NaN is MSIM_EINVAL
+ * otherwise).  With bounds == NULL and alive == NULL only the positives' columns are written.
+ *
+ * msim_gather_pages: out [n_slots, pad_rows, row_bytes] <- the rows of page ids[s] (int64 [n_slots] GLOBAL ids) of the packed
+ * corpus rows [d_rows, row_bytes] / d_off int32 [n_d + 1]: min(len, pad_rows) rows copied, every row after them zero,
+ * lengths[s] (int32) = the rows copied.  A slot whose id is negative or outside [id_base, id_base + n_d), or whose offsets are not
+ * 0 <= d_off[c] <= d_off[c + 1] <= d_rows, is a page of zeros of length 0.  Every byte of out is written.  row_bytes: a positive
+ * multiple of 16 (MSIM_EINVAL otherwise), at most 65536; rows and out 16-byte aligned; d_rows, pad_rows, n_slots <= 2^31 - 1
+ * (MSIM_EUNSUPPORTED).  Bytes moved: n_slots x pad_rows x row_bytes written + the copied rows read + 12 per slot.
+ *
+ * MSIM_EINVAL for a negative size, a null or misaligned pointer, ld < n.  n_q == 0 (n_slots == 0) returns 0 before a pointer is
+ * looked at.  All three are asynchronous on `stream`, allocate nothing, never synchronise with the host and are hipGraph-capturable.
+ */
+int msim_mine_bounds(const float *scores, int64_t ld, int n_q, int64_t n, const int64_t *pos_ids, const int32_t *pos_off, int64_t nnz,
+                     int64_t id_base, const uint8_t *alive /* or NULL */, int local, float *bounds, void *stream);
+int msim_mine_mask(float *scores, int64_t ld, int n_q, int64_t n, const float *bounds /* or NULL */, float max_ratio,
+                   const uint8_t *alive /* or NULL */, const int64_t *pos_ids, const int32_t *pos_off, int64_t nnz, int64_t id_base,
+                   void *stream);
+int msim_gather_pages(const void *rows, int64_t row_bytes, int64_t d_rows, const int32_t *d_off, int n_d, int64_t id_base,
+                      const int64_t *ids, int64_t n_slots, int64_t pad_rows, void *out, int32_t *lengths, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
