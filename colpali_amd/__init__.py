@@ -12,12 +12,15 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      box of the chosen pages for ColbertNegativeCELoss / ColbertPairwiseNegativeCELoss
   * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
+  * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
+                                     centroid interaction): a first stage for prefilter= at 2 bytes per row
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
 colpali_amd/csrc/); this package is the thin host-side mirror of the reference interface.
 """
 from .align import Alignment, align
+from .centroid import CentroidIndex, centroid_scores, train_centroids
 from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pack_queries
 from . import loss
 from .embed import CorpusWriter, embedding_head
@@ -48,6 +51,9 @@ __all__ = [
     "Int8Index",
     "int8_scores",
     "quantize_queries",
+    "CentroidIndex",
+    "centroid_scores",
+    "train_centroids",
     "LiveCorpus",
     "mine_hard_negatives",
     "gather_pages",

@@ -34,6 +34,7 @@
 #include "maxsim_candidates_panels.hip"
 #include "fde.hip"
 #include "int8_index.hip"
+#include "centroid_index.hip"
 #include "live_corpus.hip"
 #include "maxsim_align.hip"
 #include "mine.hip"
@@ -2825,6 +2826,148 @@ int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int 
                                           scores, ld_scores, st);
     return i8_scores_launch<NT, 4, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw,
                                       (int)n_groups, scores, ld_scores, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the centroid-code index (centroid_index.hip)
+namespace {
+
+int cent_check_format(const char *who, int dtype, int dim, int K) {
+    if (dim != msim::kDim) return fail(MSIM_EUNSUPPORTED, "%s: rows of width %d; the centroid index takes width %d", who, dim, msim::kDim);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 rows (dtype code %d)", who, dtype);
+    if (K < msim::kCentMinK || K > msim::kCentMaxK || K % 256 != 0)
+        return fail(MSIM_EINVAL, "%s: %d centroids; the count is a multiple of 256 from %d to %d", who, K, msim::kCentMinK, msim::kCentMaxK);
+    return MSIM_OK;
+}
+
+int cent_blocks(int max_q_tokens) {
+    return max_q_tokens > 0 ? (max_q_tokens + msim::kCentBlockTok - 1) / msim::kCentBlockTok : 1;
+}
+
+struct CentPlan {
+    int nb, ppw, n_pr;
+    long long wgs;
+};
+
+// pages per wave: enough rows behind every table load (K x 64 B per workgroup and block) that the load is a small part of the
+// workgroup's LDS traffic (16 K rows = 16 x the table), but never so many that the chip has fewer than 2 workgroups per CU to run
+CentPlan cent_plan(int n_q, int max_q_tokens, int K, int n_d, int64_t d_rows, int cus) {
+    CentPlan p;
+    p.nb = cent_blocks(max_q_tokens);
+    const long long avg = n_d > 0 && d_rows / n_d > 0 ? d_rows / n_d : 1;
+    const long long amort = (2LL * K + avg - 1) / avg;
+    const long long fill = (long long)n_q * n_d / ((long long)msim::kCentWaves * 2 * (cus > 0 ? cus : 1));
+    long long ppw = amort < fill ? amort : fill;
+    ppw = ppw < 1 ? 1 : ppw > msim::kCentMaxPpw ? msim::kCentMaxPpw : ppw;
+    p.ppw = (int)ppw;
+    const long long per_wg = ppw * msim::kCentWaves;
+    p.n_pr = (int)((n_d + per_wg - 1) / per_wg);
+    p.wgs = (long long)p.n_pr * n_q;
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_cent_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows,
+                          const void *C, int K, uint16_t *codes, int32_t *status, void *stream) {
+    const char *who = "msim_cent_encode_docs";
+    if (n_d < 0 || n_rows < 0 || max_doc_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_d=%d rows=%lld max_doc_rows=%d)", who, n_d, (long long)n_rows, max_doc_rows);
+    if (int rc = cent_check_format(who, dtype, dim, K)) return rc;
+    if (n_d == 0 || max_doc_rows == 0) return MSIM_OK;
+    if ((!D && n_rows > 0) || !d_off || !C || (!codes && n_rows > 0)) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(D, 16) || misaligned(C, 16) || misaligned(codes, 16) || misaligned(d_off, 4) || misaligned(status, 4))
+        return fail(MSIM_EINVAL, "%s: rows, centroids and codes must be 16-byte aligned, offsets and status 4-byte aligned", who);
+    const long long gy = ((long long)max_doc_rows + msim::kCentEncRows - 1) / msim::kCentEncRows;
+    if (gy > 65535) return fail(MSIM_EUNSUPPORTED, "%s: max_doc_rows=%d above %d", who, max_doc_rows, 65535 * msim::kCentEncRows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::cent_encode_kernel<true> : msim::cent_encode_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_d, (unsigned)gy), dim3(256), 0, st, static_cast<const uint16_t *>(D), d_off, n_d,
+                       (long long)n_rows, max_doc_rows, static_cast<const uint16_t *>(C), K, codes, status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "cent_encode_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+size_t msim_cent_table_bytes(int n_q, int max_q_tokens, int K) {
+    if (n_q <= 0 || K <= 0 || max_q_tokens < 0) return 0;
+    return (size_t)n_q * cent_blocks(max_q_tokens) * K * msim::kCentTableRow;
+}
+
+int msim_cent_table(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int dim,
+                    const void *C, int K, void *table, void *stream) {
+    const char *who = "msim_cent_table";
+    if (n_q < 0 || q_rows < 0 || max_q_tokens < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d q_rows=%lld max_q_tokens=%d)", who, n_q, (long long)q_rows, max_q_tokens);
+    if (int rc = cent_check_format(who, dtype, dim, K)) return rc;
+    if (max_q_tokens > msim::kCentMaxTokens)
+        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, msim::kCentMaxTokens);
+    if (n_q == 0) return MSIM_OK;
+    if ((!Qt && q_rows > 0) || !q_off || !C || !table) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(C, 16) || misaligned(table, 16) || misaligned(q_off, 4))
+        return fail(MSIM_EINVAL, "%s: tokens, centroids and table must be 16-byte aligned, offsets 4-byte aligned", who);
+    const int nb = cent_blocks(max_q_tokens);
+    if ((long long)n_q * nb > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld blocks exceed one launch", who, (long long)n_q * nb);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::cent_table_kernel<true> : msim::cent_table_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(n_q * nb), (unsigned)(K / 256)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), q_off,
+                       n_q, (long long)q_rows, nb, static_cast<const uint16_t *>(C), K, static_cast<_Float16 *>(table));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "cent_table_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_cent_scores_plan(int n_q, int max_q_tokens, int K, int n_d, int64_t d_rows, int32_t *plan) {
+    const char *who = "msim_cent_scores_plan";
+    if (n_q < 0 || n_d < 0 || d_rows < 0 || max_q_tokens < 0 || !plan) return fail(MSIM_EINVAL, "%s: bad argument", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const CentPlan p = cent_plan(n_q, max_q_tokens, K, n_d, d_rows, di->cus);
+    plan[0] = p.nb;
+    plan[1] = p.ppw;
+    plan[2] = msim::kCentWaves;
+    plan[3] = (int32_t)(p.wgs > 0x7fffffffLL ? 0x7fffffffLL : p.wgs);
+    return MSIM_OK;
+}
+
+int msim_cent_scores(const void *table, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int K, const uint16_t *codes,
+                     const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, float *scores, int64_t ld_scores,
+                     void *stream) {
+    const char *who = "msim_cent_scores";
+    if (n_q < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d,
+                    (long long)q_rows, (long long)d_rows, max_q_tokens);
+    if (int rc = cent_check_format(who, MSIM_DTYPE_BF16, msim::kDim, K)) return rc;
+    if (max_q_tokens > msim::kCentMaxTokens)
+        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, msim::kCentMaxTokens);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if (!table || !q_off || (!codes && d_rows > 0) || !d_off || !scores) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(table, 16) || misaligned(codes, 16) || misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(scores, 4))
+        return fail(MSIM_EINVAL, "%s: table and codes must be 16-byte aligned; offsets and scores 4-byte aligned", who);
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
+    if (d_rows > 0x7fffffffLL - 1024) return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld exceeds 32-bit row indices", who, (long long)d_rows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const CentPlan p = cent_plan(n_q, max_q_tokens, K, n_d, d_rows, di->cus);
+    if (p.wgs > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld workgroups exceed one launch", who, p.wgs);
+    constexpr int park = msim::kCentWaves * msim::kCentBatch * msim::kCentTableRow;
+    static std::atomic<int> configured[kMaxDevices];
+    if (int rc = allow_lds(msim::cent_scores_kernel, msim::kCentMaxK * msim::kCentTableRow + park, configured)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(msim::cent_scores_kernel, dim3((unsigned)p.wgs), dim3(msim::kCentWaves * 64), K * msim::kCentTableRow + park, st,
+                       static_cast<const _Float16 *>(table), q_off, n_q, (long long)q_rows, p.nb, K, codes, d_off, clamp0, n_d,
+                       (long long)d_rows, p.ppw, p.n_pr, scores, (long long)ld_scores);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "cent_scores_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@ from .align import Alignment, align
 from .corpus import PackedCorpus
 from .corpus import PackedQueries, pack_queries
 from .fde import FdeIndex, fde_scores
+from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
 from .scoring import _require_gpu, maxsim_scores
@@ -206,7 +207,7 @@ class ShardedRetriever:
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
                  rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores,
-                 int8_score_fn: Callable = int8_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
+                 int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask):
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
@@ -214,6 +215,7 @@ class ShardedRetriever:
         self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
         self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
         self._int8_score = int8_score_fn  # (queries, Int8Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Int8Index>
+        self._centroid_score = centroid_score_fn  # (queries, CentroidIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<CentroidIndex>
         self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
         self._mine_bounds = mine_bounds_fn    # (scores, csr, id_base, local=, alive=) -> fp32 [n_q]: the best in-shard positive of each query
         self._mine_mask = mine_mask_fn        # (scores, csr, id_base, bounds, max_ratio, alive) -> scores, -inf where ineligible
@@ -239,7 +241,9 @@ class ShardedRetriever:
         so the answer does not depend on the number of shards), stage 2 reranks that list exactly on the full-resolution shard.
         `prefilter` may also be an `FdeIndex` of the shard (same count, same id_base): stage 1 is then the fixed-dimensional-encoding
         GEMM (`fde_scores`), under the same rules; or an `Int8Index` of the shard or of its pooled pages: stage 1 is then the int8
-        token-level scan (`int8_scores`)."""
+        token-level scan (`int8_scores`); or a `CentroidIndex` of the shard: stage 1 is then the centroid-code scan
+        (`centroid_scores`).  With world > 1 every rank must build its `CentroidIndex` from the SAME centroids: stage-1 scores of
+        different centroid sets are not comparable, and the global top `n_candidates` is taken across the shards."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
         if candidates is not None or prefilter is not None:
@@ -299,16 +303,17 @@ class ShardedRetriever:
         if candidates is not None and prefilter is not None:
             raise ValueError("pass either candidates= or prefilter=, not both")
         if prefilter is not None:
-            if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index)):
-                raise ValueError("prefilter must be a PackedCorpus, an FdeIndex or an Int8Index")
+            if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex)):
+                raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index or a CentroidIndex")
             if len(prefilter) != len(self.shard) or prefilter.id_base != self.shard.id_base:
                 raise ValueError(f"prefilter holds {len(prefilter)} documents from id {prefilter.id_base}; the shard holds "
                                  f"{len(self.shard)} from id {self.shard.id_base}: it must cover the same documents")
             if n_candidates is None or int(n_candidates) < 1:
                 raise ValueError("prefilter= needs n_candidates >= 1")
         stage1 = (self._fde_score if isinstance(prefilter, FdeIndex) else self._int8_score if isinstance(prefilter, Int8Index)
-                  else self._score)
-        uses_kernels = self._rerank is rerank_scores or (prefilter is not None and stage1 in (maxsim_scores, fde_scores, int8_scores))
+                  else self._centroid_score if isinstance(prefilter, CentroidIndex) else self._score)
+        uses_kernels = self._rerank is rerank_scores or (prefilter is not None and
+                                                         stage1 in (maxsim_scores, fde_scores, int8_scores, centroid_scores))
         if uses_kernels and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)

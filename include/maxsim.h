@@ -647,6 +647,47 @@ int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int 
                    int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
 /*
+ * CENTROID-CODE INDEX (centroid_index.hip; additions to ABI 22): every corpus row stored as the uint16 id of its nearest of K
+ * centroids, pages scored by centroid interaction (PLAID's first stage) -- a first stage for two-stage search that reads 2 bytes
+ * per row, reranked exactly by msim_fwd_candidates.  C: K centroid rows [K, 128] in the dtype of the rows they meet; K a multiple
+ * of 256, 256 <= K <= 2048 (the fp16 table of 32 query tokens, K x 64 B, has to fit the 160 KiB LDS).
+ *   Encode (msim_cent_encode_docs): code[r] = argmax_k <row_r, C_k>, each dot product one fp32-accumulated MFMA chain (products
+ *     exact, k ascending in steps of 32); on equal fp32 values the lowest k wins.  codes uint16 [n_rows] in the corpus's row order
+ *     (row r of the input is entry r of the codes).  max_doc_rows: the caller's upper bound on a page's row count.  A page whose
+ *     offsets fall outside 0 .. n_rows, or that is longer than max_doc_rows, gets no codes and status[c] = 1 (every other page:
+ *     0); status int32 [n_d] or NULL.
+ *   Table (msim_cent_table): S[i, k] = fp16(fl32 <q_i, C_k>) (the same chain, rounded to nearest even once) for every token of the
+ *     flat layout, written to table as [n_q * nb][K][32] fp16, nb = max(1, ceil(max_q_tokens / 32)): block b of query q holds its
+ *     tokens 32 b .. 32 b + 31, 0 where the query has no such token (and everywhere for a query whose offsets fall outside
+ *     0 .. q_rows or that is longer than 32 nb).  msim_cent_table_bytes(n_q, max_q_tokens, K) = n_q * nb * K * 64.  A table's bits
+ *     depend on its query and the centroids only.
+ *   Score (msim_cent_scores): M_i = max_j S[i, code_j] over the page's rows j (an exact maximum of fp16 values), max(M_i, 0)
+ *     where clamp0[c] is set; scores[q, c] = the SEQUENTIAL fp32 sum in token order of float(M_i), carried across the 32-token
+ *     blocks.  A page of 0 rows scores -inf, flagged or not; a query of 0 tokens scores 0 against every page that has rows.  A
+ *     page with a code >= K, or whose offsets fall outside 0 .. d_rows, scores NaN (the code is checked before it becomes an
+ *     address; other pages are not affected); so does every page against a query whose offsets fall outside 0 .. q_rows or that
+ *     is longer than 32 nb.  A score's bits depend on its query, the centroids and the page's codes only -- not on the batch,
+ *     the page's position, the launch plan or a rerun; no float atomics.  table and max_q_tokens: as passed to msim_cent_table.
+ *     clamp0: uint8 [n_d] or NULL.  scores fp32 [n_q, ld_scores], ld_scores >= n_d.  d_rows <= 2^31 - 1025.  No workspace.
+ *     msim_cent_scores_plan writes the launch plan of the same arguments: plan[0] = nb, plan[1] = pages per wave (1 .. 64),
+ *     plan[2] = waves per workgroup, plan[3] = workgroups (a workgroup scores one query against plan[1] * plan[2] consecutive
+ *     pages).
+ * Width 128, bf16 / f16 and max_q_tokens <= 128 only (MSIM_EUNSUPPORTED otherwise); K outside the rule is MSIM_EINVAL.  Rows,
+ * centroids, table and codes 16-byte aligned; offsets, status and scores 4-byte aligned.  A call with nothing to do (n_d == 0,
+ * n_q == 0, max_doc_rows == 0) returns 0 before it looks at a pointer.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation: hipGraph-capturable.
+ */
+int msim_cent_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows,
+                          const void *C, int K, uint16_t *codes, int32_t *status /* or NULL */, void *stream);
+size_t msim_cent_table_bytes(int n_q, int max_q_tokens, int K);
+int msim_cent_table(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int dim,
+                    const void *C, int K, void *table, void *stream);
+int msim_cent_scores_plan(int n_q, int max_q_tokens, int K, int n_d, int64_t d_rows, int32_t *plan /* [4] */);
+int msim_cent_scores(const void *table, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int K,
+                     const uint16_t *codes, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d, int64_t d_rows,
+                     float *scores, int64_t ld_scores, void *stream);
+
+/*
  * LIVE CORPUS (live_corpus.hip; additions to ABI 22): a packed corpus whose pages can be deleted and whose rows can be handed
  * back, without a change to any scorer.  A page's slot c never moves (its id stays id_base + c); `alive` uint8 [n_slots] is the
  * tombstone mask (0 = deleted).
