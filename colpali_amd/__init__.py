@@ -10,6 +10,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
   * align / Alignment             -- which page row matched each query token of a search hit, and its similarity maps
   * mine_hard_negatives / gather_pages -- hard negatives by the model's own MaxSim score over the resident corpus, and the padded
                                      box of the chosen pages for ColbertNegativeCELoss / ColbertPairwiseNegativeCELoss
+  * PageFilter                    -- filtered search (ShardedRetriever.search(filter=), LiveCorpus.search(filter=)): the top-k within
+                                     one tenant's / collection's pages, by masking the scan or by listing and reranking them
   * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
@@ -25,6 +27,7 @@ from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pa
 from . import loss
 from .embed import CorpusWriter, embedding_head
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
+from .filter import PageFilter
 from .int8_index import Int8Index, int8_scores, quantize_queries
 from .live import LiveCorpus
 from .mine import gather_pages, mine_hard_negatives
@@ -55,6 +58,7 @@ __all__ = [
     "centroid_scores",
     "train_centroids",
     "LiveCorpus",
+    "PageFilter",
     "mine_hard_negatives",
     "gather_pages",
     "ColbertLoss",

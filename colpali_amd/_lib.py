@@ -199,6 +199,16 @@ def lib() -> ctypes.CDLL:
     L.msim_mine_mask.restype = i32
     L.msim_gather_pages.argtypes = [vp, i64, i64, vp, i32, i64, vp, i64, i64, vp, vp, vp]
     L.msim_gather_pages.restype = i32
+    L.msim_filter_pack.argtypes = [vp, i64, i32, i64, vp, i64, vp]
+    L.msim_filter_pack.restype = i32
+    L.msim_filter_mask.argtypes = [vp, i64, i32, i64, vp, i64, vp, vp, vp, vp]
+    L.msim_filter_mask.restype = i32
+    L.msim_filter_list_workspace_bytes.argtypes = [i32, i64]
+    L.msim_filter_list_workspace_bytes.restype = sz
+    L.msim_filter_list.argtypes = [vp, i64, vp, vp, vp, i32, i64, i64, vp, i64, i32, vp, vp, vp]
+    L.msim_filter_list.restype = i32
+    L.msim_filter_ids.argtypes = [vp, i64, i32, i64, i64, i64, vp, i64, vp, vp, vp, vp]
+    L.msim_filter_ids.restype = i32
     L.msim_align_candidates.argtypes =[i32, vp, vp, i32, i64, i32, vp, vp, vp, i32, i64, i32, vp, i32, i64, i64, vp, vp, vp, i32, vp]
     L.msim_align_candidates.restype = i32
     L.msim_topk_workspace_bytes.argtypes = [i32, i64, i32]

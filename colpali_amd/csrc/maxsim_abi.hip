@@ -38,6 +38,7 @@
 #include "live_corpus.hip"
 #include "maxsim_align.hip"
 #include "mine.hip"
+#include "filter.hip"
 
 namespace {
 
@@ -3172,6 +3173,150 @@ int msim_gather_pages(const void *rows, int64_t row_bytes, int64_t d_rows, const
                        (long long)pad_rows, static_cast<uint8_t *>(out), lengths);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "gather_pages_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- page filters (filter.hip)
+namespace {
+
+// what msim_filter_mask / _list / _ids share: sizes first, then (n_q == 0 || n == 0: nothing to do, *done = true), then the filter
+int filter_check(const char *who, int n_q, int64_t n, const uint32_t *bits, int64_t ld_words, const int32_t *page_labels,
+                 const int32_t *query_labels, const uint8_t *alive, msim::FilterArgs *f, int *mode, bool *done) {
+    *done = false;
+    if (n_q < 0 || n < 0 || ld_words < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld ld_words=%lld)", who, n_q, (long long)n, (long long)ld_words);
+    if (n_q == 0 || n == 0) {
+        *done = true;
+        return MSIM_OK;
+    }
+    if (n > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: n=%lld above 2^31 - 1", who, (long long)n);
+    const bool labels = page_labels || query_labels;
+    if ((bits != nullptr) == labels)
+        return fail(MSIM_EINVAL, "%s: exactly one of (bits) and (page_labels, query_labels) must be given", who);
+    if (labels && (!page_labels || !query_labels)) return fail(MSIM_EINVAL, "%s: page_labels and query_labels go together", who);
+    if (misaligned(bits, 4) || misaligned(page_labels, 4) || misaligned(query_labels, 4))
+        return fail(MSIM_EINVAL, "%s: bits, page_labels and query_labels must be 4-byte aligned", who);
+    if (bits && ld_words != 0 && ld_words < (n + 31) / 32)
+        return fail(MSIM_EINVAL, "%s: ld_words=%lld < ceil(n / 32)=%lld", who, (long long)ld_words, (long long)((n + 31) / 32));
+    *f = msim::FilterArgs{bits, (long long)ld_words, page_labels, query_labels, alive};
+    *mode = labels ? msim::kFilterLabels : ld_words ? msim::kFilterPerQuery : msim::kFilterShared;
+    return MSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_filter_pack(const uint8_t *mask, int64_t ld_mask, int rows, int64_t n, uint32_t *words, int64_t ld_words, void *stream) {
+    const char *who = "msim_filter_pack";
+    if (rows < 0 || n < 0) return fail(MSIM_EINVAL, "%s: negative size (rows=%d n=%lld)", who, rows, (long long)n);
+    if (rows == 0 || n == 0) return MSIM_OK;
+    if (!mask || !words) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(words, 4)) return fail(MSIM_EINVAL, "%s: words must be 4-byte aligned", who);
+    if (ld_mask < n) return fail(MSIM_EINVAL, "%s: ld_mask=%lld < n=%lld", who, (long long)ld_mask, (long long)n);
+    if (ld_words < (n + 31) / 32)
+        return fail(MSIM_EINVAL, "%s: ld_words=%lld < ceil(n / 32)=%lld", who, (long long)ld_words, (long long)((n + 31) / 32));
+    const int64_t tiles = (n + msim::kFilterTileCols - 1) / msim::kFilterTileCols;
+    if (tiles > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)n);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int vec_ok = !misaligned(mask, 4) && (ld_mask % 4 == 0 || rows == 1);
+    const unsigned row_groups = (unsigned)(rows < msim::kFilterRowGroups ? rows : msim::kFilterRowGroups);
+    hipLaunchKernelGGL(msim::filter_pack_kernel, dim3((unsigned)tiles, row_groups), dim3(msim::kFilterThreads), 0, st, mask,
+                       (long long)ld_mask, rows, (long long)n, words, (long long)ld_words, vec_ok);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_pack_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_filter_mask(float *scores, int64_t ld, int n_q, int64_t n, const uint32_t *bits, int64_t ld_words, const int32_t *page_labels,
+                     const int32_t *query_labels, const uint8_t *alive, void *stream) {
+    const char *who = "msim_filter_mask";
+    msim::FilterArgs f;
+    int mode = 0;
+    bool done = false;
+    if (int rc = filter_check(who, n_q, n, bits, ld_words, page_labels, query_labels, alive, &f, &mode, &done)) return rc;
+    if (done) return MSIM_OK;
+    if (!scores || misaligned(scores, 4)) return fail(MSIM_EINVAL, "%s: scores must be a 4-byte aligned pointer", who);
+    if (ld < n) return fail(MSIM_EINVAL, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
+    const int64_t tiles = (n + msim::kFilterTileCols - 1) / msim::kFilterTileCols;
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int vec_ok = !misaligned(scores, 16) && (ld % 4 == 0 || n_q == 1);
+    const int labels_vec_ok = !misaligned(page_labels, 16);
+    const unsigned row_groups = (unsigned)(n_q < msim::kFilterRowGroups ? n_q : msim::kFilterRowGroups);
+    auto kern = mode == msim::kFilterLabels     ? msim::filter_mask_kernel<msim::kFilterLabels>
+                : mode == msim::kFilterPerQuery ? msim::filter_mask_kernel<msim::kFilterPerQuery>
+                                                : msim::filter_mask_kernel<msim::kFilterShared>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, row_groups), dim3(msim::kFilterThreads), 0, st, scores, (long long)ld, n_q, (long long)n,
+                       f, vec_ok, labels_vec_ok);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_mask_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+size_t msim_filter_list_workspace_bytes(int n_q, int64_t n) {
+    (void)n_q, (void)n;
+    return 16;                                           // the status word
+}
+
+int msim_filter_list(const uint32_t *bits, int64_t ld_words, const int32_t *page_labels, const int32_t *query_labels,
+                     const uint8_t *alive, int n_q, int64_t n, int64_t id_base, int64_t *cand, int64_t ld_cand, int m_cap,
+                     int32_t *counts, void *workspace, void *stream) {
+    const char *who = "msim_filter_list";
+    if (m_cap < 0) return fail(MSIM_EINVAL, "%s: negative size (m_cap=%d)", who, m_cap);
+    msim::FilterArgs f;
+    int mode = 0;
+    bool done = false;
+    if (int rc = filter_check(who, n_q, n, bits, ld_words, page_labels, query_labels, alive, &f, &mode, &done)) return rc;
+    if (done) return MSIM_OK;
+    if (!counts || !workspace || (!cand && m_cap > 0)) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(cand, 8) || misaligned(counts, 4) || misaligned(workspace, 16))
+        return fail(MSIM_EINVAL, "%s: cand must be 8-byte, counts 4-byte and workspace 16-byte aligned", who);
+    if (ld_cand < m_cap) return fail(MSIM_EINVAL, "%s: ld_cand=%lld < m_cap=%d", who, (long long)ld_cand, m_cap);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *status = static_cast<int32_t *>(workspace);
+    hipLaunchKernelGGL(msim::filter_status_reset_kernel, dim3(1), dim3(1), 0, st, status);
+    auto kern = mode == msim::kFilterLabels     ? msim::filter_list_kernel<msim::kFilterLabels>
+                : mode == msim::kFilterPerQuery ? msim::filter_list_kernel<msim::kFilterPerQuery>
+                                                : msim::filter_list_kernel<msim::kFilterShared>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_q), dim3(msim::kFilterThreads), 0, st, f, (long long)n, (long long)id_base, cand,
+                       (long long)ld_cand, m_cap, counts, status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_list_kernel launch: %s", hipGetErrorString(e));
+    return MSIM_OK;
+}
+
+int msim_filter_ids(int64_t *ids, int64_t ld, int n_q, int64_t m, int64_t n, int64_t id_base, const uint32_t *bits, int64_t ld_words,
+                    const int32_t *page_labels, const int32_t *query_labels, const uint8_t *alive, void *stream) {
+    const char *who = "msim_filter_ids";
+    if (m < 0) return fail(MSIM_EINVAL, "%s: negative size (m=%lld)", who, (long long)m);
+    msim::FilterArgs f;
+    int mode = 0;
+    bool done = false;
+    if (int rc = filter_check(who, n_q, n, bits, ld_words, page_labels, query_labels, alive, &f, &mode, &done)) return rc;
+    if (done || m == 0) return MSIM_OK;
+    if (!ids || misaligned(ids, 8)) return fail(MSIM_EINVAL, "%s: ids must be an 8-byte aligned pointer", who);
+    if (ld < m) return fail(MSIM_EINVAL, "%s: ld=%lld < m=%lld", who, (long long)ld, (long long)m);
+    const int64_t tiles = (m + msim::kFilterThreads - 1) / msim::kFilterThreads;
+    if (tiles > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)m);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned row_groups = (unsigned)(n_q < 65535 ? n_q : 65535);
+    auto kern = mode == msim::kFilterLabels     ? msim::filter_ids_kernel<msim::kFilterLabels>
+                : mode == msim::kFilterPerQuery ? msim::filter_ids_kernel<msim::kFilterPerQuery>
+                                                : msim::filter_ids_kernel<msim::kFilterShared>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, row_groups), dim3(msim::kFilterThreads), 0, st, ids, (long long)ld, n_q, (long long)m,
+                       (long long)n, (long long)id_base, f);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_ids_kernel launch: %s", hipGetErrorString(e));
     return MSIM_OK;
 }
 

@@ -20,6 +20,8 @@ from .align import Alignment, align
 from .corpus import PackedCorpus
 from .corpus import PackedQueries, pack_queries
 from .fde import FdeIndex, fde_scores
+from . import filter as _filter
+from .filter import PageFilter, filter_ids, filter_list, filter_mask
 from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
@@ -208,7 +210,8 @@ class ShardedRetriever:
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
                  rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores,
                  int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
-                 mine_mask_fn: Callable = mine_mask):
+                 mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
+                 filter_ids_fn: Callable = filter_ids):
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
@@ -219,6 +222,9 @@ class ShardedRetriever:
         self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
         self._mine_bounds = mine_bounds_fn    # (scores, csr, id_base, local=, alive=) -> fp32 [n_q]: the best in-shard positive of each query
         self._mine_mask = mine_mask_fn        # (scores, csr, id_base, bounds, max_ratio, alive) -> scores, -inf where ineligible
+        self._filter_mask = filter_mask_fn    # (scores, PageFilter, alive) -> scores, -inf where the page is not allowed
+        self._filter_list = filter_list_fn    # (PageFilter, n_q, m_cap, alive) -> (cand int64 [n_q, m_cap], counts, status)
+        self._filter_ids = filter_ids_fn      # (ids, PageFilter, alive) -> ids, -1 where an in-shard id is not allowed (in place)
         self.force_collective = force_collective
         if world > 1 and dist is None:
             import torch.distributed as dist_mod
@@ -226,7 +232,8 @@ class ShardedRetriever:
             self.dist = dist_mod
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None,
-               prefilter=None, n_candidates: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               prefilter=None, n_candidates: Optional[int] = None, filter: Optional[PageFilter] = None,
+               filter_route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
         """queries (replicated on every rank): a `PackedQueries`, a list of [len_i, 128] tensors, or a [n_q, Lq, 128] tensor.
         A host list is packed into the flat layout (ragged lengths, zero rows dropped on the way into the staging buffer).  A dense
         DEVICE tensor is scored as it stands unless `compact=True`: dropping its zero padding rows needs the per-query counts on the
@@ -243,9 +250,34 @@ class ShardedRetriever:
         GEMM (`fde_scores`), under the same rules; or an `Int8Index` of the shard or of its pooled pages: stage 1 is then the int8
         token-level scan (`int8_scores`); or a `CentroidIndex` of the shard: stage 1 is then the centroid-code scan
         (`centroid_scores`).  With world > 1 every rank must build its `CentroidIndex` from the SAME centroids: stage-1 scores of
-        different centroid sets are not comparable, and the global top `n_candidates` is taken across the shards."""
+        different centroid sets are not comparable, and the global top `n_candidates` is taken across the shards.
+
+        Filtered search: `filter` -- a `PageFilter` over this shard (same count, same id_base, same device; ValueError otherwise, and
+        for a per-query filter whose rows differ from the number of queries) -- restricts every query to its allowed pages.  For each
+        query the result is the allowed pages whose full-scan score is not -inf, ordered by (score descending, id ascending), cut
+        at k and padded with (-inf, -1); the scores carry the bits of `maxsim_scores(queries, shard)`.  An id is -1 WHEREVER the
+        score is -inf: unlike the unfiltered search, an empty (0-row) page never comes back with its id.  The answer does not depend
+        on the number of shards.  Two routes give that answer, chosen by `filter_route`:
+          "mask"  the scan as without a filter, -inf over the columns that are not allowed (`filter_mask`), the top-k.  Every dtype
+                  and width the scan takes.
+          "list"  the allowed pages of every query as an id list (`filter_list`, `filter.max_allowed` wide), `rerank_scores` on that
+                  list, the top-k: only the allowed pages are read.  The formats of `rerank` (bfloat16 / float16, width 128 or 320,
+                  queries of at most 128 tokens; NotImplementedError otherwise); not with `candidates=` / `prefilter=` (ValueError).
+          "auto"  "list" when the formats fit, neither `candidates=` nor `prefilter=` is given, n_q x max_allowed < 2^31 and
+                  max_allowed <= len(shard) x `filter.LIST_ROUTE_MAX_FRACTION`; "mask" otherwise.
+        At width 128 the two routes are bit-identical.  At width 320 the rerank carries the bits of the flat scan kernel every ragged
+        batch runs; a scan of ONE query length and at most four 32-token tiles runs another kernel, whose token sum is a butterfly:
+        against such a scan the list route agrees to the bound include/maxsim.h states for msim_fwd_candidates_wide, not bit for bit.
+        With `prefilter=` the filter masks the stage-1 scores, so all `n_candidates` are allowed pages, and a candidate whose stage-1
+        score is -inf becomes -1 (it is not reranked); stage 2 is unchanged.  With `candidates=` the disallowed ids of this shard
+        become -1 before the rerank (`filter_ids`).  `search` calls `filter.prepare()` on first use (one host synchronisation); with
+        a prepared filter and a `PackedQueries` the call is hipGraph-capturable."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
+        if filter is not None:
+            return self._search_filtered(queries, k, compact, candidates, prefilter, n_candidates, filter, filter_route)
+        if filter_route != "auto":
+            raise ValueError("filter_route goes with filter=")
         if candidates is not None or prefilter is not None:
             return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates)
         if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
@@ -299,7 +331,67 @@ class ShardedRetriever:
             return shard_topk(s, k, id_base, self.world, self.dist, self.group, self._select, force_collective=self.force_collective)
         return select_window(masked, int(self.shard.id_base), n_neg, skip_top, shard_select)
 
-    def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates):
+    def _list_formats_fit(self, queries) -> bool:
+        """what `rerank_scores` takes: bfloat16 / float16, width 128 or 320, at most 128 tokens per query (host metadata only)"""
+        q_dtype, dim = _query_format(queries)
+        blob = self.shard.blob
+        if q_dtype != blob.dtype or q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or blob.shape[1] != dim:
+            return False
+        if isinstance(queries, PackedQueries):
+            return len(queries) == 0 or int(queries.lengths.max()) <= 128
+        if isinstance(queries, torch.Tensor):
+            return int(queries.shape[1]) <= 128
+        return all(int(q.shape[0]) <= 128 for q in queries)
+
+    def _search_filtered(self, queries, k, compact, candidates, prefilter, n_candidates, flt, route):
+        if route not in ("auto", "mask", "list"):
+            raise ValueError(f"filter_route={route!r}: 'auto', 'mask' or 'list'")
+        if not isinstance(flt, PageFilter):
+            raise ValueError("filter must be a PageFilter")
+        shard = self.shard
+        if len(flt) != len(shard) or flt.id_base != shard.id_base:
+            raise ValueError(f"filter covers {len(flt)} pages from id {flt.id_base}; the shard holds {len(shard)} from id "
+                             f"{shard.id_base}: it must cover the same pages")
+        if flt.device != shard.device:
+            raise ValueError(f"the filter lives on {flt.device}, the shard on {shard.device}")
+        two_stage = candidates is not None or prefilter is not None
+        if two_stage:
+            if route == "list":
+                raise ValueError("filter_route='list' lists the allowed pages itself: it does not go with candidates= / prefilter=")
+            top_s, top_i = self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt)
+        else:
+            if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
+                dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+                queries = pack_queries(queries, shard.device, compact=compact or not dense_on_device)
+            n_q = len(queries)
+            self._check_filter_rows(flt, n_q)
+            flt.prepare()
+            fits = self._list_formats_fit(queries)
+            if route == "list" and not fits:
+                q_dtype, dim = _query_format(queries)
+                raise NotImplementedError(f"filter_route='list' reranks the listed pages: rerank takes bfloat16 / float16 embeddings of "
+                                          f"width 128 or 320 and queries of at most 128 tokens (got {q_dtype}, width {dim}, corpus "
+                                          f"{shard.blob.dtype} of width {shard.blob.shape[1]})")
+            if route == "auto":
+                route = "list" if (fits and n_q * flt.max_allowed < 2**31
+                                   and flt.max_allowed <= len(shard) * _filter.LIST_ROUTE_MAX_FRACTION) else "mask"
+            if route == "list":
+                cand = self._filter_list(flt, n_q, max(flt.max_allowed, 1), None)[0]
+                scores, ids = self._rerank(queries, shard, cand)
+                top_s, top_i = shard_topk(scores, k, 0, self.world, self.dist, self.group, self._select,
+                                          force_collective=self.force_collective, ids=ids)
+            else:
+                scores = self._filter_mask(self._score(queries, shard), flt, None)
+                top_s, top_i = shard_topk(scores, k, shard.id_base, self.world, self.dist, self.group, self._select,
+                                          force_collective=self.force_collective)
+        return top_s, torch.where(top_s == float("-inf"), torch.full_like(top_i, -1), top_i)     # -inf is "no page", whatever filled the row
+
+    @staticmethod
+    def _check_filter_rows(flt, n_q):
+        if flt.rows is not None and flt.rows != n_q:
+            raise ValueError(f"a per-query filter of {flt.rows} rows was given for {n_q} queries")
+
+    def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates, flt=None):
         if candidates is not None and prefilter is not None:
             raise ValueError("pass either candidates= or prefilter=, not both")
         if prefilter is not None:
@@ -317,10 +409,21 @@ class ShardedRetriever:
         if uses_kernels and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
+        if flt is not None:
+            self._check_filter_rows(flt, len(queries))
         if prefilter is not None:
             coarse = stage1(queries, prefilter)                          # stage 1: the cheap corpus, or the encodings
-            _, candidates = shard_topk(coarse, int(n_candidates), prefilter.id_base, self.world, self.dist, self.group, self._select,
-                                       force_collective=self.force_collective)
+            if flt is not None:
+                coarse = self._filter_mask(coarse, flt, None)            # all n_candidates are allowed pages
+            cand_s, candidates = shard_topk(coarse, int(n_candidates), prefilter.id_base, self.world, self.dist, self.group, self._select,
+                                            force_collective=self.force_collective)
+            if flt is not None:                                          # a masked column that filled a short list is not reranked
+                candidates = torch.where(cand_s == float("-inf"), torch.full_like(candidates, -1), candidates)
+        elif flt is not None:
+            if (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2
+                    or candidates.shape[0] != len(queries) or candidates.device != self.shard.device):
+                raise ValueError(f"candidates must be an int64 [n_q={len(queries)}, m] tensor on {self.shard.device}")
+            candidates = self._filter_ids(candidates.clone(memory_format=torch.contiguous_format), flt, None)
         scores, ids = self._rerank(queries, self.shard, candidates)      # stage 2: exact, this shard's candidates only
         return shard_topk(scores, k, 0, self.world, self.dist, self.group, self._select, force_collective=self.force_collective,
                           ids=ids)

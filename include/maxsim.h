@@ -756,6 +756,58 @@ int msim_mine_mask(float *scores, int64_t ld, int n_q, int64_t n, const float *b
 int msim_gather_pages(const void *rows, int64_t row_bytes, int64_t d_rows, const int32_t *d_off, int n_d, int64_t id_base,
                       const int64_t *ids, int64_t n_slots, int64_t pad_rows, void *out, int32_t *lengths, void *stream);
 
+/*
+ * PAGE FILTERS (filter.hip; additions to ABI 22): which pages of a shard each query may return -- a tenant, a collection, the pages a
+ * metadata query matched.  A filter either masks a score matrix ("mask, then msim_topk_f32", as mining does) or becomes a candidate
+ * list for msim_fwd_candidates; no scorer and no selection kernel changes.
+ *
+ * A filter over the n pages of a shard (page c has id id_base + c) is given in exactly one of two forms:
+ *     bits         uint32 words, bit c % 32 of word c / 32 is page c (1 = allowed).  ld_words == 0: ONE row of ceil(n / 32) words
+ *                  shared by every query; otherwise [n_q, ld_words], ld_words >= ceil(n / 32), one row per query.  Bits at
+ *                  positions >= n are never relied upon: every consumer clips to n.
+ *     labels       page_labels int32 [n] and query_labels int32 [n_q]: page c is allowed for q iff page_labels[c] ==
+ *                  query_labels[q].  No [n_q, n] object exists anywhere.
+ * alive (uint8 [n], or NULL) is ANDed in: alive[c] == 0 is a deleted page, allowed for nobody.
+ *
+ * msim_filter_pack: mask bytes [rows, ld_mask] (ld_mask >= n, any alignment; non-zero = allowed) -> words [rows, ld_words],
+ * ld_words >= ceil(n / 32).  Words 0 .. ceil(n / 32) - 1 of every row are written, bits at positions >= n as 0.  One wave ballot
+ * yields two words; the mask is read 4 bytes per lane where its rows are 4-byte aligned.
+ *
+ * msim_filter_mask writes -inf, in place, into scores[q, c] (fp32 [n_q, ld], ld >= n, 4-byte aligned; c < n) wherever page c is not
+ * allowed for q or is not alive, and touches nothing else: the scores are never read, only changing columns are stored (a kept
+ * column keeps its bits, NaN and -0.0 included), 16 bytes at a time where four neighbours change and the rows are 16-byte aligned;
+ * rows of any 4-byte alignment work.
+ *
+ * msim_filter_list, the ordered compaction: for every query row q the GLOBAL ids id_base + c of its allowed and alive pages go,
+ * ascending, into cand[q, 0 .. count) (int64 [n_q, ld_cand], ld_cand >= m_cap); cand[q, count .. m_cap) = -1; counts[q] (int32) =
+ * the true count.  A shared filter writes the same list into all n_q rows.  A row with more than m_cap allowed pages keeps its first
+ * m_cap, reports the true count and sets the status word (msim_fwd_candidates' convention): the first int32 of `workspace`
+ * (msim_filter_list_workspace_bytes(n_q, n) bytes, 16-byte aligned, initialised by the call) is 0 once the call's work is done, or
+ * 1 when a row overflowed.  The order is by construction, not by sorting: one workgroup per row walks the row in passes of
+ * S = 8192 columns (256 lanes x one 32-bit word), and a popcount per lane, a wave prefix, a per-wave carry through LDS and a running
+ * carry across passes give every page its position.  No atomics.  n <= 2^31 - 1 (MSIM_EUNSUPPORTED).
+ *
+ * msim_filter_ids: in ids (int64 [n_q, ld], m columns, GLOBAL ids) every id inside [id_base, id_base + n) that is not allowed for
+ * its row, or not alive, becomes -1, in place.  -1 and ids outside the shard are left alone: another rank holds them, and
+ * msim_fwd_candidates answers them with (-inf, -1).
+ *
+ * MSIM_EINVAL for a negative size, a null or misaligned pointer, ld < n (ld_mask < n, ld_cand < m_cap, ld < m, 0 < ld_words <
+ * ceil(n / 32)), and for both or neither of (bits) and (page_labels, query_labels).  n_q == 0 (rows == 0) or n == 0 returns 0
+ * before a pointer is looked at (and writes nothing).  All are asynchronous on `stream`, allocate nothing, never synchronise with
+ * the host and are hipGraph-capturable.
+ */
+int msim_filter_pack(const uint8_t *mask, int64_t ld_mask, int rows, int64_t n, uint32_t *words, int64_t ld_words, void *stream);
+int msim_filter_mask(float *scores, int64_t ld, int n_q, int64_t n, const uint32_t *bits /* or NULL */, int64_t ld_words,
+                     const int32_t *page_labels /* or NULL */, const int32_t *query_labels /* or NULL */,
+                     const uint8_t *alive /* or NULL */, void *stream);
+size_t msim_filter_list_workspace_bytes(int n_q, int64_t n);
+int msim_filter_list(const uint32_t *bits /* or NULL */, int64_t ld_words, const int32_t *page_labels /* or NULL */,
+                     const int32_t *query_labels /* or NULL */, const uint8_t *alive /* or NULL */, int n_q, int64_t n,
+                     int64_t id_base, int64_t *cand, int64_t ld_cand, int m_cap, int32_t *counts, void *workspace, void *stream);
+int msim_filter_ids(int64_t *ids, int64_t ld, int n_q, int64_t m, int64_t n, int64_t id_base, const uint32_t *bits /* or NULL */,
+                    int64_t ld_words, const int32_t *page_labels /* or NULL */, const int32_t *query_labels /* or NULL */,
+                    const uint8_t *alive /* or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
