@@ -1,0 +1,357 @@
+// C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the first-stage indexes -- fixed dimensional encodings, the int8
+// token-level index and the centroid-code index.
+// Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
+// frees or synchronises, so every entry point is hipGraph-capturable.  The kernels included below are defined and launched in
+// this translation unit and in no other.
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+
+#include "../../include/maxsim.h"
+#include "abi_common.hpp"
+#include "fde.hip"
+#include "int8_index.hip"
+#include "centroid_index.hip"
+
+using namespace msim_abi;
+
+// ---------------------------------------------------------------- fixed dimensional encodings (fde.hip)
+namespace {
+
+// the encoding's configuration: what the kernels implement, or MSIM_EUNSUPPORTED / MSIM_EINVAL
+int fde_check_config(const char *who, int dtype, int dim, int reps, int ksim, int dproj, long long *F_out) {
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || dim != msim::kDim)
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 embeddings of width %d (dtype code %d, dim %d)", who, msim::kDim,
+                    dtype, dim);
+    if (reps < 1) return fail(MSIM_EINVAL, "%s: reps=%d < 1", who, reps);
+    if (ksim < 1 || ksim > msim::kFdeMaxKsim) return fail(MSIM_EUNSUPPORTED, "%s: k_sim=%d outside 1..%d", who, ksim, msim::kFdeMaxKsim);
+    if (!(dproj == 8 || dproj == 16 || dproj == 32 || dproj == 64))
+        return fail(MSIM_EUNSUPPORTED, "%s: d_proj=%d is not 8, 16, 32 or 64", who, dproj);
+    const long long F = (long long)reps * (1LL << ksim) * dproj;
+    if (F % 256 != 0 || F > 65536)
+        return fail(MSIM_EUNSUPPORTED, "%s: F = reps x 2^k_sim x d_proj = %lld must be a multiple of 256 and at most 65536", who, F);
+    *F_out = F;
+    return MSIM_OK;
+}
+
+int fde_encode(const char *who, int dtype, const void *X, const int32_t *off, int n, int64_t n_rows, int dim, const float *G,
+               const float *S, int reps, int ksim, int dproj, int is_doc, int fill_empty, void *out, uint8_t *codes, void *stream) {
+    if (n < 0 || n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (n=%d rows=%lld)", who, n, (long long)n_rows);
+    long long F = 0;
+    if (int rc = fde_check_config(who, dtype, dim, reps, ksim, dproj, &F)) return rc;
+    if (n == 0) return MSIM_OK;
+    if ((!X && n_rows > 0) || !off || !G || !S || !out) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(out) & 1))
+        return fail(MSIM_EINVAL, "%s: the rows must be 16-byte aligned and the output 2-byte aligned", who);
+    if (fill_empty != 0 && fill_empty != 1) return fail(MSIM_EINVAL, "%s: fill_empty=%d is not 0 or 1", who, fill_empty);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = f16 ? msim::fde_encode_kernel<true> : msim::fde_encode_kernel<false>;
+    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
+    constexpr int kMaxLds = msim::fde_encode_lds_bytes(msim::kFdeMaxKsim, 64);
+    if (int rc = allow_lds(kern, kMaxLds, f16 ? configured_f16 : configured_bf16)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(256), msim::fde_encode_lds_bytes(ksim, dproj), st, static_cast<const uint16_t *>(X),
+                       off, n, (long long)n_rows, G, S, reps, ksim, dproj, is_doc, fill_empty, static_cast<uint16_t *>(out), codes);
+    return launch_failed("fde_encode_kernel");
+}
+
+template <int QB, int DB, int NBUF>
+int fde_scores_launch(bool f16, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld, hipStream_t st) {
+    auto kern = f16 ? msim::fde_scores_kernel<QB, DB, NBUF, true> : msim::fde_scores_kernel<QB, DB, NBUF, false>;
+    constexpr int lds = msim::fde_scores_lds_bytes<QB, DB, NBUF>();
+    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
+    if (int rc = allow_lds(kern, lds, f16 ? configured_f16 : configured_bf16)) return rc;
+    const long long n_qt = (n_q + QB - 1) / QB, n_dt = ((long long)n_d + DB - 1) / DB;
+    if (n_qt * n_dt > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "msim_fde_scores: %lld tiles exceed one launch", n_qt * n_dt);
+    const int vec = (reinterpret_cast<uintptr_t>(scores) & 15) == 0 && (ld & 3) == 0;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(n_qt * n_dt)), dim3(256), lds, st, static_cast<const uint16_t *>(Fq), n_q,
+                       static_cast<const uint16_t *>(Fd), n_d, F, scores, (long long)ld, (int)n_qt, vec);
+    return launch_failed("fde_scores_kernel");
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_fde_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, const float *G, const float *S,
+                         int reps, int ksim, int dproj, int fill_empty, void *out, uint8_t *codes, void *stream) {
+    return fde_encode("msim_fde_encode_docs", dtype, D, d_off, n_d, n_rows, dim, G, S, reps, ksim, dproj, 1, fill_empty, out, codes,
+                      stream);
+}
+
+int msim_fde_encode_queries(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t n_rows, int dim, const float *G,
+                            const float *S, int reps, int ksim, int dproj, void *out, uint8_t *codes, void *stream) {
+    return fde_encode("msim_fde_encode_queries", dtype, Qt, q_off, n_q, n_rows, dim, G, S, reps, ksim, dproj, 0, 0, out, codes, stream);
+}
+
+int msim_fde_scores(int dtype, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld_scores, void *stream) {
+    if (n_q < 0 || n_d < 0 || F < 0) return fail(MSIM_EINVAL, "msim_fde_scores: negative size (n_q=%d n_d=%d F=%d)", n_q, n_d, F);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
+        return fail(MSIM_EUNSUPPORTED, "msim_fde_scores takes bfloat16 / float16 encodings (dtype code %d)", dtype);
+    if (F % 256 != 0 || F == 0 || F > 65536)
+        return fail(MSIM_EUNSUPPORTED, "msim_fde_scores: F=%d must be a positive multiple of 256, at most 65536", F);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if (!Fq || !Fd || !scores) return fail(MSIM_EINVAL, "msim_fde_scores: null pointer argument");
+    if ((reinterpret_cast<uintptr_t>(Fq) | reinterpret_cast<uintptr_t>(Fd)) & 15)
+        return fail(MSIM_EINVAL, "msim_fde_scores: Fq and Fd must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(scores) & 3)) return fail(MSIM_EINVAL, "msim_fde_scores: scores must be 4-byte aligned");
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "msim_fde_scores: ld_scores=%lld < n_d=%d", (long long)ld_scores, n_d);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    // a few queries: a narrow query tile and a 4-deep ring (HBM-bound: Fd streams once); many: 128 x 128 tiles (MFMA-bound)
+    if (n_q <= 64) return fde_scores_launch<32, 128, 4>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
+    return fde_scores_launch<128, 128, 2>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the int8 token-level index (int8_index.hip)
+namespace {
+
+int i8_check_rows(const char *who, int dtype, int dim) {
+    if (dim != msim::kDim) return fail(MSIM_EINVAL, "%s: rows of width %d; the int8 index takes width %d", who, dim, msim::kDim);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 rows (dtype code %d)", who, dtype);
+    return MSIM_OK;
+}
+
+template <int NT, int GW, int D>
+int i8_scores_launch(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int QG, int TPQ, int passes,
+                     const int8_t *d8, const float *sd, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int ppw,
+                     int n_groups, float *scores, int64_t ld, hipStream_t st) {
+    const long long n_gb = (n_groups + GW - 1) / GW;
+    const long long n_ranges = ((long long)n_d + ppw - 1) / ppw, n_pb = (n_ranges + 4 / GW - 1) / (4 / GW);
+    if (n_gb * n_pb > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "msim_i8_scores: %lld workgroups exceed one launch", n_gb * n_pb);
+    hipLaunchKernelGGL((msim::i8_scores_kernel<NT, GW, D>), dim3((unsigned)(n_gb * n_pb)), dim3(256), 0, st, q8, sq, q_off, n_q,
+                       (long long)q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, (long long)d_rows, ppw, n_groups, (int)n_gb,
+                       scores, (long long)ld);
+    return launch_failed("i8_scores_kernel");
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_i8_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int8_t *codes, float *scales,
+                        void *stream) {
+    const char *who = "msim_i8_encode_docs";
+    if (n_d < 0 || n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (n_d=%d rows=%lld)", who, n_d, (long long)n_rows);
+    if (int rc = i8_check_rows(who, dtype, dim)) return rc;
+    if (n_d == 0) return MSIM_OK;
+    if ((!D && n_rows > 0) || !d_off || (!codes && n_rows > 0) || !scales) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(D, 16) || misaligned(codes, 16) || misaligned(d_off, 4) || misaligned(scales, 4))
+        return fail(MSIM_EINVAL, "%s: rows and codes must be 16-byte aligned, offsets and scales 4-byte aligned", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::i8_encode_docs_kernel<true> : msim::i8_encode_docs_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_d), dim3(256), 0, st, static_cast<const uint16_t *>(D), d_off, n_d, (long long)n_rows, codes,
+                       scales);
+    return launch_failed("i8_encode_docs_kernel");
+}
+
+int msim_i8_encode_queries(int dtype, const void *Qt, int64_t n_rows, int dim, int8_t *codes, float *scales, void *stream) {
+    const char *who = "msim_i8_encode_queries";
+    if (n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (rows=%lld)", who, (long long)n_rows);
+    if (int rc = i8_check_rows(who, dtype, dim)) return rc;
+    if (n_rows == 0) return MSIM_OK;
+    if (!Qt || !codes || !scales) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(codes, 16) || misaligned(scales, 4))
+        return fail(MSIM_EINVAL, "%s: rows and codes must be 16-byte aligned, scales 4-byte aligned", who);
+    if ((n_rows + 15) / 16 > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld rows exceed one launch", who, (long long)n_rows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::i8_encode_rows_kernel<true> : msim::i8_encode_rows_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n_rows + 15) / 16)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), (long long)n_rows,
+                       codes, scales);
+    return launch_failed("i8_encode_rows_kernel");
+}
+
+int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, const int8_t *d8,
+                   const float *sd, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int dim, float *scores,
+                   int64_t ld_scores, void *stream) {
+    const char *who = "msim_i8_scores";
+    if (n_q < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d,
+                    (long long)q_rows, (long long)d_rows, max_q_tokens);
+    if (dim != msim::kDim) return fail(MSIM_EINVAL, "%s: rows of width %d; the int8 index takes width %d", who, dim, msim::kDim);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if ((!q8 && q_rows > 0) || (!sq && q_rows > 0) || !q_off || (!d8 && d_rows > 0) || !sd || !d_off || !scores)
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(q8, 16) || misaligned(d8, 16) || misaligned(sq, 4) || misaligned(sd, 4) || misaligned(q_off, 4) ||
+        misaligned(d_off, 4) || misaligned(scores, 4))
+        return fail(MSIM_EINVAL, "%s: codes must be 16-byte aligned; scales, offsets and scores 4-byte aligned", who);
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
+    if (max_q_tokens > (1 << 20)) return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, 1 << 20);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the query plan: every query gets TPQ 16-token tiles, QG queries fill one wave's NT tiles; a longer query takes several passes
+    constexpr int NT = 8;
+    const int tiles = max_q_tokens ? (max_q_tokens + msim::kI8Tile - 1) / msim::kI8Tile : 1;
+    int QG = 1, TPQ = NT, passes = 1;
+    if (tiles <= NT) {
+        TPQ = tiles;
+        QG = NT / tiles;
+    } else {
+        passes = (tiles + NT - 1) / NT;
+    }
+    const long long n_groups = ((long long)n_q + QG - 1) / QG;
+    // page ranges: enough waves to fill the chip (8 per CU, ~4 rounds); at most 16 pages a range when several query groups re-read it
+    const long long want = (long long)di->cus * 32;
+    const long long work = n_groups * n_d;
+    const int cap = n_groups == 1 ? msim::kI8MaxRange : 16;
+    long long ppw = (work + want - 1) / want;
+    ppw = ppw < 1 ? 1 : ppw > cap ? cap : ppw;
+    if (n_groups == 1)
+        return i8_scores_launch<NT, 1, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw, 1,
+                                          scores, ld_scores, st);
+    if (n_groups == 2)
+        return i8_scores_launch<NT, 2, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw, 2,
+                                          scores, ld_scores, st);
+    return i8_scores_launch<NT, 4, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw,
+                                      (int)n_groups, scores, ld_scores, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the centroid-code index (centroid_index.hip)
+namespace {
+
+int cent_check_format(const char *who, int dtype, int dim, int K) {
+    if (dim != msim::kDim) return fail(MSIM_EUNSUPPORTED, "%s: rows of width %d; the centroid index takes width %d", who, dim, msim::kDim);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 rows (dtype code %d)", who, dtype);
+    if (K < msim::kCentMinK || K > msim::kCentMaxK || K % 256 != 0)
+        return fail(MSIM_EINVAL, "%s: %d centroids; the count is a multiple of 256 from %d to %d", who, K, msim::kCentMinK, msim::kCentMaxK);
+    return MSIM_OK;
+}
+
+int cent_blocks(int max_q_tokens) {
+    return max_q_tokens > 0 ? (max_q_tokens + msim::kCentBlockTok - 1) / msim::kCentBlockTok : 1;
+}
+
+struct CentPlan {
+    int nb, ppw, n_pr;
+    long long wgs;
+};
+
+// pages per wave: enough rows behind every table load (K x 64 B per workgroup and block) that the load is a small part of the
+// workgroup's LDS traffic (16 K rows = 16 x the table), but never so many that the chip has fewer than 2 workgroups per CU to run
+CentPlan cent_plan(int n_q, int max_q_tokens, int K, int n_d, int64_t d_rows, int cus) {
+    CentPlan p;
+    p.nb = cent_blocks(max_q_tokens);
+    const long long avg = n_d > 0 && d_rows / n_d > 0 ? d_rows / n_d : 1;
+    const long long amort = (2LL * K + avg - 1) / avg;
+    const long long fill = (long long)n_q * n_d / ((long long)msim::kCentWaves * 2 * (cus > 0 ? cus : 1));
+    long long ppw = amort < fill ? amort : fill;
+    ppw = ppw < 1 ? 1 : ppw > msim::kCentMaxPpw ? msim::kCentMaxPpw : ppw;
+    p.ppw = (int)ppw;
+    const long long per_wg = ppw * msim::kCentWaves;
+    p.n_pr = (int)((n_d + per_wg - 1) / per_wg);
+    p.wgs = (long long)p.n_pr * n_q;
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_cent_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows,
+                          const void *C, int K, uint16_t *codes, int32_t *status, void *stream) {
+    const char *who = "msim_cent_encode_docs";
+    if (n_d < 0 || n_rows < 0 || max_doc_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_d=%d rows=%lld max_doc_rows=%d)", who, n_d, (long long)n_rows, max_doc_rows);
+    if (int rc = cent_check_format(who, dtype, dim, K)) return rc;
+    if (n_d == 0 || max_doc_rows == 0) return MSIM_OK;
+    if ((!D && n_rows > 0) || !d_off || !C || (!codes && n_rows > 0)) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(D, 16) || misaligned(C, 16) || misaligned(codes, 16) || misaligned(d_off, 4) || misaligned(status, 4))
+        return fail(MSIM_EINVAL, "%s: rows, centroids and codes must be 16-byte aligned, offsets and status 4-byte aligned", who);
+    const long long gy = ((long long)max_doc_rows + msim::kCentEncRows - 1) / msim::kCentEncRows;
+    if (gy > 65535) return fail(MSIM_EUNSUPPORTED, "%s: max_doc_rows=%d above %d", who, max_doc_rows, 65535 * msim::kCentEncRows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::cent_encode_kernel<true> : msim::cent_encode_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_d, (unsigned)gy), dim3(256), 0, st, static_cast<const uint16_t *>(D), d_off, n_d,
+                       (long long)n_rows, max_doc_rows, static_cast<const uint16_t *>(C), K, codes, status);
+    return launch_failed("cent_encode_kernel");
+}
+
+size_t msim_cent_table_bytes(int n_q, int max_q_tokens, int K) {
+    if (n_q <= 0 || K <= 0 || max_q_tokens < 0) return 0;
+    return (size_t)n_q * cent_blocks(max_q_tokens) * K * msim::kCentTableRow;
+}
+
+int msim_cent_table(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int dim,
+                    const void *C, int K, void *table, void *stream) {
+    const char *who = "msim_cent_table";
+    if (n_q < 0 || q_rows < 0 || max_q_tokens < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d q_rows=%lld max_q_tokens=%d)", who, n_q, (long long)q_rows, max_q_tokens);
+    if (int rc = cent_check_format(who, dtype, dim, K)) return rc;
+    if (max_q_tokens > msim::kCentMaxTokens)
+        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, msim::kCentMaxTokens);
+    if (n_q == 0) return MSIM_OK;
+    if ((!Qt && q_rows > 0) || !q_off || !C || !table) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(C, 16) || misaligned(table, 16) || misaligned(q_off, 4))
+        return fail(MSIM_EINVAL, "%s: tokens, centroids and table must be 16-byte aligned, offsets 4-byte aligned", who);
+    const int nb = cent_blocks(max_q_tokens);
+    if ((long long)n_q * nb > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld blocks exceed one launch", who, (long long)n_q * nb);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::cent_table_kernel<true> : msim::cent_table_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(n_q * nb), (unsigned)(K / 256)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), q_off,
+                       n_q, (long long)q_rows, nb, static_cast<const uint16_t *>(C), K, static_cast<_Float16 *>(table));
+    return launch_failed("cent_table_kernel");
+}
+
+int msim_cent_scores_plan(int n_q, int max_q_tokens, int K, int n_d, int64_t d_rows, int32_t *plan) {
+    const char *who = "msim_cent_scores_plan";
+    if (n_q < 0 || n_d < 0 || d_rows < 0 || max_q_tokens < 0 || !plan) return fail(MSIM_EINVAL, "%s: bad argument", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const CentPlan p = cent_plan(n_q, max_q_tokens, K, n_d, d_rows, di->cus);
+    plan[0] = p.nb;
+    plan[1] = p.ppw;
+    plan[2] = msim::kCentWaves;
+    plan[3] = (int32_t)(p.wgs > 0x7fffffffLL ? 0x7fffffffLL : p.wgs);
+    return MSIM_OK;
+}
+
+int msim_cent_scores(const void *table, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int K, const uint16_t *codes,
+                     const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, float *scores, int64_t ld_scores,
+                     void *stream) {
+    const char *who = "msim_cent_scores";
+    if (n_q < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d,
+                    (long long)q_rows, (long long)d_rows, max_q_tokens);
+    if (int rc = cent_check_format(who, MSIM_DTYPE_BF16, msim::kDim, K)) return rc;
+    if (max_q_tokens > msim::kCentMaxTokens)
+        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, msim::kCentMaxTokens);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if (!table || !q_off || (!codes && d_rows > 0) || !d_off || !scores) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(table, 16) || misaligned(codes, 16) || misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(scores, 4))
+        return fail(MSIM_EINVAL, "%s: table and codes must be 16-byte aligned; offsets and scores 4-byte aligned", who);
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
+    if (d_rows > 0x7fffffffLL - 1024) return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld exceeds 32-bit row indices", who, (long long)d_rows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const CentPlan p = cent_plan(n_q, max_q_tokens, K, n_d, d_rows, di->cus);
+    if (p.wgs > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld workgroups exceed one launch", who, p.wgs);
+    constexpr int park = msim::kCentWaves * msim::kCentBatch * msim::kCentTableRow;
+    static std::atomic<int> configured[kMaxDevices];
+    if (int rc = allow_lds(msim::cent_scores_kernel, msim::kCentMaxK * msim::kCentTableRow + park, configured)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(msim::cent_scores_kernel, dim3((unsigned)p.wgs), dim3(msim::kCentWaves * 64), K * msim::kCentTableRow + park, st,
+                       static_cast<const _Float16 *>(table), q_off, n_q, (long long)q_rows, p.nb, K, codes, d_off, clamp0, n_d,
+                       (long long)d_rows, p.ppw, p.n_pr, scores, (long long)ld_scores);
+    return launch_failed("cent_scores_kernel");
+}
+
+}  // extern "C"

@@ -1,145 +1,34 @@
-// C ABI of libmaxsim_gfx950.so (see include/maxsim.h).  Host-side dispatch only: argument
-// validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
-// frees or synchronises, so every entry point is hipGraph-capturable.
+// C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the forward scorers -- msim_fwd, msim_fwd_ragged and their plans and
+// workspace sizes, the plain similarity matrix, msim_query_compact and candidate reranking (msim_fwd_candidates, both widths).
+// Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
+// frees or synchronises, so every entry point is hipGraph-capturable.  The other families of entry points live in abi_train.hip,
+// abi_head_pool.hip, abi_search.hip and abi_index.hip, the state they share in abi_core.cpp; the kernels included below are
+// defined and launched in this translation unit and in no other.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/maxsim.h"
+#include "abi_common.hpp"
+#include "abi_shapes.hpp"
 #include "maxsim_stream.hip"
 #include "maxsim_batch.hip"
 #if defined(MSIM_AB) || defined(MSIM_TRACE)
 #include "maxsim_batch_packed.hip"     // K1bK: several short documents per chunk -- measured, slower than K1b, measurement builds only
 #endif
-#include "maxsim_batch_t.hip"
-#include "maxsim_dense_t.hip"
-#include "maxsim_pairs.hip"
 #include "maxsim_generic.hip"
-#include "maxsim_bwd.hip"
 #include "maxsim_panels.hip"
-#include "maxsim_smooth.hip"
-#include "embed_head.hip"
-#include "token_pooling.hip"
-#include "loss_epilogue.hip"
-#include "topk_select.hip"
 #include "maxsim_candidates.hip"
 #include "maxsim_candidates_panels.hip"
-#include "fde.hip"
-#include "int8_index.hip"
-#include "centroid_index.hip"
-#include "live_corpus.hip"
-#include "maxsim_align.hip"
-#include "mine.hip"
-#include "filter.hip"
+#include "query_compact.hip"
+
+using namespace msim_abi;
 
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// an integer A/B knob from the environment -- measurement builds only (maxsim_common.hpp: kAbBuild); the shipped library returns
-// the default without looking
-int ab_env(const char *name, int dflt) {
-#if defined(MSIM_AB) || defined(MSIM_TRACE)
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
-
-struct DeviceInfo {
-    int cus = 0;
-    int lds_per_cu = 0;
-};
-
-// once-initialised per-device cache (the only mutable global state of the library)
-constexpr int kMaxDevices = 64;
-DeviceInfo g_dev[kMaxDevices];
-std::atomic<int> g_dev_ready[kMaxDevices];
-
-int device_info(const DeviceInfo **out) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "hipGetDevice: %s", hipGetErrorString(e));
-    if (dev < 0 || dev >= kMaxDevices) return fail(MSIM_ELAUNCH, "device ordinal %d out of range", dev);
-    if (!g_dev_ready[dev].load(std::memory_order_acquire)) {
-        hipDeviceProp_t p;
-        e = hipGetDeviceProperties(&p, dev);
-        if (e != hipSuccess) return fail(MSIM_ELAUNCH, "hipGetDeviceProperties: %s", hipGetErrorString(e));
-        if (strncmp(p.gcnArchName, "gfx950", 6) != 0)
-            return fail(MSIM_EUNSUPPORTED, "libmaxsim_gfx950 is built for gfx950 (MI355X) only; device %d is %s", dev,
-                        p.gcnArchName);
-        g_dev[dev].cus = p.multiProcessorCount;
-        g_dev[dev].lds_per_cu = 160 * 1024;
-        g_dev_ready[dev].store(1, std::memory_order_release);
-    }
-    *out = &g_dev[dev];
-    return MSIM_OK;
-}
-
-// kernels that ask for more than 64 KiB of dynamic LDS need the attribute raised once per (kernel, device)
-template <class Kern>
-int allow_lds(Kern kern, int bytes, std::atomic<int> *configured) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!configured[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return fail(MSIM_ELAUNCH, "hipFuncSetAttribute(%d B LDS): %s", bytes, hipGetErrorString(e));
-        configured[dev].store(1, std::memory_order_release);
-    }
-    return MSIM_OK;
-}
-
-// tuned = the dim=128 16-bit kernels (K1s / K1b / pair-list); everything else goes to the generic kernels (K1g)
-bool is_tuned(int dtype, int dim, int Lq) {
-    return (dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) && dim == msim::kDim &&
-           (Lq + msim::kTokTile - 1) / msim::kTokTile <= 4;
-}
-
-// queries longer than 128 tokens in the tuned dtype / width: scored as 128-token segments on K1b (MaxSim is a sum over query
-// tokens) when the caller passes scratch for the partial sums; otherwise (and for every other shape) the generic kernels take them
-constexpr int kLongSegRows = 4 * msim::kTokTile;
-bool is_long_tuned(int dtype, int dim, int Lq) {
-    return (dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) && dim == msim::kDim && Lq > kLongSegRows;
-}
-int long_segments(int Lq) { return (Lq + kLongSegRows - 1) / kLongSegRows; }
-
-int elem_bytes(int dtype) { return dtype == MSIM_DTYPE_F32 ? 4 : 2; }
-
-int check_common(const void *Q, const void *D, const int32_t *d_off, int dtype, int dim, int Lq) {
-    if (!Q || !D || !d_off) return fail(MSIM_EINVAL, "null pointer argument");
-    if (dtype != MSIM_DTYPE_BF16 && dtype != MSIM_DTYPE_F16 && dtype != MSIM_DTYPE_F32)
-        return fail(MSIM_EUNSUPPORTED, "dtype code %d: the gfx950 kernels take bfloat16 (0), float16 (1) or float32 (2) embeddings",
-                    dtype);
-    if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D)) & 15)
-        return fail(MSIM_EINVAL, "Q and D must be 16-byte aligned");
-    if (dim <= 0) return fail(MSIM_EINVAL, "dim=%d", dim);
-    if (!is_tuned(dtype, dim, Lq)) {
-        const long long row_bytes = (long long)dim * elem_bytes(dtype);
-        if (row_bytes % 32 != 0)
-            return fail(MSIM_EUNSUPPORTED, "dim=%d: an embedding row must be a multiple of 32 bytes (pad the width with zero columns)", dim);
-        if (row_bytes > msim::kGenericMaxRowBytes)
-            return fail(MSIM_EUNSUPPORTED, "dim=%d: embedding rows above %d bytes are not supported", dim, msim::kGenericMaxRowBytes);
-    }
-    return MSIM_OK;
-}
 
 struct FwdCall {
     const uint16_t *Q, *D;       // Q: the [n_q, Lq, 128] box (uniform queries: also a flat token matrix) or the flat token matrix (q_off)
@@ -571,267 +460,7 @@ size_t flat_workspace_bytes(const HostQ &hq, int n_q) {
     return (!plan.stream && plan.n_blocks() > 1) ? kFwdWorkspaceBytes : 0;
 }
 
-template <int TPQ, bool F16, int WPP, int RING = msim::kPairsRing>
-int launch_pairs_argmax(const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const uint8_t *clamp0,
-                        const int32_t *pairs, float *out_scores, int32_t *out_argmax, const msim::PairsArgs &a,
-                        const DeviceInfo &di, hipStream_t st) {
-    auto kern = msim::maxsim_pairs_argmax_kernel<TPQ, F16, WPP, RING>;
-    constexpr int lds = 4 * RING * msim::kSlabBytes + (WPP > 1 ? 4 * TPQ * msim::kTokTile * 8 : 0);
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(kern, lds, configured)) return rc;
-    const int wg_needed = WPP > 1 ? a.n_pairs : (a.n_pairs + 3) / 4;
-    const int wg_cap = di.cus * (di.lds_per_cu / lds);
-    hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), lds, st, Q, D, d_off, clamp0, pairs,
-                       out_scores, out_argmax, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_pairs_argmax_kernel<%d,%d> launch: %s", TPQ, WPP, hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-template <int TPQ1, int GQ, bool F16>
-int launch_allpairs_argmax(const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const uint8_t *clamp0, float *out_scores,
-                           long long ld, int32_t *out_argmax, const msim::PairsArgs &a, const DeviceInfo &di, hipStream_t st) {
-    auto kern = msim::maxsim_allpairs_argmax_kernel<TPQ1, GQ, F16>;
-    constexpr int lds = 4 * msim::kPairsRing * msim::kSlabBytes;
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(kern, lds, configured)) return rc;
-    const long long work = (long long)((a.n_q + GQ - 1) / GQ) * a.n_d;
-    const long long wg_needed = (work + 3) / 4;
-    const int wg_cap = di.cus * (di.lds_per_cu / lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(wg_needed < wg_cap ? wg_needed : wg_cap)), dim3(256), lds, st, Q, D, d_off, clamp0, out_scores, ld,
-                       out_argmax, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_allpairs_argmax_kernel<%d,%d> launch: %s", TPQ1, GQ, hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-template <bool F16>
-int allpairs_argmax_dispatch(int tpq, const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const uint8_t *clamp0, float *out_scores,
-                             long long ld, int32_t *out_argmax, const msim::PairsArgs &a, const DeviceInfo &di, hipStream_t st) {
-    switch (tpq) {
-        case 1: return launch_allpairs_argmax<1, 4, F16>(Q, D, d_off, clamp0, out_scores, ld, out_argmax, a, di, st);
-        case 2: return launch_allpairs_argmax<2, 2, F16>(Q, D, d_off, clamp0, out_scores, ld, out_argmax, a, di, st);
-        case 3: return launch_allpairs_argmax<3, 1, F16>(Q, D, d_off, clamp0, out_scores, ld, out_argmax, a, di, st);
-        default: return launch_allpairs_argmax<4, 1, F16>(Q, D, d_off, clamp0, out_scores, ld, out_argmax, a, di, st);
-    }
-}
-
-// short pair lists (the 2B pairs of the pairwise loss): one workgroup per pair, four waves sharing the document (latency);
-// long lists: one wave per pair (throughput)
-constexpr int kPairsSplitMax = 1024;
-
-template <bool F16>
-int pairs_argmax_dispatch(int tpq, const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const uint8_t *clamp0,
-                          const int32_t *pairs, float *out_scores, int32_t *out_argmax, const msim::PairsArgs &a,
-                          const DeviceInfo &di, hipStream_t st) {
-    if (a.n_pairs <= di.cus) {       // every pair's workgroup is resident at once: a deep ring (three slabs in flight per wave) costs nothing
-        switch (tpq) {
-            case 1: return launch_pairs_argmax<1, F16, 4, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            case 2: return launch_pairs_argmax<2, F16, 4, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            case 3: return launch_pairs_argmax<3, F16, 4, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            default: return launch_pairs_argmax<4, F16, 4, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        }
-    }
-    if (a.n_pairs <= kPairsSplitMax) {
-        switch (tpq) {
-            case 1: return launch_pairs_argmax<1, F16, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            case 2: return launch_pairs_argmax<2, F16, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            case 3: return launch_pairs_argmax<3, F16, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            default: return launch_pairs_argmax<4, F16, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        }
-    }
-    switch (tpq) {
-        case 1: return launch_pairs_argmax<1, F16, 1>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        case 2: return launch_pairs_argmax<2, F16, 1>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        case 3: return launch_pairs_argmax<3, F16, 1>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        default: return launch_pairs_argmax<4, F16, 1>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-    }
-}
-
-// long queries against short documents (the trainer's symmetric direction): the transposed pair kernel, one workgroup per pair
-template <int TPD, bool F16, int RING>
-int launch_pairs_argmax_t(const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const uint8_t *clamp0,
-                          const int32_t *pairs, float *out_scores, int32_t *out_argmax, const msim::PairsArgs &a,
-                          const DeviceInfo &di, hipStream_t st) {
-    auto kern = msim::maxsim_pairs_argmax_t_kernel<TPD, F16, RING>;
-    constexpr int lds = 4 * RING * msim::kSlabBytes + 16;
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(kern, lds, configured)) return rc;
-    const int wg_cap = 4 * di.cus * (di.lds_per_cu / lds);        // a few rounds of resident workgroups; the kernel strides beyond
-    hipLaunchKernelGGL(kern, dim3(a.n_pairs < wg_cap ? a.n_pairs : wg_cap), dim3(256), lds, st, Q, D, d_off, clamp0, pairs,
-                       out_scores, out_argmax, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_pairs_argmax_t_kernel<%d> launch: %s", TPD, hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-template <bool F16>
-int pairs_argmax_t_dispatch(int tpd, const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const uint8_t *clamp0,
-                            const int32_t *pairs, float *out_scores, int32_t *out_argmax, const msim::PairsArgs &a,
-                            const DeviceInfo &di, hipStream_t st) {
-    // few pairs (the pairwise loss' 2B): every workgroup resident at once, a 4-slab ring per wave hides the LDS-DMA round trips;
-    // many (dense upstream gradients: B x C pairs): the 2-slab ring keeps two workgroups on a CU
-    if (a.n_pairs <= di.cus) {
-        switch (tpd) {
-            case 1: return launch_pairs_argmax_t<1, F16, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            case 2: return launch_pairs_argmax_t<2, F16, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-            default: return launch_pairs_argmax_t<4, F16, 4>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        }
-    }
-    switch (tpd) {
-        case 1: return launch_pairs_argmax_t<1, F16, 2>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        case 2: return launch_pairs_argmax_t<2, F16, 2>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-        default: return launch_pairs_argmax_t<4, F16, 2>(Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, di, st);
-    }
-}
-
-// dD for SHORT documents with LONG entry lists (the trainer's symmetric direction: maxsim_bwd.hip, dense form): number of splits of
-// every document's pair list, 0 = use the row-range kernel.  A function of the sizes alone (host side, no device read).
-struct DdPlan {
-    int mode = 0;          // 0: the row-range kernel; 1: dense, per (document, split); 2: dense, per (pair, split)
-    int splits = 0;
-    size_t bytes = 0;      // scratch
-};
-
-DdPlan dd_plan(int n_pairs, int Lq, int n_d, int dim, int max_doc_rows, int cus) {
-    DdPlan pl;
-    if (n_d <= 0 || n_pairs <= 0 || max_doc_rows <= 0 || max_doc_rows > msim::kBwdRows || dim <= 0) return pl;
-    const long long entries_per_doc = (long long)n_pairs * Lq / n_d;
-    if (entries_per_doc >= 1024) {                                // long lists on average: the dense upstream gradient of ColbertLoss
-        int splits = (4 * cus + n_d - 1) / n_d;                   // ~4 workgroups per CU (16-32 KiB of LDS each)
-        const long long by_work = entries_per_doc / 256;          // at least 256 (pair, token) entries per split
-        if (splits > by_work) splits = (int)by_work;
-        if (splits > 64) splits = 64;
-        pl.mode = 1;
-        pl.splits = splits < 1 ? 1 : splits;
-        pl.bytes = (size_t)pl.splits * n_d * max_doc_rows * dim * sizeof(float);
-    } else if (Lq >= 256) {
-        // few pairs, but each brings a long list to ITS document (the pairwise loss in the symmetric direction: 2B pairs of 780 tokens
-        // over 256 documents -- 195 entries per document on average, 780 or more for the <= 2B documents that have any): the row-range
-        // kernel walked those 780 entries as three rounds of dependent gathers on ONE workgroup per document, 159 us of a 370 us step.
-        // One workgroup per (pair, split of ~64 tokens): every step of the walk is a dependent gather, so few of them per workgroup
-        pl.mode = 2;
-        pl.splits = Lq / 64 > 16 ? 16 : Lq / 64;
-        pl.bytes = (size_t)pl.splits * n_pairs * max_doc_rows * dim * sizeof(float);
-    }
-    if (pl.bytes > ((size_t)256 << 20)) pl = DdPlan{};            // scratch stays bounded: the row-range kernel serves the rest
-    return pl;
-}
-
-// A side stream and a few events per device, created on first use (round 6).  The two GEMM kernels of msim_dense_t_bwd (dP, dR) are
-// independent of each other and each alone keeps the matrix cores ~27 % busy (latency chains, one workgroup per CU): the call forks
-// them onto two streams and joins before it returns to the caller's stream, so they share the CUs (LDS 67 + 70 KiB, 4 waves per
-// SIMD) and cover each other's stalls (ColbertLoss, both directions at config 5's shape: 0.468 -> 0.390 ms).  Fork / join with
-// events is the capturable pattern: a hipGraph of the step gets two parallel branches.
-struct SideStream {
-    hipStream_t st = nullptr;
-    hipEvent_t ev[8] = {};
-    std::atomic<int> ready{0};
-    std::atomic<unsigned> next{0};
-};
-SideStream g_side[kMaxDevices];
-
-int side_stream(SideStream **out) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) return fail(MSIM_ELAUNCH, "device ordinal %d out of range", dev);
-    SideStream &s = g_side[dev];
-    if (!s.ready.load(std::memory_order_acquire)) {
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lock(mu);
-        if (!s.ready.load(std::memory_order_relaxed)) {
-            hipError_t e = hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking);
-            if (e != hipSuccess) return fail(MSIM_ELAUNCH, "hipStreamCreateWithFlags: %s", hipGetErrorString(e));
-            for (auto &ev : s.ev) {
-                e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-                if (e != hipSuccess) return fail(MSIM_ELAUNCH, "hipEventCreateWithFlags: %s", hipGetErrorString(e));
-            }
-            s.ready.store(1, std::memory_order_release);
-        }
-    }
-    *out = &s;
-    return MSIM_OK;
-}
-
-// every gradient kernel of one msim_pairs_bwd call; OUT16: dQ / dD in the embeddings' own 16-bit dtype
-template <int DT, bool OUT16>
-void launch_bwd_kernels(const char *Q, const char *D, const int32_t *d_off, int max_doc_rows, const int32_t *pairs,
-                        const int32_t *order_by_doc, const float *g, const int32_t *argmax, void *dQ, void *dD,
-                        const msim::PairsArgs &a, int dim, int cus, hipStream_t st, float *partial, const DdPlan &pl, msim::GScale gs) {
-    const int row_bytes = dim * msim::elem_size<DT>();
-    // (round 6, measured and NOT kept: dQ on a second stream beside dD, as msim_dense_t_bwd does with its two GEMM kernels -- the
-    // fork / join edges cost more than the 5-20 us of overlap they buy here: pairwise loss 0.102 -> 0.123 ms, ColbertLoss 0.188 -> 0.209)
-    if (a.n_q > 0 && a.Lq > 0) {
-        // tokens per wave: the pair-range lookup is per wave, so few waves per query once there are more tokens than the chip has waves
-        const long long tokens = (long long)a.n_q * a.Lq;
-        int tpw = (int)((tokens + 4095) / 4096);
-        tpw = tpw < 1 ? 1 : (tpw > 16 ? 16 : tpw);
-        // few tokens with long pair lists (a dense gradient: 1024 tokens x 256 pairs at config 5's shape): the four waves of a workgroup
-        // share the tokens and split the pairs (maxsim_bwd.hip: psplit)
-        const int psplit = (tokens <= 2048 && (long long)a.n_pairs >= 64LL * a.n_q) ? 1 : 0;
-        if (psplit) tpw = 1;
-        const int chunks = psplit ? a.Lq : (a.Lq + 4 * tpw - 1) / (4 * tpw);
-        hipLaunchKernelGGL((msim::maxsim_bwd_dq_kernel<DT, OUT16>), dim3((unsigned)a.n_q * chunks), dim3(256), 0, st, D, d_off, pairs, g,
-                           argmax, dQ, a, row_bytes, tpw, gs, psplit);
-    }
-    const int ry = (max_doc_rows + msim::kBwdRows - 1) / msim::kBwdRows;
-    const int zc = (dim + 127) / 128;
-    if (a.n_d <= 0 || ry <= 0) return;
-    const int splits = pl.splits;
-    if (pl.mode == 2 && partial) {
-        const int lds = 2 * max_doc_rows * 128 * (int)sizeof(float);  // <= 64 KiB
-        hipLaunchKernelGGL(msim::maxsim_bwd_dd_pairs_kernel<DT>, dim3(a.n_pairs, splits, zc), dim3(256), lds, st, Q, d_off, pairs, order_by_doc,
-                           g, argmax, partial, a, dim, max_doc_rows, splits, gs);
-        const int per_wg = 256 * (OUT16 ? 2 : 1);                     // one step per thread
-        hipLaunchKernelGGL((msim::maxsim_bwd_dd_pairsum_kernel<DT, OUT16>), dim3(a.n_d, (max_doc_rows * dim + per_wg - 1) / per_wg), dim3(256), 0,
-                           st, partial, d_off, pairs, order_by_doc, dD, a.n_pairs, dim, max_doc_rows, splits);
-        return;
-    }
-    if (pl.mode == 1 && partial) {
-        const int lds = 2 * max_doc_rows * 128 * (int)sizeof(float);  // <= 64 KiB
-        hipLaunchKernelGGL(msim::maxsim_bwd_dd_dense_kernel<DT>, dim3(a.n_d, splits, zc), dim3(256), lds, st, Q, d_off, pairs, order_by_doc,
-                           g, argmax, partial, a, dim, max_doc_rows, splits, gs);
-        const int per_thread = OUT16 ? 2 : 1;
-        hipLaunchKernelGGL((msim::maxsim_bwd_dd_sum_kernel<DT, OUT16>), dim3(a.n_d, (max_doc_rows * dim + 256 * per_thread - 1) / (256 * per_thread)),
-                           dim3(256), 0, st, partial, d_off, pairs, order_by_doc, dD, a.n_d, a.n_pairs, dim, max_doc_rows, splits);
-        return;
-    }
-    // round 6: documents whose entry lists fit the LDS lists of the row-list kernel (a bound the host can know: a document meets every
-    // query at most twice in the lists the losses make) are bucketed by row once instead of re-scanned per 64-row range
-    static const bool rows_off = ab_env("MSIM_DD_ROWS", 1) == 0;          // tuning knob (A/B), not part of the ABI
-    const long long pairs_per_doc = std::min<long long>(a.n_pairs, 2LL * a.n_q);
-    // (a list with a handful of entries per document -- the pairwise loss: 2B pairs over C documents -- stays with the kernel below,
-    // whose eight small workgroups per CU zero-fill the untouched documents faster: 13.5 against 18 us at config 5's shape)
-    const bool dense_enough = (long long)a.n_pairs * a.Lq >= 64LL * a.n_d;
-    if (!rows_off && dense_enough && pairs_per_doc <= msim::kRowsMaxPairs && pairs_per_doc * a.Lq <= msim::kRowsMaxEnt) {
-        int sy = (2 * cus + a.n_d - 1) / a.n_d;                            // about two 512-thread workgroups per CU
-        const int by_rows = (max_doc_rows + 63) / 64, need = (max_doc_rows + msim::kRowsMaxRows - 1) / msim::kRowsMaxRows;
-        sy = sy > by_rows ? by_rows : sy;
-        sy = sy < need ? need : (sy < 1 ? 1 : sy);
-        hipLaunchKernelGGL((msim::maxsim_bwd_dd_rows_kernel<DT, OUT16>), dim3(a.n_d, sy, zc), dim3(msim::kRowsThreads), 0, st, Q, d_off, pairs,
-                           order_by_doc, g, argmax, dD, a, dim, gs);
-        return;
-    }
-    // row ranges per workgroup: about eight workgroups per CU in total (each looks its document's pair range up once)
-    int gy = (8 * cus + a.n_d - 1) / a.n_d;
-    gy = gy < 1 ? 1 : (gy > ry ? ry : gy);
-    hipLaunchKernelGGL((msim::maxsim_bwd_dd_kernel<DT, OUT16>), dim3(a.n_d, gy, zc), dim3(256), 0, st, Q, d_off, pairs, order_by_doc, g,
-                       argmax, dD, a, dim, gs);
-}
-
 // ---------------------------------------------------------------- generic kernels (K1g)
-struct GenericCall {
-    const char *Q, *D;
-    const int32_t *d_off;
-    const uint8_t *clamp0;
-    float *scores;
-    long long ld;
-    int n_q, Lq, n_d, row_bytes;
-    unsigned flags;
-    const DeviceInfo *di;
-    hipStream_t st;
-};
-
 template <int DT, int T>
 int launch_generic(const GenericCall &c) {
     auto kern = msim::maxsim_generic_kernel<DT, T>;
@@ -881,158 +510,6 @@ int generic_fwd(int dtype, const GenericCall &c) {
     }
 }
 
-template <int DT>
-int generic_pairs_argmax(const char *Q, const char *D, const int32_t *d_off, const uint8_t *clamp0, const int32_t *pairs,
-                         float *out_scores, int32_t *out_argmax, const msim::PairsArgs &a, int row_bytes, const DeviceInfo &di,
-                         hipStream_t st) {
-    const int wg_needed = (a.n_pairs + 3) / 4;
-    const int wg_cap = di.cus * 8;
-    hipLaunchKernelGGL(msim::maxsim_generic_pairs_argmax_kernel<DT>, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), 0,
-                       st, Q, D, d_off, clamp0, pairs, out_scores, out_argmax, a, row_bytes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_generic_pairs_argmax_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-
-// ---------------------------------------------------------------- smooth-max (tau * logsumexp) kernels
-int check_smooth(const void *Q, const void *D, const int32_t *d_off, int dtype, int dim, int Lq, float tau) {
-    if (!Q || !D || !d_off) return fail(MSIM_EINVAL, "null pointer argument");
-    if (dtype != MSIM_DTYPE_BF16 && dtype != MSIM_DTYPE_F16 && dtype != MSIM_DTYPE_F32)
-        return fail(MSIM_EUNSUPPORTED, "dtype code %d", dtype);
-    if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D)) & 15)
-        return fail(MSIM_EINVAL, "Q and D must be 16-byte aligned");
-    if (!(tau > 0.0f)) return fail(MSIM_EINVAL, "tau must be positive");
-    if (dim <= 0 || Lq <= 0) return fail(MSIM_EINVAL, "bad size (dim=%d Lq=%d)", dim, Lq);
-    const long long row_bytes = (long long)dim * elem_bytes(dtype);
-    if (row_bytes % 32 != 0)
-        return fail(MSIM_EUNSUPPORTED, "dim=%d: an embedding row must be a multiple of 32 bytes (pad the width with zero columns)", dim);
-    if (row_bytes > msim::kGenericMaxRowBytes)
-        return fail(MSIM_EUNSUPPORTED, "dim=%d: embedding rows above %d bytes are not supported", dim, msim::kGenericMaxRowBytes);
-    return MSIM_OK;
-}
-
-template <int DT, int T>
-int launch_smooth(const GenericCall &c, float tau) {
-    auto kern = msim::maxsim_smooth_kernel<DT, T>;
-    const int lds = T * msim::kTokTile * (c.row_bytes + 16);
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(kern, 160 * 1024, configured)) return rc;
-    msim::SmoothArgs a;
-    a.ld = c.ld;
-    a.n_q = c.n_q;
-    a.Lq = c.Lq;
-    a.n_d = c.n_d;
-    a.row_bytes = c.row_bytes;
-    a.tau = tau;
-    const int tpq = (c.Lq + msim::kTokTile - 1) / msim::kTokTile;
-    const int groups = tpq <= T ? (c.n_q + (T / tpq) - 1) / (T / tpq) : c.n_q;
-    if (groups > 65535) return fail(MSIM_EUNSUPPORTED, "too many query groups (%d) for one launch", groups);
-    const int wg_needed = (c.n_d + msim::kGenericWaves - 1) / msim::kGenericWaves;
-    int per_cu = c.di->lds_per_cu / lds;
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int wg_cap = c.di->cus * per_cu;
-    hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap, groups), dim3(msim::kGenericWaves * 64), lds, c.st,
-                       c.Q, c.D, c.d_off, c.scores, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_smooth_kernel<%d,%d> launch: %s", DT, T, hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-template <int DT>
-int smooth_dispatch(const GenericCall &c, float tau) {
-    const int tpq = (c.Lq + msim::kTokTile - 1) / msim::kTokTile;
-    const long long tiles = (long long)c.n_q * tpq;
-    const int tile_lds = msim::kTokTile * (c.row_bytes + 16);
-    int T = 2;                                   // (max, sum) state per tile on top of the accumulators: two tiles per wave
-    while (T > 1 && (T * tile_lds > 80 * 1024 || T / 2 >= tiles)) T >>= 1;
-    return T == 2 ? launch_smooth<DT, 2>(c, tau) : launch_smooth<DT, 1>(c, tau);
-}
-
-template <int DT>
-int smooth_pairs(const char *Q, const char *D, const int32_t *d_off, const int32_t *pairs, float *out_scores, float *out_lse,
-                 const msim::PairsArgs &a, int row_bytes, float tau, const DeviceInfo &di, hipStream_t st) {
-    const int wg_needed = (a.n_pairs + 3) / 4;
-    const int wg_cap = di.cus * 8;
-    hipLaunchKernelGGL(msim::maxsim_smooth_pairs_kernel<DT>, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), 0, st, Q, D,
-                       d_off, pairs, out_scores, out_lse, a, row_bytes, tau);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_smooth_pairs_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-template <int DT>
-int smooth_bwd(const char *Q, const char *D, const int32_t *d_off, int max_doc_rows, const int32_t *pairs,
-               const int32_t *order_by_doc, const float *g, const float *lse, float *dQ, float *dD, float *workspace,
-               msim::SmoothBwdArgs a, int n_split, hipStream_t st) {
-    const int tpq = (a.Lq + msim::kTokTile - 1) / msim::kTokTile;
-    const int cg = (a.dim + 32 * msim::kSmoothCB - 1) / (32 * msim::kSmoothCB);
-    const bool hoist = a.row_bytes <= 256;                       // the owner tile's fragments fit 8 registers quads
-    static const bool no_stage = ab_env("MSIM_SMOOTH_NO_STAGE", 0) != 0;   // A/B knob (measurement builds)
-    const int slabs = (max_doc_rows + 31) / 32;
-    if constexpr (DT != msim::kDtypeF32) {
-        if (a.row_bytes == msim::kRowBytes && a.dim == msim::kDim && !no_stage) {   // 128 x 16-bit rows: staged "other" tiles
-            constexpr bool F16 = DT == msim::kDtypeF16;
-            if (a.n_q > 0) {
-                a.n_split = n_split;
-                auto kern = msim::maxsim_smooth_bwd_staged_kernel<F16, true>;
-                constexpr int lds = msim::kSmoothWavesDQ * msim::kSmoothStageBytes;
-                static std::atomic<int> configured[kMaxDevices];
-                if (int rc = allow_lds(kern, lds, configured)) return rc;
-                hipLaunchKernelGGL(kern, dim3(a.n_q * n_split, tpq, 1), dim3(msim::kSmoothWavesDQ * 64), lds, st, Q, D, d_off, pairs,
-                                   order_by_doc, g, lse, n_split > 1 ? workspace : dQ, a);
-                if (n_split > 1) {
-                    const long long n = (long long)a.n_q * a.Lq * a.dim;
-                    hipLaunchKernelGGL(msim::smooth_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, workspace, dQ, n,
-                                       n_split);
-                }
-            }
-            if (a.n_d > 0 && slabs > 0) {
-                a.n_split = 1;
-                auto kern = msim::maxsim_smooth_bwd_staged_kernel<F16, false>;
-                constexpr int lds = msim::kSmoothWavesDD * msim::kSmoothStageBytes;
-                static std::atomic<int> configured[kMaxDevices];
-                if (int rc = allow_lds(kern, lds, configured)) return rc;
-                hipLaunchKernelGGL(kern, dim3(a.n_d, slabs, 1), dim3(msim::kSmoothWavesDD * 64), lds, st, Q, D, d_off, pairs, order_by_doc, g,
-                                   lse, dD, a);
-            }
-            hipError_t es = hipGetLastError();
-            if (es != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_smooth_bwd_staged_kernel launch: %s", hipGetErrorString(es));
-            return MSIM_OK;
-        }
-    }
-    if (a.n_q > 0) {
-        a.n_split = n_split;
-        const dim3 grid(a.n_q * n_split, tpq, cg), block(msim::kSmoothWavesDQ * 64);
-        float *dst = n_split > 1 ? workspace : dQ;
-        if (hoist)
-            hipLaunchKernelGGL((msim::maxsim_smooth_bwd_kernel<DT, true, true>), grid, block, 0, st, Q, D, d_off, pairs, order_by_doc, g, lse, dst, a);
-        else
-            hipLaunchKernelGGL((msim::maxsim_smooth_bwd_kernel<DT, true, false>), grid, block, 0, st, Q, D, d_off, pairs, order_by_doc, g, lse, dst, a);
-        if (n_split > 1) {
-            const long long n = (long long)a.n_q * a.Lq * a.dim;
-            hipLaunchKernelGGL(msim::smooth_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, workspace, dQ, n, n_split);
-        }
-    }
-    if (a.n_d > 0 && slabs > 0) {
-        a.n_split = 1;
-        const dim3 grid(a.n_d, slabs, cg), block(msim::kSmoothWavesDD * 64);
-        if (hoist)
-            hipLaunchKernelGGL((msim::maxsim_smooth_bwd_kernel<DT, false, true>), grid, block, 0, st, Q, D, d_off, pairs, order_by_doc, g, lse, dD, a);
-        else
-            hipLaunchKernelGGL((msim::maxsim_smooth_bwd_kernel<DT, false, false>), grid, block, 0, st, Q, D, d_off, pairs, order_by_doc, g, lse, dD, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_smooth_bwd_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-// number of workgroups that share one owner tile's pair list in the dQ pass (enough to fill the chip twice)
-int smooth_dq_split(int n_q, int Lq, const DeviceInfo &di) {
-    const int tiles = n_q * ((Lq + msim::kTokTile - 1) / msim::kTokTile);
-    int s = (2 * di.cus + tiles - 1) / (tiles > 0 ? tiles : 1);
-    return s < 1 ? 1 : (s > 32 ? 32 : s);
-}
 
 // ---------------------------------------------------------------- plain similarity matrix
 template <int DT, int T>
@@ -1221,16 +698,6 @@ bool box_on_panels_flat(int dtype, int dim, int n_q, int Lq) {
 }  // namespace
 
 extern "C" {
-
-int msim_abi_version(void) { return MSIM_ABI_VERSION; }
-#ifdef MSIM_AB
-int msim_ab_rows_trace(unsigned long long *out16) {      // measurement builds only
-    return hipMemcpyFromSymbol(out16, HIP_SYMBOL(msim::g_rows_trace), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : -3;
-}
-#endif
-
-
-const char *msim_last_error(void) { return g_err; }
 
 size_t msim_fwd_workspace_bytes(int dtype, int n_q, int Lq, int n_d, int dim) {
     // the only scratch msim_fwd uses: the progress counters of K1b's convoy, needed once more than one query block streams a
@@ -1431,719 +898,6 @@ int msim_fwd(int dtype, const void *Q, int n_q, int Lq, const void *D, const int
     return dtype == MSIM_DTYPE_F16 ? fwd_dispatch<true>(c) : fwd_dispatch<false>(c);
 }
 
-// ---------------------------------------------------------------- K1t: long queries x short documents, all pairs
-}  // extern "C"
-
-namespace {
-template <bool F16, int U, int DPW, bool ROUTE>
-int launch_batch_t(const uint16_t *Q, const uint16_t *D, float *scores, int32_t *q_lengths, uint8_t *route, msim::BatchTArgs a,
-                   const DeviceInfo &di, hipStream_t st) {
-    auto kern = msim::maxsim_batch_t_kernel<F16, U, DPW, ROUTE>;
-    constexpr int lds = 3 * 4 * msim::kSlabBytes;                  // 96 KiB ring
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(kern, lds, configured)) return rc;
-    a.n_blocks = (a.n_d + 8 * DPW - 1) / (8 * DPW);
-    // page slots per XCD: every page its own slot until the launch holds ~4 workgroups per CU, then the workgroups walk pages
-    int slots_p = (a.n_q + 7) / 8;
-    const int cap = (4 * di.cus / 8 + a.n_blocks - 1) / a.n_blocks;
-    if (slots_p > cap) slots_p = cap < 1 ? 1 : cap;
-    a.slots_p = slots_p;
-    a.n_slots = slots_p * a.n_blocks;
-    hipLaunchKernelGGL(kern, dim3(8 * a.n_slots), dim3(512), lds, st, Q, D, scores, q_lengths, route, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_batch_t_kernel<%d,%d> launch: %s", U, DPW, hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-template <bool F16>
-int batch_t_dispatch(int units, const uint16_t *Q, const uint16_t *D, float *scores, int32_t *ql, uint8_t *route,
-                     const msim::BatchTArgs &a, const DeviceInfo &di, hipStream_t st) {
-    if (route) {        // with the routing bytes of the dense backward (documents of at most 64 rows)
-        if (units <= 1) return launch_batch_t<F16, 1, 8, true>(Q, D, scores, ql, route, a, di, st);
-        if (units == 2) return launch_batch_t<F16, 2, 4, true>(Q, D, scores, ql, route, a, di, st);
-        if (units == 3) return launch_batch_t<F16, 3, 2, true>(Q, D, scores, ql, route, a, di, st);
-        return launch_batch_t<F16, 4, 2, true>(Q, D, scores, ql, route, a, di, st);
-    }
-    if (units <= 1) return launch_batch_t<F16, 1, 8, false>(Q, D, scores, ql, nullptr, a, di, st);
-    if (units == 2) return launch_batch_t<F16, 2, 4, false>(Q, D, scores, ql, nullptr, a, di, st);
-    if (units == 3) return launch_batch_t<F16, 3, 2, false>(Q, D, scores, ql, nullptr, a, di, st);
-    if (units == 4) return launch_batch_t<F16, 4, 2, false>(Q, D, scores, ql, nullptr, a, di, st);
-    return launch_batch_t<F16, 8, 1, false>(Q, D, scores, ql, nullptr, a, di, st);
-}
-
-int fwd_transposed(int dtype, const void *Q, int n_q, int Lq, const void *D, int n_d, int Ld, int dim, float *scores,
-                   int64_t ld_scores, int32_t *q_lengths, uint8_t *route, void *stream) {
-    if (n_q < 0 || n_d < 0 || Lq <= 0 || Ld <= 0) return fail(MSIM_EINVAL, "negative or empty size");
-    if (n_q == 0 || n_d == 0) return MSIM_OK;
-    if (!Q || !D || !scores) return fail(MSIM_EINVAL, "null pointer argument");
-    if ((dtype != MSIM_DTYPE_BF16 && dtype != MSIM_DTYPE_F16) || dim != msim::kDim)
-        return fail(MSIM_EUNSUPPORTED, "msim_fwd_transposed takes bf16 / f16 embeddings of width %d", msim::kDim);
-    if (Ld > 8 * msim::kUnitTok) return fail(MSIM_EUNSUPPORTED, "resident documents of at most %d rows (got %d)", 8 * msim::kUnitTok, Ld);
-    if (route && Ld > msim::kDenseTMaxLd)
-        return fail(MSIM_EUNSUPPORTED, "the routing is kept for resident documents of at most %d rows (got %d)", msim::kDenseTMaxLd, Ld);
-    if ((long long)Lq * msim::kRowBytes >= (1ll << 31)) return fail(MSIM_EUNSUPPORTED, "queries of %d rows", Lq);
-    if (ld_scores < n_d) return fail(MSIM_EINVAL, "ld_scores < n_d");
-    if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D)) & 15) return fail(MSIM_EINVAL, "embeddings must be 16-byte aligned");
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    msim::BatchTArgs a{};
-    a.ld = ld_scores;
-    a.n_q = n_q;
-    a.Lq = Lq;
-    a.n_d = n_d;
-    a.Ld = Ld;
-    a.Lq_pad = msim::dense_t_lq_pad(Lq);
-    const int units = (Ld + msim::kUnitTok - 1) / msim::kUnitTok;
-    const uint16_t *q = static_cast<const uint16_t *>(Q), *d = static_cast<const uint16_t *>(D);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return dtype == MSIM_DTYPE_F16 ? batch_t_dispatch<true>(units, q, d, scores, q_lengths, route, a, *di, st)
-                                   : batch_t_dispatch<false>(units, q, d, scores, q_lengths, route, a, *di, st);
-}
-
-// ---- the dense hard-max backward of the transposed shape (maxsim_dense_t.hip)
-constexpr int kDenseTMaxDocs = 4096;        // dP keeps one weight pair per document of the page in LDS
-constexpr int kDenseTMaxPagesPer = 256;     // dR keeps one weight pair per (page of its split, document of the workgroup) in LDS
-struct DenseTPlan {
-    size_t rimg, pimg, partial, bytes;   // byte offsets of the two operand images and the page-split partials; total
-    int ks, nsb, nc, n_split, pages_per, doc_groups;
-};
-static inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-DenseTPlan dense_t_plan(int n_q, int Lq, int n_d, int Ld, int cus) {
-    DenseTPlan p{};
-    p.ks = (Ld + 31) / 32;
-    p.nsb = Ld <= 16 ? 1 : Ld <= 32 ? 2 : 4;     // 16-row blocks per document: NSB * NC = 4 combinations per wave pair
-    p.nc = 4 / p.nsb;
-    p.doc_groups = (n_d + 4 * p.nc - 1) / (4 * p.nc);
-    int split = (cus + p.doc_groups - 1) / (p.doc_groups > 0 ? p.doc_groups : 1);
-    const int min_split = (n_q + kDenseTMaxPagesPer - 1) / kDenseTMaxPagesPer;
-    split = split < min_split ? min_split : split;
-    split = split < 1 ? 1 : split > n_q ? n_q : split;
-    p.pages_per = split > 0 ? (n_q + split - 1) / split : 1;
-    p.n_split = p.pages_per > 0 ? (n_q + p.pages_per - 1) / p.pages_per : 0;
-    const size_t ksp = msim::dense_t_lq_pad(Lq) / 32;
-    p.rimg = 0;
-    p.pimg = up16((size_t)n_d * p.ks * msim::kKStepBytes);
-    p.partial = p.pimg + up16((size_t)n_q * ksp * msim::kKStepBytes);
-    p.bytes = p.partial + up16((size_t)p.n_split * n_d * Ld * msim::kDim * sizeof(float));
-    return p;
-}
-bool dense_t_supported(int dtype, int n_q, int Lq, int n_d, int Ld, int dim) {
-    if ((dtype != MSIM_DTYPE_BF16 && dtype != MSIM_DTYPE_F16) || dim != msim::kDim) return false;
-    if (Ld <= 0 || Ld > msim::kDenseTMaxLd || Lq <= 0 || n_q <= 0 || n_d <= 0 || n_d > kDenseTMaxDocs) return false;
-    const long long lq_pad = msim::dense_t_lq_pad(Lq);
-    return (long long)n_q * lq_pad * msim::kRowBytes < (1ll << 31) && (long long)n_q * n_d * lq_pad < (1ll << 31) &&
-           (long long)n_d * 64 * msim::kRowBytes < (1ll << 31);
-}
-
-template <bool F16>
-int dense_t_bwd_launch(const uint16_t *Q, const uint16_t *D, const float *G, msim::GScale gs, const uint8_t *route, uint16_t *dQ,
-                       uint16_t *dD, char *ws, const DenseTPlan &pl, msim::DenseTArgs a, hipStream_t st) {
-    uint16_t *rimg = reinterpret_cast<uint16_t *>(ws + pl.rimg), *pimg = reinterpret_cast<uint16_t *>(ws + pl.pimg);
-    float *partial = reinterpret_cast<float *>(ws + pl.partial);
-    SideStream *side = nullptr;
-    if (int rc = side_stream(&side)) return rc;
-    const unsigned e0 = side->next.fetch_add(2) % 8;      // two events of the pool per call (fork, join)
-    hipEvent_t fork = side->ev[e0], join = side->ev[(e0 + 1) % 8];
-    // fork: the side stream takes the page image and dR (+ its split sum), the caller's stream the document image and dP
-    hipError_t e = hipEventRecord(fork, st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side->st, fork, 0);
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "msim_dense_t_bwd fork: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(msim::dense_t_image_kernel, dim3(a.n_d * pl.ks), dim3(256), 0, st, D, rimg, a.n_d, a.Ld, pl.ks);
-    hipLaunchKernelGGL(msim::dense_t_image_kernel, dim3(a.n_q * a.ksp), dim3(256), 0, side->st, Q, pimg, a.n_q, a.Lq, a.ksp);
-    static std::atomic<int> conf_long[2][kMaxDevices], conf_short[4][kMaxDevices];
-    // LDS: the operand ring + the routing bytes + the W patterns / weight pairs (dP: one per document of the page, padded to whole
-    // stages; dR: one per (page of the split, document of the workgroup)); the attribute is raised once to what dense_t_supported admits
-    constexpr int kLongRing = msim::kDenseTLongRing, kShortRing = msim::kDenseTShortRing;
-    constexpr int kLongStage = msim::kDenseTLongSteps * (8192 + 128 + 144);      // image + routing bytes + W patterns (KS = 1: one document per step)
-    constexpr int lds_long_max = kLongRing * kLongStage + 4 * (kDenseTMaxDocs + 4), lds_short_max = kShortRing * (16384 + 1024) + 4 * 16 * kDenseTMaxPagesPer;
-    const int lds_long = kLongRing * kLongStage + 4 * ((a.n_d + 3) / 4 * 4 + 4);
-    const int lds_short = kShortRing * (16384 + 1024) + 4 * 16 * pl.pages_per;
-    const dim3 grid_long((a.Lq + 127) / 128, a.n_q);
-    if (pl.ks == 1) {
-        auto k = msim::dense_t_bwd_long_kernel<F16, 1>;
-        if (int rc = allow_lds(k, lds_long_max, conf_long[0])) return rc;
-        hipLaunchKernelGGL(k, grid_long, dim3(512), lds_long, st, rimg, route, G, gs, dQ, a);
-    } else {
-        auto k = msim::dense_t_bwd_long_kernel<F16, 2>;
-        if (int rc = allow_lds(k, lds_long_max, conf_long[1])) return rc;
-        hipLaunchKernelGGL(k, grid_long, dim3(512), lds_long, st, rimg, route, G, gs, dQ, a);
-    }
-    const dim3 grid_short(pl.doc_groups, pl.n_split);
-#define MSIM_SHORT(NSB, NC, SLOT)                                                                         \
-    {                                                                                                     \
-        auto k = msim::dense_t_bwd_short_kernel<F16, NSB, NC>;                                            \
-        if (int rc = allow_lds(k, lds_short_max, conf_short[SLOT])) return rc;                            \
-        hipLaunchKernelGGL(k, grid_short, dim3(512), lds_short, side->st, pimg, route, G, gs, partial, a); \
-    }
-    if (pl.nsb <= 1) MSIM_SHORT(1, 4, 0)
-    else if (pl.nsb == 2) MSIM_SHORT(2, 2, 1)
-    else MSIM_SHORT(4, 1, 2)
-#undef MSIM_SHORT
-    const long long n_elems = (long long)a.n_d * a.Ld * msim::kDim;
-    hipLaunchKernelGGL(msim::dense_t_bwd_short_sum_kernel<F16>, dim3((unsigned)((n_elems / 4 + 255) / 256)), dim3(256), 0, side->st, partial, dD,
-                       n_elems, pl.n_split);
-    // join: the caller's stream continues when both halves are done
-    e = hipEventRecord(join, side->st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(st, join, 0);
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "msim_dense_t_bwd join: %s", hipGetErrorString(e));
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "msim_dense_t_bwd launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int msim_fwd_transposed(int dtype, const void *Q, int n_q, int Lq, const void *D, int n_d, int Ld, int dim, float *scores,
-                        int64_t ld_scores, int32_t *q_lengths, void *stream) {
-    return fwd_transposed(dtype, Q, n_q, Lq, D, n_d, Ld, dim, scores, ld_scores, q_lengths, nullptr, stream);
-}
-
-size_t msim_dense_t_route_bytes(int n_q, int Lq, int n_d) {
-    if (n_q <= 0 || Lq <= 0 || n_d <= 0) return 0;
-    return (size_t)n_q * n_d * msim::dense_t_lq_pad(Lq);
-}
-
-int msim_dense_t_supported(int dtype, int n_q, int Lq, int n_d, int Ld, int dim) {
-    return dense_t_supported(dtype, n_q, Lq, n_d, Ld, dim) ? 1 : 0;
-}
-
-int msim_fwd_transposed_route(int dtype, const void *Q, int n_q, int Lq, const void *D, int n_d, int Ld, int dim, float *scores,
-                              int64_t ld_scores, int32_t *q_lengths, uint8_t *route, void *stream) {
-    if (!route) return fail(MSIM_EINVAL, "null routing buffer");
-    if (n_q > 0 && n_d > 0 && !dense_t_supported(dtype, n_q, Lq, n_d, Ld, dim))
-        return fail(MSIM_EUNSUPPORTED, "msim_fwd_transposed_route: bf16 / f16, width %d, documents of at most %d rows, sizes below 2^31 bytes",
-                    msim::kDim, msim::kDenseTMaxLd);
-    return fwd_transposed(dtype, Q, n_q, Lq, D, n_d, Ld, dim, scores, ld_scores, q_lengths, route, stream);
-}
-
-size_t msim_dense_t_bwd_workspace_bytes(int n_q, int Lq, int n_d, int Ld, int dim) {
-    (void)dim;
-    if (n_q <= 0 || n_d <= 0 || Lq <= 0 || Ld <= 0) return 0;
-    const DeviceInfo *di = nullptr;
-    const int cus = device_info(&di) == MSIM_OK ? di->cus : 256;            // the plan only has to be the same in both calls
-    return dense_t_plan(n_q, Lq, n_d, Ld, cus).bytes;
-}
-
-int msim_dense_t_bwd(int dtype, const void *Q, int n_q, int Lq, const void *D, int n_d, int Ld, int dim, const float *G, int64_t ldg,
-                     const void *g_scale, int g_scale_dtype, const uint8_t *route, void *dQ, void *dD, void *workspace, void *stream) {
-    if (n_q < 0 || n_d < 0 || Lq <= 0 || Ld <= 0) return fail(MSIM_EINVAL, "negative or empty size");
-    if (n_q == 0 || n_d == 0) return MSIM_OK;
-    if (!Q || !D || !G || !route || !dQ || !dD || !workspace) return fail(MSIM_EINVAL, "null pointer argument");
-    if (!dense_t_supported(dtype, n_q, Lq, n_d, Ld, dim))
-        return fail(MSIM_EUNSUPPORTED, "msim_dense_t_bwd: bf16 / f16, width %d, documents of at most %d rows, sizes below 2^31 bytes",
-                    msim::kDim, msim::kDenseTMaxLd);
-    if (ldg < n_d) return fail(MSIM_EINVAL, "ldg < n_d");
-    if (g_scale && g_scale_dtype != MSIM_DTYPE_BF16 && g_scale_dtype != MSIM_DTYPE_F16 && g_scale_dtype != MSIM_DTYPE_F32)
-        return fail(MSIM_EINVAL, "g_scale dtype code %d", g_scale_dtype);
-    if ((reinterpret_cast<uintptr_t>(Q) | reinterpret_cast<uintptr_t>(D) | reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dD) |
-         reinterpret_cast<uintptr_t>(workspace)) & 15)
-        return fail(MSIM_EINVAL, "embeddings, gradients and workspace must be 16-byte aligned");
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const DenseTPlan pl = dense_t_plan(n_q, Lq, n_d, Ld, di->cus);
-    msim::DenseTArgs a{};
-    a.ldg = ldg;
-    a.n_q = n_q;
-    a.Lq = Lq;
-    a.n_d = n_d;
-    a.Ld = Ld;
-    a.Lq_pad = msim::dense_t_lq_pad(Lq);
-    a.ksp = a.Lq_pad / 32;
-    a.n_split = pl.n_split;
-    a.pages_per = pl.pages_per;
-    if (msim::kAbBuild) {
-        const char *e = getenv("MSIM_DENSE_T_DBG");
-        a.dbg = e ? atoi(e) : 0;
-        const char *o = getenv("MSIM_DENSE_T_DBG_OUT");
-        a.dbg_out = o ? reinterpret_cast<unsigned long long *>(strtoull(o, nullptr, 0)) : nullptr;
-    }
-    const msim::GScale gs{g_scale, g_scale_dtype};
-    const uint16_t *q = static_cast<const uint16_t *>(Q), *d = static_cast<const uint16_t *>(D);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    return dtype == MSIM_DTYPE_F16
-               ? dense_t_bwd_launch<true>(q, d, G, gs, route, static_cast<uint16_t *>(dQ), static_cast<uint16_t *>(dD),
-                                          static_cast<char *>(workspace), pl, a, st)
-               : dense_t_bwd_launch<false>(q, d, G, gs, route, static_cast<uint16_t *>(dQ), static_cast<uint16_t *>(dD),
-                                           static_cast<char *>(workspace), pl, a, st);
-}
-
-// ---------------------------------------------------------------- pair lists (training losses)
-int msim_pairs_argmax(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off,
-                      const uint8_t *d_clamp0, int n_d, int dim, int max_doc_rows, const int32_t *pairs, int n_pairs,
-                      float *out_scores, int32_t *out_argmax, void *stream) {
-    if (n_q < 0 || n_d < 0 || Lq <= 0 || n_pairs < 0 || max_doc_rows < 0) return fail(MSIM_EINVAL, "negative size");
-    if (n_pairs == 0) return MSIM_OK;
-    if (!pairs) return fail(MSIM_EINVAL, "null pointer argument");
-    if (int rc = check_common(Q, D, d_off, dtype, dim, Lq)) return rc;
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const int tpq = (Lq + msim::kTokTile - 1) / msim::kTokTile;
-    msim::PairsArgs a{n_q, Lq, n_d, n_pairs};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *q = static_cast<const uint16_t *>(Q), *d = static_cast<const uint16_t *>(D);
-    // long queries x short documents in the tuned dtype / width (pages as queries, the trainer's symmetric direction): transposed form
-    if (dtype != MSIM_DTYPE_F32 && dim == msim::kDim && Lq > kLongSegRows && max_doc_rows > 0 && max_doc_rows <= 4 * msim::kTokTile &&
-        (long long)Lq * msim::kRowBytes < (1ll << 31)) {
-        const int tpd = (max_doc_rows + msim::kTokTile - 1) / msim::kTokTile;
-        return dtype == MSIM_DTYPE_F16
-                   ? pairs_argmax_t_dispatch<true>(tpd, q, d, d_off, d_clamp0, pairs, out_scores, out_argmax, a, *di, st)
-                   : pairs_argmax_t_dispatch<false>(tpd, q, d, d_off, d_clamp0, pairs, out_scores, out_argmax, a, *di, st);
-    }
-    if (!is_tuned(dtype, dim, Lq)) {
-        const char *qc = static_cast<const char *>(Q), *dc = static_cast<const char *>(D);
-        const int rb = dim * elem_bytes(dtype);
-        switch (dtype) {
-            case MSIM_DTYPE_F32:
-                return generic_pairs_argmax<msim::kDtypeF32>(qc, dc, d_off, d_clamp0, pairs, out_scores, out_argmax, a, rb, *di, st);
-            case MSIM_DTYPE_F16:
-                return generic_pairs_argmax<msim::kDtypeF16>(qc, dc, d_off, d_clamp0, pairs, out_scores, out_argmax, a, rb, *di, st);
-            default:
-                return generic_pairs_argmax<msim::kDtypeBf16>(qc, dc, d_off, d_clamp0, pairs, out_scores, out_argmax, a, rb, *di, st);
-        }
-    }
-    return dtype == MSIM_DTYPE_F16
-               ? pairs_argmax_dispatch<true>(tpq, q, d, d_off, d_clamp0, pairs, out_scores, out_argmax, a, *di, st)
-               : pairs_argmax_dispatch<false>(tpq, q, d, d_off, d_clamp0, pairs, out_scores, out_argmax, a, *di, st);
-}
-
-int msim_allpairs_argmax(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, const uint8_t *d_clamp0,
-                         int n_d, int dim, float *out_scores, int64_t ld_scores, int32_t *out_argmax, void *stream) {
-    if (n_q < 0 || n_d < 0 || Lq <= 0) return fail(MSIM_EINVAL, "negative size");
-    if (n_q == 0 || n_d == 0) return MSIM_OK;
-    if (!out_scores && !out_argmax) return fail(MSIM_EINVAL, "nothing to compute");
-    if (out_scores && ld_scores < n_d) return fail(MSIM_EINVAL, "ld_scores < n_d");
-    if (int rc = check_common(Q, D, d_off, dtype, dim, Lq)) return rc;
-    if (!is_tuned(dtype, dim, Lq))
-        return fail(MSIM_EUNSUPPORTED, "msim_allpairs_argmax takes bf16 / f16 embeddings of width %d and queries of at most %d tokens "
-                    "(list the pairs and call msim_pairs_argmax otherwise)", msim::kDim, 4 * msim::kTokTile);
-    if ((long long)n_q * n_d > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "more than 2^31 pairs");
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const int tpq = (Lq + msim::kTokTile - 1) / msim::kTokTile;
-    msim::PairsArgs a{n_q, Lq, n_d, n_q * n_d};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *q = static_cast<const uint16_t *>(Q), *d = static_cast<const uint16_t *>(D);
-    return dtype == MSIM_DTYPE_F16 ? allpairs_argmax_dispatch<true>(tpq, q, d, d_off, d_clamp0, out_scores, ld_scores, out_argmax, a, *di, st)
-                                   : allpairs_argmax_dispatch<false>(tpq, q, d, d_off, d_clamp0, out_scores, ld_scores, out_argmax, a, *di, st);
-}
-
-size_t msim_pairs_bwd_workspace_bytes(int n_q, int Lq, int n_d, int dim, int max_doc_rows, int n_pairs) {
-    (void)n_q;
-    const DeviceInfo *di = nullptr;
-    const int cus = device_info(&di) == MSIM_OK ? di->cus : 256;            // the plan only has to be the same in both calls
-    return dd_plan(n_pairs, Lq, n_d, dim, max_doc_rows, cus).bytes;
-}
-
-int msim_pairs_bwd(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, int n_d, int dim,
-                   int max_doc_rows, const int32_t *pairs, const int32_t *order_by_doc, const float *g,
-                   const void *g_scale, int g_scale_dtype, const int32_t *argmax, int n_pairs, int out_dtype, void *dQ, void *dD,
-                   void *workspace, void *stream) {
-    if (n_q < 0 || n_d < 0 || Lq <= 0 || n_pairs < 0 || max_doc_rows < 0) return fail(MSIM_EINVAL, "negative size");
-    if (!dQ || !dD) return fail(MSIM_EINVAL, "null pointer argument");
-    if (n_pairs > 0 && (!pairs || !order_by_doc || !g || !argmax)) return fail(MSIM_EINVAL, "null pair-list argument");
-    if (int rc = check_common(Q, D, d_off, dtype, dim, Lq)) return rc;
-    if ((max_doc_rows + msim::kBwdRows - 1) / msim::kBwdRows > 65535)
-        return fail(MSIM_EUNSUPPORTED, "max_doc_rows=%d too large", max_doc_rows);
-    if (n_d > 0x7fffffff / 2) return fail(MSIM_EUNSUPPORTED, "too many documents");
-    if (out_dtype != MSIM_DTYPE_F32 && out_dtype != dtype)
-        return fail(MSIM_EINVAL, "gradients come out as fp32 or in the embeddings' own dtype (out_dtype %d, dtype %d)", out_dtype, dtype);
-    if (g_scale && g_scale_dtype != MSIM_DTYPE_BF16 && g_scale_dtype != MSIM_DTYPE_F16 && g_scale_dtype != MSIM_DTYPE_F32)
-        return fail(MSIM_EINVAL, "g_scale dtype code %d", g_scale_dtype);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    msim::PairsArgs a{n_q, Lq, n_d, n_pairs};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // short documents with long entry lists (the trainer's symmetric direction): the dense dD form, through the caller's scratch
-    DdPlan pl;
-    float *partial = static_cast<float *>(workspace);
-    if (partial) {
-        pl = dd_plan(n_pairs, Lq, n_d, dim, max_doc_rows, di->cus);
-        if (reinterpret_cast<uintptr_t>(workspace) & 15) return fail(MSIM_EINVAL, "workspace must be 16-byte aligned");
-    }
-    const msim::GScale gs{g_scale, g_scale_dtype};
-    const char *qc = static_cast<const char *>(Q), *dc = static_cast<const char *>(D);
-    const bool out16 = out_dtype != MSIM_DTYPE_F32;
-#define MSIM_BWD(DT, O16) \
-    launch_bwd_kernels<DT, O16>(qc, dc, d_off, max_doc_rows, pairs, order_by_doc, g, argmax, dQ, dD, a, dim, di->cus, st, partial, pl, gs)
-    if (dtype == MSIM_DTYPE_F32) MSIM_BWD(msim::kDtypeF32, false);
-    else if (dtype == MSIM_DTYPE_F16) { if (out16) MSIM_BWD(msim::kDtypeF16, true); else MSIM_BWD(msim::kDtypeF16, false); }
-    else { if (out16) MSIM_BWD(msim::kDtypeBf16, true); else MSIM_BWD(msim::kDtypeBf16, false); }
-#undef MSIM_BWD
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_pairs_bwd launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-// ---------------------------------------------------------------- loss epilogue
-// one workgroup reads the whole score matrix when it is small (loss_epilogue_small_kernel): no scratch, no ticket
-static bool epilogue_is_small(int B, int C) { return B > 0 && B <= msim::kEpiSmallRows && (long long)B * C <= (1 << 18); }
-
-size_t msim_loss_epilogue_workspace_bytes(int B, int C) {
-    if (epilogue_is_small(B, C)) return 0;
-    return B > 0 ? 16 + (size_t)3 * B * sizeof(float) : 16;
-}
-
-int msim_loss_epilogue(int mode, const float *scores, int64_t ld, int B, int C, const void *Q, int q_dtype, int Lq, int width,
-                       int offset, float temperature, int normalize, int filter, float filter_threshold, float filter_factor,
-                       float *G, int32_t *pairs, float *coef, int32_t *order, void *workspace, float *out, void *loss_out,
-                       const int32_t *q_lengths, void *stream) {
-    if (B < 0 || C < 0 || Lq < 0 || width <= 0) return fail(MSIM_EINVAL, "negative size");
-    if (mode != MSIM_LOSS_PAIRWISE && mode != MSIM_LOSS_INFONCE && mode != MSIM_LOSS_SIGMOID) return fail(MSIM_EINVAL, "unknown loss mode %d", mode);
-    if (mode == MSIM_LOSS_SIGMOID && C != B)
-        return fail(MSIM_EINVAL, "the sigmoid loss is defined on the in-batch square: %d queries, %d documents", B, C);
-    if (!scores || !Q || !out) return fail(MSIM_EINVAL, "null pointer argument");
-    if (q_dtype != MSIM_DTYPE_BF16 && q_dtype != MSIM_DTYPE_F16 && q_dtype != MSIM_DTYPE_F32)
-        return fail(MSIM_EUNSUPPORTED, "dtype code %d", q_dtype);
-    if (B == 0) return fail(MSIM_EINVAL, "empty batch");
-    if (offset < 0 || (long long)offset + B > C) return fail(MSIM_EINVAL, "offset %d + batch %d exceeds the %d documents", offset, B, C);
-    if (ld < C) return fail(MSIM_EINVAL, "ld=%lld < C=%d", (long long)ld, C);
-    if (temperature == 0.0f) return fail(MSIM_EINVAL, "temperature must be non-zero");
-    if (mode == MSIM_LOSS_PAIRWISE) {
-        if (C < 2) return fail(MSIM_EINVAL, "the pairwise loss needs at least 2 documents (topk(2))");
-        if (!pairs || !coef || !order) return fail(MSIM_EINVAL, "null pair-list output");
-    }
-    const bool small = epilogue_is_small(B, C);
-    if (!small && !workspace) return fail(MSIM_EINVAL, "this batch needs msim_loss_epilogue_workspace_bytes(B, C) bytes of zero-filled scratch");
-    if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15)) return fail(MSIM_EINVAL, "workspace must be 16-byte aligned");
-    msim::EpiArgs a;
-    a.ld = ld;
-    a.B = B;
-    a.C = C;
-    a.Lq = Lq;
-    a.q_elem_bytes = elem_bytes(q_dtype);
-    a.q_is_f16 = q_dtype == MSIM_DTYPE_F16;
-    a.q_row_bytes = width * a.q_elem_bytes;
-    a.offset = offset;
-    a.mode = mode == MSIM_LOSS_PAIRWISE ? msim::kEpiPairwise : mode == MSIM_LOSS_SIGMOID ? msim::kEpiSigmoid : msim::kEpiInfoNCE;
-    a.normalize = normalize != 0;
-    a.filter = filter != 0;
-    a.inv_T = 1.0f / temperature;
-    a.filter_threshold = filter_threshold;
-    a.filter_factor = filter_factor;
-    if (small) {
-        const int staged = (long long)B * C <= msim::kEpiStageFloats;
-        const int lds = staged ? B * C * (int)sizeof(float) : 0;
-        static std::atomic<int> configured[kMaxDevices];
-        if (int rc = allow_lds(msim::loss_epilogue_small_kernel, msim::kEpiStageFloats * (int)sizeof(float), configured)) return rc;
-        hipLaunchKernelGGL(msim::loss_epilogue_small_kernel, dim3(1), dim3(msim::kEpiSmallThreads), lds, static_cast<hipStream_t>(stream),
-                           scores, static_cast<const char *>(Q), q_lengths, G, pairs, coef, order, out, loss_out, a, staged);
-    } else {
-        char *ws = static_cast<char *>(workspace);
-        hipLaunchKernelGGL(msim::loss_epilogue_kernel, dim3(B), dim3(msim::kEpiThreads), 0, static_cast<hipStream_t>(stream), scores,
-                           static_cast<const char *>(Q), G, pairs, coef, order, reinterpret_cast<float *>(ws + 16),
-                           reinterpret_cast<unsigned int *>(ws), out, loss_out, q_lengths, a);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "loss_epilogue_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-// ---------------------------------------------------------------- smooth-max entry points
-int msim_smooth_fwd(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, int n_d, int dim, float tau,
-                    float *scores, int64_t ld_scores, void *stream) {
-    if (n_q < 0 || n_d < 0) return fail(MSIM_EINVAL, "negative size (n_q=%d n_d=%d)", n_q, n_d);
-    if (n_q == 0 || n_d == 0) return MSIM_OK;
-    if (!scores) return fail(MSIM_EINVAL, "null pointer argument");
-    if (int rc = check_smooth(Q, D, d_off, dtype, dim, Lq, tau)) return rc;
-    if (ld_scores < n_d) return fail(MSIM_EINVAL, "ld_scores=%lld < n_d=%d", (long long)ld_scores, n_d);
-    GenericCall c;
-    if (int rc = device_info(&c.di)) return rc;
-    c.Q = static_cast<const char *>(Q);
-    c.D = static_cast<const char *>(D);
-    c.d_off = d_off;
-    c.clamp0 = nullptr;
-    c.scores = scores;
-    c.ld = ld_scores;
-    c.n_q = n_q;
-    c.Lq = Lq;
-    c.n_d = n_d;
-    c.row_bytes = dim * elem_bytes(dtype);
-    c.flags = 0;
-    c.st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case MSIM_DTYPE_F32: return smooth_dispatch<msim::kDtypeF32>(c, tau);
-        case MSIM_DTYPE_F16: return smooth_dispatch<msim::kDtypeF16>(c, tau);
-        default: return smooth_dispatch<msim::kDtypeBf16>(c, tau);
-    }
-}
-
-}  // extern "C"
-
-namespace {
-template <int TPQ, bool F16>
-int launch_smooth_pairs_stream(const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const int32_t *pairs, float *out_scores,
-                               float *out_lse, const msim::PairsArgs &a, float tau, const DeviceInfo &di, hipStream_t st) {
-    auto kern = msim::maxsim_smooth_pairs_stream_kernel<TPQ, F16>;
-    constexpr int lds = 4 * msim::kPairsRing * msim::kSlabBytes;
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(kern, lds, configured)) return rc;
-    const int wg_needed = (a.n_pairs + 3) / 4;
-    const int wg_cap = di.cus * (di.lds_per_cu / lds);
-    hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), lds, st, Q, D, d_off, pairs, out_scores, out_lse,
-                       a, tau);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_smooth_pairs_stream_kernel<%d> launch: %s", TPQ, hipGetErrorString(e));
-    return MSIM_OK;
-}
-template <bool F16>
-int smooth_pairs_stream_dispatch(int tpq, const uint16_t *Q, const uint16_t *D, const int32_t *d_off, const int32_t *pairs,
-                                 float *out_scores, float *out_lse, const msim::PairsArgs &a, float tau, const DeviceInfo &di,
-                                 hipStream_t st) {
-    switch (tpq) {
-        case 1: return launch_smooth_pairs_stream<1, F16>(Q, D, d_off, pairs, out_scores, out_lse, a, tau, di, st);
-        case 2: return launch_smooth_pairs_stream<2, F16>(Q, D, d_off, pairs, out_scores, out_lse, a, tau, di, st);
-        case 3: return launch_smooth_pairs_stream<3, F16>(Q, D, d_off, pairs, out_scores, out_lse, a, tau, di, st);
-        default: return launch_smooth_pairs_stream<4, F16>(Q, D, d_off, pairs, out_scores, out_lse, a, tau, di, st);
-    }
-}
-}  // namespace
-
-extern "C" {
-
-int msim_smooth_pairs(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, int n_d, int dim,
-                      const int32_t *pairs, int n_pairs, float tau, float *out_scores, float *out_lse, void *stream) {
-    if (n_q < 0 || n_d < 0 || n_pairs < 0) return fail(MSIM_EINVAL, "negative size");
-    if (n_pairs == 0) return MSIM_OK;
-    if (!pairs) return fail(MSIM_EINVAL, "null pointer argument");
-    if (int rc = check_smooth(Q, D, d_off, dtype, dim, Lq, tau)) return rc;
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    msim::PairsArgs a{n_q, Lq, n_d, n_pairs};
-    const char *qc = static_cast<const char *>(Q), *dc = static_cast<const char *>(D);
-    const int rb = dim * elem_bytes(dtype);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int tpq = (Lq + msim::kTokTile - 1) / msim::kTokTile;
-    if (dim == msim::kDim && dtype != MSIM_DTYPE_F32 && tpq <= 4) {   // 128 x 16-bit rows: the LDS-DMA pipeline
-        const uint16_t *q16 = static_cast<const uint16_t *>(Q), *d16 = static_cast<const uint16_t *>(D);
-        return dtype == MSIM_DTYPE_F16 ? smooth_pairs_stream_dispatch<true>(tpq, q16, d16, d_off, pairs, out_scores, out_lse, a, tau, *di, st)
-                                       : smooth_pairs_stream_dispatch<false>(tpq, q16, d16, d_off, pairs, out_scores, out_lse, a, tau, *di, st);
-    }
-    switch (dtype) {
-        case MSIM_DTYPE_F32: return smooth_pairs<msim::kDtypeF32>(qc, dc, d_off, pairs, out_scores, out_lse, a, rb, tau, *di, st);
-        case MSIM_DTYPE_F16: return smooth_pairs<msim::kDtypeF16>(qc, dc, d_off, pairs, out_scores, out_lse, a, rb, tau, *di, st);
-        default: return smooth_pairs<msim::kDtypeBf16>(qc, dc, d_off, pairs, out_scores, out_lse, a, rb, tau, *di, st);
-    }
-}
-
-size_t msim_smooth_bwd_workspace_bytes(int n_q, int Lq, int dim) {
-    const DeviceInfo *di = nullptr;
-    if (n_q <= 0 || Lq <= 0 || dim <= 0 || device_info(&di)) return 0;
-    const int ns = smooth_dq_split(n_q, Lq, *di);
-    return ns > 1 ? (size_t)ns * n_q * Lq * dim * sizeof(float) : 0;
-}
-
-int msim_smooth_pairs_bwd(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, int n_d, int dim,
-                          int max_doc_rows, const int32_t *pairs, const int32_t *order_by_doc, const float *g, const float *lse,
-                          int n_pairs, float tau, float *dQ, float *dD, void *workspace, void *stream) {
-    if (n_q < 0 || n_d < 0 || n_pairs < 0 || max_doc_rows < 0) return fail(MSIM_EINVAL, "negative size");
-    if (!dQ || !dD) return fail(MSIM_EINVAL, "null pointer argument");
-    if (n_pairs > 0 && (!pairs || !order_by_doc || !g || !lse)) return fail(MSIM_EINVAL, "null pair-list argument");
-    if (int rc = check_smooth(Q, D, d_off, dtype, dim, Lq, tau)) return rc;
-    if ((max_doc_rows + 31) / 32 > 65535) return fail(MSIM_EUNSUPPORTED, "max_doc_rows=%d too large", max_doc_rows);
-    if ((Lq + 31) / 32 > 65535) return fail(MSIM_EUNSUPPORTED, "Lq=%d too large", Lq);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const int ns = smooth_dq_split(n_q, Lq, *di);
-    if (ns > 1 && !workspace) return fail(MSIM_EINVAL, "workspace required (msim_smooth_bwd_workspace_bytes)");
-    if ((reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dD) | reinterpret_cast<uintptr_t>(workspace)) & 15)
-        return fail(MSIM_EINVAL, "dQ, dD and the workspace must be 16-byte aligned");
-    msim::SmoothBwdArgs a{n_q, Lq, n_d, n_pairs, dim * elem_bytes(dtype), dim, tau, 1};
-    const char *qc = static_cast<const char *>(Q), *dc = static_cast<const char *>(D);
-    float *ws = static_cast<float *>(workspace);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (dtype) {
-        case MSIM_DTYPE_F32: return smooth_bwd<msim::kDtypeF32>(qc, dc, d_off, max_doc_rows, pairs, order_by_doc, g, lse, dQ, dD, ws, a, ns, st);
-        case MSIM_DTYPE_F16: return smooth_bwd<msim::kDtypeF16>(qc, dc, d_off, max_doc_rows, pairs, order_by_doc, g, lse, dQ, dD, ws, a, ns, st);
-        default: return smooth_bwd<msim::kDtypeBf16>(qc, dc, d_off, max_doc_rows, pairs, order_by_doc, g, lse, dQ, dD, ws, a, ns, st);
-    }
-}
-
-// ---------------------------------------------------------------- embedding head (the producer of the corpus format)
-int msim_embed_head_row_map(const void *mask, int mask_kind, const void *extra, int extra_kind, int64_t M, int32_t *row_map, void *stream) {
-    if (M < 0) return fail(MSIM_EINVAL, "bad size (M=%lld)", (long long)M);
-    if (M == 0) return MSIM_OK;
-    if (!mask || !row_map) return fail(MSIM_EINVAL, "null pointer argument");
-    if (mask_kind < 0 || mask_kind > 6 || (extra && (extra_kind < 0 || extra_kind > 6))) return fail(MSIM_EINVAL, "unknown mask kind");
-    if (M > 0x7ffffffdLL) return fail(MSIM_EUNSUPPORTED, "too many rows for an int32 row map");
-    const long long padded = (M + msim::kHeadBM - 1) / msim::kHeadBM * msim::kHeadBM;
-    hipLaunchKernelGGL(msim::head_row_map_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), mask,
-                       mask_kind, extra, extra_kind, (long long)M, padded, row_map);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "head_row_map_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_embed_head_writer_map(const void *mask, int mask_kind, const void *extra, int extra_kind, int B, int S, const int64_t *rows_before,
-                               int64_t *counts, int32_t *row_map, int64_t *rows_after, void *stream) {
-    if (B < 0 || S <= 0) return fail(MSIM_EINVAL, "bad size (B=%d S=%d)", B, S);
-    if (B == 0) return MSIM_OK;
-    if (!mask || !rows_before || !counts || !row_map || !rows_after) return fail(MSIM_EINVAL, "null pointer argument");
-    if (mask_kind < 0 || mask_kind > 6 || (extra && (extra_kind < 0 || extra_kind > 6))) return fail(MSIM_EINVAL, "unknown mask kind");
-    const long long M = (long long)B * S;
-    const long long padded = (M + msim::kHeadBM - 1) / msim::kHeadBM * msim::kHeadBM;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(msim::head_page_count_kernel, dim3(B), dim3(256), 0, st, mask, mask_kind, extra, extra_kind, S,
-                       reinterpret_cast<long long *>(counts));
-    hipLaunchKernelGGL(msim::head_writer_map_kernel, dim3(B + 1), dim3(256), 0, st, mask, mask_kind, extra, extra_kind, B, S,
-                       reinterpret_cast<const long long *>(rows_before), reinterpret_cast<const long long *>(counts), padded, row_map,
-                       reinterpret_cast<long long *>(rows_after));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "head_writer_map_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_embed_head_bwd(int dtype, const void *proj, const void *grad_out, const int32_t *row_map, int64_t M, int n_out,
-                        void *dproj, void *stream) {
-    if (M < 0) return fail(MSIM_EINVAL, "bad size (M=%lld)", (long long)M);
-    if (M == 0) return MSIM_OK;
-    if (!proj || !grad_out || !row_map || !dproj) return fail(MSIM_EINVAL, "null pointer argument");
-    if (dtype != MSIM_DTYPE_BF16 && dtype != MSIM_DTYPE_F16)
-        return fail(MSIM_EUNSUPPORTED, "dtype code %d: the embedding head takes bfloat16 (0) or float16 (1)", dtype);
-    if (n_out != msim::kHeadN) return fail(MSIM_EUNSUPPORTED, "n_out=%d: the embedding head is built for 128 output columns", n_out);
-    if ((reinterpret_cast<uintptr_t>(proj) | reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(dproj)) & 15)
-        return fail(MSIM_EINVAL, "proj, grad_out and dproj must be 16-byte aligned");
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const long long blocks = (M + 15) / 16;
-    const int grid = (int)(blocks < (long long)di->cus * 16 ? blocks : (long long)di->cus * 16);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *p = static_cast<const uint16_t *>(proj), *g = static_cast<const uint16_t *>(grad_out);
-    uint16_t *o = static_cast<uint16_t *>(dproj);
-    if (dtype == MSIM_DTYPE_F16)
-        hipLaunchKernelGGL(msim::embed_head_bwd_rows_kernel<true>, dim3(grid), dim3(256), 0, st, p, g, row_map, (long long)M, o);
-    else
-        hipLaunchKernelGGL(msim::embed_head_bwd_rows_kernel<false>, dim3(grid), dim3(256), 0, st, p, g, row_map, (long long)M, o);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "embed_head_bwd_rows_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_embed_head(int dtype, const void *X, int64_t M, int H, const void *W, const void *bias, int n_out,
-                    const int32_t *row_map, void *out, int64_t ld_out, void *stream) {
-    if (M < 0 || H <= 0) return fail(MSIM_EINVAL, "bad size (M=%lld H=%d)", (long long)M, H);
-    if (M == 0) return MSIM_OK;
-    if (!X || !W || !row_map || !out) return fail(MSIM_EINVAL, "null pointer argument");
-    if (dtype != MSIM_DTYPE_BF16 && dtype != MSIM_DTYPE_F16)
-        return fail(MSIM_EUNSUPPORTED, "dtype code %d: the embedding head takes bfloat16 (0) or float16 (1) hidden states", dtype);
-    if (n_out != msim::kHeadN) return fail(MSIM_EUNSUPPORTED, "n_out=%d: the embedding head is built for 128 output columns", n_out);
-    if (H % msim::kHeadBK != 0 || H > 16384) return fail(MSIM_EUNSUPPORTED, "H=%d: hidden size must be a multiple of 64, <= 16384", H);
-    if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W)) & 15) return fail(MSIM_EINVAL, "X and W must be 16-byte aligned");
-    if (ld_out < msim::kHeadN) return fail(MSIM_EINVAL, "ld_out=%lld < 128", (long long)ld_out);
-    if (M > (int64_t)0x7fffffff * 128) return fail(MSIM_EUNSUPPORTED, "too many rows");
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    msim::HeadArgs a;
-    a.M = M;
-    a.H = H;
-    a.ld_out = ld_out;
-    a.trace = nullptr;
-    a.stagger = ab_env("MSIM_HEAD_STAGGER", 0);
-    a.stagger_sleep = ab_env("MSIM_HEAD_STAGGER_SLEEP", 1);
-#ifdef MSIM_TRACE                                            // `make trace` only: device address of 9 x 8 uint64 (tools/trace_head.py)
-    if (const char *tp = getenv("MSIM_HEAD_TRACE_PTR")) a.trace = reinterpret_cast<unsigned long long *>(strtoull(tp, nullptr, 0));
-#endif
-    const long long tiles = (M + msim::kHeadBM - 1) / msim::kHeadBM;
-    const int grid = tiles < di->cus ? (int)tiles : di->cus;
-    const long long tiles_h = (M + 127) / 128;                               // HALF variant: 128-row tiles, two workgroups per CU
-    const int grid_h = tiles_h < 2 * di->cus ? (int)tiles_h : 2 * di->cus;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint16_t *x = static_cast<const uint16_t *>(X), *w = static_cast<const uint16_t *>(W), *b = static_cast<const uint16_t *>(bias);
-    uint16_t *o = static_cast<uint16_t *>(out);
-    auto go = [&](auto kern, std::atomic<int> *configured, int lds) -> int {
-        if (int rc = allow_lds(kern, lds, configured)) return rc;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(msim::kHeadThreads), lds, st, x, w, b, row_map, o, a);
-        return MSIM_OK;
-    };
-    auto go_half = [&](auto kern, std::atomic<int> *configured) -> int {
-        constexpr int lds = 3 * 128 * 128 + 2 * msim::kHeadWBytes;             // 48 + 32 KiB
-        if (int rc = allow_lds(kern, lds, configured)) return rc;
-        hipLaunchKernelGGL(kern, dim3(grid_h), dim3(320), lds, st, x, w, b, row_map, o, a);
-        return MSIM_OK;
-    };
-    int rc;
-    const bool f16 = dtype == MSIM_DTYPE_F16;
-    // Shipped: loader two weight chunks ahead (rings 3 + 3), output rows staged through LDS and stored as whole rows with the
-    // streaming policy (needs 16-byte aligned output rows; the 2-byte-store form of the same kernel otherwise).  Every other
-    // variant of embed_head_kernel was measured and not kept; they are compiled into measurement builds only
-    // (preprocessor, not `if constexpr`: in a non-template function a discarded branch is still instantiated and code-generated).
-#if !defined(MSIM_AB) && !defined(MSIM_TRACE)
-    {
-        const bool whole_rows = ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        static std::atomic<int> cfg[4][kMaxDevices];
-        if (whole_rows)
-            rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true, false, false, true>, cfg[0], msim::kHeadFLds)
-                     : go(msim::embed_head_kernel<false, false, false, false, true, false, false, true>, cfg[1], msim::kHeadFLds);
-        else
-            rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true>, cfg[2], msim::kHeadFLds)
-                     : go(msim::embed_head_kernel<false, false, false, false, true>, cfg[3], msim::kHeadFLds);
-        (void)go_half;
-    }
-#else
-    {
-        static std::atomic<int> configured[12][kMaxDevices];
-        // MSIM_HEAD_VARIANT = bit 0: flag-synchronised weight ring instead of one s_barrier per K chunk; bit 1: hand-pipelined operand
-        // fetch; bit 2: swapped MFMA roles + per-row epilogue; bit 3 (default): loader two weight chunks ahead, rings 3 + 3; bit 4: two half-size workgroups per CU; bit 5: DMA pieces between the
-        // MFMAs; bit 6 (default): whole-row output stores through LDS
-        // (tuning knob for A/B measurements, not part of the ABI; profiles/r02_logs/ab_head_variants.log)
-        static const int variant = ab_env("MSIM_HEAD_VARIANT", 72) & 127;
-        const bool epi2 = (variant & 4) && ld_out % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0 &&
-                          (bias == nullptr || (reinterpret_cast<uintptr_t>(bias) & 3) == 0);   // 8-byte stores, 4-byte bias loads
-        // bit 3: loader two weight chunks ahead (rings 3 + 3)
-        // bit 6 (default): output rows staged through LDS and stored as whole rows; needs 16-byte aligned rows, else the 2-byte form
-        const bool epi3 = (variant & 64) && ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        static const int pair_env = ab_env("MSIM_HEAD_PAIR", 0);       // round 3: chunks requested two at a time (rings 4 + 2, whole-row stores)
-        if (pair_env && epi3) {
-            static std::atomic<int> configured6[2][kMaxDevices];
-            rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, false, false, false, true, true>, configured6[0], msim::kHeadLds)
-                     : go(msim::embed_head_kernel<false, false, false, false, false, false, false, true, true>, configured6[1], msim::kHeadLds);
-        } else if (epi3) {
-            static std::atomic<int> configured5[2][kMaxDevices];
-            rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true, false, false, true>, configured5[0], msim::kHeadFLds)
-                     : go(msim::embed_head_kernel<false, false, false, false, true, false, false, true>, configured5[1], msim::kHeadFLds);
-        } else if (variant & 32) {           // bit 5: hidden-state DMA pieces issued between the k-steps' MFMAs (+ bit 3 rings, + bit 2 epilogue)
-            static std::atomic<int> configured4[6][kMaxDevices];
-            if ((variant & 8) && (variant & 4) && epi2)
-                rc = f16 ? go(msim::embed_head_kernel<true, false, false, true, true, false, true>, configured4[0], msim::kHeadFLds)
-                         : go(msim::embed_head_kernel<false, false, false, true, true, false, true>, configured4[1], msim::kHeadFLds);
-            else if (variant & 8)
-                rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true, false, true>, configured4[2], msim::kHeadFLds)
-                         : go(msim::embed_head_kernel<false, false, false, false, true, false, true>, configured4[3], msim::kHeadFLds);
-            else
-                rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, false, false, true>, configured4[4], msim::kHeadLds)
-                         : go(msim::embed_head_kernel<false, false, false, false, false, false, true>, configured4[5], msim::kHeadLds);
-        } else if (variant & 16) {           // bit 4: two half-size workgroups per CU
-            static std::atomic<int> configured3[2][kMaxDevices];
-            rc = f16 ? go_half(msim::embed_head_kernel<true, false, false, false, false, true>, configured3[0])
-                     : go_half(msim::embed_head_kernel<false, false, false, false, false, true>, configured3[1]);
-        } else if ((variant & 8) && (variant & 4) && epi2) {
-            static std::atomic<int> configured2[2][kMaxDevices];
-            rc = f16 ? go(msim::embed_head_kernel<true, false, false, true, true>, configured2[0], msim::kHeadFLds)
-                     : go(msim::embed_head_kernel<false, false, false, true, true>, configured2[1], msim::kHeadFLds);
-        } else if (variant & 8) {
-            rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true>, configured[10], msim::kHeadFLds)
-                     : go(msim::embed_head_kernel<false, false, false, false, true>, configured[11], msim::kHeadFLds);
-        } else
-        switch (epi2 ? 4 : (variant & 3)) {
-            case 1: rc = f16 ? go(msim::embed_head_kernel<true, true, false>, configured[0], msim::kHeadFLds)
-                             : go(msim::embed_head_kernel<false, true, false>, configured[1], msim::kHeadFLds); break;
-            case 2: rc = f16 ? go(msim::embed_head_kernel<true, false, true>, configured[2], msim::kHeadLds)
-                             : go(msim::embed_head_kernel<false, false, true>, configured[3], msim::kHeadLds); break;
-            case 3: rc = f16 ? go(msim::embed_head_kernel<true, true, true>, configured[4], msim::kHeadFLds)
-                             : go(msim::embed_head_kernel<false, true, true>, configured[5], msim::kHeadFLds); break;
-            case 4: rc = f16 ? go(msim::embed_head_kernel<true, false, false, true>, configured[8], msim::kHeadLds)
-                             : go(msim::embed_head_kernel<false, false, false, true>, configured[9], msim::kHeadLds); break;
-            default: rc = f16 ? go(msim::embed_head_kernel<true, false, false>, configured[6], msim::kHeadLds)
-                              : go(msim::embed_head_kernel<false, false, false>, configured[7], msim::kHeadLds); break;
-        }
-    }
-#endif
-    if (rc) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "embed_head_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
 // ---------------------------------------------------------------- plain similarity matrix entry point
 int msim_sim_matrix(int dtype, const void *A, int n_a, const void *B, int n_b, int dim, float *out, int64_t ld_out,
                     uint32_t flags, void *stream) {
@@ -2166,185 +920,6 @@ int msim_sim_matrix(int dtype, const void *A, int n_a, const void *B, int n_b, i
     }
 }
 
-// ---------------------------------------------------------------- hierarchical token pooling
-int msim_pool_cluster(int dtype, const void *E, const int32_t *d_off, int n_pages, int dim, int max_rows,
-                      const int64_t *ws_off, int pool_factor, float *X_ws, double *D_ws, int32_t *labels,
-                      int32_t *n_clusters, void *stream) {
-    if (n_pages < 0 || max_rows < 0) return fail(MSIM_EINVAL, "negative size");
-    if (n_pages == 0) return MSIM_OK;
-    if (!E || !d_off || !ws_off || !X_ws || !D_ws || !labels || !n_clusters) return fail(MSIM_EINVAL, "null pointer argument");
-    if (pool_factor < 1) return fail(MSIM_EINVAL, "pool_factor must be >= 1");
-    static const int32_t dummy_off[2] = {0, 0};
-    if (int rc = check_smooth(E, E, dummy_off, dtype, dim, 1, 1.0f)) return rc;      // row layout contract of the generic kernels
-    if (max_rows > msim::kPoolMaxRows) return fail(MSIM_EUNSUPPORTED, "a page of %d rows: at most %d are supported", max_rows, msim::kPoolMaxRows);
-    if (n_pages > 65535) return fail(MSIM_EUNSUPPORTED, "at most 65535 pages per call");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    msim::PoolArgs a{n_pages, dim, dim * elem_bytes(dtype), pool_factor};
-    const char *e = static_cast<const char *>(E);
-    if (max_rows > 0) {
-        const dim3 ggrid((max_rows + 127) / 128, (max_rows + 31) / 32, n_pages);
-        switch (dtype) {
-            case MSIM_DTYPE_F32: hipLaunchKernelGGL(msim::pool_gram_kernel<msim::kDtypeF32>, ggrid, dim3(256), 0, st, e, d_off, ws_off, X_ws, a); break;
-            case MSIM_DTYPE_F16: hipLaunchKernelGGL(msim::pool_gram_kernel<msim::kDtypeF16>, ggrid, dim3(256), 0, st, e, d_off, ws_off, X_ws, a); break;
-            default: hipLaunchKernelGGL(msim::pool_gram_kernel<msim::kDtypeBf16>, ggrid, dim3(256), 0, st, e, d_off, ws_off, X_ws, a); break;
-        }
-        const int tiles = (max_rows + 15) / 16;
-        hipLaunchKernelGGL(msim::pool_pdist_kernel, dim3(tiles, tiles, n_pages), dim3(256), 0, st, d_off, ws_off, X_ws, D_ws);
-    }
-    // pages of at most kPoolMaxN rows keep the clustering state in LDS; a call with a longer page runs the variant whose long pages
-    // keep it in their (by then dead) region of X_ws
-    if (max_rows > msim::kPoolMaxN) {
-        static std::atomic<int> configured_big[kMaxDevices];
-        if (int rc = allow_lds(msim::pool_cluster_kernel<true>, (int)sizeof(msim::PoolLds), configured_big)) return rc;
-        hipLaunchKernelGGL(msim::pool_cluster_kernel<true>, dim3(n_pages), dim3(msim::kPoolThreads), sizeof(msim::PoolLds), st, d_off, ws_off,
-                           X_ws, D_ws, labels, n_clusters, pool_factor);
-    } else {
-        static std::atomic<int> configured[kMaxDevices];
-        if (int rc = allow_lds(msim::pool_cluster_kernel<false>, (int)sizeof(msim::PoolLds), configured)) return rc;
-        hipLaunchKernelGGL(msim::pool_cluster_kernel<false>, dim3(n_pages), dim3(msim::kPoolThreads), sizeof(msim::PoolLds), st, d_off, ws_off,
-                           X_ws, D_ws, labels, n_clusters, pool_factor);
-    }
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(MSIM_ELAUNCH, "token pooling launch: %s", hipGetErrorString(err));
-    return MSIM_OK;
-}
-
-int msim_pool_reduce(int dtype, const void *E, const int32_t *d_off, int n_pages, int dim, int ld_in, const int32_t *labels,
-                     const int32_t *out_off, void *out, int ld_out, void *stream) {
-    if (n_pages < 0) return fail(MSIM_EINVAL, "negative size");
-    if (n_pages == 0) return MSIM_OK;
-    if (!E || !d_off || !labels || !out_off || !out) return fail(MSIM_EINVAL, "null pointer argument");
-    if (dtype != MSIM_DTYPE_BF16 && dtype != MSIM_DTYPE_F16 && dtype != MSIM_DTYPE_F32) return fail(MSIM_EUNSUPPORTED, "dtype code %d", dtype);
-    if (dim <= 0 || dim > 2048 || ld_in < dim || ld_out < dim) return fail(MSIM_EUNSUPPORTED, "dim=%d (ld_in=%d ld_out=%d)", dim, ld_in, ld_out);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const char *e = static_cast<const char *>(E);
-    char *o = static_cast<char *>(out);
-    const int es = elem_bytes(dtype);
-    switch (dtype) {
-        case MSIM_DTYPE_F32: hipLaunchKernelGGL(msim::pool_reduce_kernel<msim::kDtypeF32>, dim3(n_pages), dim3(256), 0, st, e, d_off, labels, out_off, o, dim, ld_in * es, ld_out * es); break;
-        case MSIM_DTYPE_F16: hipLaunchKernelGGL(msim::pool_reduce_kernel<msim::kDtypeF16>, dim3(n_pages), dim3(256), 0, st, e, d_off, labels, out_off, o, dim, ld_in * es, ld_out * es); break;
-        default: hipLaunchKernelGGL(msim::pool_reduce_kernel<msim::kDtypeBf16>, dim3(n_pages), dim3(256), 0, st, e, d_off, labels, out_off, o, dim, ld_in * es, ld_out * es); break;
-    }
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(MSIM_ELAUNCH, "pool_reduce_kernel launch: %s", hipGetErrorString(err));
-    return MSIM_OK;
-}
-
-int msim_host_gather(void *dst, const void *const *src, const int64_t *dst_off, const int64_t *nbytes, int64_t n, int n_threads) {
-    if (n < 0) return fail(MSIM_EINVAL, "negative count");
-    if (n == 0) return MSIM_OK;
-    if (!dst || !src || !dst_off || !nbytes) return fail(MSIM_EINVAL, "null pointer argument");
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (nbytes[i] < 0 || dst_off[i] < 0 || (nbytes[i] > 0 && !src[i])) return fail(MSIM_EINVAL, "bad buffer %lld", (long long)i);
-        total += nbytes[i];
-    }
-    char *d = static_cast<char *>(dst);
-    auto run = [&](int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i)
-            if (nbytes[i]) memcpy(d + dst_off[i], src[i], (size_t)nbytes[i]);
-    };
-    int nt = n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads);
-    if (total < (int64_t)(4 << 20) * nt) nt = (int)(total >> 22) < 1 ? 1 : (int)(total >> 22);   // below ~4 MiB per thread: fewer
-    if (nt <= 1 || n < 2) {
-        run(0, n);
-        return MSIM_OK;
-    }
-    std::vector<std::thread> pool;
-    pool.reserve(nt);
-    const int64_t per = (total + nt - 1) / nt;
-    int64_t lo = 0, acc = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        acc += nbytes[i];
-        if (acc >= per || i + 1 == n) {
-            pool.emplace_back(run, lo, i + 1);
-            lo = i + 1;
-            acc = 0;
-        }
-    }
-    for (auto &t : pool) t.join();
-    return MSIM_OK;
-}
-
-}  // extern "C"
-
-namespace {
-inline bool row_is_zero(const char *p, int64_t row_bytes) {
-    int64_t i = 0;
-    uint64_t acc = 0;
-    for (; i + 8 <= row_bytes; i += 8) {
-        uint64_t v;
-        memcpy(&v, p + i, 8);
-        acc |= v;
-    }
-    for (; i < row_bytes; ++i) acc |= (unsigned char)p[i];
-    return acc == 0;
-}
-
-template <class F>
-void host_parallel(int64_t n, int n_threads, int64_t work_bytes, F &&body) {
-    int nt = n_threads < 1 ? 1 : (n_threads > 64 ? 64 : n_threads);
-    if (work_bytes < (int64_t)(4 << 20) * nt) nt = (int)(work_bytes >> 22) < 1 ? 1 : (int)(work_bytes >> 22);
-    if (nt <= 1 || n < 2) {
-        body(0, n);
-        return;
-    }
-    std::vector<std::thread> pool;
-    pool.reserve(nt);
-    const int64_t per = (n + nt - 1) / nt;
-    for (int64_t lo = 0; lo < n; lo += per) pool.emplace_back(body, lo, lo + per < n ? lo + per : n);
-    for (auto &t : pool) t.join();
-}
-}  // namespace
-
-extern "C" {
-
-int msim_host_count_nonzero_rows(const void *const *src, const int64_t *rows, int64_t row_bytes, int64_t n, int32_t *counts,
-                                 int n_threads) {
-    if (n < 0 || row_bytes <= 0) return fail(MSIM_EINVAL, "bad size");
-    if (n == 0) return MSIM_OK;
-    if (!src || !rows || !counts) return fail(MSIM_EINVAL, "null pointer argument");
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (rows[i] < 0 || rows[i] > 0x7fffffff || (rows[i] > 0 && !src[i])) return fail(MSIM_EINVAL, "bad buffer %lld", (long long)i);
-        total += rows[i] * row_bytes;
-    }
-    host_parallel(n, n_threads, total, [&](int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i) {
-            const char *p = static_cast<const char *>(src[i]);
-            int32_t c = 0;
-            for (int64_t r = 0; r < rows[i]; ++r) c += row_is_zero(p + r * row_bytes, row_bytes) ? 0 : 1;
-            counts[i] = c;
-        }
-    });
-    return MSIM_OK;
-}
-
-int msim_host_gather_nonzero_rows(void *dst, const void *const *src, const int64_t *rows, int64_t row_bytes, const int64_t *dst_row,
-                                  int64_t n, int n_threads) {
-    if (n < 0 || row_bytes <= 0) return fail(MSIM_EINVAL, "bad size");
-    if (n == 0) return MSIM_OK;
-    if (!dst || !src || !rows || !dst_row) return fail(MSIM_EINVAL, "null pointer argument");
-    int64_t total = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (rows[i] < 0 || dst_row[i] < 0 || (rows[i] > 0 && !src[i])) return fail(MSIM_EINVAL, "bad buffer %lld", (long long)i);
-        total += rows[i] * row_bytes;
-    }
-    char *d = static_cast<char *>(dst);
-    host_parallel(n, n_threads, total, [&](int64_t lo, int64_t hi) {
-        for (int64_t i = lo; i < hi; ++i) {
-            const char *p = static_cast<const char *>(src[i]);
-            char *o = d + dst_row[i] * row_bytes;
-            for (int64_t r = 0; r < rows[i]; ++r) {
-                if (row_is_zero(p + r * row_bytes, row_bytes)) continue;
-                memcpy(o, p + r * row_bytes, (size_t)row_bytes);
-                o += row_bytes;
-            }
-        }
-    });
-    return MSIM_OK;
-}
-
 int msim_query_compact(const void *box, int n_q, int Lq, int row_bytes, const int32_t *q_off, int32_t *counts, void *out,
                        void *stream) {
     if (n_q < 0 || Lq < 0 || row_bytes <= 0 || (row_bytes & 15)) return fail(MSIM_EINVAL, "bad size (row bytes must be a multiple of 16)");
@@ -2354,128 +929,15 @@ int msim_query_compact(const void *box, int n_q, int Lq, int row_bytes, const in
     if (reinterpret_cast<uintptr_t>(box) & 15 || reinterpret_cast<uintptr_t>(out) & 15) return fail(MSIM_EINVAL, "buffers must be 16-byte aligned");
     hipLaunchKernelGGL(msim::query_compact_kernel, dim3(n_q), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const char *>(box), Lq, row_bytes, q_off, counts, static_cast<char *>(out));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "query_compact_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-// ---------------------------------------------------------------- top-k selection
-// Level plan: level 0 splits each row into segments of `seg0` candidates (a power of two chosen so that the
-// launch has enough workgroups to fill the chip even for a single row); later levels use full segments.
-static inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// level 0 as the streaming threshold filter (topk_select.hip: topk_filter_kernel): rows of raw scores long enough for it, few
-// enough winners per row, and enough (row, segment) workgroups to fill the chip -- the many-query regime, where the bitonic level
-// was the one kernel of the timed step two orders off its roof
-static bool topk_use_filter(const int64_t *ids, int n_q, long long n, int k) {
-    if (ids != nullptr || k > msim::kTopkFilterMaxK || n < (long long)msim::kTopkFilterSeg) return false;
-    return (long long)n_q * ((n + msim::kTopkFilterSeg - 1) / msim::kTopkFilterSeg) >= 512;      // two workgroups per CU at least
-}
-
-static int topk_first_segment(int n_q, long long n, int k) {
-    int seg = 512;
-    while (seg < 4 * k) seg <<= 1;                       // every level must shrink its input at least 4x
-    while (seg < msim::kTopkSeg && (long long)n_q * ((n + seg - 1) / seg) > 1024) seg <<= 1;   // ~4 workgroups per CU is plenty
-    return seg;
-}
-static inline long long topk_level_out(long long n, int seg, int k) { return ((n + seg - 1) / seg) * (long long)k; }
-// Later levels: the smallest legal segment.  A bitonic sort of s candidates costs ~log2(s)^2 / 2 barrier-separated stages of s / 512
-// passes each, so two levels of 512 (45 stages + a tiny final sort) beat one 4096-candidate sort (78 stages x 8 passes) several
-// times over -- the single-workgroup last level was 157 us of a 200 us top-k at 4 queries x 125 000 documents.
-static int topk_later_segment(int k) {
-    int seg = 512;
-    while (seg < 4 * k) seg <<= 1;
-    return seg;
-}
-// one more workgroup-per-segment level only while the row is longer than two segments; otherwise one workgroup finishes the row
-static inline bool topk_is_last(long long n, int seg) { return n <= 2LL * seg && n <= msim::kTopkSeg; }
-
-static size_t topk_plan_bytes(int n_q, long long n, int k, int seg0) {
-    if (topk_is_last(n, seg0)) return 0;
-    const int seg1 = topk_later_segment(k);
-    const long long na = topk_level_out(n, seg0, k);
-    const long long nb = topk_is_last(na, seg1) ? 0 : topk_level_out(na, seg1, k);
-    return align16((size_t)n_q * na * 4) + align16((size_t)n_q * na * 8) + align16((size_t)n_q * nb * 4) +
-           align16((size_t)n_q * nb * 8);
-}
-
-size_t msim_topk_workspace_bytes(int n_q, int64_t n, int k) {
-    if (n_q <= 0 || k <= 0 || k > msim::kTopkMaxK) return 0;
-    // the same problem takes the filter level without explicit ids and the plain level with them: room for either
-    size_t need = topk_plan_bytes(n_q, n, k, topk_first_segment(n_q, n, k));
-    if (topk_use_filter(nullptr, n_q, n, k)) {
-        const size_t f = topk_plan_bytes(n_q, n, k, msim::kTopkFilterSeg);
-        if (f > need) need = f;
-    }
-    return need;
-}
-
-int msim_topk_f32(const float *scores, const int64_t *ids, int n_q, int64_t n, int64_t ld, int k, int64_t id_base,
-                  float *out_scores, int64_t *out_ids, void *workspace, void *stream) {
-    if (n_q < 0 || n < 0 || k <= 0) return fail(MSIM_EINVAL, "bad size (n_q=%d n=%lld k=%d)", n_q, (long long)n, k);
-    if (n_q == 0) return MSIM_OK;
-    if (!out_scores || !out_ids || (n > 0 && !scores)) return fail(MSIM_EINVAL, "null pointer argument");
-    if (k > msim::kTopkMaxK) return fail(MSIM_EUNSUPPORTED, "k=%d > %d", k, msim::kTopkMaxK);
-    if (ld < n) return fail(MSIM_EINVAL, "ld=%lld < n=%lld", (long long)ld, (long long)n);
-    const bool filter0 = topk_use_filter(ids, n_q, n, k);
-    const int seg0 = filter0 ? msim::kTopkFilterSeg : topk_first_segment(n_q, n, k);
-    const int seg1 = topk_later_segment(k);
-    if (!topk_is_last(n, seg0) && !workspace) return fail(MSIM_EINVAL, "workspace required (msim_topk_workspace_bytes)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-
-    const long long na = topk_is_last(n, seg0) ? 0 : topk_level_out(n, seg0, k);
-    const long long nb = (na == 0 || topk_is_last(na, seg1)) ? 0 : topk_level_out(na, seg1, k);
-    char *w = static_cast<char *>(workspace);
-    float *bufs_s[2];
-    int64_t *bufs_i[2];
-    long long bufs_ld[2] = {na, nb};
-    bufs_s[0] = reinterpret_cast<float *>(w);
-    w += align16((size_t)n_q * na * 4);
-    bufs_i[0] = reinterpret_cast<int64_t *>(w);
-    w += align16((size_t)n_q * na * 8);
-    bufs_s[1] = reinterpret_cast<float *>(w);
-    w += align16((size_t)n_q * nb * 4);
-    bufs_i[1] = reinterpret_cast<int64_t *>(w);
-
-    const float *in_s = scores;
-    const int64_t *in_i = ids;
-    long long in_n = n, in_ld = ld, in_base = id_base;
-    int which = 0, seg = seg0;
-    for (;;) {
-        const bool last = topk_is_last(in_n, seg);
-        const long long segs = last ? 1 : (in_n + seg - 1) / seg;
-        float *o_s = last ? out_scores : bufs_s[which];
-        int64_t *o_i = last ? out_ids : bufs_i[which];
-        const long long o_ld = last ? k : segs * k;
-        if (!last && o_ld > bufs_ld[which]) return fail(MSIM_ELAUNCH, "internal: top-k level does not fit its buffer");
-        for (int r0 = 0; r0 < n_q; r0 += 65535) {   // grid.y limit
-            const int rows = (n_q - r0 < 65535) ? (n_q - r0) : 65535;
-            if (filter0 && in_s == scores) {        // level 0: the streaming filter
-                hipLaunchKernelGGL(msim::topk_filter_kernel, dim3((unsigned)segs, (unsigned)rows), dim3(msim::kTopkThreads), 0, st,
-                                   in_s + (size_t)r0 * in_ld, in_n, in_ld, in_base, k, o_s + (size_t)r0 * o_ld, o_i + (size_t)r0 * o_ld, o_ld);
-                continue;
-            }
-            hipLaunchKernelGGL(msim::topk_segment_kernel, dim3((unsigned)segs, (unsigned)rows), dim3(msim::kTopkThreads), 0, st,
-                               in_s + (size_t)r0 * in_ld, in_i ? in_i + (size_t)r0 * in_ld : nullptr, in_n, in_ld, in_base, k,
-                               last ? msim::kTopkSeg : seg, o_s + (size_t)r0 * o_ld, o_i + (size_t)r0 * o_ld, o_ld);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(MSIM_ELAUNCH, "topk_segment_kernel launch: %s", hipGetErrorString(e));
-        if (last) break;
-        in_s = o_s;
-        in_i = o_i;
-        in_n = o_ld;
-        in_ld = o_ld;
-        in_base = 0;
-        which ^= 1;
-        seg = seg1;
-    }
-    return MSIM_OK;
+    return launch_failed("query_compact_kernel");
 }
 
 }  // extern "C"
 
 // ---------------------------------------------------------------- candidate reranking (K1c, maxsim_candidates.hip)
+// In this unit and not with the other search entry points (abi_search.hip): K1c is built from K1s's slab helpers, and next to K1s and
+// K1b the compiler emits for it the machine code it emitted when the library was one translation unit; in a unit without them two
+// instantiations came out with another register allocation and schedule (104 bytes shorter, same descriptor), unmeasured.
 namespace {
 
 struct CandLayout {        // msim_fwd_candidates' workspace, every piece 16-byte aligned
@@ -2483,24 +945,21 @@ struct CandLayout {        // msim_fwd_candidates' workspace, every piece 16-byt
 };
 
 CandLayout cand_layout(int n_q, int m, int n_d) {
-    auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t E = (size_t)n_q * (size_t)m;
     const size_t nb = ((size_t)n_d + msim::kCandScanDocs - 1) / msim::kCandScanDocs;
     CandLayout L;
     size_t w = 0;
     L.status = w;   w += 16;                                             // zeroed together with the counts
-    L.cnt = w;      w += a16((size_t)n_d * msim::kCandClasses * 4);
-    L.bsum = w;     w += a16((2 * nb + 2) * 4);
-    L.estart = w;   w += a16(((size_t)n_d + 1) * 4);
-    L.istart = w;   w += a16(((size_t)n_d + 1) * 4);
-    L.rank = w;     w += a16(E * 4);
-    L.entries = w;  w += a16(E * sizeof(int2));
-    L.items = w;    w += a16(E * sizeof(msim::CandItem));
+    L.cnt = w;      w += align16((size_t)n_d * msim::kCandClasses * 4);
+    L.bsum = w;     w += align16((2 * nb + 2) * 4);
+    L.estart = w;   w += align16(((size_t)n_d + 1) * 4);
+    L.istart = w;   w += align16(((size_t)n_d + 1) * 4);
+    L.rank = w;     w += align16(E * 4);
+    L.entries = w;  w += align16(E * sizeof(int2));
+    L.items = w;    w += align16(E * sizeof(msim::CandItem));
     L.total = w;
     return L;
 }
-
-constexpr int kCandWideDim = 320;      // the width msim_fwd_candidates_wide takes: 3 panels, 4 k-steps of 16 in the last
 
 // both entries: `width` = the one row width the entry takes (128: K1c, 320: its panel form K1cP)
 int fwd_candidates(const char *who, int width, int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q,
@@ -2610,777 +1069,6 @@ int msim_fwd_candidates_wide(int dtype, const void *Qt, const int32_t *q_off, co
                              void *workspace, void *stream) {
     return fwd_candidates("msim_fwd_candidates_wide", kCandWideDim, dtype, Qt, q_off, q_off_host, n_q, D, d_off, d_clamp0, n_d, dim, cand,
                           m, ld_cand, id_base, out_scores, ld_scores, out_ids, flags, workspace, stream);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- fixed dimensional encodings (fde.hip)
-namespace {
-
-// the encoding's configuration: what the kernels implement, or MSIM_EUNSUPPORTED / MSIM_EINVAL
-int fde_check_config(const char *who, int dtype, int dim, int reps, int ksim, int dproj, long long *F_out) {
-    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || dim != msim::kDim)
-        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 embeddings of width %d (dtype code %d, dim %d)", who, msim::kDim,
-                    dtype, dim);
-    if (reps < 1) return fail(MSIM_EINVAL, "%s: reps=%d < 1", who, reps);
-    if (ksim < 1 || ksim > msim::kFdeMaxKsim) return fail(MSIM_EUNSUPPORTED, "%s: k_sim=%d outside 1..%d", who, ksim, msim::kFdeMaxKsim);
-    if (!(dproj == 8 || dproj == 16 || dproj == 32 || dproj == 64))
-        return fail(MSIM_EUNSUPPORTED, "%s: d_proj=%d is not 8, 16, 32 or 64", who, dproj);
-    const long long F = (long long)reps * (1LL << ksim) * dproj;
-    if (F % 256 != 0 || F > 65536)
-        return fail(MSIM_EUNSUPPORTED, "%s: F = reps x 2^k_sim x d_proj = %lld must be a multiple of 256 and at most 65536", who, F);
-    *F_out = F;
-    return MSIM_OK;
-}
-
-int fde_encode(const char *who, int dtype, const void *X, const int32_t *off, int n, int64_t n_rows, int dim, const float *G,
-               const float *S, int reps, int ksim, int dproj, int is_doc, int fill_empty, void *out, uint8_t *codes, void *stream) {
-    if (n < 0 || n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (n=%d rows=%lld)", who, n, (long long)n_rows);
-    long long F = 0;
-    if (int rc = fde_check_config(who, dtype, dim, reps, ksim, dproj, &F)) return rc;
-    if (n == 0) return MSIM_OK;
-    if ((!X && n_rows > 0) || !off || !G || !S || !out) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if ((reinterpret_cast<uintptr_t>(X) & 15) || (reinterpret_cast<uintptr_t>(out) & 1))
-        return fail(MSIM_EINVAL, "%s: the rows must be 16-byte aligned and the output 2-byte aligned", who);
-    if (fill_empty != 0 && fill_empty != 1) return fail(MSIM_EINVAL, "%s: fill_empty=%d is not 0 or 1", who, fill_empty);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const bool f16 = dtype == MSIM_DTYPE_F16;
-    auto kern = f16 ? msim::fde_encode_kernel<true> : msim::fde_encode_kernel<false>;
-    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
-    constexpr int kMaxLds = msim::fde_encode_lds_bytes(msim::kFdeMaxKsim, 64);
-    if (int rc = allow_lds(kern, kMaxLds, f16 ? configured_f16 : configured_bf16)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(256), msim::fde_encode_lds_bytes(ksim, dproj), st, static_cast<const uint16_t *>(X),
-                       off, n, (long long)n_rows, G, S, reps, ksim, dproj, is_doc, fill_empty, static_cast<uint16_t *>(out), codes);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "fde_encode_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-template <int QB, int DB, int NBUF>
-int fde_scores_launch(bool f16, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld, hipStream_t st) {
-    auto kern = f16 ? msim::fde_scores_kernel<QB, DB, NBUF, true> : msim::fde_scores_kernel<QB, DB, NBUF, false>;
-    constexpr int lds = msim::fde_scores_lds_bytes<QB, DB, NBUF>();
-    static std::atomic<int> configured_bf16[kMaxDevices], configured_f16[kMaxDevices];
-    if (int rc = allow_lds(kern, lds, f16 ? configured_f16 : configured_bf16)) return rc;
-    const long long n_qt = (n_q + QB - 1) / QB, n_dt = ((long long)n_d + DB - 1) / DB;
-    if (n_qt * n_dt > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "msim_fde_scores: %lld tiles exceed one launch", n_qt * n_dt);
-    const int vec = (reinterpret_cast<uintptr_t>(scores) & 15) == 0 && (ld & 3) == 0;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(n_qt * n_dt)), dim3(256), lds, st, static_cast<const uint16_t *>(Fq), n_q,
-                       static_cast<const uint16_t *>(Fd), n_d, F, scores, (long long)ld, (int)n_qt, vec);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "fde_scores_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msim_fde_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, const float *G, const float *S,
-                         int reps, int ksim, int dproj, int fill_empty, void *out, uint8_t *codes, void *stream) {
-    return fde_encode("msim_fde_encode_docs", dtype, D, d_off, n_d, n_rows, dim, G, S, reps, ksim, dproj, 1, fill_empty, out, codes,
-                      stream);
-}
-
-int msim_fde_encode_queries(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t n_rows, int dim, const float *G,
-                            const float *S, int reps, int ksim, int dproj, void *out, uint8_t *codes, void *stream) {
-    return fde_encode("msim_fde_encode_queries", dtype, Qt, q_off, n_q, n_rows, dim, G, S, reps, ksim, dproj, 0, 0, out, codes, stream);
-}
-
-int msim_fde_scores(int dtype, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld_scores, void *stream) {
-    if (n_q < 0 || n_d < 0 || F < 0) return fail(MSIM_EINVAL, "msim_fde_scores: negative size (n_q=%d n_d=%d F=%d)", n_q, n_d, F);
-    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
-        return fail(MSIM_EUNSUPPORTED, "msim_fde_scores takes bfloat16 / float16 encodings (dtype code %d)", dtype);
-    if (F % 256 != 0 || F == 0 || F > 65536)
-        return fail(MSIM_EUNSUPPORTED, "msim_fde_scores: F=%d must be a positive multiple of 256, at most 65536", F);
-    if (n_q == 0 || n_d == 0) return MSIM_OK;
-    if (!Fq || !Fd || !scores) return fail(MSIM_EINVAL, "msim_fde_scores: null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(Fq) | reinterpret_cast<uintptr_t>(Fd)) & 15)
-        return fail(MSIM_EINVAL, "msim_fde_scores: Fq and Fd must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(scores) & 3)) return fail(MSIM_EINVAL, "msim_fde_scores: scores must be 4-byte aligned");
-    if (ld_scores < n_d) return fail(MSIM_EINVAL, "msim_fde_scores: ld_scores=%lld < n_d=%d", (long long)ld_scores, n_d);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool f16 = dtype == MSIM_DTYPE_F16;
-    // a few queries: a narrow query tile and a 4-deep ring (HBM-bound: Fd streams once); many: 128 x 128 tiles (MFMA-bound)
-    if (n_q <= 64) return fde_scores_launch<32, 128, 4>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
-    return fde_scores_launch<128, 128, 2>(f16, Fq, n_q, Fd, n_d, F, scores, ld_scores, st);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- the int8 token-level index (int8_index.hip)
-namespace {
-
-int i8_check_rows(const char *who, int dtype, int dim) {
-    if (dim != msim::kDim) return fail(MSIM_EINVAL, "%s: rows of width %d; the int8 index takes width %d", who, dim, msim::kDim);
-    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
-        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 rows (dtype code %d)", who, dtype);
-    return MSIM_OK;
-}
-
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-template <int NT, int GW, int D>
-int i8_scores_launch(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int QG, int TPQ, int passes,
-                     const int8_t *d8, const float *sd, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int ppw,
-                     int n_groups, float *scores, int64_t ld, hipStream_t st) {
-    const long long n_gb = (n_groups + GW - 1) / GW;
-    const long long n_ranges = ((long long)n_d + ppw - 1) / ppw, n_pb = (n_ranges + 4 / GW - 1) / (4 / GW);
-    if (n_gb * n_pb > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "msim_i8_scores: %lld workgroups exceed one launch", n_gb * n_pb);
-    hipLaunchKernelGGL((msim::i8_scores_kernel<NT, GW, D>), dim3((unsigned)(n_gb * n_pb)), dim3(256), 0, st, q8, sq, q_off, n_q,
-                       (long long)q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, (long long)d_rows, ppw, n_groups, (int)n_gb,
-                       scores, (long long)ld);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "i8_scores_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msim_i8_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int8_t *codes, float *scales,
-                        void *stream) {
-    const char *who = "msim_i8_encode_docs";
-    if (n_d < 0 || n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (n_d=%d rows=%lld)", who, n_d, (long long)n_rows);
-    if (int rc = i8_check_rows(who, dtype, dim)) return rc;
-    if (n_d == 0) return MSIM_OK;
-    if ((!D && n_rows > 0) || !d_off || (!codes && n_rows > 0) || !scales) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(D, 16) || misaligned(codes, 16) || misaligned(d_off, 4) || misaligned(scales, 4))
-        return fail(MSIM_EINVAL, "%s: rows and codes must be 16-byte aligned, offsets and scales 4-byte aligned", who);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    auto kern = dtype == MSIM_DTYPE_F16 ? msim::i8_encode_docs_kernel<true> : msim::i8_encode_docs_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_d), dim3(256), 0, st, static_cast<const uint16_t *>(D), d_off, n_d, (long long)n_rows, codes,
-                       scales);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "i8_encode_docs_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_i8_encode_queries(int dtype, const void *Qt, int64_t n_rows, int dim, int8_t *codes, float *scales, void *stream) {
-    const char *who = "msim_i8_encode_queries";
-    if (n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (rows=%lld)", who, (long long)n_rows);
-    if (int rc = i8_check_rows(who, dtype, dim)) return rc;
-    if (n_rows == 0) return MSIM_OK;
-    if (!Qt || !codes || !scales) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(Qt, 16) || misaligned(codes, 16) || misaligned(scales, 4))
-        return fail(MSIM_EINVAL, "%s: rows and codes must be 16-byte aligned, scales 4-byte aligned", who);
-    if ((n_rows + 15) / 16 > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld rows exceed one launch", who, (long long)n_rows);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    auto kern = dtype == MSIM_DTYPE_F16 ? msim::i8_encode_rows_kernel<true> : msim::i8_encode_rows_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((n_rows + 15) / 16)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), (long long)n_rows,
-                       codes, scales);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "i8_encode_rows_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, const int8_t *d8,
-                   const float *sd, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int dim, float *scores,
-                   int64_t ld_scores, void *stream) {
-    const char *who = "msim_i8_scores";
-    if (n_q < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d,
-                    (long long)q_rows, (long long)d_rows, max_q_tokens);
-    if (dim != msim::kDim) return fail(MSIM_EINVAL, "%s: rows of width %d; the int8 index takes width %d", who, dim, msim::kDim);
-    if (n_q == 0 || n_d == 0) return MSIM_OK;
-    if ((!q8 && q_rows > 0) || (!sq && q_rows > 0) || !q_off || (!d8 && d_rows > 0) || !sd || !d_off || !scores)
-        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(q8, 16) || misaligned(d8, 16) || misaligned(sq, 4) || misaligned(sd, 4) || misaligned(q_off, 4) ||
-        misaligned(d_off, 4) || misaligned(scores, 4))
-        return fail(MSIM_EINVAL, "%s: codes must be 16-byte aligned; scales, offsets and scores 4-byte aligned", who);
-    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
-    if (max_q_tokens > (1 << 20)) return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, 1 << 20);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // the query plan: every query gets TPQ 16-token tiles, QG queries fill one wave's NT tiles; a longer query takes several passes
-    constexpr int NT = 8;
-    const int tiles = max_q_tokens ? (max_q_tokens + msim::kI8Tile - 1) / msim::kI8Tile : 1;
-    int QG = 1, TPQ = NT, passes = 1;
-    if (tiles <= NT) {
-        TPQ = tiles;
-        QG = NT / tiles;
-    } else {
-        passes = (tiles + NT - 1) / NT;
-    }
-    const long long n_groups = ((long long)n_q + QG - 1) / QG;
-    // page ranges: enough waves to fill the chip (8 per CU, ~4 rounds); at most 16 pages a range when several query groups re-read it
-    const long long want = (long long)di->cus * 32;
-    const long long work = n_groups * n_d;
-    const int cap = n_groups == 1 ? msim::kI8MaxRange : 16;
-    long long ppw = (work + want - 1) / want;
-    ppw = ppw < 1 ? 1 : ppw > cap ? cap : ppw;
-    if (n_groups == 1)
-        return i8_scores_launch<NT, 1, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw, 1,
-                                          scores, ld_scores, st);
-    if (n_groups == 2)
-        return i8_scores_launch<NT, 2, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw, 2,
-                                          scores, ld_scores, st);
-    return i8_scores_launch<NT, 4, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw,
-                                      (int)n_groups, scores, ld_scores, st);
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- the centroid-code index (centroid_index.hip)
-namespace {
-
-int cent_check_format(const char *who, int dtype, int dim, int K) {
-    if (dim != msim::kDim) return fail(MSIM_EUNSUPPORTED, "%s: rows of width %d; the centroid index takes width %d", who, dim, msim::kDim);
-    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
-        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 rows (dtype code %d)", who, dtype);
-    if (K < msim::kCentMinK || K > msim::kCentMaxK || K % 256 != 0)
-        return fail(MSIM_EINVAL, "%s: %d centroids; the count is a multiple of 256 from %d to %d", who, K, msim::kCentMinK, msim::kCentMaxK);
-    return MSIM_OK;
-}
-
-int cent_blocks(int max_q_tokens) {
-    return max_q_tokens > 0 ? (max_q_tokens + msim::kCentBlockTok - 1) / msim::kCentBlockTok : 1;
-}
-
-struct CentPlan {
-    int nb, ppw, n_pr;
-    long long wgs;
-};
-
-// pages per wave: enough rows behind every table load (K x 64 B per workgroup and block) that the load is a small part of the
-// workgroup's LDS traffic (16 K rows = 16 x the table), but never so many that the chip has fewer than 2 workgroups per CU to run
-CentPlan cent_plan(int n_q, int max_q_tokens, int K, int n_d, int64_t d_rows, int cus) {
-    CentPlan p;
-    p.nb = cent_blocks(max_q_tokens);
-    const long long avg = n_d > 0 && d_rows / n_d > 0 ? d_rows / n_d : 1;
-    const long long amort = (2LL * K + avg - 1) / avg;
-    const long long fill = (long long)n_q * n_d / ((long long)msim::kCentWaves * 2 * (cus > 0 ? cus : 1));
-    long long ppw = amort < fill ? amort : fill;
-    ppw = ppw < 1 ? 1 : ppw > msim::kCentMaxPpw ? msim::kCentMaxPpw : ppw;
-    p.ppw = (int)ppw;
-    const long long per_wg = ppw * msim::kCentWaves;
-    p.n_pr = (int)((n_d + per_wg - 1) / per_wg);
-    p.wgs = (long long)p.n_pr * n_q;
-    return p;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msim_cent_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows,
-                          const void *C, int K, uint16_t *codes, int32_t *status, void *stream) {
-    const char *who = "msim_cent_encode_docs";
-    if (n_d < 0 || n_rows < 0 || max_doc_rows < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_d=%d rows=%lld max_doc_rows=%d)", who, n_d, (long long)n_rows, max_doc_rows);
-    if (int rc = cent_check_format(who, dtype, dim, K)) return rc;
-    if (n_d == 0 || max_doc_rows == 0) return MSIM_OK;
-    if ((!D && n_rows > 0) || !d_off || !C || (!codes && n_rows > 0)) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(D, 16) || misaligned(C, 16) || misaligned(codes, 16) || misaligned(d_off, 4) || misaligned(status, 4))
-        return fail(MSIM_EINVAL, "%s: rows, centroids and codes must be 16-byte aligned, offsets and status 4-byte aligned", who);
-    const long long gy = ((long long)max_doc_rows + msim::kCentEncRows - 1) / msim::kCentEncRows;
-    if (gy > 65535) return fail(MSIM_EUNSUPPORTED, "%s: max_doc_rows=%d above %d", who, max_doc_rows, 65535 * msim::kCentEncRows);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    auto kern = dtype == MSIM_DTYPE_F16 ? msim::cent_encode_kernel<true> : msim::cent_encode_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_d, (unsigned)gy), dim3(256), 0, st, static_cast<const uint16_t *>(D), d_off, n_d,
-                       (long long)n_rows, max_doc_rows, static_cast<const uint16_t *>(C), K, codes, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "cent_encode_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-size_t msim_cent_table_bytes(int n_q, int max_q_tokens, int K) {
-    if (n_q <= 0 || K <= 0 || max_q_tokens < 0) return 0;
-    return (size_t)n_q * cent_blocks(max_q_tokens) * K * msim::kCentTableRow;
-}
-
-int msim_cent_table(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int dim,
-                    const void *C, int K, void *table, void *stream) {
-    const char *who = "msim_cent_table";
-    if (n_q < 0 || q_rows < 0 || max_q_tokens < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d q_rows=%lld max_q_tokens=%d)", who, n_q, (long long)q_rows, max_q_tokens);
-    if (int rc = cent_check_format(who, dtype, dim, K)) return rc;
-    if (max_q_tokens > msim::kCentMaxTokens)
-        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, msim::kCentMaxTokens);
-    if (n_q == 0) return MSIM_OK;
-    if ((!Qt && q_rows > 0) || !q_off || !C || !table) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(Qt, 16) || misaligned(C, 16) || misaligned(table, 16) || misaligned(q_off, 4))
-        return fail(MSIM_EINVAL, "%s: tokens, centroids and table must be 16-byte aligned, offsets 4-byte aligned", who);
-    const int nb = cent_blocks(max_q_tokens);
-    if ((long long)n_q * nb > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld blocks exceed one launch", who, (long long)n_q * nb);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    auto kern = dtype == MSIM_DTYPE_F16 ? msim::cent_table_kernel<true> : msim::cent_table_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(n_q * nb), (unsigned)(K / 256)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), q_off,
-                       n_q, (long long)q_rows, nb, static_cast<const uint16_t *>(C), K, static_cast<_Float16 *>(table));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "cent_table_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_cent_scores_plan(int n_q, int max_q_tokens, int K, int n_d, int64_t d_rows, int32_t *plan) {
-    const char *who = "msim_cent_scores_plan";
-    if (n_q < 0 || n_d < 0 || d_rows < 0 || max_q_tokens < 0 || !plan) return fail(MSIM_EINVAL, "%s: bad argument", who);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const CentPlan p = cent_plan(n_q, max_q_tokens, K, n_d, d_rows, di->cus);
-    plan[0] = p.nb;
-    plan[1] = p.ppw;
-    plan[2] = msim::kCentWaves;
-    plan[3] = (int32_t)(p.wgs > 0x7fffffffLL ? 0x7fffffffLL : p.wgs);
-    return MSIM_OK;
-}
-
-int msim_cent_scores(const void *table, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int K, const uint16_t *codes,
-                     const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, float *scores, int64_t ld_scores,
-                     void *stream) {
-    const char *who = "msim_cent_scores";
-    if (n_q < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d,
-                    (long long)q_rows, (long long)d_rows, max_q_tokens);
-    if (int rc = cent_check_format(who, MSIM_DTYPE_BF16, msim::kDim, K)) return rc;
-    if (max_q_tokens > msim::kCentMaxTokens)
-        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, msim::kCentMaxTokens);
-    if (n_q == 0 || n_d == 0) return MSIM_OK;
-    if (!table || !q_off || (!codes && d_rows > 0) || !d_off || !scores) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(table, 16) || misaligned(codes, 16) || misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(scores, 4))
-        return fail(MSIM_EINVAL, "%s: table and codes must be 16-byte aligned; offsets and scores 4-byte aligned", who);
-    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
-    if (d_rows > 0x7fffffffLL - 1024) return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld exceeds 32-bit row indices", who, (long long)d_rows);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    const CentPlan p = cent_plan(n_q, max_q_tokens, K, n_d, d_rows, di->cus);
-    if (p.wgs > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld workgroups exceed one launch", who, p.wgs);
-    constexpr int park = msim::kCentWaves * msim::kCentBatch * msim::kCentTableRow;
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(msim::cent_scores_kernel, msim::kCentMaxK * msim::kCentTableRow + park, configured)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(msim::cent_scores_kernel, dim3((unsigned)p.wgs), dim3(msim::kCentWaves * 64), K * msim::kCentTableRow + park, st,
-                       static_cast<const _Float16 *>(table), q_off, n_q, (long long)q_rows, p.nb, K, codes, d_off, clamp0, n_d,
-                       (long long)d_rows, p.ppw, p.n_pr, scores, (long long)ld_scores);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "cent_scores_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- the live corpus (live_corpus.hip)
-namespace {
-
-constexpr int64_t kLiveMaxRowBytes = 65536;
-constexpr int64_t kLiveMaxChunks = 1 << 16;          // two launches per chunk: a bounce buffer of a few rows is for small corpora
-
-struct LiveWorkspace {
-    size_t old_off, tile_sum, tile_base, total;
-    int n_tiles;
-};
-
-LiveWorkspace live_workspace(int n_slots) {
-    LiveWorkspace w;
-    w.n_tiles = (n_slots + msim::kLiveTile - 1) / msim::kLiveTile;
-    w.old_off = up16(msim::kLiveHeaderWords * sizeof(int32_t));
-    w.tile_sum = w.old_off + up16(((size_t)n_slots + 1) * sizeof(int32_t));
-    w.tile_base = w.tile_sum + up16((size_t)w.n_tiles * sizeof(long long));
-    w.total = w.tile_base + up16((size_t)w.n_tiles * sizeof(long long));
-    return w;
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t msim_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes) {
-    (void)bounce_bytes;                                // the bounce buffer is the caller's; the workspace holds the slot tables only
-    if (n_slots <= 0) return 0;
-    return live_workspace(n_slots).total;
-}
-
-int msim_live_compact(void *rows, int64_t row_bytes, int64_t rows_bound, int32_t *off, const uint8_t *alive, int n_slots,
-                      int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream) {
-    const char *who = "msim_live_compact";
-    if (n_slots < 0 || rows_bound < 0 || bounce_bytes < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_slots=%d rows_bound=%lld bounce_bytes=%lld)", who, n_slots, (long long)rows_bound,
-                    (long long)bounce_bytes);
-    if (row_bytes <= 0 || row_bytes % 16 != 0)
-        return fail(MSIM_EINVAL, "%s: row_bytes=%lld must be a positive multiple of 16", who, (long long)row_bytes);
-    if (row_bytes > kLiveMaxRowBytes)
-        return fail(MSIM_EUNSUPPORTED, "%s: rows of %lld bytes (at most %lld)", who, (long long)row_bytes, (long long)kLiveMaxRowBytes);
-    if (rows_bound > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: rows_bound=%lld above 2^31 - 1", who, (long long)rows_bound);
-    if (n_slots == 0) return MSIM_OK;
-    if (!off || !alive || !rows_used_out || !workspace || (!rows && rows_bound > 0) || (!bounce && rows_bound > 0))
-        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(rows, 16) || misaligned(bounce, 16) || misaligned(workspace, 16) || misaligned(off, 4) || misaligned(rows_used_out, 8))
-        return fail(MSIM_EINVAL, "%s: rows, bounce and workspace must be 16-byte aligned, off 4-byte and rows_used_out 8-byte aligned", who);
-    if (rows_bound > 0 && bounce_bytes < row_bytes)
-        return fail(MSIM_EINVAL, "%s: a bounce buffer of %lld bytes holds no row of %lld bytes", who, (long long)bounce_bytes,
-                    (long long)row_bytes);
-    int64_t chunk_rows = rows_bound > 0 ? bounce_bytes / row_bytes : 1;
-    if (chunk_rows > (1 << 30)) chunk_rows = 1 << 30;
-    const int64_t n_chunks = (rows_bound + chunk_rows - 1) / chunk_rows;
-    if (n_chunks > kLiveMaxChunks)
-        return fail(MSIM_EUNSUPPORTED, "%s: %lld rows through a bounce buffer of %lld rows are %lld chunks (at most %lld)", who,
-                    (long long)rows_bound, (long long)chunk_rows, (long long)n_chunks, (long long)kLiveMaxChunks);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LiveWorkspace w = live_workspace(n_slots);
-    char *ws = static_cast<char *>(workspace);
-    int32_t *hdr = reinterpret_cast<int32_t *>(ws);
-    int32_t *old_off = reinterpret_cast<int32_t *>(ws + w.old_off);
-    long long *tile_sum = reinterpret_cast<long long *>(ws + w.tile_sum);
-    long long *tile_base = reinterpret_cast<long long *>(ws + w.tile_base);
-    hipLaunchKernelGGL(msim::live_reset_kernel, dim3(1), dim3(64), 0, st, hdr);
-    hipLaunchKernelGGL(msim::live_lens_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots,
-                       (long long)rows_bound, hdr, old_off, tile_sum);
-    hipLaunchKernelGGL(msim::live_scan_kernel, dim3(1), dim3(msim::kLiveTile), 0, st, w.n_tiles, n_slots, (long long)rows_bound, hdr,
-                       old_off, tile_sum, tile_base, reinterpret_cast<long long *>(rows_used_out));
-    hipLaunchKernelGGL(msim::live_apply_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots, hdr, old_off,
-                       tile_base);
-    int block_rows = (int)(msim::kLiveBlockBytes / row_bytes);
-    block_rows = block_rows < 1 ? 1 : block_rows > msim::kLiveMaxBlockRows ? msim::kLiveMaxBlockRows : block_rows;
-    const int lpr = (int)(row_bytes / 16);
-    for (int64_t k = 0; k < n_chunks; ++k) {
-        const long long chunk0 = k * chunk_rows;
-        const int rows_here = (int)(rows_bound - chunk0 < chunk_rows ? rows_bound - chunk0 : chunk_rows);
-        const unsigned blocks = (unsigned)((rows_here + block_rows - 1) / block_rows);
-        hipLaunchKernelGGL(msim::live_move_kernel<true>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, static_cast<uint8_t *>(rows),
-                           lpr, (long long)rows_bound, off, old_off, n_slots, hdr, static_cast<uint8_t *>(bounce), chunk0, rows_here,
-                           block_rows);
-        hipLaunchKernelGGL(msim::live_move_kernel<false>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, static_cast<uint8_t *>(rows),
-                           lpr, (long long)rows_bound, off, old_off, n_slots, hdr, static_cast<uint8_t *>(bounce), chunk0, rows_here,
-                           block_rows);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "live compaction launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const uint8_t *alive, void *stream) {
-    const char *who = "msim_live_mask_scores";
-    if (n_q < 0 || n < 0) return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld)", who, n_q, (long long)n);
-    if (n_q == 0 || n == 0) return MSIM_OK;
-    if (!scores || !alive) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(scores, 4)) return fail(MSIM_EINVAL, "%s: scores must be 4-byte aligned", who);
-    if (ld < n) return fail(MSIM_EINVAL, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
-    const int64_t tiles = (n + 1023) / 1024;
-    if (tiles > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)n);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int vec_ok = !misaligned(scores, 16) && ld % 4 == 0;
-    const unsigned row_groups = (unsigned)(n_q < 64 ? n_q : 64);
-    hipLaunchKernelGGL(msim::live_mask_kernel, dim3((unsigned)tiles, row_groups), dim3(256), 0, st, scores, (long long)ld, n_q, (long long)n,
-                       alive, vec_ok);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "live_mask_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- hard-negative mining and the page gather (mine.hip)
-namespace {
-
-// what msim_mine_bounds and msim_mine_mask share: the score matrix and the positives list
-int mine_check(const char *who, const float *scores, int64_t ld, int n_q, int64_t n, const int64_t *pos_ids, const int32_t *pos_off,
-               int64_t nnz) {
-    if (n_q < 0 || n < 0 || nnz < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld nnz=%lld)", who, n_q, (long long)n, (long long)nnz);
-    if (n_q == 0) return MSIM_OK;
-    if (!pos_off || (nnz > 0 && !pos_ids) || (n > 0 && !scores)) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(scores, 4) || misaligned(pos_off, 4) || misaligned(pos_ids, 8))
-        return fail(MSIM_EINVAL, "%s: scores and pos_off must be 4-byte aligned, pos_ids 8-byte aligned", who);
-    if (ld < n) return fail(MSIM_EINVAL, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
-    return MSIM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msim_mine_bounds(const float *scores, int64_t ld, int n_q, int64_t n, const int64_t *pos_ids, const int32_t *pos_off, int64_t nnz,
-                     int64_t id_base, const uint8_t *alive, int local, float *bounds, void *stream) {
-    const char *who = "msim_mine_bounds";
-    if (int rc = mine_check(who, scores, ld, n_q, n, pos_ids, pos_off, nnz)) return rc;
-    if (n_q == 0) return MSIM_OK;
-    if (!bounds || misaligned(bounds, 4)) return fail(MSIM_EINVAL, "%s: bounds must be a 4-byte aligned pointer", who);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned blocks = (unsigned)((n_q + 3) / 4);
-    hipLaunchKernelGGL(msim::mine_bounds_kernel, dim3(blocks), dim3(msim::kMineThreads), 0, st, scores, (long long)ld, n_q, (long long)n,
-                       pos_ids, pos_off, (long long)nnz, (long long)id_base, alive, local != 0, bounds);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "mine_bounds_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_mine_mask(float *scores, int64_t ld, int n_q, int64_t n, const float *bounds, float max_ratio, const uint8_t *alive,
-                   const int64_t *pos_ids, const int32_t *pos_off, int64_t nnz, int64_t id_base, void *stream) {
-    const char *who = "msim_mine_mask";
-    if (int rc = mine_check(who, scores, ld, n_q, n, pos_ids, pos_off, nnz)) return rc;
-    if (n_q == 0 || n == 0) return MSIM_OK;
-    if (misaligned(bounds, 4)) return fail(MSIM_EINVAL, "%s: bounds must be 4-byte aligned", who);
-    if (bounds && max_ratio != max_ratio) return fail(MSIM_EINVAL, "%s: max_ratio is NaN", who);
-    const int64_t all_tiles = (n + msim::kMineTileCols - 1) / msim::kMineTileCols;
-    if (all_tiles >= 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)n);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned tiles = (bounds || alive) ? (unsigned)all_tiles : 0u;     // neither: only the positives' columns change
-    const int vec_ok = !misaligned(scores, 16) && ld % 4 == 0;
-    const unsigned row_groups = (unsigned)(n_q < msim::kMineRowGroups ? n_q : msim::kMineRowGroups);
-    auto kern = bounds ? msim::mine_mask_kernel<true> : msim::mine_mask_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3(tiles + 1, row_groups), dim3(msim::kMineThreads), 0, st, scores, (long long)ld, n_q, (long long)n, bounds,
-                       max_ratio, alive, pos_ids, pos_off, (long long)nnz, (long long)id_base, tiles, vec_ok);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "mine_mask_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_gather_pages(const void *rows, int64_t row_bytes, int64_t d_rows, const int32_t *d_off, int n_d, int64_t id_base,
-                      const int64_t *ids, int64_t n_slots, int64_t pad_rows, void *out, int32_t *lengths, void *stream) {
-    const char *who = "msim_gather_pages";
-    if (n_slots < 0 || n_d < 0 || d_rows < 0 || pad_rows < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_slots=%lld n_d=%d d_rows=%lld pad_rows=%lld)", who, (long long)n_slots, n_d,
-                    (long long)d_rows, (long long)pad_rows);
-    if (row_bytes <= 0 || row_bytes % 16 != 0)
-        return fail(MSIM_EINVAL, "%s: row_bytes=%lld must be a positive multiple of 16", who, (long long)row_bytes);
-    if (row_bytes > kLiveMaxRowBytes)
-        return fail(MSIM_EUNSUPPORTED, "%s: rows of %lld bytes (at most %lld)", who, (long long)row_bytes, (long long)kLiveMaxRowBytes);
-    if (d_rows > 0x7fffffffLL || pad_rows > 0x7fffffffLL || n_slots > 0x7fffffffLL)
-        return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld, pad_rows=%lld or n_slots=%lld above 2^31 - 1", who, (long long)d_rows,
-                    (long long)pad_rows, (long long)n_slots);
-    if (n_slots == 0) return MSIM_OK;
-    if (!ids || !lengths || !d_off || (!rows && d_rows > 0) || (!out && pad_rows > 0))
-        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(rows, 16) || misaligned(out, 16) || misaligned(ids, 8) || misaligned(d_off, 4) || misaligned(lengths, 4))
-        return fail(MSIM_EINVAL, "%s: rows and out must be 16-byte aligned, ids 8-byte, d_off and lengths 4-byte aligned", who);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(msim::gather_pages_kernel, dim3((unsigned)n_slots), dim3(msim::kMineThreads), 0, st,
-                       static_cast<const uint8_t *>(rows), (int)(row_bytes / 16), (long long)d_rows, d_off, n_d, (long long)id_base, ids,
-                       (long long)pad_rows, static_cast<uint8_t *>(out), lengths);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "gather_pages_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- page filters (filter.hip)
-namespace {
-
-// what msim_filter_mask / _list / _ids share: sizes first, then (n_q == 0 || n == 0: nothing to do, *done = true), then the filter
-int filter_check(const char *who, int n_q, int64_t n, const uint32_t *bits, int64_t ld_words, const int32_t *page_labels,
-                 const int32_t *query_labels, const uint8_t *alive, msim::FilterArgs *f, int *mode, bool *done) {
-    *done = false;
-    if (n_q < 0 || n < 0 || ld_words < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld ld_words=%lld)", who, n_q, (long long)n, (long long)ld_words);
-    if (n_q == 0 || n == 0) {
-        *done = true;
-        return MSIM_OK;
-    }
-    if (n > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: n=%lld above 2^31 - 1", who, (long long)n);
-    const bool labels = page_labels || query_labels;
-    if ((bits != nullptr) == labels)
-        return fail(MSIM_EINVAL, "%s: exactly one of (bits) and (page_labels, query_labels) must be given", who);
-    if (labels && (!page_labels || !query_labels)) return fail(MSIM_EINVAL, "%s: page_labels and query_labels go together", who);
-    if (misaligned(bits, 4) || misaligned(page_labels, 4) || misaligned(query_labels, 4))
-        return fail(MSIM_EINVAL, "%s: bits, page_labels and query_labels must be 4-byte aligned", who);
-    if (bits && ld_words != 0 && ld_words < (n + 31) / 32)
-        return fail(MSIM_EINVAL, "%s: ld_words=%lld < ceil(n / 32)=%lld", who, (long long)ld_words, (long long)((n + 31) / 32));
-    *f = msim::FilterArgs{bits, (long long)ld_words, page_labels, query_labels, alive};
-    *mode = labels ? msim::kFilterLabels : ld_words ? msim::kFilterPerQuery : msim::kFilterShared;
-    return MSIM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msim_filter_pack(const uint8_t *mask, int64_t ld_mask, int rows, int64_t n, uint32_t *words, int64_t ld_words, void *stream) {
-    const char *who = "msim_filter_pack";
-    if (rows < 0 || n < 0) return fail(MSIM_EINVAL, "%s: negative size (rows=%d n=%lld)", who, rows, (long long)n);
-    if (rows == 0 || n == 0) return MSIM_OK;
-    if (!mask || !words) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(words, 4)) return fail(MSIM_EINVAL, "%s: words must be 4-byte aligned", who);
-    if (ld_mask < n) return fail(MSIM_EINVAL, "%s: ld_mask=%lld < n=%lld", who, (long long)ld_mask, (long long)n);
-    if (ld_words < (n + 31) / 32)
-        return fail(MSIM_EINVAL, "%s: ld_words=%lld < ceil(n / 32)=%lld", who, (long long)ld_words, (long long)((n + 31) / 32));
-    const int64_t tiles = (n + msim::kFilterTileCols - 1) / msim::kFilterTileCols;
-    if (tiles > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)n);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int vec_ok = !misaligned(mask, 4) && (ld_mask % 4 == 0 || rows == 1);
-    const unsigned row_groups = (unsigned)(rows < msim::kFilterRowGroups ? rows : msim::kFilterRowGroups);
-    hipLaunchKernelGGL(msim::filter_pack_kernel, dim3((unsigned)tiles, row_groups), dim3(msim::kFilterThreads), 0, st, mask,
-                       (long long)ld_mask, rows, (long long)n, words, (long long)ld_words, vec_ok);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_pack_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_filter_mask(float *scores, int64_t ld, int n_q, int64_t n, const uint32_t *bits, int64_t ld_words, const int32_t *page_labels,
-                     const int32_t *query_labels, const uint8_t *alive, void *stream) {
-    const char *who = "msim_filter_mask";
-    msim::FilterArgs f;
-    int mode = 0;
-    bool done = false;
-    if (int rc = filter_check(who, n_q, n, bits, ld_words, page_labels, query_labels, alive, &f, &mode, &done)) return rc;
-    if (done) return MSIM_OK;
-    if (!scores || misaligned(scores, 4)) return fail(MSIM_EINVAL, "%s: scores must be a 4-byte aligned pointer", who);
-    if (ld < n) return fail(MSIM_EINVAL, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
-    const int64_t tiles = (n + msim::kFilterTileCols - 1) / msim::kFilterTileCols;
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int vec_ok = !misaligned(scores, 16) && (ld % 4 == 0 || n_q == 1);
-    const int labels_vec_ok = !misaligned(page_labels, 16);
-    const unsigned row_groups = (unsigned)(n_q < msim::kFilterRowGroups ? n_q : msim::kFilterRowGroups);
-    auto kern = mode == msim::kFilterLabels     ? msim::filter_mask_kernel<msim::kFilterLabels>
-                : mode == msim::kFilterPerQuery ? msim::filter_mask_kernel<msim::kFilterPerQuery>
-                                                : msim::filter_mask_kernel<msim::kFilterShared>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, row_groups), dim3(msim::kFilterThreads), 0, st, scores, (long long)ld, n_q, (long long)n,
-                       f, vec_ok, labels_vec_ok);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_mask_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-size_t msim_filter_list_workspace_bytes(int n_q, int64_t n) {
-    (void)n_q, (void)n;
-    return 16;                                           // the status word
-}
-
-int msim_filter_list(const uint32_t *bits, int64_t ld_words, const int32_t *page_labels, const int32_t *query_labels,
-                     const uint8_t *alive, int n_q, int64_t n, int64_t id_base, int64_t *cand, int64_t ld_cand, int m_cap,
-                     int32_t *counts, void *workspace, void *stream) {
-    const char *who = "msim_filter_list";
-    if (m_cap < 0) return fail(MSIM_EINVAL, "%s: negative size (m_cap=%d)", who, m_cap);
-    msim::FilterArgs f;
-    int mode = 0;
-    bool done = false;
-    if (int rc = filter_check(who, n_q, n, bits, ld_words, page_labels, query_labels, alive, &f, &mode, &done)) return rc;
-    if (done) return MSIM_OK;
-    if (!counts || !workspace || (!cand && m_cap > 0)) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(cand, 8) || misaligned(counts, 4) || misaligned(workspace, 16))
-        return fail(MSIM_EINVAL, "%s: cand must be 8-byte, counts 4-byte and workspace 16-byte aligned", who);
-    if (ld_cand < m_cap) return fail(MSIM_EINVAL, "%s: ld_cand=%lld < m_cap=%d", who, (long long)ld_cand, m_cap);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int32_t *status = static_cast<int32_t *>(workspace);
-    hipLaunchKernelGGL(msim::filter_status_reset_kernel, dim3(1), dim3(1), 0, st, status);
-    auto kern = mode == msim::kFilterLabels     ? msim::filter_list_kernel<msim::kFilterLabels>
-                : mode == msim::kFilterPerQuery ? msim::filter_list_kernel<msim::kFilterPerQuery>
-                                                : msim::filter_list_kernel<msim::kFilterShared>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)n_q), dim3(msim::kFilterThreads), 0, st, f, (long long)n, (long long)id_base, cand,
-                       (long long)ld_cand, m_cap, counts, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_list_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-int msim_filter_ids(int64_t *ids, int64_t ld, int n_q, int64_t m, int64_t n, int64_t id_base, const uint32_t *bits, int64_t ld_words,
-                    const int32_t *page_labels, const int32_t *query_labels, const uint8_t *alive, void *stream) {
-    const char *who = "msim_filter_ids";
-    if (m < 0) return fail(MSIM_EINVAL, "%s: negative size (m=%lld)", who, (long long)m);
-    msim::FilterArgs f;
-    int mode = 0;
-    bool done = false;
-    if (int rc = filter_check(who, n_q, n, bits, ld_words, page_labels, query_labels, alive, &f, &mode, &done)) return rc;
-    if (done || m == 0) return MSIM_OK;
-    if (!ids || misaligned(ids, 8)) return fail(MSIM_EINVAL, "%s: ids must be an 8-byte aligned pointer", who);
-    if (ld < m) return fail(MSIM_EINVAL, "%s: ld=%lld < m=%lld", who, (long long)ld, (long long)m);
-    const int64_t tiles = (m + msim::kFilterThreads - 1) / msim::kFilterThreads;
-    if (tiles > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld columns exceed one launch", who, (long long)m);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const unsigned row_groups = (unsigned)(n_q < 65535 ? n_q : 65535);
-    auto kern = mode == msim::kFilterLabels     ? msim::filter_ids_kernel<msim::kFilterLabels>
-                : mode == msim::kFilterPerQuery ? msim::filter_ids_kernel<msim::kFilterPerQuery>
-                                                : msim::filter_ids_kernel<msim::kFilterShared>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, row_groups), dim3(msim::kFilterThreads), 0, st, ids, (long long)ld, n_q, (long long)m,
-                       (long long)n, (long long)id_base, f);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "filter_ids_kernel launch: %s", hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------- token-to-patch alignment of listed entries (K1a, maxsim_align.hip)
-namespace {
-
-template <int DIM>
-int align_launch(bool f16, const void *Qt, const int32_t *q_off, const void *D, const int32_t *d_off, const uint8_t *clamp0,
-                 const int64_t *cand, float *best_sim, int32_t *best_row, float *sims, const msim::AlignArgs &a, hipStream_t st) {
-    auto kern = f16 ? msim::maxsim_align_kernel<DIM, true> : msim::maxsim_align_kernel<DIM, false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)a.n_q * a.m)), dim3(256), 0, st, static_cast<const uint16_t *>(Qt), q_off,
-                       static_cast<const uint16_t *>(D), d_off, clamp0, cand, best_sim, best_row, sims, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_align_kernel<%d> launch: %s", DIM, hipGetErrorString(e));
-    return MSIM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msim_align_candidates(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, const void *D,
-                          const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int64_t d_rows, int dim, const int64_t *cand, int m,
-                          int64_t ld_cand, int64_t id_base, float *best_sim, int32_t *best_row, float *sims, int max_rows,
-                          void *stream) {
-    const char *who = "msim_align_candidates";
-    if (n_q < 0 || m < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0 || max_rows < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d m=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d max_rows=%d)", who, n_q,
-                    m, n_d, (long long)q_rows, (long long)d_rows, max_q_tokens, max_rows);
-    if (n_q == 0 || m == 0) return MSIM_OK;
-    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16) || !(dim == msim::kDim || dim == kCandWideDim))
-        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 embeddings of width %d or %d (dtype code %d, dim %d)", who,
-                    msim::kDim, kCandWideDim, dtype, dim);
-    if (max_q_tokens > msim::kAlignMaxTokens)
-        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d: queries of at most %d tokens", who, max_q_tokens, msim::kAlignMaxTokens);
-    if ((!Qt && q_rows > 0) || !q_off || (!D && d_rows > 0) || !d_off || !cand || ((!best_sim || !best_row) && max_q_tokens > 0))
-        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(Qt, 16) || misaligned(D, 16)) return fail(MSIM_EINVAL, "%s: Qt and D must be 16-byte aligned", who);
-    if (misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(cand, 8) || misaligned(best_sim, 4) || misaligned(best_row, 4) ||
-        misaligned(sims, 4))
-        return fail(MSIM_EINVAL, "%s: offsets and outputs must be 4-byte aligned, cand 8-byte aligned", who);
-    if (ld_cand < m) return fail(MSIM_EINVAL, "%s: ld_cand=%lld < m=%d", who, (long long)ld_cand, m);
-    if ((long long)n_q * m > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: more than 2^31 - 1 entries (n_q=%d x m=%d)", who, n_q, m);
-    if (max_q_tokens == 0) return MSIM_OK;                       // no token slot: nothing to write
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
-    msim::AlignArgs a;
-    a.ld_cand = ld_cand;
-    a.id_base = id_base;
-    a.q_rows = q_rows;
-    a.d_rows = d_rows;
-    a.n_q = n_q;
-    a.m = m;
-    a.n_d = n_d;
-    a.T = max_q_tokens;
-    a.R = max_rows;
-    a.vec = sims && !misaligned(sims, 16) && max_rows % 4 == 0;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool f16 = dtype == MSIM_DTYPE_F16;
-    if (dim == msim::kDim)
-        return align_launch<msim::kDim>(f16, Qt, q_off, D, d_off, d_clamp0, cand, best_sim, best_row, sims, a, st);
-    return align_launch<kCandWideDim>(f16, Qt, q_off, D, d_off, d_clamp0, cand, best_sim, best_row, sims, a, st);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@ constexpr int kSlabRows = 32;             // MFMA M: patches per slab
 constexpr int kSlabBytes = kSlabRows * kRowBytes;  // 8 KiB
 constexpr int kKSteps = kDim / 16;        // 8 x (32x32x16) MFMAs per 32x32 output tile
 constexpr int kTokTile = 32;              // MFMA N: query tokens per tile
+constexpr int kGenericMaxRowBytes = 4096;  // widest embedding row of the generic kernels (maxsim_generic.hip); the host checks it
 
 #define MSIM_LDS(p) ((__attribute__((address_space(3))) void *)(p))
 

@@ -26,7 +26,6 @@
 namespace msim {
 
 constexpr int kDtypeF32 = 2;
-constexpr int kGenericMaxRowBytes = 4096;
 constexpr int kGenericWaves = 8;
 
 struct GenericArgs {

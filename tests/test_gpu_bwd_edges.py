@@ -3,7 +3,7 @@
 The routing is SYNTHETIC: a hand-made int32 argmax [n_pairs, Lq] with values in [-1, len_c), so that entries land exactly on each
 limit whatever a forward kernel would have produced; the corpus is packed and ragged (a few long documents among many of 1-8 rows).
 Truth is the contract formula in float64 (tests/helpers.py: pairs_bwd_truth).  Every case asserts the launcher branch it claims
-(a mirror of maxsim_abi.hip's host-side choices, below) and checks:
+(a mirror of abi_train.hip's host-side choices, below) and checks:
   - outputs pre-filled with NaN come back finite everywhere; rows / tokens without entries come back exactly 0;
   - fp32 output within 2e-6 * max|truth|;
   - two runs bit-identical;
@@ -36,9 +36,9 @@ def cus():
     return torch.cuda.get_device_properties(torch.device("cuda", torch.cuda.current_device())).multi_processor_count
 
 
-# ---- mirror of the launcher (colpali_amd/csrc/maxsim_abi.hip)
+# ---- mirror of the launcher (colpali_amd/csrc/abi_train.hip: dd_plan, launch_bwd_kernels)
 def dd_plan(n_pairs, Lq, n_d, dim, max_doc_rows, n_cus):
-    """dd_plan (maxsim_abi.hip:687-710) -> (mode, splits, scratch bytes); mode 0: no dense form."""
+    """dd_plan (abi_train.hip: dd_plan) -> (mode, splits, scratch bytes); mode 0: no dense form."""
     if n_d <= 0 or n_pairs <= 0 or max_doc_rows <= 0 or max_doc_rows > BWD_ROWS or dim <= 0:
         return 0, 0, 0
     mode, splits, nbytes = 0, 0, 0
@@ -56,7 +56,7 @@ def dd_plan(n_pairs, Lq, n_d, dim, max_doc_rows, n_cus):
 
 
 def dd_form(n_q, Lq, n_d, n_pairs, dim, max_doc_rows, n_cus, workspace):
-    """The dD kernel launch_bwd_kernels picks (maxsim_abi.hip:768-810): ("dense", splits) / ("pairs", splits) for dd_plan modes 1 / 2
+    """The dD kernel launch_bwd_kernels picks (abi_train.hip: launch_bwd_kernels, the dD half): ("dense", splits) / ("pairs", splits) for dd_plan modes 1 / 2
     (only with a workspace), ("rows", sy) for the row-list kernel, ("range", gy) for the row-range kernel."""
     if workspace:
         mode, splits, _ = dd_plan(n_pairs, Lq, n_d, dim, max_doc_rows, n_cus)
@@ -73,7 +73,7 @@ def dd_form(n_q, Lq, n_d, n_pairs, dim, max_doc_rows, n_cus, workspace):
 
 
 def dq_plan(n_q, Lq, n_pairs):
-    """(tpw, psplit) of the dQ launch (maxsim_abi.hip:757-763)."""
+    """(tpw, psplit) of the dQ launch (abi_train.hip: launch_bwd_kernels, the dQ half)."""
     tokens = n_q * Lq
     tpw = min(max(_cdiv(tokens, 4096), 1), 16)
     psplit = tokens <= 2048 and n_pairs >= 64 * n_q

@@ -5,7 +5,7 @@ lengths on both sides of a 32-row slab, max_doc_rows not a multiple of 32), pair
 that no pair names and documents shared by several queries, and the stable by-document permutation.  Truth is the contract formula of
 include/maxsim.h in float64 (tests/helpers.py: smooth_truth, smooth_bwd_truth; themselves tested on the CPU in
 tests/test_smooth_truth.py) on the exact values the kernels read.  Every case ASSERTS the launcher branch it is named after through a
-mirror of maxsim_abi.hip's host-side choices (`plan`, computed from the device's CU count), so that a case cannot drift onto another
+mirror of abi_train.hip's host-side choices (`plan`, computed from the device's CU count), so that a case cannot drift onto another
 branch unnoticed.
 
 Forward: scores and per-token lse within 1e-5 of the truth relative to max(|truth|, 1); dense entry point against the pair-list one over
@@ -46,7 +46,7 @@ from tests.helpers import smooth_bwd_truth, smooth_truth
 gpu = pytest.mark.gpu
 
 ESIZE = {torch.bfloat16: 2, torch.float16: 2, torch.float32: 4}
-TOK, WAVES_GENERIC, LDS_PER_CU, PAIRS_RING, SLAB_BYTES = 32, 8, 160 * 1024, 2, 8192     # maxsim_common.hpp, maxsim_generic.hip, maxsim_abi.hip
+TOK, WAVES_GENERIC, LDS_PER_CU, PAIRS_RING, SLAB_BYTES = 32, 8, 160 * 1024, 2, 8192     # maxsim_common.hpp, maxsim_generic.hip, abi_common.hpp / abi_core.cpp (device_info)
 WAVES_DQ, WAVES_DD = 8, 4                                                                # maxsim_smooth.hip: kSmoothWavesDQ / DD
 
 
@@ -60,7 +60,7 @@ def cus():
     return torch.cuda.get_device_properties(torch.device("cuda", torch.cuda.current_device())).multi_processor_count
 
 
-# ---- mirror of the launcher (colpali_amd/csrc/maxsim_abi.hip: smooth_dispatch, launch_smooth, msim_smooth_pairs, smooth_bwd, smooth_dq_split)
+# ---- mirror of the launcher (colpali_amd/csrc/abi_train.hip: smooth_dispatch, launch_smooth, msim_smooth_pairs, smooth_bwd, smooth_dq_split)
 def plan(dtype, dim, n_q, Lq, n_d, n_pairs, n_cus):
     rb = dim * ESIZE[dtype]
     n_steps, tpq = rb // 32, _cdiv(Lq, TOK)

@@ -42,6 +42,53 @@ def test_abi_library_loads_and_exports_every_declared_symbol():
     assert not any("probe" in s for s in exported)
 
 
+def test_every_translation_unit_reports_errors_through_the_one_thread_local_message():
+    """The library is linked from one translation unit per family of entry points; the error message they
+    format lives in abi_core.cpp.  One entry point of each unit is called with an argument its check refuses before any HIP call:
+    the documented code comes back, and msim_last_error() on the same thread holds THAT call's message, not an earlier unit's."""
+    import threading
+
+    L = ctypes.CDLL(colpali_amd._lib.LIB_PATH)          # no argtypes: every argument below is passed as what the header declares
+    L.msim_last_error.restype = ctypes.c_char_p
+    i64, u32, null = ctypes.c_int64, ctypes.c_uint32, None
+    EINVAL = -1
+    calls = [
+        # maxsim_abi.hip: msim_fwd_ragged, n_q < 0
+        (lambda: L.msim_fwd_ragged(0, null, null, null, -1, null, null, null, 2, 128, null, i64(2), u32(0), null, null),
+         b"negative size (n_q=-1 n_d=2)"),
+        # abi_train.hip: msim_fwd_transposed_route without its routing buffer
+        (lambda: L.msim_fwd_transposed_route(0, null, 1, 32, null, 1, 16, 128, null, i64(1), null, null, null),
+         b"null routing buffer"),
+        # abi_head_pool.hip: msim_pool_cluster, null pointers
+        (lambda: L.msim_pool_cluster(0, null, null, 1, 128, 16, null, 2, null, null, null, null, null),
+         b"null pointer argument"),
+        # abi_search.hip: msim_topk_f32, k <= 0
+        (lambda: L.msim_topk_f32(null, null, 3, i64(7), i64(7), 0, i64(0), null, null, null, null),
+         b"bad size (n_q=3 n=7 k=0)"),
+        # abi_index.hip: msim_i8_scores, n_q < 0
+        (lambda: L.msim_i8_scores(null, null, null, -1, i64(0), 0, null, null, null, null, 4, i64(0), 128, null, i64(4), null),
+         b"msim_i8_scores: negative size (n_q=-1 n_d=4 q_rows=0 d_rows=0 max_q_tokens=0)"),
+        # maxsim_abi.hip again, the entry whose kernels share the forward scorers' unit: msim_fwd_candidates, n_q < 0
+        (lambda: L.msim_fwd_candidates(0, null, null, null, -1, null, null, null, 5, 128, null, 6, i64(6), i64(0), null, i64(6), null,
+                                       u32(0), null, null),
+         b"negative size (n_q=-1 m=6 n_d=5)"),
+    ]
+    for call, message in calls + calls[:1]:              # ... and round again: the first unit overwrites the last one's message
+        assert call() == EINVAL
+        assert L.msim_last_error() == message
+    # thread-local: another thread starts with an empty message, and what it provokes does not reach this thread's
+    seen = []
+
+    def other():
+        seen.extend([L.msim_last_error(), calls[1][0](), L.msim_last_error()])
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen == [b"", EINVAL, calls[1][1]]
+    assert L.msim_last_error() == calls[0][1]
+
+
 def test_probe_library_is_separate_from_the_product():
     """bench.py's ceilings come from tools/probe/libmaxsim_probe.so (include/maxsim_probe.h); it exports what that header declares."""
     from tools import probe
