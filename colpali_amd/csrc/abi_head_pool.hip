@@ -125,8 +125,15 @@ int msim_embed_head(int dtype, const void *X, int64_t M, int H, const void *W, c
 #if !defined(MSIM_AB) && !defined(MSIM_TRACE)
     {
         const bool whole_rows = ld_out % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        static std::atomic<int> cfg[4][kMaxDevices];
-        if (whole_rows)
+        static std::atomic<int> cfg[8][kMaxDevices];
+        // hidden sizes above 4096: the same two forms with the accumulator folded every 1024 K (WIDE, embed_head.hip)
+        if (H > 4096 && whole_rows)
+            rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true, false, false, true, false, true>, cfg[4], msim::kHeadFLds)
+                     : go(msim::embed_head_kernel<false, false, false, false, true, false, false, true, false, true>, cfg[5], msim::kHeadFLds);
+        else if (H > 4096)
+            rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true, false, false, false, false, true>, cfg[6], msim::kHeadFLds)
+                     : go(msim::embed_head_kernel<false, false, false, false, true, false, false, false, false, true>, cfg[7], msim::kHeadFLds);
+        else if (whole_rows)
             rc = f16 ? go(msim::embed_head_kernel<true, false, false, false, true, false, false, true>, cfg[0], msim::kHeadFLds)
                      : go(msim::embed_head_kernel<false, false, false, false, true, false, false, true>, cfg[1], msim::kHeadFLds);
         else
