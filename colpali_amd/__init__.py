@@ -12,6 +12,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      box of the chosen pages for ColbertNegativeCELoss / ColbertPairwiseNegativeCELoss
   * PageFilter                    -- filtered search (ShardedRetriever.search(filter=), LiveCorpus.search(filter=)): the top-k within
                                      one tenant's / collection's pages, by masking the scan or by listing and reranking them
+  * PageGroups                    -- document-level search (ShardedRetriever.search(group_by=), LiveCorpus.search(group_by=)): pages
+                                     grouped into documents, the top-k DOCUMENTS, each scored by (and returned with) its best page
   * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
@@ -28,6 +30,7 @@ from . import loss
 from .embed import CorpusWriter, embedding_head
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .filter import PageFilter
+from .group import PageGroups, group_reduce, group_select
 from .int8_index import Int8Index, int8_scores, quantize_queries
 from .live import LiveCorpus
 from .mine import gather_pages, mine_hard_negatives
@@ -59,6 +62,9 @@ __all__ = [
     "train_centroids",
     "LiveCorpus",
     "PageFilter",
+    "PageGroups",
+    "group_reduce",
+    "group_select",
     "mine_hard_negatives",
     "gather_pages",
     "ColbertLoss",

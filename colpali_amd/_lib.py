@@ -209,6 +209,10 @@ def lib() -> ctypes.CDLL:
     L.msim_filter_list.restype = i32
     L.msim_filter_ids.argtypes = [vp, i64, i32, i64, i64, i64, vp, i64, vp, vp, vp, vp]
     L.msim_filter_ids.restype = i32
+    L.msim_group_reduce.argtypes = [vp, i64, i32, i64, vp, vp, i32, i64, vp, vp, i64, vp]
+    L.msim_group_reduce.restype = i32
+    L.msim_group_select.argtypes = [vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, vp]
+    L.msim_group_select.restype = i32
     L.msim_align_candidates.argtypes =[i32, vp, vp, i32, i64, i32, vp, vp, vp, i32, i64, i32, vp, i32, i64, i64, vp, vp, vp, i32, vp]
     L.msim_align_candidates.restype = i32
     L.msim_topk_workspace_bytes.argtypes = [i32, i64, i32]

@@ -1,5 +1,5 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): search over the resident corpus -- top-k, the live corpus, hard-negative
-// mining and the page gather, page filters and token-to-patch alignment.
+// mining and the page gather, page filters, document-level search and token-to-patch alignment.
 // Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
 // frees or synchronises, so every entry point is hipGraph-capturable.  The kernels included below are defined and launched in
 // this translation unit and in no other.
@@ -13,6 +13,7 @@
 #include "live_corpus.hip"
 #include "mine.hip"
 #include "filter.hip"
+#include "group.hip"
 #include "maxsim_align.hip"
 
 using namespace msim_abi;
@@ -461,6 +462,63 @@ int msim_filter_ids(int64_t *ids, int64_t ld, int n_q, int64_t m, int64_t n, int
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, row_groups), dim3(msim::kFilterThreads), 0, st, ids, (long long)ld, n_q, (long long)m,
                        (long long)n, (long long)id_base, f);
     return launch_failed("filter_ids_kernel");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- document-level search (group.hip)
+extern "C" {
+
+int msim_group_reduce(const float *scores, int64_t ld, int n_q, int64_t n, const int32_t *offsets, const int32_t *pages, int n_groups,
+                      int64_t id_base, float *group_scores, int64_t *group_pages, int64_t ld_out, void *stream) {
+    const char *who = "msim_group_reduce";
+    if (n_q < 0 || n < 0 || n_groups < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld n_groups=%d)", who, n_q, (long long)n, n_groups);
+    if (n_q == 0 || n_groups == 0) return MSIM_OK;
+    if (n > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: n=%lld above 2^31 - 1", who, (long long)n);
+    if (!offsets || !group_scores || !group_pages || (n > 0 && (!scores || !pages))) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(scores, 4) || misaligned(offsets, 4) || misaligned(pages, 4) || misaligned(group_scores, 4) || misaligned(group_pages, 8))
+        return fail(MSIM_EINVAL, "%s: scores, offsets, pages and group_scores must be 4-byte aligned, group_pages 8-byte aligned", who);
+    if (ld < n) return fail(MSIM_EINVAL, "%s: ld=%lld < n=%lld", who, (long long)ld, (long long)n);
+    if (ld_out < n_groups) return fail(MSIM_EINVAL, "%s: ld_out=%lld < n_groups=%d", who, (long long)ld_out, n_groups);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const long long tiles = ((long long)n_groups + msim::kGroupThreads - 1) / msim::kGroupThreads;
+    // rows are shared out over grid.y: 64 row groups keep a lane's page registers in use for many rows; where the documents fill
+    // few tiles, more row groups (down to one row each) keep ~16 workgroups per CU in the launch
+    long long row_groups = (4096 + tiles - 1) / tiles;
+    row_groups = row_groups < 64 ? 64 : row_groups;
+    row_groups = row_groups > n_q ? n_q : row_groups > 65535 ? 65535 : row_groups;
+    hipLaunchKernelGGL(msim::group_reduce_kernel, dim3((unsigned)tiles, (unsigned)row_groups), dim3(msim::kGroupThreads), 0, st, scores,
+                       (long long)ld, n_q, (long long)n, offsets, pages, n_groups, (long long)id_base, group_scores, group_pages,
+                       (long long)ld_out);
+    return launch_failed("group_reduce_kernel");
+}
+
+int msim_group_select(const float *scores, const int64_t *gids, const int64_t *pages, int n_q, int m, int64_t ld, int k,
+                      float *out_scores, int64_t *out_gids, int64_t *out_pages, void *stream) {
+    const char *who = "msim_group_select";
+    static std::atomic<int> configured[kMaxDevices];
+    if (n_q < 0 || m < 0 || k <= 0) return fail(MSIM_EINVAL, "%s: bad size (n_q=%d m=%d k=%d)", who, n_q, m, k);
+    if (n_q == 0 || m == 0) return MSIM_OK;
+    if (m > msim::kGroupSelectMaxM) return fail(MSIM_EUNSUPPORTED, "%s: m=%d > %d", who, m, msim::kGroupSelectMaxM);
+    if (k > msim::kGroupSelectMaxK) return fail(MSIM_EUNSUPPORTED, "%s: k=%d > %d", who, k, msim::kGroupSelectMaxK);
+    if (!scores || !gids || !pages || !out_scores || !out_gids || !out_pages) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(scores, 4) || misaligned(out_scores, 4) || misaligned(gids, 8) || misaligned(pages, 8) || misaligned(out_gids, 8) ||
+        misaligned(out_pages, 8))
+        return fail(MSIM_EINVAL, "%s: scores must be 4-byte aligned, ids 8-byte aligned", who);
+    if (ld < m) return fail(MSIM_EINVAL, "%s: ld=%lld < m=%d", who, (long long)ld, m);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    if (int rc = allow_lds(msim::group_select_kernel, msim::kGroupSelectMaxM * msim::kGroupSelectEntryBytes, configured)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int npow2 = 64;
+    while (npow2 < m) npow2 <<= 1;
+    hipLaunchKernelGGL(msim::group_select_kernel, dim3((unsigned)n_q), dim3(msim::kGroupThreads),
+                       (size_t)npow2 * msim::kGroupSelectEntryBytes, st, scores, gids, pages, m, (long long)ld, k, npow2, out_scores,
+                       out_gids, out_pages);
+    return launch_failed("group_select_kernel");
 }
 
 }  // extern "C"

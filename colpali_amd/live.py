@@ -26,6 +26,7 @@ from .int8_index import DIM as I8_DIM
 from .int8_index import Int8Index, int8_scores
 from .align import Alignment, align
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
+from .group import PageGroups, group_reduce, group_select
 from .mine import mine_bounds, mine_mask
 from .retrieval import ShardedRetriever, rerank_scores, topk
 from .scoring import maxsim_scores
@@ -61,7 +62,7 @@ class LiveCorpus:
                  rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, select: Callable = topk,
                  mask_fn: Callable = mask_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
-                 filter_ids_fn: Callable = filter_ids):
+                 filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
         capacity_rows, capacity_docs = int(capacity_rows), int(capacity_docs)
         if capacity_rows < 1 or capacity_docs < 1:
             raise ValueError("capacity_rows and capacity_docs must be positive")
@@ -84,7 +85,8 @@ class LiveCorpus:
         self._select, self._mask_fn = select, mask_fn
         self._align_fn = align_fn
         self._mine_bounds_fn, self._mine_mask_fn = mine_bounds_fn, mine_mask_fn
-        self._filter_fns = dict(filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn)
+        self._filter_fns = dict(filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
+                                group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn)
         self._i8_codes: Optional[torch.Tensor] = None
         self._i8_scales: Optional[torch.Tensor] = None
         self._compactions = 0
@@ -351,18 +353,23 @@ class LiveCorpus:
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None, prefilter=None,
                n_candidates: Optional[int] = None, world: int = 1, rank: int = 0, dist=None, group=None,
-               filter: Optional[PageFilter] = None, filter_route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+               filter: Optional[PageFilter] = None, filter_route: str = "auto", group_by: Optional[PageGroups] = None):
         """`ShardedRetriever.search` over the live pages: the same arguments, rules and return value; a deleted page is never
         returned, and where fewer than `k` live pages exist the tail is (-inf, -1).  `prefilter` is `self.int8_index()`, or a
         `PackedCorpus` over the same slots (e.g. pooled pages; its deleted slots are masked too).  `filter` covers the slots
         (`len(filter) == len(self)`, deleted ones included) and is ANDed with the tombstones on both routes: the scores of deleted
-        slots are -inf before the filter masks the rest, and a listed id that is deleted is no page to the rerank."""
+        slots are -inf before the filter masks the rest, and a listed id that is deleted is no page to the rerank.  `group_by` covers
+        the slots too (`len(group_by) == len(self)`, deleted ones included): a document is scored by its surviving pages, and one
+        whose every page is deleted is not returned.  A `PageGroups` is immutable: build a new one over all slots after `add`."""
         shard = self.view()
         if self.device.type == "cuda" and not isinstance(queries, PackedQueries):     # an injected hook packs host queries itself
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.device, compact=compact or not dense_on_device)
         r = ShardedRetriever(shard, world, rank, dist, group, score_fn=self._score, select=self._select, rerank_fn=self._rerank,
                              int8_score_fn=self._int8_score, **self._filter_fns)
+        if group_by is not None:                 # (-inf, -1, -1) is already the rule there
+            return r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates, filter=filter,
+                            filter_route=filter_route, group_by=group_by)
         scores, ids = r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates,
                                filter=filter, filter_route=filter_route)
         return scores, torch.where(scores == float("-inf"), torch.full_like(ids, -1), ids)   # a deleted slot that filled a short row

@@ -22,6 +22,7 @@ from .corpus import PackedQueries, pack_queries
 from .fde import FdeIndex, fde_scores
 from . import filter as _filter
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
+from .group import SELECT_MAX_M, PageGroups, group_reduce, group_select
 from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
@@ -211,7 +212,7 @@ class ShardedRetriever:
                  rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores,
                  int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
-                 filter_ids_fn: Callable = filter_ids):
+                 filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
@@ -225,6 +226,8 @@ class ShardedRetriever:
         self._filter_mask = filter_mask_fn    # (scores, PageFilter, alive) -> scores, -inf where the page is not allowed
         self._filter_list = filter_list_fn    # (PageFilter, n_q, m_cap, alive) -> (cand int64 [n_q, m_cap], counts, status)
         self._filter_ids = filter_ids_fn      # (ids, PageFilter, alive) -> ids, -1 where an in-shard id is not allowed (in place)
+        self._group_reduce = group_reduce_fn  # (scores, PageGroups) -> (fp32 [n_q, G], int64 [n_q, G]): every document's best page
+        self._group_select = group_select_fn  # (scores, gids, pages, k) -> the k best documents of every candidate row
         self.force_collective = force_collective
         if world > 1 and dist is None:
             import torch.distributed as dist_mod
@@ -233,7 +236,7 @@ class ShardedRetriever:
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None,
                prefilter=None, n_candidates: Optional[int] = None, filter: Optional[PageFilter] = None,
-               filter_route: str = "auto") -> Tuple[torch.Tensor, torch.Tensor]:
+               filter_route: str = "auto", group_by: Optional[PageGroups] = None):
         """queries (replicated on every rank): a `PackedQueries`, a list of [len_i, 128] tensors, or a [n_q, Lq, 128] tensor.
         A host list is packed into the flat layout (ragged lengths, zero rows dropped on the way into the staging buffer).  A dense
         DEVICE tensor is scored as it stands unless `compact=True`: dropping its zero padding rows needs the per-query counts on the
@@ -271,21 +274,120 @@ class ShardedRetriever:
         With `prefilter=` the filter masks the stage-1 scores, so all `n_candidates` are allowed pages, and a candidate whose stage-1
         score is -inf becomes -1 (it is not reranked); stage 2 is unchanged.  With `candidates=` the disallowed ids of this shard
         become -1 before the rerank (`filter_ids`).  `search` calls `filter.prepare()` on first use (one host synchronisation); with
-        a prepared filter and a `PackedQueries` the call is hipGraph-capturable."""
+        a prepared filter and a `PackedQueries` the call is hipGraph-capturable.
+
+        Document-level search: `group_by` -- a `PageGroups` over this shard (same count, same id_base, same device; ValueError
+        otherwise) -- makes the call return the k best DOCUMENTS instead of the k best pages: (scores, group_ids, page_ids), each
+        [n_q, k].  A document's score is the score of its best page among those the route may return (allowed by `filter`, listed
+        by `candidates=` / kept by `prefilter=`, live in a `LiveCorpus`, and not scoring -inf); the order is (score descending,
+        document id ascending); `page_ids` is that best page -- the lower id on a tie --, ready for `align`; the padding is
+        (-inf, -1, -1), and -inf always comes with -1 / -1.  The scores carry the bits of the route's scorer.  Without `group_by`
+        nothing changes: the return stays (scores, ids).  The routes:
+          full scan    the scan, `group_reduce` (every document's best page, [n_q, G] in ascending document-id order), the `topk`
+                       over the documents -- its column order is the tie order.
+          candidates= / prefilter=   stage 1 and the rerank run unchanged: candidates stay PAGES and `n_candidates` counts PAGES, not
+                       documents; the reranked list is mapped to document ids and `group_select` keeps the k best documents.  Lists
+                       of at most 4096 entries (NotImplementedError beyond).
+          filter=      "mask" masks, then reduces; "list" lists, reranks, then `group_select`: "auto" takes it only when its rule
+                       above holds AND max_allowed <= 4096, an explicit "list" beyond raises NotImplementedError.  The two routes give
+                       the same bits and ids wherever they do without `group_by`.
+        With world > 1 (or `force_collective`) every rank computes its local top-k documents, ONE all-gather carries
+        [scores | pad to 8 | document ids | page ids] (20 bytes per entry) and `group_select` runs over the world x k gathered
+        entries (world x k <= 4096, ValueError otherwise).  This is exact: a document's global score is the maximum of its per-rank
+        scores, so it is attained on the rank R that holds its best page.  If the document is in the global top k it is in R's
+        local top k: any document ranked above it on R has a local score no better than its global one, so it ranks above it
+        globally as well, and there are fewer than k of those.  Its best entry therefore reaches the merge, which deduplicates
+        documents that several ranks sent.  The answer does not depend on the number of shards, also where a document's pages
+        straddle a boundary.  `search` calls `group_by.prepare()` on first use (one host synchronisation); with prepared groups
+        and a `PackedQueries` the call is hipGraph-capturable."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
+        groups = self._check_groups(group_by, k)
         if filter is not None:
-            return self._search_filtered(queries, k, compact, candidates, prefilter, n_candidates, filter, filter_route)
+            return self._search_filtered(queries, k, compact, candidates, prefilter, n_candidates, filter, filter_route, groups)
         if filter_route != "auto":
             raise ValueError("filter_route goes with filter=")
         if candidates is not None or prefilter is not None:
-            return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates)
+            return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, groups=groups)
         if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
         scores = self._score(queries, self.shard)
+        if groups is not None:
+            return self._group_scan(scores, k, groups)
         return shard_topk(scores, k, self.shard.id_base, self.world, self.dist, self.group, self._select,
                           force_collective=self.force_collective)
+
+    # ------------------------------------------------------------------------------------------------- document-level search
+    def _check_groups(self, groups, k) -> Optional[PageGroups]:
+        if groups is None:
+            return None
+        if not isinstance(groups, PageGroups):
+            raise ValueError("group_by must be a PageGroups")
+        shard = self.shard
+        if len(groups) != len(shard) or groups.id_base != shard.id_base:
+            raise ValueError(f"group_by covers {len(groups)} pages from id {groups.id_base}; the shard holds {len(shard)} from id "
+                             f"{shard.id_base}: it must cover the same pages")
+        if groups.device != shard.device:
+            raise ValueError(f"the groups live on {groups.device}, the shard on {shard.device}")
+        collective = self.world > 1 or self.force_collective
+        if collective and max(self.world, 1) * int(k) > SELECT_MAX_M:
+            raise ValueError(f"group_by with world={max(self.world, 1)} and k={k}: the merge selects among world x k gathered "
+                             f"entries, at most {SELECT_MAX_M}")
+        return groups.prepare()
+
+    @staticmethod
+    def _group_result(top_s, gid, page):
+        """-inf is "no document", whatever filled the row"""
+        none = top_s == float("-inf")
+        return top_s, torch.where(none, torch.full_like(gid, -1), gid), torch.where(none, torch.full_like(page, -1), page)
+
+    def _group_scan(self, scores: torch.Tensor, k: int, groups: PageGroups):
+        """a score matrix over the shard's pages -> this shard's best k documents, then the merge"""
+        n_q, g = scores.shape[0], groups.n_groups
+        if g == 0:
+            top_s = torch.full((n_q, k), float("-inf"), dtype=torch.float32, device=scores.device)
+            gid = torch.full((n_q, k), -1, dtype=torch.int64, device=scores.device)
+            page = gid.clone()
+        else:
+            doc_s, doc_p = self._group_reduce(scores, groups)
+            top_s, col = self._select(doc_s, k, 0, None)               # columns are in ascending document-id order: the tie order
+            c = col.clamp(0, g - 1)
+            gid = torch.where(col >= 0, groups.group_ids[c], torch.full_like(col, -1))
+            page = torch.where(col >= 0, torch.gather(doc_p, 1, c), torch.full_like(col, -1))
+        return self._group_merge(*self._group_result(top_s, gid, page), k)
+
+    def _group_list(self, scores: torch.Tensor, ids: torch.Tensor, k: int, groups: PageGroups):
+        """reranked (scores, page ids) rows -> this shard's best k documents, then the merge"""
+        if scores.shape[1] > SELECT_MAX_M:
+            raise NotImplementedError(f"group_by over a list of {scores.shape[1]} pages: group_select takes at most {SELECT_MAX_M}")
+        return self._group_merge(*self._group_select(scores, groups.doc_ids(ids), ids, k), k)
+
+    def _group_merge(self, top_s, gid, page, k: int):
+        """(world > 1) ONE all-gather of every rank's k best documents, and the grouped selection over the world x k entries"""
+        if self.world <= 1 and not self.force_collective:
+            return self._group_result(top_s, gid, page)
+        world = max(self.world, 1)
+        dist = self.dist
+        if dist is None:
+            import torch.distributed as dist  # noqa: PLW0642 - the default collective library
+        # one message per rank: [scores fp32 n_q*k | pad to 8 | document ids int64 n_q*k | page ids int64 n_q*k]: 20 bytes per entry
+        n_q = top_s.shape[0]
+        sb, ib = n_q * k * 4, n_q * k * 8
+        sbp = (sb + 7) // 8 * 8
+        nbytes = sbp + 2 * ib
+        mine = torch.empty((nbytes,), dtype=torch.uint8, device=top_s.device)
+        mine[:sb].view(torch.float32).view(n_q, k).copy_(top_s)
+        mine[sbp:sbp + ib].view(torch.int64).view(n_q, k).copy_(gid)
+        mine[sbp + ib:].view(torch.int64).view(n_q, k).copy_(page)
+        flat = torch.empty((world * nbytes,), dtype=torch.uint8, device=top_s.device)
+        dist.all_gather_into_tensor(flat, mine, group=self.group)
+        gathered = flat.view(world, nbytes)
+
+        def rows(part, dtype):
+            return part.view(dtype).view(world, n_q, k).permute(1, 0, 2).reshape(n_q, world * k).contiguous()
+        return self._group_result(*self._group_select(rows(gathered[:, :sb], torch.float32), rows(gathered[:, sbp:sbp + ib], torch.int64),
+                                                      rows(gathered[:, sbp + ib:], torch.int64), k))
 
     def align(self, queries, ids: torch.Tensor, maps: bool = False) -> Alignment:
         """Explain hits (`align`): for every entry of `ids` -- int64 [n_q, m] GLOBAL ids, the same on every rank, e.g. what `search`
@@ -343,7 +445,7 @@ class ShardedRetriever:
             return int(queries.shape[1]) <= 128
         return all(int(q.shape[0]) <= 128 for q in queries)
 
-    def _search_filtered(self, queries, k, compact, candidates, prefilter, n_candidates, flt, route):
+    def _search_filtered(self, queries, k, compact, candidates, prefilter, n_candidates, flt, route, groups=None):
         if route not in ("auto", "mask", "list"):
             raise ValueError(f"filter_route={route!r}: 'auto', 'mask' or 'list'")
         if not isinstance(flt, PageFilter):
@@ -358,6 +460,8 @@ class ShardedRetriever:
         if two_stage:
             if route == "list":
                 raise ValueError("filter_route='list' lists the allowed pages itself: it does not go with candidates= / prefilter=")
+            if groups is not None:
+                return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt, groups)
             top_s, top_i = self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt)
         else:
             if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
@@ -372,16 +476,24 @@ class ShardedRetriever:
                 raise NotImplementedError(f"filter_route='list' reranks the listed pages: rerank takes bfloat16 / float16 embeddings of "
                                           f"width 128 or 320 and queries of at most 128 tokens (got {q_dtype}, width {dim}, corpus "
                                           f"{shard.blob.dtype} of width {shard.blob.shape[1]})")
+            if route == "list" and groups is not None and flt.max_allowed > SELECT_MAX_M:
+                raise NotImplementedError(f"filter_route='list' with group_by: a query is allowed {flt.max_allowed} pages, group_select "
+                                          f"takes lists of at most {SELECT_MAX_M}")
             if route == "auto":
                 route = "list" if (fits and n_q * flt.max_allowed < 2**31
-                                   and flt.max_allowed <= len(shard) * _filter.LIST_ROUTE_MAX_FRACTION) else "mask"
+                                   and flt.max_allowed <= len(shard) * _filter.LIST_ROUTE_MAX_FRACTION
+                                   and (groups is None or flt.max_allowed <= SELECT_MAX_M)) else "mask"
             if route == "list":
                 cand = self._filter_list(flt, n_q, max(flt.max_allowed, 1), None)[0]
                 scores, ids = self._rerank(queries, shard, cand)
+                if groups is not None:
+                    return self._group_list(scores, ids, k, groups)
                 top_s, top_i = shard_topk(scores, k, 0, self.world, self.dist, self.group, self._select,
                                           force_collective=self.force_collective, ids=ids)
             else:
                 scores = self._filter_mask(self._score(queries, shard), flt, None)
+                if groups is not None:
+                    return self._group_scan(scores, k, groups)
                 top_s, top_i = shard_topk(scores, k, shard.id_base, self.world, self.dist, self.group, self._select,
                                           force_collective=self.force_collective)
         return top_s, torch.where(top_s == float("-inf"), torch.full_like(top_i, -1), top_i)     # -inf is "no page", whatever filled the row
@@ -391,9 +503,14 @@ class ShardedRetriever:
         if flt.rows is not None and flt.rows != n_q:
             raise ValueError(f"a per-query filter of {flt.rows} rows was given for {n_q} queries")
 
-    def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates, flt=None):
+    def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates, flt=None, groups=None):
         if candidates is not None and prefilter is not None:
             raise ValueError("pass either candidates= or prefilter=, not both")
+        if groups is not None:
+            m = int(n_candidates) if prefilter is not None and n_candidates is not None else (
+                int(candidates.shape[-1]) if isinstance(candidates, torch.Tensor) and candidates.dim() == 2 else 0)
+            if m > SELECT_MAX_M:
+                raise NotImplementedError(f"group_by over a list of {m} pages: group_select takes at most {SELECT_MAX_M}")
         if prefilter is not None:
             if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex)):
                 raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index or a CentroidIndex")
@@ -425,6 +542,8 @@ class ShardedRetriever:
                 raise ValueError(f"candidates must be an int64 [n_q={len(queries)}, m] tensor on {self.shard.device}")
             candidates = self._filter_ids(candidates.clone(memory_format=torch.contiguous_format), flt, None)
         scores, ids = self._rerank(queries, self.shard, candidates)      # stage 2: exact, this shard's candidates only
+        if groups is not None:
+            return self._group_list(scores, ids, k, groups)
         return shard_topk(scores, k, 0, self.world, self.dist, self.group, self._select, force_collective=self.force_collective,
                           ids=ids)
 

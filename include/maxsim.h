@@ -808,6 +808,46 @@ int msim_filter_ids(int64_t *ids, int64_t ld, int n_q, int64_t m, int64_t n, int
                     int64_t ld_words, const int32_t *page_labels /* or NULL */, const int32_t *query_labels /* or NULL */,
                     const uint8_t *alive /* or NULL */, void *stream);
 
+/*
+ * DOCUMENT-LEVEL SEARCH (group.hip; additions to ABI 22): the n pages of a shard belong to G documents, and a search returns the
+ * top-k DOCUMENTS, each scored by its best page.  No scorer and no selection kernel changes: msim_group_reduce sits between a score
+ * matrix and msim_topk_f32, msim_group_select behind msim_fwd_candidates and behind the all-gather of a sharded search.
+ *
+ * The grouping is a CSR over LOCAL page indices (page c has id id_base + c): offsets int32 [n_groups + 1], pages int32 [n]; document
+ * g owns pages[offsets[g] .. offsets[g + 1]), ascending.  Documents may have any length >= 1 and their pages need not be contiguous.
+ *
+ * msim_group_reduce: scores fp32 [n_q, ld] (ld >= n, 4-byte aligned, any row alignment) -> group_scores fp32 [n_q, ld_out] and
+ * group_pages int64 [n_q, ld_out] (ld_out >= n_groups; columns 0 .. n_groups - 1 are written, nothing else).  Entry (q, g) is the
+ * best page of document g for query q under the project's order: the higher score first, equal floats tie (-0.0 and +0.0 tie, as in
+ * msim_topk_f32), and on a tie the lower page wins.  group_scores holds the winner's own bits, group_pages its GLOBAL id.  A
+ * document whose pages all score -inf (or that owns no page) is (-inf, -1).  NaN is outside the contract, as for msim_topk_f32.
+ * A gather: every output has one owner, there is no atomic, the result does not depend on scheduling.  A document is reduced by
+ * one lane, one wave or one workgroup by its length: up to MSIM_GROUP_THREAD_MAX pages by a lane, up to MSIM_GROUP_WAVE_MAX by a
+ * wave, longer ones by the 256 lanes of the workgroup.  HBM traffic: 4 B per scored pair read, 12 B per (q, g) written; the CSR is
+ * read once per workgroup into registers (the workgroup form re-reads it per row, from L2).  Offsets are clipped to [0, n] and a
+ * page index outside [0, n) is skipped before it becomes an address.  n <= 2^31 - 1 (MSIM_EUNSUPPORTED).
+ *
+ * msim_group_select, the grouped top-k of candidate rows: scores fp32, gids int64 (document ids), pages int64 (page ids), each
+ * [n_q, ld] with m columns (ld >= m).  An entry with gid < 0 or a score of -inf is no entry.  Per row the best entry of every
+ * document by (score descending, page id ascending) survives, the survivors are ordered by (score descending, document id
+ * ascending), the first k go to out_scores / out_gids / out_pages (each contiguous [n_q, k]) and the rest of the row is
+ * (-inf, -1, -1).  Scores come back as msim_topk_f32 returns them (-0.0 as +0.0).  One workgroup per row, two bitonic sorts in
+ * dynamic LDS of 20 B per entry (80 KiB at m = 4096).  m <= MSIM_GROUP_SELECT_MAX_M, k <= MSIM_GROUP_SELECT_MAX_K
+ * (MSIM_EUNSUPPORTED beyond).
+ *
+ * MSIM_EINVAL for a negative size, k <= 0, a null or misaligned pointer, ld < n, ld_out < n_groups, ld < m.  n_q == 0 or
+ * n_groups == 0 (msim_group_reduce), n_q == 0 or m == 0 (msim_group_select) return 0 before a pointer is looked at and write
+ * nothing.  Both are asynchronous on `stream`, allocate nothing, never synchronise with the host and are hipGraph-capturable.
+ */
+#define MSIM_GROUP_THREAD_MAX 16     /* a document of at most this many pages is reduced by one lane */
+#define MSIM_GROUP_WAVE_MAX 1024     /* ... of at most this many by one wave; longer ones by the workgroup */
+#define MSIM_GROUP_SELECT_MAX_M 4096 /* widest candidate row of msim_group_select */
+#define MSIM_GROUP_SELECT_MAX_K 1024 /* largest k of msim_group_select */
+int msim_group_reduce(const float *scores, int64_t ld, int n_q, int64_t n, const int32_t *offsets, const int32_t *pages, int n_groups,
+                      int64_t id_base, float *group_scores, int64_t *group_pages, int64_t ld_out, void *stream);
+int msim_group_select(const float *scores, const int64_t *gids, const int64_t *pages, int n_q, int m, int64_t ld, int k,
+                      float *out_scores, int64_t *out_gids, int64_t *out_pages, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
