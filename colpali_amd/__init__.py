@@ -18,6 +18,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
                                      centroid interaction): a first stage for prefilter= at 2 bytes per row
+  * ResidualCorpus / residual_rerank_scores -- PLAID's second half: the shard itself as centroid codes + 2 / 4 residual bits per
+                                     dimension (34 / 66 bytes per row instead of 256), candidate lists reranked straight from them
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
@@ -38,7 +40,8 @@ from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPai
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
 from .patch import patch_colpali_engine, unpatch_colpali_engine
-from .retrieval import (ExactMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered, rerank, shard_range,
+from .residual import ResidualCorpus, residual_rerank_scores, train_residual_codec
+from .retrieval import (ExactMaxSimIndex, ResidualMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered, rerank, shard_range,
                         shard_topk, topk)
 from .scoring import (get_similarity_maps_from_embeddings, get_torch_device, maxsim_scores, score_multi_vector,
                       score_single_vector, similarity_matrix)
@@ -60,6 +63,10 @@ __all__ = [
     "CentroidIndex",
     "centroid_scores",
     "train_centroids",
+    "ResidualCorpus",
+    "ResidualMaxSimIndex",
+    "residual_rerank_scores",
+    "train_residual_codec",
     "LiveCorpus",
     "PageFilter",
     "PageGroups",

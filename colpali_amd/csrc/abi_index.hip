@@ -1,5 +1,5 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the first-stage indexes -- fixed dimensional encodings, the int8
-// token-level index and the centroid-code index.
+// token-level index and the centroid-code index -- and the residual-compressed corpus built on the centroid codes.
 // Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
 // frees or synchronises, so every entry point is hipGraph-capturable.  The kernels included below are defined and launched in
 // this translation unit and in no other.
@@ -12,6 +12,7 @@
 #include "fde.hip"
 #include "int8_index.hip"
 #include "centroid_index.hip"
+#include "residual_codec.hip"
 
 using namespace msim_abi;
 
@@ -352,6 +353,119 @@ int msim_cent_scores(const void *table, const int32_t *q_off, int n_q, int64_t q
                        static_cast<const _Float16 *>(table), q_off, n_q, (long long)q_rows, p.nb, K, codes, d_off, clamp0, n_d,
                        (long long)d_rows, p.ppw, p.n_pr, scores, (long long)ld_scores);
     return launch_failed("cent_scores_kernel");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the residual-compressed corpus (residual_codec.hip)
+namespace {
+
+int res_check_format(const char *who, int dtype, int dim, int K, int bits) {
+    if (int rc = cent_check_format(who, dtype, dim, K)) return rc;
+    if (!(bits == 2 || bits == 4)) return fail(MSIM_EUNSUPPORTED, "%s: %d residual bits; the codec stores 2 or 4 per dimension", who, bits);
+    return MSIM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_res_encode_docs(int dtype, const void *D, int64_t n_rows, int dim, const uint16_t *codes, const void *C, int K,
+                         const float *cutoffs, int bits, uint8_t *residuals, void *stream) {
+    const char *who = "msim_res_encode_docs";
+    if (n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (rows=%lld)", who, (long long)n_rows);
+    if (int rc = res_check_format(who, dtype, dim, K, bits)) return rc;
+    if (n_rows == 0) return MSIM_OK;
+    if (!D || !codes || !C || !cutoffs || !residuals) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(D, 16) || misaligned(C, 16) || misaligned(residuals, 16) || misaligned(codes, 2) || misaligned(cutoffs, 4))
+        return fail(MSIM_EINVAL, "%s: rows, centroids and residuals must be 16-byte aligned, codes 2-byte and cutoffs 4-byte aligned", who);
+    const long long blocks = (n_rows * msim::kResChunks + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld rows exceed one launch", who, (long long)n_rows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = bits == 2 ? (f16 ? msim::res_encode_kernel<true, 2> : msim::res_encode_kernel<false, 2>)
+                          : (f16 ? msim::res_encode_kernel<true, 4> : msim::res_encode_kernel<false, 4>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const uint16_t *>(D), codes,
+                       (long long)n_rows, static_cast<const uint16_t *>(C), K, cutoffs, residuals);
+    return launch_failed("res_encode_kernel");
+}
+
+int msim_res_decode_rows(int dtype, const uint16_t *codes, const uint8_t *residuals, int64_t n_rows, int64_t row0, int64_t row1,
+                         const void *C, int K, const float *weights, int bits, int dim, void *out, void *stream) {
+    const char *who = "msim_res_decode_rows";
+    if (n_rows < 0 || row0 < 0 || row1 < row0 || row1 > n_rows)
+        return fail(MSIM_EINVAL, "%s: rows %lld .. %lld of %lld", who, (long long)row0, (long long)row1, (long long)n_rows);
+    if (int rc = res_check_format(who, dtype, dim, K, bits)) return rc;
+    if (row1 == row0) return MSIM_OK;
+    if (!codes || !residuals || !C || !weights || !out) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(out, 16) || misaligned(C, 16) || misaligned(residuals, 16) || misaligned(codes, 2) || misaligned(weights, 4))
+        return fail(MSIM_EINVAL, "%s: out, centroids and residuals must be 16-byte aligned, codes 2-byte and weights 4-byte aligned", who);
+    const long long blocks = ((row1 - row0) * msim::kResChunks + 255) / 256;
+    if (blocks > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld rows exceed one launch", who, (long long)(row1 - row0));
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = bits == 2 ? (f16 ? msim::res_decode_kernel<true, 2> : msim::res_decode_kernel<false, 2>)
+                          : (f16 ? msim::res_decode_kernel<true, 4> : msim::res_decode_kernel<false, 4>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), codes, residuals, (long long)row0,
+                       (long long)row1, static_cast<const uint16_t *>(C), K, weights, static_cast<uint16_t *>(out));
+    return launch_failed("res_decode_kernel");
+}
+
+// one wave scores one entry from the page's own rows: nothing is inverted, so the workspace is the status word alone
+size_t msim_res_candidates_workspace_bytes(int n_q, int m, int n_d) {
+    if (n_q <= 0 || m <= 0 || n_d < 0) return 0;
+    return 16;
+}
+
+int msim_res_candidates(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const uint16_t *codes,
+                        const uint8_t *residuals, const void *C, int K, const float *weights, int bits, const int32_t *d_off,
+                        const uint8_t *d_clamp0, int n_d, int64_t d_rows, int dim, const int64_t *cand, int m, int64_t ld_cand,
+                        int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids, void *workspace, void *stream) {
+    const char *who = "msim_res_candidates";
+    if (n_q < 0 || m < 0 || n_d < 0 || d_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d m=%d n_d=%d d_rows=%lld)", who, n_q, m, n_d, (long long)d_rows);
+    if (n_q == 0 || m == 0) return MSIM_OK;
+    if (int rc = res_check_format(who, dtype, dim, K, bits)) return rc;
+    if (!Qt || !q_off || !q_off_host || ((!codes || !residuals) && d_rows > 0) || !C || !weights || !d_off || !cand || !out_scores ||
+        !workspace)
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(C, 16) || misaligned(residuals, 16) || misaligned(workspace, 16) || misaligned(codes, 2) ||
+        misaligned(weights, 4) || misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(out_scores, 4) || misaligned(cand, 8) ||
+        misaligned(out_ids, 8))
+        return fail(MSIM_EINVAL, "%s: Qt, centroids, residuals and workspace must be 16-byte aligned; the rest by their element size", who);
+    if (ld_cand < m) return fail(MSIM_EINVAL, "%s: ld_cand=%lld < m=%d", who, (long long)ld_cand, m);
+    if (ld_scores < m) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < m=%d", who, (long long)ld_scores, m);
+    if ((long long)n_q * m > 0x7fffffff) return fail(MSIM_EUNSUPPORTED, "%s: more than 2^31 - 1 entries (n_q=%d x m=%d)", who, n_q, m);
+    if (d_rows > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld exceeds 32-bit page offsets", who, (long long)d_rows);
+    if (q_off_host[0] != 0) return fail(MSIM_EINVAL, "%s: q_off[0] must be 0", who);
+    for (int i = 0; i < n_q; ++i) {
+        const int len = q_off_host[i + 1] - q_off_host[i];
+        if (len < 0) return fail(MSIM_EINVAL, "%s: q_off must be non-decreasing (query %d)", who, i);
+        if (len > msim::kStreamMaxUnits * msim::kUnitTok)
+            return fail(MSIM_EUNSUPPORTED, "query %d has %d tokens: %s takes queries of at most %d", i, len, who,
+                        msim::kStreamMaxUnits * msim::kUnitTok);
+    }
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *status = static_cast<int32_t *>(workspace);
+    const long long E = (long long)n_q * m;
+    const unsigned eblocks = (unsigned)((E + 255) / 256);
+    hipLaunchKernelGGL(msim::res_zero_status_kernel, dim3(1), dim3(64), 0, st, status);
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = bits == 2 ? (f16 ? msim::res_candidates_kernel<true, 2> : msim::res_candidates_kernel<false, 2>)
+                          : (f16 ? msim::res_candidates_kernel<true, 4> : msim::res_candidates_kernel<false, 4>);
+    // a persistent grid: one entry per wave at a time, as many workgroups per CU as the launch bounds keep resident (two)
+    const long long wg_needed = (E + 3) / 4;
+    const long long wg_cap = (long long)di->cus * 2;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(wg_needed < wg_cap ? wg_needed : wg_cap)), dim3(256), msim::kResLdsBytes, st,
+                       static_cast<const uint16_t *>(Qt), q_off, n_q, (long long)q_off_host[n_q], codes, residuals,
+                       static_cast<const uint16_t *>(C), K, weights, d_off, d_clamp0, n_d, (long long)d_rows, cand, (long long)ld_cand, m,
+                       (long long)id_base, out_scores, (long long)ld_scores, out_ids, status);
+    hipLaunchKernelGGL(msim::res_poison_kernel, dim3(eblocks), dim3(256), 0, st, status, n_q, m, out_scores, (long long)ld_scores);
+    return launch_failed("res_candidates_kernel");
 }
 
 }  // extern "C"

@@ -1,0 +1,264 @@
+"""A residual-compressed corpus (PLAID's second half): a resident shard that keeps no full-precision embedding.
+
+`ResidualCorpus.build` stores every row of a `PackedCorpus` as its `CentroidIndex` code (2 bytes) plus `bits` (2 or 4) of residual
+per dimension -- 34 or 66 bytes per row instead of 256 -- and the caller may then free the bf16 corpus.  The codec (include/maxsim.h:
+msim_res_*, colpali_amd/csrc/residual_codec.hip):
+
+    encode   e_k = fl32(float(x_k) - float(C[c]_k));  bucket b_k = #{cutoffs t : t <= e_k}
+    pack     dimension k = bits [k * bits, k * bits + bits) of the row's 16 * bits bytes, a little-endian bit string
+    decode   xhat_k = round_to_dtype(float(C[c]_k) + weights[b_k])   -- one rounding, NO renormalisation (ColBERTv2's Python path
+             renormalises the decoded row; PLAID's kernels do not, and neither does this)
+
+`residual_rerank_scores` reranks candidate lists straight from the compressed rows (each 32-row slab of a page is decoded in
+registers into LDS and never written to memory); every score has the bits `rerank_scores` gives the same query against
+`rc.decompress()`.  Stage 1 is `rc.index`, the `CentroidIndex` view over the same codes:
+`ShardedRetriever(rc).search(q, k, prefilter=rc.index, n_candidates=m)`.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .centroid import CentroidIndex
+from .corpus import PackedCorpus, PackedQueries, pack_queries
+from .scoring import _require_gpu
+
+DIM = 128
+BITS = (2, 4)
+
+
+def _check_bits(bits) -> int:
+    if isinstance(bits, bool) or not isinstance(bits, int) or bits not in BITS:
+        raise ValueError(f"bits must be 2 or 4 (got {bits!r})")
+    return bits
+
+
+def _check_codec(cutoffs: torch.Tensor, weights: torch.Tensor, bits: int) -> None:
+    nb = 1 << bits
+    if cutoffs.dtype != torch.float32 or cutoffs.shape != (nb - 1,) or not cutoffs.is_contiguous():
+        raise ValueError(f"cutoffs must be a contiguous fp32 [{nb - 1}] tensor")
+    if weights.dtype != torch.float32 or weights.shape != (nb,) or not weights.is_contiguous():
+        raise ValueError(f"weights must be a contiguous fp32 [{nb}] tensor")
+
+
+def train_residual_codec(residual_sample: torch.Tensor, bits: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(cutoffs fp32 [2^bits - 1], weights fp32 [2^bits]) from sampled residuals fp32 [s, 128] (any device; plain torch: this is
+    build time, like `train_centroids`).  Cutoff j (1 .. 2^bits - 1) is the j / 2^bits quantile of ALL sampled values: element
+    floor(j * N / 2^bits) of the N sorted values.  Weight b is the mean of the values falling in bucket b (the number of cutoffs
+    <= value); an empty bucket takes the midpoint of its cutoffs (an outer one, which has a single cutoff, that cutoff)."""
+    bits = _check_bits(bits)
+    if residual_sample.dim() != 2 or residual_sample.shape[1] != DIM or residual_sample.dtype != torch.float32:
+        raise ValueError(f"residual_sample must be fp32 [s, {DIM}]")
+    if residual_sample.shape[0] < 1:
+        raise ValueError("residual_sample is empty")
+    nb = 1 << bits
+    vals = residual_sample.reshape(-1)
+    srt = torch.sort(vals).values
+    n = int(srt.numel())
+    pick = torch.tensor([min(j * n // nb, n - 1) for j in range(1, nb)], dtype=torch.int64, device=srt.device)
+    cutoffs = srt[pick].contiguous()
+    # bucket b (the number of cutoffs <= value) is a contiguous run of the sorted values: it starts at the first value >= cutoff b - 1.
+    # Sums from one float64 prefix sum, not from 2^bits-way atomics over every value
+    zero = torch.zeros((1,), dtype=torch.int64, device=srt.device)
+    edges = torch.cat([zero, torch.searchsorted(srt, cutoffs), zero + n])
+    prefix = torch.cat([torch.zeros((1,), dtype=torch.float64, device=srt.device), torch.cumsum(srt.double(), 0)])
+    sums = prefix[edges[1:]] - prefix[edges[:-1]]
+    counts = edges[1:] - edges[:-1]
+    lo = torch.cat([cutoffs[:1], cutoffs])                                # bucket b spans [lo[b], hi[b]]; the outer ones end at their cutoff
+    hi = torch.cat([cutoffs, cutoffs[-1:]])
+    mid = (lo.double() + hi.double()) / 2
+    mean = sums / counts.clamp(min=1)
+    weights = torch.where(counts > 0, mean, mid).float()
+    inf = torch.full((1,), float("inf"), dtype=torch.float32, device=vals.device)
+    weights = torch.maximum(torch.minimum(weights, torch.cat([cutoffs, inf])), torch.cat([-inf, cutoffs]))    # the fp32 rounding of a mean
+    return cutoffs, weights.contiguous()
+
+
+def _query_format(queries) -> Tuple[torch.dtype, int]:
+    if isinstance(queries, PackedQueries):
+        return queries.dtype, int(queries.tokens.shape[1])
+    if isinstance(queries, torch.Tensor):
+        return queries.dtype, int(queries.shape[-1])
+    if len(queries) == 0:
+        raise ValueError("No queries provided")
+    return queries[0].dtype, int(queries[0].shape[-1])
+
+
+class ResidualCorpus:
+    """One resident shard in compressed form: `centroids` [K, 128] (bf16 / f16), `codes` uint16 [rows], `residuals` uint8
+    [rows, 16 * bits], `cutoffs` fp32 [2^bits - 1], `weights` fp32 [2^bits], the pages' `offsets` (int32 [n + 1], device), `clamp0`
+    (uint8 [n] or None), `lengths` (int64 [n], host), `id_base` and `bits`.  `.index` is a `CentroidIndex` over the SAME `codes` and
+    `centroids` tensors (no copy): the stage 1 that goes with this stage 2."""
+
+    def __init__(self, centroids: torch.Tensor, codes: torch.Tensor, residuals: torch.Tensor, cutoffs: torch.Tensor,
+                 weights: torch.Tensor, offsets: torch.Tensor, clamp0: Optional[torch.Tensor], lengths: torch.Tensor,
+                 id_base: int = 0, bits: int = 2):
+        bits = _check_bits(bits)
+        self.index = CentroidIndex(centroids, codes, offsets, clamp0, lengths, id_base)       # validates what the two share
+        _check_codec(cutoffs, weights, bits)
+        if (residuals.dtype != torch.uint8 or residuals.dim() != 2 or residuals.shape != (codes.shape[0], 16 * bits)
+                or not residuals.is_contiguous()):
+            raise ValueError(f"residuals must be a contiguous uint8 [{codes.shape[0]}, {16 * bits}] tensor")
+        for name, t in (("centroids", centroids), ("residuals", residuals), ("cutoffs", cutoffs), ("weights", weights),
+                        ("offsets", offsets)):
+            if t.device != codes.device:
+                raise ValueError(f"{name} live on {t.device}, the codes on {codes.device}")
+        self.centroids, self.codes, self.residuals = centroids, codes, residuals
+        self.cutoffs, self.weights = cutoffs, weights
+        self.offsets, self.clamp0, self.lengths = offsets, clamp0, lengths
+        self.id_base, self.bits = int(id_base), bits
+
+    def __len__(self) -> int:
+        return int(self.lengths.numel())
+
+    @property
+    def device(self) -> torch.device:
+        return self.codes.device
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.centroids.dtype
+
+    @property
+    def n_centroids(self) -> int:
+        return int(self.centroids.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        n = sum(t.numel() * t.element_size() for t in (self.centroids, self.codes, self.residuals, self.cutoffs, self.weights,
+                                                       self.offsets))
+        return n + (self.clamp0.numel() if self.clamp0 is not None else 0)
+
+    @classmethod
+    def build(cls, corpus: PackedCorpus, index: Optional[CentroidIndex] = None, bits: int = 2,
+              cutoffs: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None, sample_rows: int = 1 << 18,
+              seed: int = 0, **centroid_kwargs) -> "ResidualCorpus":
+        """Compress `corpus` (bf16 / f16, width 128).  `index=None` builds a `CentroidIndex` first (`**centroid_kwargs` go to
+        `CentroidIndex.build`); a given one must cover the corpus's pages and rows.  With given `cutoffs` and `weights` the build is
+        bit-reproducible; otherwise they are trained (`train_residual_codec`) on the residuals of a seeded sample of `sample_rows`
+        rows.  The corpus is not kept: the caller may free it.  Asynchronous on torch's current stream (training reads a few
+        numbers back)."""
+        bits = _check_bits(bits)
+        dev = _require_gpu(corpus.device)
+        if corpus.blob.dtype not in (torch.bfloat16, torch.float16) or int(corpus.blob.shape[1]) != DIM:
+            raise NotImplementedError(f"the residual codec takes bfloat16 / float16 pages of width {DIM} (got {corpus.blob.dtype}, "
+                                      f"width {int(corpus.blob.shape[1])})")
+        if (cutoffs is None) != (weights is None):
+            raise ValueError("pass both cutoffs and weights, or neither")
+        if sample_rows < 1:
+            raise ValueError("sample_rows must be >= 1")
+        if index is None:
+            index = CentroidIndex.build(corpus, **centroid_kwargs)
+        elif centroid_kwargs:
+            raise ValueError(f"{sorted(centroid_kwargs)} go to CentroidIndex.build: they do not go with index=")
+        rows = int(corpus.blob.shape[0])
+        if (len(index) != len(corpus) or index.id_base != corpus.id_base or int(index.codes.shape[0]) != rows
+                or index.device != dev or index.centroids.dtype != corpus.blob.dtype):
+            raise ValueError("index must be a CentroidIndex of this corpus (same pages, rows, id_base, dtype and device)")
+        blob = corpus.blob if corpus.blob.is_contiguous() else corpus.blob.contiguous()
+        if cutoffs is None:
+            g = torch.Generator().manual_seed(int(seed))
+            n_s = min(int(sample_rows), rows)
+            pick = (torch.randperm(rows, generator=g)[:n_s] if rows <= 1 << 24 else torch.randint(0, rows, (n_s,), generator=g)).to(dev)
+            c_of = (index.codes.view(torch.int16)[pick].to(torch.int64) & 0xFFFF).clamp(max=index.n_centroids - 1)
+            sample = blob.index_select(0, pick).float() - index.centroids.index_select(0, c_of).float()
+            cutoffs, weights = train_residual_codec(sample, bits)
+        cutoffs, weights = cutoffs.to(dev), weights.to(dev)
+        _check_codec(cutoffs, weights, bits)
+        residuals = torch.empty((rows, 16 * bits), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().msim_res_encode_docs(_lib.dtype_code(blob.dtype), _lib.ptr(blob), rows, DIM, _lib.ptr(index.codes),
+                                                 _lib.ptr(index.centroids), index.n_centroids, _lib.ptr(cutoffs), bits,
+                                                 _lib.ptr(residuals), _lib.current_stream_handle(dev))
+        _lib.check(rc, "msim_res_encode_docs")
+        return cls(index.centroids, index.codes, residuals, cutoffs, weights, index.offsets, index.clamp0, index.lengths,
+                   index.id_base, bits)
+
+    def _decode(self, row0: int, row1: int, out: torch.Tensor) -> None:
+        dev = self.device
+        with torch.cuda.device(dev):
+            rc = _lib.lib().msim_res_decode_rows(_lib.dtype_code(self.dtype), _lib.ptr(self.codes), _lib.ptr(self.residuals),
+                                                 int(self.codes.shape[0]), row0, row1, _lib.ptr(self.centroids), self.n_centroids,
+                                                 _lib.ptr(self.weights), self.bits, DIM, out.data_ptr(), _lib.current_stream_handle(dev))
+        _lib.check(rc, "msim_res_decode_rows")
+
+    def decompress(self, ids: Union[None, Sequence[int], torch.Tensor] = None) -> PackedCorpus:
+        """The decoded pages as a `PackedCorpus` (msim_res_decode_rows): all of them (same offsets, clamp0 and id_base), or the
+        listed LOCAL pages in the order given (id_base 0; only their rows are read)."""
+        dev = _require_gpu(self.device)
+        if ids is None:
+            rows = int(self.lengths.sum()) if len(self) else 0
+            blob = torch.zeros((max(rows, 1), DIM), dtype=self.dtype, device=dev)
+            self._decode(0, rows, blob)
+            clamp0 = self.clamp0.clone() if self.clamp0 is not None else None
+            return PackedCorpus(blob=blob, offsets=self.offsets.clone(), clamp0=clamp0, lengths=self.lengths.clone(),
+                                id_base=self.id_base)
+        pages = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else list(ids), dtype=np.int64).reshape(-1)
+        n = len(self)
+        if pages.size and (pages.min() < 0 or pages.max() >= n):
+            raise ValueError(f"decompress takes local page indices in 0 .. {n - 1}")
+        ln = self.lengths.numpy().astype(np.int64, copy=False)
+        start = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(ln, out=start[1:])
+        sel = ln[pages]
+        off = np.zeros(pages.size + 1, dtype=np.int64)
+        np.cumsum(sel, out=off[1:])
+        blob = torch.zeros((max(int(off[-1]), 1), DIM), dtype=self.dtype, device=dev)
+        for i, p in enumerate(pages):
+            if sel[i]:
+                self._decode(int(start[p]), int(start[p + 1]), blob[int(off[i]):])
+        clamp0 = self.clamp0[torch.from_numpy(pages).to(dev)] if self.clamp0 is not None else None
+        return PackedCorpus(blob=blob, offsets=torch.from_numpy(off.astype(np.int32)).to(dev), clamp0=clamp0,
+                            lengths=torch.from_numpy(sel.copy()), id_base=0)
+
+
+def residual_rerank_scores(queries, rc: ResidualCorpus, candidates: torch.Tensor, *,
+                           out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MaxSim of listed candidates against the compressed pages (include/maxsim.h: msim_res_candidates): (scores fp32 [n_q, m], ids
+    int64 [n_q, m]) with the signature, the query forms and the checks of `rerank_scores`.  Entry (q, j) has the bits
+    `rerank_scores(queries, rc.decompress(), candidates)` gives; an id of -1 or outside [id_base, id_base + len(rc)) comes back as
+    (-inf, -1).  bfloat16 / float16, width 128, queries of at most 128 tokens (NotImplementedError otherwise).  Given a
+    `PackedQueries` it never synchronises with the host and is hipGraph-capturable."""
+    if not isinstance(rc, ResidualCorpus):
+        raise ValueError("rc must be a ResidualCorpus")
+    dev = _require_gpu(rc.device)
+    q_dtype, dim = _query_format(queries)
+    if q_dtype != rc.dtype:
+        raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {rc.dtype}")
+    if q_dtype not in (torch.bfloat16, torch.float16) or dim != DIM:
+        raise NotImplementedError(f"the residual rerank takes bfloat16 / float16 embeddings of width {DIM} (got {q_dtype}, width {dim})")
+    if not isinstance(queries, PackedQueries):
+        dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+        queries = pack_queries(queries, dev, layout="flat", compact=not dense_on_device)
+    if queries.device != dev:
+        raise ValueError("queries and corpus live on different devices")
+    n_q = len(queries)
+    if (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2
+            or candidates.shape[0] != n_q or candidates.device != dev):
+        raise ValueError(f"candidates must be an int64 [n_q={n_q}, m] tensor on {dev}")
+    if (candidates.shape[1] > 1 and candidates.stride(1) != 1) or (n_q > 1 and candidates.stride(0) < candidates.shape[1]):
+        candidates = candidates.contiguous()          # e.g. one shared list broadcast to every query (row stride 0)
+    m = int(candidates.shape[1])
+    ld_cand = candidates.stride(0) if n_q > 1 else max(m, 1)
+    if out is None:
+        out = torch.empty((n_q, m), dtype=torch.float32, device=dev)
+    elif out.shape != (n_q, m) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous fp32 [n_q, m] tensor on the corpus' device")
+    ids = torch.empty((n_q, m), dtype=torch.int64, device=dev)
+    L = _lib.lib()
+    n = len(rc)
+    tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
+    with torch.cuda.device(dev):
+        nbytes = int(L.msim_res_candidates_workspace_bytes(n_q, m, n))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        rcode = L.msim_res_candidates(_lib.dtype_code(q_dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets),
+                                      queries.offsets_host.data_ptr(), n_q, _lib.ptr(rc.codes), _lib.ptr(rc.residuals),
+                                      _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets),
+                                      _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM, _lib.ptr(candidates), m, ld_cand,
+                                      int(rc.id_base), _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.ptr(ws),
+                                      _lib.current_stream_handle(dev))
+    _lib.check(rcode, "msim_res_candidates")
+    return out, ids

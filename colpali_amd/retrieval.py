@@ -26,6 +26,7 @@ from .group import SELECT_MAX_M, PageGroups, group_reduce, group_select
 from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
+from .residual import ResidualCorpus, residual_rerank_scores
 from .scoring import _require_gpu, maxsim_scores
 
 
@@ -197,7 +198,16 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
     (-inf, -1); an id listed twice in a row is scored twice and may appear twice.
     out: the fp32 [n_q, m] score tensor (k=None) or the (scores, ids) pair `topk` writes (k set).
     Asynchronous on torch's current stream; with a `PackedQueries` the call is hipGraph-capturable (no host synchronisation, no
-    allocation inside the library call)."""
+    allocation inside the library call).
+    `corpus` may be a `ResidualCorpus`: the listed pages are then scored straight from their compressed rows
+    (`residual_rerank_scores`; width 128, no `ref_rounding`), with the bits `rerank` gives over `corpus.decompress()`."""
+    if isinstance(corpus, ResidualCorpus):
+        if ref_rounding:
+            raise NotImplementedError("ref_rounding over a ResidualCorpus: the residual rerank has no reference-rounding form")
+        if k is None:
+            return residual_rerank_scores(queries, corpus, candidates, out=out)[0]
+        scores, ids = residual_rerank_scores(queries, corpus, candidates)
+        return topk(scores, k, 0, ids, out=out)
     if k is None:
         return rerank_scores(queries, corpus, candidates, ref_rounding=ref_rounding, out=out)[0]
     scores, ids = rerank_scores(queries, corpus, candidates, ref_rounding=ref_rounding)
@@ -205,7 +215,10 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 
 
 class ShardedRetriever:
-    """One instance per process/GPU; holds this rank's resident shard of the corpus."""
+    """One instance per process/GPU; holds this rank's resident shard of the corpus.  The shard may be a `ResidualCorpus`: the
+    default `rerank_fn` is then `residual_rerank_scores` and `search(candidates=)` / `search(prefilter=, n_candidates=)` work as over
+    a `PackedCorpus` (`prefilter=shard.index`, or any other index over the same pages); everything that scans, reads or returns
+    full-precision rows -- the full scan, `filter=`, `group_by=`, `align`, `mine` -- raises NotImplementedError."""
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
@@ -213,6 +226,8 @@ class ShardedRetriever:
                  int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
                  filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
+        if isinstance(shard, ResidualCorpus) and rerank_fn is rerank_scores:
+            rerank_fn = residual_rerank_scores
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
@@ -302,6 +317,11 @@ class ShardedRetriever:
         and a `PackedQueries` the call is hipGraph-capturable."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
+        if isinstance(self.shard, ResidualCorpus):
+            if filter is not None or group_by is not None:
+                self._no_rows("search(filter=) and search(group_by=)")
+            if candidates is None and prefilter is None:
+                self._no_rows("the full scan")
         groups = self._check_groups(group_by, k)
         if filter is not None:
             return self._search_filtered(queries, k, compact, candidates, prefilter, n_candidates, filter, filter_route, groups)
@@ -317,6 +337,11 @@ class ShardedRetriever:
             return self._group_scan(scores, k, groups)
         return shard_topk(scores, k, self.shard.id_base, self.world, self.dist, self.group, self._select,
                           force_collective=self.force_collective)
+
+    def _no_rows(self, what: str):
+        raise NotImplementedError(f"{what} over a ResidualCorpus: the shard keeps no full-precision rows and only candidate lists are "
+                                  "scored from the compressed ones -- use search(candidates=) or search(prefilter=shard.index, "
+                                  "n_candidates=), or shard.decompress() for a PackedCorpus")
 
     # ------------------------------------------------------------------------------------------------- document-level search
     def _check_groups(self, groups, k) -> Optional[PageGroups]:
@@ -395,6 +420,8 @@ class ShardedRetriever:
         world > 1 one element-wise MAX all-reduce of (best_sim, best_row, ids) follows: a rank that does not hold an id contributes
         (-inf, -1, -1), so every rank ends up with the holder's result (best_row is relative to the page, whichever rank holds it).
         `maps=True` is for a single shard: the maps of a sharded corpus stay on the rank that holds the page (ValueError)."""
+        if isinstance(self.shard, ResidualCorpus):
+            self._no_rows("align")
         if maps and self.world > 1:
             raise ValueError("maps=True with world > 1: similarity maps are made by the rank that holds the page; call align() on "
                              "its shard")
@@ -416,6 +443,8 @@ class ShardedRetriever:
         makes that the global bound of the `max_ratio` rule, each rank masks and selects its best `skip_top + n_neg` locally, and the
         all-gather + merge of `search` runs over those; the `skip_top` window is cut after the merge, so the answer does not depend
         on the number of shards.  `alive`: this shard's uint8 tombstones.  Queries are packed as `search` packs them."""
+        if isinstance(self.shard, ResidualCorpus):
+            self._no_rows("mine")
         n_neg, skip_top, max_ratio = check_mine_args(n_neg, skip_top, max_ratio)
         if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
@@ -521,7 +550,7 @@ class ShardedRetriever:
                 raise ValueError("prefilter= needs n_candidates >= 1")
         stage1 = (self._fde_score if isinstance(prefilter, FdeIndex) else self._int8_score if isinstance(prefilter, Int8Index)
                   else self._centroid_score if isinstance(prefilter, CentroidIndex) else self._score)
-        uses_kernels = self._rerank is rerank_scores or (prefilter is not None and
+        uses_kernels = self._rerank in (rerank_scores, residual_rerank_scores) or (prefilter is not None and
                                                          stage1 in (maxsim_scores, fde_scores, int8_scores, centroid_scores))
         if uses_kernels and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
@@ -569,17 +598,52 @@ class ExactMaxSimIndex:
         return [[(int(i), float(s)) for s, i in zip(row_s, row_i) if i >= 0] for row_s, row_i in zip(top_s, top_i)]
 
 
-def create_plaid_index(ps, device=None) -> ExactMaxSimIndex:
+class ResidualMaxSimIndex:
+    """What `create_plaid_index(nbits=2 | 4)` returns: a `ResidualCorpus` -- centroid codes plus a few residual bits per dimension,
+    no full-precision embedding, as in the FastPlaid index the reference builds -- behind the same `search(queries_embeddings,
+    top_k)` interface and result shape as `ExactMaxSimIndex`.  A search is approximate in the way PLAID is: centroid stage 1
+    (`centroid_scores`) keeps the top `min(n_candidates, n)` pages, the residual rerank scores them from the compressed rows, the
+    deterministic (score desc, id asc) top-k follows."""
+
+    def __init__(self, corpus: ResidualCorpus, n_candidates: int = 1024, world: int = 1, rank: int = 0, dist=None, group=None):
+        if int(n_candidates) < 1:
+            raise ValueError("n_candidates must be >= 1")
+        self.n_candidates = int(n_candidates)
+        self.retriever = ShardedRetriever(corpus, world, rank, dist, group)
+
+    def search(self, queries_embeddings: torch.Tensor, top_k: int = 10):
+        rc = self.retriever.shard
+        q = queries_embeddings.to(device=rc.device, dtype=rc.dtype).contiguous()
+        if q.dim() != 3:
+            raise ValueError("queries_embeddings must be [n_queries, query_length, dim]")
+        # one shard: no more candidates than pages (with world > 1 the list is global, and a short one is padded with -1)
+        m = self.n_candidates if self.retriever.world > 1 else max(min(self.n_candidates, len(rc)), 1)
+        top_s, top_i = self.retriever.search(q, k=top_k, compact=True, prefilter=rc.index, n_candidates=m)
+        top_s, top_i = top_s.cpu().tolist(), top_i.cpu().tolist()
+        return [[(int(i), float(s)) for s, i in zip(row_s, row_i) if i >= 0] for row_s, row_i in zip(top_s, top_i)]
+
+
+def create_plaid_index(ps, device=None, *, nbits: Optional[int] = None, n_centroids: int = 1024, n_candidates: int = 1024):
     """Drop-in for `BaseVisualRetrieverProcessor.create_plaid_index` (processing_utils.py:226-244): same arguments; builds
     the resident packed corpus instead of a FastPlaid index (see ExactMaxSimIndex).  Like the reference -- which hands
-    FastPlaid the unpadded pages -- no block zero-padding semantics apply here (`batch_size=None`)."""
+    FastPlaid the unpadded pages -- no block zero-padding semantics apply here (`batch_size=None`).
+    `nbits=None` (the default) is that exact index.  `nbits` = 2 or 4 builds what FastPlaid builds instead, a compressed index:
+    the pages are packed, `n_centroids` centroids and the residual codec are trained on them, a `ResidualCorpus` is built, the
+    full-precision pack is dropped, and a `ResidualMaxSimIndex` (stage 1 keeps `n_candidates` pages) comes back."""
     from .corpus import pack_passages
     from .scoring import _require_gpu, get_torch_device
 
+    if nbits is not None and (isinstance(nbits, bool) or nbits not in (2, 4)):
+        raise ValueError(f"nbits must be None, 2 or 4 (got {nbits!r})")
     if len(ps) == 0:
         raise ValueError("No passages provided")
     dev = _require_gpu(device or get_torch_device("auto"))
-    return ExactMaxSimIndex(pack_passages(list(ps) if not isinstance(ps, torch.Tensor) else ps, dev, batch_size=None))
+    corpus = pack_passages(list(ps) if not isinstance(ps, torch.Tensor) else ps, dev, batch_size=None)
+    if nbits is None:
+        return ExactMaxSimIndex(corpus)
+    rc = ResidualCorpus.build(corpus, bits=int(nbits), n_centroids=n_centroids)
+    del corpus                                    # the compressed shard is all that stays resident
+    return ResidualMaxSimIndex(rc, n_candidates)
 
 
 def get_topk_plaid(qs, plaid_index, k: int = 10, batch_size: int = 128, device=None):

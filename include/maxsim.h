@@ -688,6 +688,51 @@ int msim_cent_scores(const void *table, const int32_t *q_off, int n_q, int64_t q
                      float *scores, int64_t ld_scores, void *stream);
 
 /*
+ * RESIDUAL-COMPRESSED CORPUS (residual_codec.hip; additions to ABI 22): PLAID's second half.  Every corpus row is its centroid code
+ * (msim_cent_encode_docs) plus `bits` of residual per dimension, and candidate lists are reranked from those rows alone: no
+ * full-precision embedding is kept.  Width 128, bf16 / f16, bits 2 or 4, K as for the centroid index (MSIM_EUNSUPPORTED / MSIM_EINVAL
+ * as there).  34 / 66 bytes per row instead of 256.
+ *   Code.  For row x with code c: e_k = fl32(float(x_k) - float(C[c]_k)), one fp32 subtraction per dimension; the bucket b_k is the
+ *     number of cutoffs t with t <= e_k (a value equal to a cutoff goes to the upper bucket).  cutoffs: fp32 [2^bits - 1],
+ *     non-decreasing.
+ *   Packing.  residuals: uint8 [rows, 16 * bits]; dimension k occupies bits [k * bits, k * bits + bits) of its row read as a
+ *     little-endian bit string (bit i = bit i % 8 of byte i / 8).  Rows are 32 / 64 bytes and 16-byte aligned; the 8 consecutive k
+ *     one lane feeds an MFMA are one 16- / 32-bit little-endian field.
+ *   Decode.  xhat_k = round_to_dtype(float(C[c]_k) + weights[b_k]): one fp32 addition, ONE rounding to nearest even to the corpus
+ *     dtype, and no renormalisation (ColBERTv2's Python path renormalises the decoded row; PLAID's kernels do not, and neither does
+ *     this).  weights: fp32 [2^bits].
+ * msim_res_encode_docs: rows D [n_rows, 128] and their codes -> residuals, one pass (a row is read once; its centroid row comes
+ *   through L2).  A row whose code is >= K is written as all-zero buckets and its code stays as it is, so its page scores NaN below,
+ *   as in msim_cent_scores: such a code never becomes an address.
+ * msim_res_decode_rows: xhat of rows row0 .. row1 - 1 (0 <= row0 <= row1 <= n_rows) -> out [row1 - row0, 128] in the corpus dtype;
+ *   rows outside the range are not touched.  A row whose code is >= K decodes to NaN.
+ * msim_res_candidates: msim_fwd_candidates' contract over the compressed rows -- cand [n_q, m] int64 GLOBAL ids with row stride
+ *   ld_cand >= m, page c has id id_base + c; an id of -1 or outside [id_base, id_base + n_d) is (-inf, -1) and reads nothing; a
+ *   query of 0 tokens scores 0; queries of 0 .. 128 tokens in the flat layout (MSIM_EUNSUPPORTED beyond); d_clamp0 as msim_fwd; a
+ *   duplicate id is scored once per occurrence.  out_scores[q, j] has exactly the bits msim_fwd_candidates (flags 0) gives the same
+ *   query against the page decoded by msim_res_decode_rows: the same fp32 MFMA chain over the four 32-wide k steps with the same
+ *   k-to-lane mapping, an exact maximum over the page's rows, the same token sum.  The page is decoded slab by slab in registers
+ *   into LDS and never written to memory.  A page with a code >= K, or whose offsets fall outside 0 <= d_off[c] <= d_off[c + 1] <=
+ *   d_rows, scores NaN (checked before anything becomes an address; other pages are not affected); a device q_off that disagrees
+ *   with q_off_host makes every score of the call NaN.  One wave scores one entry.
+ *   workspace: msim_res_candidates_workspace_bytes(n_q, m, n_d) bytes (0 when there is no entry), 16-byte aligned, initialised by
+ *   the call (by a kernel); it does not depend on the number of rows.  After the call its first int32 is 0, or 1 for a broken q_off.
+ * MSIM_EINVAL for a negative size, a null or misaligned pointer (rows, centroids, residuals, out, workspace: 16 bytes), ld < m.  A
+ * call with nothing to do (n_rows == 0, row0 == row1, n_q == 0, m == 0) returns 0 before it looks at a pointer.  Asynchronous on
+ * `stream`, no allocation, no host synchronisation: hipGraph-capturable.
+ */
+int msim_res_encode_docs(int dtype, const void *D, int64_t n_rows, int dim, const uint16_t *codes, const void *C, int K,
+                         const float *cutoffs, int bits, uint8_t *residuals, void *stream);
+int msim_res_decode_rows(int dtype, const uint16_t *codes, const uint8_t *residuals, int64_t n_rows, int64_t row0, int64_t row1,
+                         const void *C, int K, const float *weights, int bits, int dim, void *out, void *stream);
+size_t msim_res_candidates_workspace_bytes(int n_q, int m, int n_d);
+int msim_res_candidates(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const uint16_t *codes,
+                        const uint8_t *residuals, const void *C, int K, const float *weights, int bits, const int32_t *d_off,
+                        const uint8_t *d_clamp0 /* or NULL */, int n_d, int64_t d_rows, int dim, const int64_t *cand, int m,
+                        int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids /* or NULL */,
+                        void *workspace, void *stream);
+
+/*
  * LIVE CORPUS (live_corpus.hip; additions to ABI 22): a packed corpus whose pages can be deleted and whose rows can be handed
  * back, without a change to any scorer.  A page's slot c never moves (its id stays id_base + c); `alive` uint8 [n_slots] is the
  * tombstone mask (0 = deleted).

@@ -1,0 +1,151 @@
+"""The residual-compressed corpus (msim_res_*, colpali_amd.ResidualCorpus) on the headline shard; one JSON object on stdout (not part
+of bench.py).
+
+    python tools/bench_residual.py [--out FILE] [--steps 10 --warmup 3] [--docs 125000 --doc-len 1024] [--legs build,rerank,two_stage,recall]
+
+Legs, each timed with device events after a warm-up, for 2 and 4 residual bits (K = 1024 centroids):
+  * build: `train_residual_codec` on the residuals of 2^18 sampled rows, and `ResidualCorpus.build` with a given index, cutoffs
+    and weights (the encode pass alone); `nbytes` beside the bf16 corpus's.
+  * rerank: `residual_rerank_scores` (msim_res_candidates) at 1000 x 32 x m = 100 and at 4 x 32 x m = 1000, uniform and clustered
+    lists (tools/bench_rerank.py; a cluster of 10 queries draws its lists from a pool of max(200, 2 m) pages), beside `rerank` over
+    `rc.decompress()` on the SAME lists in the same run, and whether the two agree bit for bit.  The compressed rerank reads 34 / 66 bytes per row from HBM but 256 bytes per row of centroids from L2, and it
+    reads a page once per entry where K1c reads it once per group of queries: which one is faster is what this leg is for.
+  * two_stage: ShardedRetriever(rc).search(prefilter=rc.index, n_candidates=m) at 1000 x 32 for m in {100, 400, 1000}, beside the
+    same search over the bf16 shard with the same centroid index.
+  * recall: recall@10 and the mean absolute score error of the two-stage search over the compressed shard against the exact search
+    on the planted 10 000-page set of tools/bench_fde.py:planted_pages (centroids and codec trained on that set).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from bench_legs.common import make_queries, make_shard  # noqa: E402
+from tools.bench_fde import planted_pages  # noqa: E402
+from tools.bench_rerank import clustered_candidates, timed, uniform_candidates  # noqa: E402
+
+MS = (100, 400, 1000)
+BITS = (2, 4)
+K = 1024
+SHAPES = ((1000, 100), (4, 1000))           # (queries, list length)
+
+
+def rerank_leg(amd, rc, dec, n_q, m, q_len, dev, steps, warmup):
+    pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
+    out = {}
+    lists = (("uniform", uniform_candidates(n_q, len(rc), m, dev, 7)),
+             ("clustered", clustered_candidates(n_q, len(rc), m, dev, 8, pool=max(200, 2 * m))))
+    for name, cand in lists:
+        scores = torch.empty((n_q, m), dtype=torch.float32, device=dev)
+        leg = {"residual": timed(lambda: amd.residual_rerank_scores(pq, rc, cand, out=scores), steps, warmup),
+               "bf16_decompressed": timed(lambda: amd.rerank(pq, dec, cand, out=scores), steps, warmup)}
+        leg["residual_over_bf16"] = leg["residual"]["median_ms"] / leg["bf16_decompressed"]["median_ms"]
+        got = amd.residual_rerank_scores(pq, rc, cand)[0]
+        want = amd.rerank(pq, dec, cand)
+        torch.cuda.synchronize()
+        leg["bit_identical"] = bool(torch.equal(got.view(torch.int32), want.view(torch.int32)))
+        rows = int(rc.lengths[0]) * n_q * m
+        leg["residual_row_bytes_per_s"] = rows * (2 + 16 * rc.bits) / (leg["residual"]["median_ms"] * 1e-3)
+        out[name] = leg
+    return out
+
+
+def recall_leg(amd, dev, n_docs, k=10):
+    pages, q = planted_pages(dev, n_docs=n_docs)
+    full = amd.pack_passages(pages, dev, batch_size=None)
+    del pages
+    pq = amd.pack_queries(q, dev, compact=False)
+    exact_s, exact_i = amd.ShardedRetriever(full).search(pq, k=k)
+    index = amd.CentroidIndex.build(full, n_centroids=K)
+    out = {"docs": n_docs, "queries": len(pq), "k": k, "n_centroids": K}
+    for bits in BITS:
+        rc = amd.ResidualCorpus.build(full, index=index, bits=bits)
+        r = amd.ShardedRetriever(rc)
+        leg = {}
+        for m in MS:
+            s, i = r.search(pq, k=k, prefilter=rc.index, n_candidates=m)
+            leg[str(m)] = sum(len(set(a) & set(b)) for a, b in zip(exact_i.tolist(), i.tolist())) / (len(pq) * k)
+        # the codec's own error: the exact top-k pages rescored from the compressed rows
+        approx = amd.rerank(pq, rc, exact_i)
+        ok = exact_i >= 0
+        leg["mean_abs_score_error"] = float((approx - exact_s)[ok].abs().mean())
+        leg["mean_exact_score"] = float(exact_s[ok].mean())
+        out[f"bits{bits}"] = leg
+        del rc, r
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--docs", type=int, default=125_000)
+    ap.add_argument("--doc-len", type=int, default=1024)
+    ap.add_argument("--q-len", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--legs", default="build,rerank,two_stage,recall")
+    ap.add_argument("--recall-docs", type=int, default=10_000)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_residual.py needs an MI355X (there is no CPU fallback)")
+    import colpali_amd as amd
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    amd._lib.lib()
+    legs = set(args.legs.split(","))
+    t0 = time.perf_counter()
+    res = {"tool": "bench_residual", "docs": args.docs, "doc_len": args.doc_len, "q_len": args.q_len, "n_centroids": K}
+    if legs & {"build", "rerank", "two_stage"}:
+        corpus = make_shard(args.docs, args.doc_len, dev, seed=1234)
+        index = amd.CentroidIndex.build(corpus, n_centroids=K)
+        res["corpus_bytes"] = corpus.nbytes
+        res["index_bytes"] = index.nbytes
+        for bits in BITS:
+            rc = amd.ResidualCorpus.build(corpus, index=index, bits=bits)
+            leg = {"nbytes": rc.nbytes, "bytes_per_row": rc.nbytes / max(int(rc.codes.shape[0]), 1)}
+            if "build" in legs:
+                g = torch.Generator().manual_seed(0)
+                pick = torch.randperm(int(corpus.blob.shape[0]), generator=g)[:1 << 18].to(dev)
+                sample = (corpus.blob[pick].float() - index.centroids[(index.codes.view(torch.int16)[pick].to(torch.int64) & 0xFFFF)].float())
+                leg["build"] = {"train_codec": timed(lambda: amd.train_residual_codec(sample, bits), 2, 1),
+                                "encode": timed(lambda: amd.ResidualCorpus.build(corpus, index=index, bits=bits, cutoffs=rc.cutoffs,
+                                                                                 weights=rc.weights), 2, 1)}
+                del sample, pick
+            if "rerank" in legs:
+                dec = rc.decompress()
+                leg["decompress"] = timed(lambda: rc.decompress(), 2, 1)
+                leg["rerank"] = {f"{n_q}x{m}": rerank_leg(amd, rc, dec, n_q, m, args.q_len, dev, args.steps, args.warmup) for n_q, m in SHAPES}
+                del dec
+            if "two_stage" in legs:
+                pq = amd.pack_queries(make_queries(1000, args.q_len, dev, seed=99), dev, compact=False)
+                r_c, r_b = amd.ShardedRetriever(rc), amd.ShardedRetriever(corpus)
+                leg["two_stage"] = {str(m): {"residual": timed(lambda: r_c.search(pq, k=10, prefilter=rc.index, n_candidates=m), args.steps,
+                                                               args.warmup),
+                                             "bf16": timed(lambda: r_b.search(pq, k=10, prefilter=index, n_candidates=m), args.steps,
+                                                           args.warmup)} for m in MS}
+            res[f"bits{bits}"] = leg
+            del rc
+            torch.cuda.empty_cache()
+        del corpus, index
+        torch.cuda.empty_cache()
+    if "recall" in legs:
+        res["recall"] = recall_leg(amd, dev, args.recall_docs)
+    res["wall_s"] = time.perf_counter() - t0
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
