@@ -20,6 +20,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      centroid interaction): a first stage for prefilter= at 2 bytes per row
   * ResidualCorpus / residual_rerank_scores -- PLAID's second half: the shard itself as centroid codes + 2 / 4 residual bits per
                                      dimension (34 / 66 bytes per row instead of 256), candidate lists reranked straight from them
+  * residual_scores               -- the full scan of such a shard, a page decoded once per group of queries: the score matrix
+                                     behind ShardedRetriever(rc, score_fn=residual_scores) -- search, filter=, group_by=, mine
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
@@ -40,7 +42,7 @@ from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPai
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
 from .patch import patch_colpali_engine, unpatch_colpali_engine
-from .residual import ResidualCorpus, residual_rerank_scores, train_residual_codec
+from .residual import ResidualCorpus, residual_rerank_scores, residual_scores, train_residual_codec
 from .retrieval import (ExactMaxSimIndex, ResidualMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered, rerank, shard_range,
                         shard_topk, topk)
 from .scoring import (get_similarity_maps_from_embeddings, get_torch_device, maxsim_scores, score_multi_vector,
@@ -66,6 +68,7 @@ __all__ = [
     "ResidualCorpus",
     "ResidualMaxSimIndex",
     "residual_rerank_scores",
+    "residual_scores",
     "train_residual_codec",
     "LiveCorpus",
     "PageFilter",

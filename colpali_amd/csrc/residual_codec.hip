@@ -21,7 +21,8 @@
 //                          (1 register: lane r holds row r's code, handed round by ds_bpermute); with more units the 40 registers
 //                          do not fit next to the query and the loads are issued at the top of the slab.  Rows past the page's end
 //                          in the last slab re-read the page's last row and are masked to -inf behind the MFMAs (slab_units' tail
-//                          form), never zero-filled.
+//                          form), never zero-filled.  The page loop (res_page_max) is shared with the full scan
+//                          (residual_scan.hip), which keeps a group of queries resident and walks the shard's pages.
 //   LDS per wave: 8 KiB slab + the per-token max table (kStreamTokBytes) + 64 B of weights = 10 368 B; 41 472 B per workgroup of four
 //   waves.  Registers: up to 8 units x 16 query VGPRs + 32 operand + 32 accumulator (+ 40 in flight): launch bounds of two waves per
 //   SIMD, 256 VGPRs; 4 VGPRs of per-lane constants sit in scratch, stored once at kernel start and reloaded outside the slab loops.
@@ -133,17 +134,13 @@ struct ResPage {                                    // one checked page: rows r0
     int len;
 };
 
-// the score of one entry: the query's NU units against the page, decoded slab by slab.  Returns in lanes 0 .. 7; lane 0 stores.
+// one page against NU resident query units, decoded slab by slab: mx[u] = the running maxima of unit u over this lane's rows
+// (-inf for a page without rows).  Shared by the rerank (res_entry) and the scan (residual_scan.hip: res_scan_group).
 template <int NU, bool F16, int BITS>
-__device__ __forceinline__ float res_entry(const uint16_t *__restrict__ Qt, int qs, int qe, const uint16_t *__restrict__ codes,
-                                           const uint8_t *__restrict__ res, const uint16_t *__restrict__ C, int K, const ResPage &pg,
-                                           bool clamp, bool &bad, char *slab, char *tokmax, const float *wtab,
-                                           const int (&rd_off)[2][kKSteps16], int lane) {
+__device__ __forceinline__ void res_page_max(float (&mx)[NU], const QueryUnit (&qu)[NU], const uint16_t *__restrict__ codes,
+                                             const uint8_t *__restrict__ res, const uint16_t *__restrict__ C, int K, const ResPage &pg,
+                                             bool &bad, char *slab, const float *wtab, const int (&rd_off)[2][kKSteps16], int lane) {
     const int l16 = lane & 15, l4 = lane >> 4;
-    QueryUnit qu[NU];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) load_query_unit(qu[u], Qt, qs + u * kUnitTok, qe, lane, true);
-    float mx[NU];
 #pragma unroll
     for (int u = 0; u < NU; ++u) mx[u] = -INFINITY;
 
@@ -206,6 +203,19 @@ __device__ __forceinline__ float res_entry(const uint16_t *__restrict__ Qt, int 
     const int n_full = len / kSlabRows, rem = len - n_full * kSlabRows;
     for (int s = 0; s < n_full; ++s) body(std::false_type{}, s, kSlabRows);
     if (rem > 0) body(std::true_type{}, n_full, rem);
+}
+
+// the score of one entry: the query's NU units against the page.  Returns in lanes 0 .. 7; lane 0 stores.
+template <int NU, bool F16, int BITS>
+__device__ __forceinline__ float res_entry(const uint16_t *__restrict__ Qt, int qs, int qe, const uint16_t *__restrict__ codes,
+                                           const uint8_t *__restrict__ res, const uint16_t *__restrict__ C, int K, const ResPage &pg,
+                                           bool clamp, bool &bad, char *slab, char *tokmax, const float *wtab,
+                                           const int (&rd_off)[2][kKSteps16], int lane) {
+    QueryUnit qu[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) load_query_unit(qu[u], Qt, qs + u * kUnitTok, qe, lane, true);
+    float mx[NU];
+    res_page_max<NU, F16, BITS>(mx, qu, codes, res, C, K, pg, bad, slab, wtab, rd_off, lane);
 
 #pragma unroll
     for (int u = 0; u < NU; ++u) store_token_max(tokmax, u, mx[u], lane);

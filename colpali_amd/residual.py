@@ -13,6 +13,11 @@ msim_res_*, colpali_amd/csrc/residual_codec.hip):
 registers into LDS and never written to memory); every score has the bits `rerank_scores` gives the same query against
 `rc.decompress()`.  Stage 1 is `rc.index`, the `CentroidIndex` view over the same codes:
 `ShardedRetriever(rc).search(q, k, prefilter=rc.index, n_candidates=m)`.
+
+`residual_scores` is the full scan of such a shard (a page is decoded once per group of up to 8 queries, never written to memory):
+the `[n_q, len(rc)]` matrix with the bits of `maxsim_scores(queries, rc.decompress())`.  It decodes every row of the shard, so the
+retriever only scans on request: `ShardedRetriever(rc, score_fn=residual_scores)` opens the full scan, `filter=`, `group_by=` and
+`mine`.
 """
 from __future__ import annotations
 
@@ -215,13 +220,8 @@ class ResidualCorpus:
                             lengths=torch.from_numpy(sel.copy()), id_base=0)
 
 
-def residual_rerank_scores(queries, rc: ResidualCorpus, candidates: torch.Tensor, *,
-                           out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """MaxSim of listed candidates against the compressed pages (include/maxsim.h: msim_res_candidates): (scores fp32 [n_q, m], ids
-    int64 [n_q, m]) with the signature, the query forms and the checks of `rerank_scores`.  Entry (q, j) has the bits
-    `rerank_scores(queries, rc.decompress(), candidates)` gives; an id of -1 or outside [id_base, id_base + len(rc)) comes back as
-    (-inf, -1).  bfloat16 / float16, width 128, queries of at most 128 tokens (NotImplementedError otherwise).  Given a
-    `PackedQueries` it never synchronises with the host and is hipGraph-capturable."""
+def _flat_queries(queries, rc: ResidualCorpus, what: str) -> Tuple[torch.device, PackedQueries]:
+    """the query forms and checks the residual kernels share: a `PackedQueries`, a host list, or a dense device box"""
     if not isinstance(rc, ResidualCorpus):
         raise ValueError("rc must be a ResidualCorpus")
     dev = _require_gpu(rc.device)
@@ -229,12 +229,53 @@ def residual_rerank_scores(queries, rc: ResidualCorpus, candidates: torch.Tensor
     if q_dtype != rc.dtype:
         raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {rc.dtype}")
     if q_dtype not in (torch.bfloat16, torch.float16) or dim != DIM:
-        raise NotImplementedError(f"the residual rerank takes bfloat16 / float16 embeddings of width {DIM} (got {q_dtype}, width {dim})")
+        raise NotImplementedError(f"the residual {what} takes bfloat16 / float16 embeddings of width {DIM} (got {q_dtype}, width {dim})")
     if not isinstance(queries, PackedQueries):
         dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
         queries = pack_queries(queries, dev, layout="flat", compact=not dense_on_device)
     if queries.device != dev:
         raise ValueError("queries and corpus live on different devices")
+    return dev, queries
+
+
+def residual_scores(queries, rc: ResidualCorpus, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaxSim of every query against every page of the compressed shard (include/maxsim.h: msim_res_scores): fp32 [n_q, len(rc)],
+    the counterpart of `maxsim_scores` over a `PackedCorpus`.  Entry (q, c) has the bits `maxsim_scores(queries, rc.decompress())`
+    gives; every row of the shard is decoded, once per group of up to 8 queries (128 tokens).  The query forms and checks of
+    `residual_rerank_scores`: a `PackedQueries`, a host list or a dense device box; RuntimeError on a dtype mismatch;
+    NotImplementedError for fp32, a width other than 128 or a query over 128 tokens.  `out`: fp32 [n_q, n] with unit inner stride on
+    the corpus' device -- it may be a column slice of a wider matrix, whose other columns are not touched.  Given a `PackedQueries`
+    it never synchronises with the host and is hipGraph-capturable."""
+    dev, queries = _flat_queries(queries, rc, "scan")
+    n_q, n = len(queries), len(rc)
+    if out is None:
+        out = torch.empty((n_q, n), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.shape != (n_q, n) or out.dtype != torch.float32 or out.device != dev
+          or (n > 1 and out.stride(1) != 1) or (n_q > 1 and out.stride(0) < n)):
+        raise ValueError(f"out must be an fp32 [n_q={n_q}, n={n}] tensor with unit inner stride on the corpus' device")
+    ld = out.stride(0) if n_q > 1 else max(n, 1)
+    L = _lib.lib()
+    tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
+    with torch.cuda.device(dev):
+        nbytes = int(L.msim_res_scores_workspace_bytes(n_q, n))
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        rcode = L.msim_res_scores(_lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets), queries.offsets_host.data_ptr(),
+                                  n_q, _lib.ptr(rc.codes), _lib.ptr(rc.residuals), _lib.ptr(rc.centroids), rc.n_centroids,
+                                  _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets), _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM,
+                                  _lib.ptr(out), max(ld, 1), _lib.ptr(ws), _lib.current_stream_handle(dev))
+    _lib.check(rcode, "msim_res_scores")
+    return out
+
+
+def residual_rerank_scores(queries, rc: ResidualCorpus, candidates: torch.Tensor, *,
+                           out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MaxSim of listed candidates against the compressed pages (include/maxsim.h: msim_res_candidates): (scores fp32 [n_q, m], ids
+    int64 [n_q, m]) with the signature, the query forms and the checks of `rerank_scores`.  Entry (q, j) has the bits
+    `rerank_scores(queries, rc.decompress(), candidates)` gives; an id of -1 or outside [id_base, id_base + len(rc)) comes back as
+    (-inf, -1).  bfloat16 / float16, width 128, queries of at most 128 tokens (NotImplementedError otherwise).  Given a
+    `PackedQueries` it never synchronises with the host and is hipGraph-capturable."""
+    dev, queries = _flat_queries(queries, rc, "rerank")
+    q_dtype = rc.dtype
     n_q = len(queries)
     if (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2
             or candidates.shape[0] != n_q or candidates.device != dev):

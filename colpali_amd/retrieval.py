@@ -26,7 +26,7 @@ from .group import SELECT_MAX_M, PageGroups, group_reduce, group_select
 from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
-from .residual import ResidualCorpus, residual_rerank_scores
+from .residual import ResidualCorpus, residual_rerank_scores, residual_scores
 from .scoring import _require_gpu, maxsim_scores
 
 
@@ -218,7 +218,12 @@ class ShardedRetriever:
     """One instance per process/GPU; holds this rank's resident shard of the corpus.  The shard may be a `ResidualCorpus`: the
     default `rerank_fn` is then `residual_rerank_scores` and `search(candidates=)` / `search(prefilter=, n_candidates=)` work as over
     a `PackedCorpus` (`prefilter=shard.index`, or any other index over the same pages); everything that scans, reads or returns
-    full-precision rows -- the full scan, `filter=`, `group_by=`, `align`, `mine` -- raises NotImplementedError."""
+    full-precision rows -- the full scan, `filter=`, `group_by=`, `align`, `mine` -- raises NotImplementedError.  Scanning such a
+    shard decodes every row of it and is opt-in: with `score_fn=residual_scores` (or any other scorer over a `ResidualCorpus`; the
+    default `maxsim_scores` is not one) the routes that need only the score matrix or the rerank open -- the full scan, `filter=`
+    on the mask, list and auto routes (the list route runs the residual rerank), `group_by=` on every route, `filter=` with
+    `candidates=` / `prefilter=`, and `mine` -- each with the bits of the same call over `shard.decompress()`.  `align` keeps
+    raising: it returns rows."""
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
@@ -231,6 +236,8 @@ class ShardedRetriever:
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = dist, group
         self._score, self._select = score_fn, select
+        # a compressed shard is scanned on request only: a scorer of its own must be handed in (residual_scores)
+        self._res_refuses = isinstance(shard, ResidualCorpus) and score_fn is maxsim_scores
         self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
         self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
         self._int8_score = int8_score_fn  # (queries, Int8Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Int8Index>
@@ -317,7 +324,7 @@ class ShardedRetriever:
         and a `PackedQueries` the call is hipGraph-capturable."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
-        if isinstance(self.shard, ResidualCorpus):
+        if self._res_refuses:
             if filter is not None or group_by is not None:
                 self._no_rows("search(filter=) and search(group_by=)")
             if candidates is None and prefilter is None:
@@ -329,7 +336,7 @@ class ShardedRetriever:
             raise ValueError("filter_route goes with filter=")
         if candidates is not None or prefilter is not None:
             return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, groups=groups)
-        if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
+        if self._score in (maxsim_scores, residual_scores) and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
         scores = self._score(queries, self.shard)
@@ -341,7 +348,9 @@ class ShardedRetriever:
     def _no_rows(self, what: str):
         raise NotImplementedError(f"{what} over a ResidualCorpus: the shard keeps no full-precision rows and only candidate lists are "
                                   "scored from the compressed ones -- use search(candidates=) or search(prefilter=shard.index, "
-                                  "n_candidates=), or shard.decompress() for a PackedCorpus")
+                                  "n_candidates=), or shard.decompress() for a PackedCorpus; ShardedRetriever(shard, "
+                                  "score_fn=residual_scores) opts in to scanning the compressed rows (the full scan, filter=, "
+                                  "group_by= and mine; align needs rows either way)")
 
     # ------------------------------------------------------------------------------------------------- document-level search
     def _check_groups(self, groups, k) -> Optional[PageGroups]:
@@ -443,10 +452,10 @@ class ShardedRetriever:
         makes that the global bound of the `max_ratio` rule, each rank masks and selects its best `skip_top + n_neg` locally, and the
         all-gather + merge of `search` runs over those; the `skip_top` window is cut after the merge, so the answer does not depend
         on the number of shards.  `alive`: this shard's uint8 tombstones.  Queries are packed as `search` packs them."""
-        if isinstance(self.shard, ResidualCorpus):
+        if self._res_refuses:
             self._no_rows("mine")
         n_neg, skip_top, max_ratio = check_mine_args(n_neg, skip_top, max_ratio)
-        if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
+        if self._score in (maxsim_scores, residual_scores) and not isinstance(queries, PackedQueries):
             dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
             queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
         scores = self._score(queries, self.shard)
@@ -462,11 +471,17 @@ class ShardedRetriever:
             return shard_topk(s, k, id_base, self.world, self.dist, self.group, self._select, force_collective=self.force_collective)
         return select_window(masked, int(self.shard.id_base), n_neg, skip_top, shard_select)
 
+    def _shard_format(self) -> Tuple[torch.dtype, int]:
+        """(dtype, width) of the shard's pages; a residual shard stores its centroids' dtype at width 128"""
+        if isinstance(self.shard, ResidualCorpus):
+            return self.shard.dtype, 128
+        return self.shard.blob.dtype, int(self.shard.blob.shape[1])
+
     def _list_formats_fit(self, queries) -> bool:
         """what `rerank_scores` takes: bfloat16 / float16, width 128 or 320, at most 128 tokens per query (host metadata only)"""
         q_dtype, dim = _query_format(queries)
-        blob = self.shard.blob
-        if q_dtype != blob.dtype or q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or blob.shape[1] != dim:
+        s_dtype, s_dim = self._shard_format()
+        if q_dtype != s_dtype or q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or s_dim != dim:
             return False
         if isinstance(queries, PackedQueries):
             return len(queries) == 0 or int(queries.lengths.max()) <= 128
@@ -493,7 +508,7 @@ class ShardedRetriever:
                 return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt, groups)
             top_s, top_i = self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt)
         else:
-            if self._score is maxsim_scores and not isinstance(queries, PackedQueries):
+            if self._score in (maxsim_scores, residual_scores) and not isinstance(queries, PackedQueries):
                 dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
                 queries = pack_queries(queries, shard.device, compact=compact or not dense_on_device)
             n_q = len(queries)
@@ -502,9 +517,10 @@ class ShardedRetriever:
             fits = self._list_formats_fit(queries)
             if route == "list" and not fits:
                 q_dtype, dim = _query_format(queries)
+                s_dtype, s_dim = self._shard_format()
                 raise NotImplementedError(f"filter_route='list' reranks the listed pages: rerank takes bfloat16 / float16 embeddings of "
                                           f"width 128 or 320 and queries of at most 128 tokens (got {q_dtype}, width {dim}, corpus "
-                                          f"{shard.blob.dtype} of width {shard.blob.shape[1]})")
+                                          f"{s_dtype} of width {s_dim})")
             if route == "list" and groups is not None and flt.max_allowed > SELECT_MAX_M:
                 raise NotImplementedError(f"filter_route='list' with group_by: a query is allowed {flt.max_allowed} pages, group_select "
                                           f"takes lists of at most {SELECT_MAX_M}")

@@ -717,9 +717,25 @@ int msim_cent_scores(const void *table, const int32_t *q_off, int n_q, int64_t q
  *   with q_off_host makes every score of the call NaN.  One wave scores one entry.
  *   workspace: msim_res_candidates_workspace_bytes(n_q, m, n_d) bytes (0 when there is no entry), 16-byte aligned, initialised by
  *   the call (by a kernel); it does not depend on the number of rows.  After the call its first int32 is 0, or 1 for a broken q_off.
+ * msim_res_scores: the FULL SCAN of the compressed shard (residual_scan.hip) -- out_scores[q, c] for every query q and every page c,
+ *   row stride ld_scores >= n_d (columns >= n_d of a wider matrix are not written).  Bit identity: entry (q, c) has exactly the
+ *   bits msim_fwd_ragged (flags 0) gives the same query against the page decoded by msim_res_decode_rows: the same fp32 MFMA chain
+ *   over the four 32-wide k steps with the same k-to-lane mapping, an exact maximum over the page's rows, the same token sum (a
+ *   pure function of the token values and the query's length, so the bits do not depend on which queries share a wave).  A wave
+ *   holds a group of consecutive queries (at most 8 queries and 8 units of 16 tokens) and decodes a page once per group, not once
+ *   per query.  Formats as msim_res_candidates: bf16 / f16, width 128, bits 2 or 4, K a multiple of 256 in 256 .. 2048, queries
+ *   of 0 .. 128 tokens in the flat layout (MSIM_EUNSUPPORTED beyond), d_clamp0 as msim_fwd.  A query of 0 tokens scores 0; a page
+ *   of 0 rows scores what the scan of the decompressed page gives (-inf, or 0 when flagged).  A page with a code >= K, or whose
+ *   offsets fall outside 0 <= d_off[c] <= d_off[c + 1] <= d_rows, scores NaN in its column for every query with at least one token
+ *   (checked before anything becomes an address; no other column changes); a device q_off that disagrees with q_off_host makes
+ *   every score of the call NaN.
+ *   workspace: msim_res_scores_workspace_bytes(n_q, n_d) bytes (0 when n_q <= 0 or n_d <= 0), 16-byte aligned, initialised by the
+ *   call (by a kernel, not a memset node); a function of n_q alone (status words plus the query-group table), never of the row
+ *   count.  After the call its first int32 is 0, or 1 for a broken q_off.
+ *   MSIM_EINVAL also for ld_scores < n_d and for a q_off_host that does not start at 0 or decreases.  No float atomics.
  * MSIM_EINVAL for a negative size, a null or misaligned pointer (rows, centroids, residuals, out, workspace: 16 bytes), ld < m.  A
- * call with nothing to do (n_rows == 0, row0 == row1, n_q == 0, m == 0) returns 0 before it looks at a pointer.  Asynchronous on
- * `stream`, no allocation, no host synchronisation: hipGraph-capturable.
+ * call with nothing to do (n_rows == 0, row0 == row1, n_q == 0, m == 0, n_d == 0 for the scan) returns 0 before it looks at a
+ * pointer.  Asynchronous on `stream`, no allocation, no host synchronisation: hipGraph-capturable.
  */
 int msim_res_encode_docs(int dtype, const void *D, int64_t n_rows, int dim, const uint16_t *codes, const void *C, int K,
                          const float *cutoffs, int bits, uint8_t *residuals, void *stream);
@@ -731,6 +747,11 @@ int msim_res_candidates(int dtype, const void *Qt, const int32_t *q_off, const i
                         const uint8_t *d_clamp0 /* or NULL */, int n_d, int64_t d_rows, int dim, const int64_t *cand, int m,
                         int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids /* or NULL */,
                         void *workspace, void *stream);
+size_t msim_res_scores_workspace_bytes(int n_q, int n_d);
+int msim_res_scores(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const uint16_t *codes,
+                    const uint8_t *residuals, const void *C, int K, const float *weights, int bits, const int32_t *d_off,
+                    const uint8_t *d_clamp0 /* or NULL */, int n_d, int64_t d_rows, int dim, float *out_scores, int64_t ld_scores,
+                    void *workspace, void *stream);
 
 /*
  * LIVE CORPUS (live_corpus.hip; additions to ABI 22): a packed corpus whose pages can be deleted and whose rows can be handed

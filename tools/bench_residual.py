@@ -1,7 +1,7 @@
 """The residual-compressed corpus (msim_res_*, colpali_amd.ResidualCorpus) on the headline shard; one JSON object on stdout (not part
 of bench.py).
 
-    python tools/bench_residual.py [--out FILE] [--steps 10 --warmup 3] [--docs 125000 --doc-len 1024] [--legs build,rerank,two_stage,recall]
+    python tools/bench_residual.py [--out FILE] [--steps 10 --warmup 3] [--docs 125000 --doc-len 1024] [--legs build,rerank,two_stage,recall,scan]
 
 Legs, each timed with device events after a warm-up, for 2 and 4 residual bits (K = 1024 centroids):
   * build: `train_residual_codec` on the residuals of 2^18 sampled rows, and `ResidualCorpus.build` with a given index, cutoffs
@@ -14,6 +14,11 @@ Legs, each timed with device events after a warm-up, for 2 and 4 residual bits (
     same search over the bf16 shard with the same centroid index.
   * recall: recall@10 and the mean absolute score error of the two-stage search over the compressed shard against the exact search
     on the planted 10 000-page set of tools/bench_fde.py:planted_pages (centroids and codec trained on that set).
+  * scan (not in the default legs): the full scan `residual_scores` (msim_res_scores) at 4 x 32, 32 x 32 and 1000 x 32 queries, beside
+    `maxsim_scores` over `rc.decompress()` at the same batches and `residual_rerank_scores` over ALL ids at 4 x 32 (the only way to
+    scan such a shard without it: every page decoded once per query).  The variants of one batch ALTERNATE step by step inside one
+    timing loop, and the outputs' bit-equality at those sizes is recorded.  `--scan-ref 0` times `residual_scores` alone (A/B runs
+    of a measurement build).
 """
 from __future__ import annotations
 
@@ -58,6 +63,61 @@ def rerank_leg(amd, rc, dec, n_q, m, q_len, dev, steps, warmup):
     return out
 
 
+def timed_alternating(fns, steps, warmup):
+    """`timed` for several variants at once: every step runs each variant in turn, so a drift of the clock hits all of them alike"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    evs = {name: [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)] for name in fns}
+    torch.cuda.synchronize()
+    for i in range(steps):
+        for name, fn in fns.items():
+            evs[name][i][0].record()
+            fn()
+            evs[name][i][1].record()
+    torch.cuda.synchronize()
+    out = {}
+    for name in fns:
+        ms = sorted(a.elapsed_time(b) for a, b in evs[name])
+        out[name] = {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
+    return out
+
+
+SCAN_BATCHES = (4, 32, 1000)
+
+
+def scan_leg(amd, rc, dec, q_len, dev, steps, warmup):
+    """dec=None: residual_scores alone"""
+    n = len(rc)
+    out = {}
+    for n_q in SCAN_BATCHES:
+        pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
+        scores = torch.empty((n_q, n), dtype=torch.float32, device=dev)
+        fns = {"residual_scan": lambda: amd.residual_scores(pq, rc, out=scores)}
+        if dec is not None:
+            ref = torch.empty((n_q, n), dtype=torch.float32, device=dev)
+            fns["bf16_decompressed_scan"] = lambda: amd.maxsim_scores(pq, dec, out=ref)
+            if n_q == SCAN_BATCHES[0]:
+                ids = (torch.arange(n, device=dev) + rc.id_base).expand(n_q, n).contiguous()
+                listed = torch.empty((n_q, n), dtype=torch.float32, device=dev)
+                fns["residual_rerank_all_ids"] = lambda: amd.residual_rerank_scores(pq, rc, ids, out=listed)
+        leg = timed_alternating(fns, steps, warmup)
+        if dec is not None:
+            leg["residual_over_bf16"] = leg["residual_scan"]["median_ms"] / leg["bf16_decompressed_scan"]["median_ms"]
+            leg["bit_identical_to_bf16_scan"] = bool(torch.equal(scores.view(torch.int32), ref.view(torch.int32)))
+            if "residual_rerank_all_ids" in fns:
+                leg["scan_over_rerank_all_ids"] = leg["residual_scan"]["median_ms"] / leg["residual_rerank_all_ids"]["median_ms"]
+                leg["bit_identical_to_rerank_all_ids"] = bool(torch.equal(scores.view(torch.int32), listed.view(torch.int32)))
+                del ids, listed
+            del ref
+        passes = (n_q * q_len + 127) // 128
+        leg["passes_over_the_shard"] = passes
+        leg["row_bytes_per_s"] = int(rc.codes.shape[0]) * (2 + 16 * rc.bits) * passes / (leg["residual_scan"]["median_ms"] * 1e-3)
+        out[f"{n_q}x{q_len}"] = leg
+        del scores, pq
+    return out
+
+
 def recall_leg(amd, dev, n_docs, k=10):
     pages, q = planted_pages(dev, n_docs=n_docs)
     full = amd.pack_passages(pages, dev, batch_size=None)
@@ -92,6 +152,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--legs", default="build,rerank,two_stage,recall")
     ap.add_argument("--recall-docs", type=int, default=10_000)
+    ap.add_argument("--scan-ref", type=int, default=1, help="0: the scan leg times residual_scores alone")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -104,7 +165,7 @@ def main():
     legs = set(args.legs.split(","))
     t0 = time.perf_counter()
     res = {"tool": "bench_residual", "docs": args.docs, "doc_len": args.doc_len, "q_len": args.q_len, "n_centroids": K}
-    if legs & {"build", "rerank", "two_stage"}:
+    if legs & {"build", "rerank", "two_stage", "scan"}:
         corpus = make_shard(args.docs, args.doc_len, dev, seed=1234)
         index = amd.CentroidIndex.build(corpus, n_centroids=K)
         res["corpus_bytes"] = corpus.nbytes
@@ -132,6 +193,10 @@ def main():
                                                                args.warmup),
                                              "bf16": timed(lambda: r_b.search(pq, k=10, prefilter=index, n_candidates=m), args.steps,
                                                            args.warmup)} for m in MS}
+            if "scan" in legs:
+                dec = rc.decompress() if args.scan_ref else None
+                leg["scan"] = scan_leg(amd, rc, dec, args.q_len, dev, args.steps, args.warmup)
+                del dec
             res[f"bits{bits}"] = leg
             del rc
             torch.cuda.empty_cache()
