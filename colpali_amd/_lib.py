@@ -453,3 +453,10 @@ def ptr(t) -> int:
 
 def current_stream_handle(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def workspace(nbytes: int, device):
+    """A library call's scratch (include/maxsim.h: one per launch in flight; the call initialises what it uses), or None for 0
+    bytes.  Allocated per call from torch's caching allocator -- stream-ordered reuse, capturable, nothing shared between streams,
+    threads or graph replays."""
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None

@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .corpus import PackedCorpus, PackedQueries, pack_queries
+from .corpus import PackedCorpus, _as_packed, _dtype_width, _id_list
 from .scoring import _require_gpu
 
 MAX_QUERY_TOKENS = 128
@@ -72,16 +72,6 @@ class Alignment:
         return sim.reshape(-1, ny, nx).permute(0, 2, 1)
 
 
-def _format(queries) -> Tuple[torch.dtype, int]:
-    if isinstance(queries, PackedQueries):
-        return queries.dtype, int(queries.tokens.shape[1])
-    if isinstance(queries, torch.Tensor):
-        return queries.dtype, int(queries.shape[-1])
-    if len(queries) == 0:
-        raise ValueError("No queries provided")
-    return queries[0].dtype, int(queries[0].shape[-1])
-
-
 def resolve_ids(ids: torch.Tensor, id_base: int, n: int) -> torch.Tensor:
     """`ids` with every id outside [id_base, id_base + n) replaced by -1: what Alignment.ids holds."""
     idx = ids - id_base
@@ -101,25 +91,17 @@ def align(queries, corpus: PackedCorpus, ids: torch.Tensor, *, maps: bool = Fals
     position, in any batch and under any m.  Asynchronous on torch's current stream; with a `PackedQueries` there is no host
     synchronisation and the call is hipGraph-capturable."""
     dev = _require_gpu(corpus.device)
-    q_dtype, dim = _format(queries)
+    q_dtype, dim = _dtype_width(queries)
     if q_dtype != corpus.blob.dtype:
         raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {corpus.blob.dtype}")
     if q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or corpus.blob.shape[1] != dim:
         raise NotImplementedError(f"align takes bfloat16 / float16 embeddings of width 128 or 320 (got {q_dtype}, width {dim}, "
                                   f"corpus width {corpus.blob.shape[1]})")
-    if not isinstance(queries, PackedQueries):
-        dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-        queries = pack_queries(queries, dev, layout="flat", compact=not dense_on_device)
+    queries = _as_packed(queries, dev, layout="flat")
     if queries.device != dev:
         raise ValueError("queries and corpus live on different devices")
     n_q = len(queries)
-    if (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != n_q
-            or ids.device != dev):
-        raise ValueError(f"ids must be an int64 [n_q={n_q}, m] tensor on {dev}")
-    if (ids.shape[1] > 1 and ids.stride(1) != 1) or (n_q > 1 and ids.stride(0) < ids.shape[1]):
-        ids = ids.contiguous()
-    m = int(ids.shape[1])
-    ld = ids.stride(0) if n_q > 1 else max(m, 1)
+    ids, m, ld = _id_list(ids, n_q, dev, "ids")
     q_lens = queries.lengths.to(torch.int64)
     T = int(q_lens.max()) if n_q else 0
     if T > MAX_QUERY_TOKENS:

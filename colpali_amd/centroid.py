@@ -14,7 +14,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .corpus import PackedCorpus, PackedQueries, pack_queries
+from .corpus import PackedCorpus, PackedQueries, _as_packed
 from .scoring import _require_gpu
 
 DIM = 128
@@ -150,13 +150,6 @@ def train_centroids(corpus: PackedCorpus, n_centroids: int = 1024, iters: int = 
     return centroids.contiguous()
 
 
-def _packed(queries, device: torch.device) -> PackedQueries:
-    if isinstance(queries, PackedQueries):
-        return queries
-    dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-    return pack_queries(queries, device, layout="flat", compact=not dense_on_device)
-
-
 def _prepare(queries, index: CentroidIndex) -> Tuple[PackedQueries, int]:
     dev = _require_gpu(index.device)
     if isinstance(queries, torch.Tensor):
@@ -164,7 +157,7 @@ def _prepare(queries, index: CentroidIndex) -> Tuple[PackedQueries, int]:
     elif not isinstance(queries, PackedQueries):
         for x in queries:
             _check_format(x.dtype, int(x.shape[-1]), "queries")
-    q = _packed(queries, dev)
+    q = _as_packed(queries, dev, layout="flat")
     _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
     if q.device != dev:
         raise ValueError("queries and index live on different devices")

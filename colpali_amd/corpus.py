@@ -88,6 +88,14 @@ class PackedCorpus:
         return self.blob.device
 
     @property
+    def dtype(self) -> torch.dtype:
+        return self.blob.dtype
+
+    @property
+    def width(self) -> int:
+        return int(self.blob.shape[1])
+
+    @property
     def nbytes(self) -> int:
         return self.blob.numel() * self.blob.element_size()
 
@@ -676,3 +684,49 @@ def pack_queries(qs: Union[torch.Tensor, Sequence[torch.Tensor]], device: torch.
     else:
         padded = torch.nn.utils.rnn.pad_sequence(list(qs), batch_first=True, padding_value=0).to(device, non_blocking=True)
     return _widen(padded).contiguous()
+
+
+# ---------------------------------------------------------------------- what every retrieval route does with the arguments it is handed
+def _dtype_width(queries):
+    """(dtype, width) of the queries in whatever form they came: a `PackedQueries`, a tensor, or a list of tensors"""
+    if isinstance(queries, PackedQueries):
+        return queries.dtype, int(queries.tokens.shape[1])
+    if isinstance(queries, torch.Tensor):
+        return queries.dtype, int(queries.shape[-1])
+    if len(queries) == 0:
+        raise ValueError("No queries provided")
+    return queries[0].dtype, int(queries[0].shape[-1])
+
+
+def _as_packed(queries, device: torch.device, *, layout: str = "auto", compact: bool = False):
+    """THE packing rule of the retrieval layer: a `PackedQueries` passes through; a dense DEVICE tensor is packed as it stands unless
+    `compact` (dropping its zero rows needs the per-query counts on the host: one D2H and a synchronisation, which a call that is
+    otherwise asynchronous and hipGraph-capturable must not make); anything else -- a host list, a host tensor -- is packed compact.
+    The retriever's routes pass `compact=compact`, the kernel wrappers `layout="flat"`."""
+    if isinstance(queries, PackedQueries):
+        return queries
+    dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
+    return pack_queries(queries, device, layout=layout, compact=compact or not dense_on_device)
+
+
+def _id_list(ids, n_q: int, device: torch.device, what: str):
+    """An id list as the list kernels read it -- int64 [n_q, m] on `device`, unit inner stride, rows that do not overlap --:
+    (the list, made contiguous where it is not that, m, its row stride).  `what` names the argument in the ValueError."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != n_q or ids.device != device:
+        raise ValueError(f"{what} must be an int64 [n_q={n_q}, m] tensor on {device}")
+    m = int(ids.shape[1])
+    if (m > 1 and ids.stride(1) != 1) or (n_q > 1 and ids.stride(0) < m):
+        ids = ids.contiguous()                        # e.g. one shared list broadcast to every query (row stride 0)
+    return ids, m, ids.stride(0) if n_q > 1 else max(m, 1)
+
+
+def _rerank_args(n_q: int, device: torch.device, candidates, out, ws_bytes):
+    """What the rerank wrappers share before their library call: the checked list (`_id_list`), the fp32 [n_q, m] `out`, the int64
+    [n_q, m] ids the kernel resolves, and the scratch of `ws_bytes(m)` bytes: (candidates, m, ld, out, ids, ws)."""
+    candidates, m, ld = _id_list(candidates, n_q, device, "candidates")
+    if out is None:
+        out = torch.empty((n_q, m), dtype=torch.float32, device=device)
+    elif out.shape != (n_q, m) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError("out must be a contiguous fp32 [n_q, m] tensor on the corpus' device")
+    ids = torch.empty((n_q, m), dtype=torch.int64, device=device)
+    return candidates, m, ld, out, ids, _lib_mod.workspace(int(ws_bytes(m)), device)

@@ -18,7 +18,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .corpus import PackedCorpus, PackedQueries, pack_queries
+from .corpus import PackedCorpus, _as_packed
 from .scoring import _require_gpu
 
 DIM = 128
@@ -146,13 +146,6 @@ class FdeIndex:
         return cls(Fd, corpus.id_base, config, params)
 
 
-def _packed(queries, device: torch.device) -> PackedQueries:
-    if isinstance(queries, PackedQueries):
-        return queries
-    dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-    return pack_queries(queries, device, layout="flat", compact=not dense_on_device)
-
-
 def encode_queries(queries, index: FdeIndex, out: Optional[torch.Tensor] = None, *,
                    codes: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Encodings [n_q, F] of `queries` (a `PackedQueries`, a host list of [len_i, 128] tensors or a [n_q, Lq, 128] tensor) under
@@ -160,7 +153,7 @@ def encode_queries(queries, index: FdeIndex, out: Optional[torch.Tensor] = None,
     With a `PackedQueries` the call is asynchronous and hipGraph-capturable."""
     dev = index.device
     config = index.config
-    q = _packed(queries, dev)
+    q = _as_packed(queries, dev, layout="flat")
     _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
     if q.dtype != index.dtype:
         raise RuntimeError(f"expected queries and index of one dtype, got {q.dtype} and {index.dtype}")

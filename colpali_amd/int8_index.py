@@ -13,7 +13,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .corpus import PackedCorpus, PackedQueries, pack_queries
+from .corpus import PackedCorpus, PackedQueries, _as_packed
 from .scoring import _require_gpu
 
 DIM = 128
@@ -76,20 +76,13 @@ class Int8Index:
         return cls(codes, scales, corpus.offsets.clone(), clamp0, corpus.lengths.clone(), corpus.id_base)
 
 
-def _packed(queries, device: torch.device) -> PackedQueries:
-    if isinstance(queries, PackedQueries):
-        return queries
-    dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-    return pack_queries(queries, device, layout="flat", compact=not dense_on_device)
-
-
 def quantize_queries(queries, device: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-token codes int8 [T, 128] and scales fp32 [T] of `queries` (a `PackedQueries`, a host list of [len_i, 128] tensors or a
     [n_q, Lq, 128] tensor, packed into the flat layout first), in the packed token order."""
     if not isinstance(queries, PackedQueries):
         if device is None:
             device = queries.device if isinstance(queries, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
-        queries = _packed(queries, device)
+        queries = _as_packed(queries, device, layout="flat")
     return _quantize_packed(queries)
 
 
@@ -136,7 +129,7 @@ def int8_scores(queries, index: Int8Index, out: Optional[torch.Tensor] = None) -
     `PackedQueries` it never synchronises with the host and is hipGraph-capturable: its only allocations are torch tensors (the
     query codes and scales, and `out` when it is None), made on the current stream before the library calls."""
     dev = index.device
-    q = _packed(queries, dev)
+    q = _as_packed(queries, dev, layout="flat")
     _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
     if q.device != dev:
         raise ValueError("queries and index live on different devices")

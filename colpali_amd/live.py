@@ -21,14 +21,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from .corpus import PackedCorpus, PackedQueries, _staging, _widen, host_list_image, pack_queries
+from .corpus import PackedCorpus, _as_packed, _staging, _widen, host_list_image
 from .int8_index import DIM as I8_DIM
 from .int8_index import Int8Index, int8_scores
 from .align import Alignment, align
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
 from .group import PageGroups, group_reduce, group_select
 from .mine import mine_bounds, mine_mask
-from .retrieval import ShardedRetriever, rerank_scores, topk
+from .retrieval import ShardedRetriever, _no_page, rerank_scores, topk
 from .scoring import maxsim_scores
 
 DEFAULT_BOUNCE_BYTES = 256 << 20     # rows a compaction moves per pair of launches (tools/bench_live.py --bounce-mb)
@@ -362,9 +362,8 @@ class LiveCorpus:
         the slots too (`len(group_by) == len(self)`, deleted ones included): a document is scored by its surviving pages, and one
         whose every page is deleted is not returned.  A `PageGroups` is immutable: build a new one over all slots after `add`."""
         shard = self.view()
-        if self.device.type == "cuda" and not isinstance(queries, PackedQueries):     # an injected hook packs host queries itself
-            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-            queries = pack_queries(queries, self.device, compact=compact or not dense_on_device)
+        if self.device.type == "cuda":     # an injected hook packs host queries itself
+            queries = _as_packed(queries, self.device, compact=compact)
         r = ShardedRetriever(shard, world, rank, dist, group, score_fn=self._score, select=self._select, rerank_fn=self._rerank,
                              int8_score_fn=self._int8_score, **self._filter_fns)
         if group_by is not None:                 # (-inf, -1, -1) is already the rule there
@@ -372,4 +371,4 @@ class LiveCorpus:
                             filter_route=filter_route, group_by=group_by)
         scores, ids = r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates,
                                filter=filter, filter_route=filter_route)
-        return scores, torch.where(scores == float("-inf"), torch.full_like(ids, -1), ids)   # a deleted slot that filled a short row
+        return _no_page(scores, ids)             # a deleted slot that filled a short row

@@ -256,7 +256,7 @@ def _pairs_backward(qc, dc, offsets, pairs, order, gp, argmax, g_scale=None):
     with torch.cuda.device(dev):
         # scratch of the dense dD form (short documents, long entry lists: the trainer's symmetric direction), per call
         ws_bytes = L.msim_pairs_bwd_workspace_bytes(B, Lq, C, dim, Ld, pairs.shape[0])
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
+        ws = _lib.workspace(ws_bytes, dev)
         rc = L.msim_pairs_bwd(code, _lib.ptr(qc), B, Lq, _lib.ptr(dc), _lib.ptr(offsets), C, dim, Ld,
                               _lib.ptr(pairs), _lib.ptr(order), _lib.ptr(gp), _lib.ptr(gs), gs_code, _lib.ptr(argmax), pairs.shape[0],
                               code, _lib.ptr(dq), _lib.ptr(dd), _lib.ptr(ws), _lib.current_stream_handle(dev))
@@ -367,7 +367,7 @@ def _smooth_backward(qc, dc, offsets, pairs, gp, tau, lse=None, order=None):
         _, lse = smooth_pairs(qc, dc, offsets, pairs, tau, want_scores=False)
     with torch.cuda.device(dev):
         ws_bytes = L.msim_smooth_bwd_workspace_bytes(B, Lq, dim)
-        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
+        ws = _lib.workspace(ws_bytes, dev)
         rc = L.msim_smooth_pairs_bwd(_lib.dtype_code(qc.dtype), _lib.ptr(qc), B, Lq, _lib.ptr(dc), _lib.ptr(offsets), C, dim, Ld,
                                      _lib.ptr(pairs), _lib.ptr(order), _lib.ptr(gp), _lib.ptr(lse), n_pairs, tau,
                                      _lib.ptr(dq), _lib.ptr(dd), _lib.ptr(ws), _lib.current_stream_handle(dev))

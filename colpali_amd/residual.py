@@ -28,7 +28,7 @@ import torch
 
 from . import _lib
 from .centroid import CentroidIndex
-from .corpus import PackedCorpus, PackedQueries, pack_queries
+from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _rerank_args
 from .scoring import _require_gpu
 
 DIM = 128
@@ -82,16 +82,6 @@ def train_residual_codec(residual_sample: torch.Tensor, bits: int = 2) -> Tuple[
     return cutoffs, weights.contiguous()
 
 
-def _query_format(queries) -> Tuple[torch.dtype, int]:
-    if isinstance(queries, PackedQueries):
-        return queries.dtype, int(queries.tokens.shape[1])
-    if isinstance(queries, torch.Tensor):
-        return queries.dtype, int(queries.shape[-1])
-    if len(queries) == 0:
-        raise ValueError("No queries provided")
-    return queries[0].dtype, int(queries[0].shape[-1])
-
-
 class ResidualCorpus:
     """One resident shard in compressed form: `centroids` [K, 128] (bf16 / f16), `codes` uint16 [rows], `residuals` uint8
     [rows, 16 * bits], `cutoffs` fp32 [2^bits - 1], `weights` fp32 [2^bits], the pages' `offsets` (int32 [n + 1], device), `clamp0`
@@ -126,6 +116,10 @@ class ResidualCorpus:
     @property
     def dtype(self) -> torch.dtype:
         return self.centroids.dtype
+
+    @property
+    def width(self) -> int:
+        return DIM
 
     @property
     def n_centroids(self) -> int:
@@ -225,14 +219,12 @@ def _flat_queries(queries, rc: ResidualCorpus, what: str) -> Tuple[torch.device,
     if not isinstance(rc, ResidualCorpus):
         raise ValueError("rc must be a ResidualCorpus")
     dev = _require_gpu(rc.device)
-    q_dtype, dim = _query_format(queries)
+    q_dtype, dim = _dtype_width(queries)
     if q_dtype != rc.dtype:
         raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {rc.dtype}")
     if q_dtype not in (torch.bfloat16, torch.float16) or dim != DIM:
         raise NotImplementedError(f"the residual {what} takes bfloat16 / float16 embeddings of width {DIM} (got {q_dtype}, width {dim})")
-    if not isinstance(queries, PackedQueries):
-        dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-        queries = pack_queries(queries, dev, layout="flat", compact=not dense_on_device)
+    queries = _as_packed(queries, dev, layout="flat")
     if queries.device != dev:
         raise ValueError("queries and corpus live on different devices")
     return dev, queries
@@ -257,8 +249,7 @@ def residual_scores(queries, rc: ResidualCorpus, *, out: Optional[torch.Tensor] 
     L = _lib.lib()
     tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
     with torch.cuda.device(dev):
-        nbytes = int(L.msim_res_scores_workspace_bytes(n_q, n))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        ws = _lib.workspace(int(L.msim_res_scores_workspace_bytes(n_q, n)), dev)
         rcode = L.msim_res_scores(_lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets), queries.offsets_host.data_ptr(),
                                   n_q, _lib.ptr(rc.codes), _lib.ptr(rc.residuals), _lib.ptr(rc.centroids), rc.n_centroids,
                                   _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets), _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM,
@@ -275,27 +266,13 @@ def residual_rerank_scores(queries, rc: ResidualCorpus, candidates: torch.Tensor
     (-inf, -1).  bfloat16 / float16, width 128, queries of at most 128 tokens (NotImplementedError otherwise).  Given a
     `PackedQueries` it never synchronises with the host and is hipGraph-capturable."""
     dev, queries = _flat_queries(queries, rc, "rerank")
-    q_dtype = rc.dtype
-    n_q = len(queries)
-    if (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2
-            or candidates.shape[0] != n_q or candidates.device != dev):
-        raise ValueError(f"candidates must be an int64 [n_q={n_q}, m] tensor on {dev}")
-    if (candidates.shape[1] > 1 and candidates.stride(1) != 1) or (n_q > 1 and candidates.stride(0) < candidates.shape[1]):
-        candidates = candidates.contiguous()          # e.g. one shared list broadcast to every query (row stride 0)
-    m = int(candidates.shape[1])
-    ld_cand = candidates.stride(0) if n_q > 1 else max(m, 1)
-    if out is None:
-        out = torch.empty((n_q, m), dtype=torch.float32, device=dev)
-    elif out.shape != (n_q, m) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous fp32 [n_q, m] tensor on the corpus' device")
-    ids = torch.empty((n_q, m), dtype=torch.int64, device=dev)
+    n_q, n = len(queries), len(rc)
     L = _lib.lib()
-    n = len(rc)
     tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
     with torch.cuda.device(dev):
-        nbytes = int(L.msim_res_candidates_workspace_bytes(n_q, m, n))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-        rcode = L.msim_res_candidates(_lib.dtype_code(q_dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets),
+        candidates, m, ld_cand, out, ids, ws = _rerank_args(n_q, dev, candidates, out,
+                                                            lambda m: L.msim_res_candidates_workspace_bytes(n_q, m, n))
+        rcode = L.msim_res_candidates(_lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets),
                                       queries.offsets_host.data_ptr(), n_q, _lib.ptr(rc.codes), _lib.ptr(rc.residuals),
                                       _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets),
                                       _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM, _lib.ptr(candidates), m, ld_cand,

@@ -11,14 +11,14 @@ depend on the number of shards.
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Callable, Optional, Tuple
 
 import torch
 
 from . import _lib
 from .align import Alignment, align
-from .corpus import PackedCorpus
-from .corpus import PackedQueries, pack_queries
+from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .fde import FdeIndex, fde_scores
 from . import filter as _filter
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
@@ -69,8 +69,7 @@ def topk(scores: torch.Tensor, k: int, id_base: int = 0, ids: Optional[torch.Ten
     else:
         out_s = torch.empty((n_q, k), dtype=torch.float32, device=dev)
         out_i = torch.empty((n_q, k), dtype=torch.int64, device=dev)
-    ws_bytes = L.msim_topk_workspace_bytes(n_q, n, k)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev) if ws_bytes else None
+    ws = _lib.workspace(L.msim_topk_workspace_bytes(n_q, n, k), dev)
     with torch.cuda.device(dev):
         rc = L.msim_topk_f32(_lib.ptr(scores), _lib.ptr(ids), n_q, n, ld, k, id_base, _lib.ptr(out_s), _lib.ptr(out_i),
                              _lib.ptr(ws), _lib.current_stream_handle(dev))
@@ -78,13 +77,39 @@ def topk(scores: torch.Tensor, k: int, id_base: int = 0, ids: Optional[torch.Ten
     return out_s, out_i
 
 
+def _rank_major_rows(part: torch.Tensor) -> torch.Tensor:
+    """[world, n_q, k] -> [n_q, world * k]: every query's entries, rank after rank"""
+    world, n_q, k = part.shape
+    return part.permute(1, 0, 2).reshape(n_q, world * k).contiguous()
+
+
 def merge_gathered(all_s: torch.Tensor, all_i: torch.Tensor, k: int,
                    select: Callable = topk) -> Tuple[torch.Tensor, torch.Tensor]:
     """[world, n_q, k] gathered candidates -> global [n_q, k]."""
-    world, n_q, kk = all_s.shape
-    cand_s = all_s.permute(1, 0, 2).reshape(n_q, world * kk).contiguous()
-    cand_i = all_i.permute(1, 0, 2).reshape(n_q, world * kk).contiguous()
-    return select(cand_s, k, 0, cand_i)
+    return select(_rank_major_rows(all_s), k, 0, _rank_major_rows(all_i))
+
+
+def _dist(dist=None):
+    """the collective library: the one handed in, or torch.distributed"""
+    if dist is None:
+        import torch.distributed as dist  # noqa: PLW0642 - the default collective library
+    return dist
+
+
+def _gather_rows(n_q: int, k: int, n_ids: int, device: torch.device, world: int, dist, group, fill: Callable):
+    """THE message of the retrieval collectives: every rank's [n_q, k] entries -- fp32 scores and `n_ids` int64 blocks -- as
+    [n_q, world * k] tensors, the same on every rank, after ONE all-gather (RCCL over xGMI under the nccl backend).  A rank's message
+    is [scores fp32 n_q*k | pad to 8 | n_ids x int64 n_q*k]: 4 + 8 * n_ids bytes per entry.  `fill(scores, *ids)` writes this
+    rank's entries into [n_q, k] views of it (a kernel may write them in place)."""
+    sb, ib = n_q * k * 4, n_q * k * 8
+    sbp = (sb + 7) // 8 * 8
+    parts = [(0, sb, torch.float32)] + [(sbp + j * ib, sbp + (j + 1) * ib, torch.int64) for j in range(n_ids)]
+    mine = torch.empty((sbp + n_ids * ib,), dtype=torch.uint8, device=device)
+    fill(*(mine[lo:hi].view(dtype).view(n_q, k) for lo, hi, dtype in parts))
+    flat = torch.empty((world * mine.numel(),), dtype=torch.uint8, device=device)      # rank-major concatenation
+    _dist(dist).all_gather_into_tensor(flat, mine, group=group)
+    gathered = flat.view(world, mine.numel())
+    return [_rank_major_rows(gathered[:, lo:hi].view(dtype).view(world, n_q, k)) for lo, hi, dtype in parts]
 
 
 def shard_topk(scores: torch.Tensor, k: int, id_base: int, world: int = 1, dist=None, group=None,
@@ -100,39 +125,22 @@ def shard_topk(scores: torch.Tensor, k: int, id_base: int, world: int = 1, dist=
     """
     if world <= 1 and not force_collective:
         return select(scores, k, id_base, ids)
-    world = max(world, 1)
-    if dist is None:
-        import torch.distributed as dist  # noqa: PLW0642 - the default collective library
-    # one message per rank: [scores fp32 n_q*k | pad to 8 | ids int64 n_q*k] -- ONE all-gather of 12 bytes per candidate
-    n_q = scores.shape[0]
-    sb = n_q * k * 4
-    sbp = (sb + 7) // 8 * 8
-    nbytes = sbp + n_q * k * 8
-    mine = torch.empty((nbytes,), dtype=torch.uint8, device=scores.device)
-    my_s = mine[:sb].view(torch.float32).view(n_q, k)
-    my_i = mine[sbp:].view(torch.int64).view(n_q, k)
-    if select is topk:
-        topk(scores, k, id_base, ids, out=(my_s, my_i))                     # the selection kernel writes the message in place
-    else:
-        loc_s, loc_i = select(scores, k, id_base, ids)
-        my_s.copy_(loc_s)
-        my_i.copy_(loc_i)
-    flat = torch.empty((world * nbytes,), dtype=torch.uint8, device=scores.device)     # rank-major concatenation
-    dist.all_gather_into_tensor(flat, mine, group=group)                   # RCCL all-gather over xGMI (nccl backend)
-    gathered = flat.view(world, nbytes)
-    all_s = gathered[:, :sb].view(torch.float32).view(world, n_q, k)
-    all_i = gathered[:, sbp:].view(torch.int64).view(world, n_q, k)
-    return merge_gathered(all_s, all_i, k, select)
+
+    def fill(my_s, my_i):
+        if select is topk:
+            topk(scores, k, id_base, ids, out=(my_s, my_i))                 # the selection kernel writes the message in place
+        else:
+            loc_s, loc_i = select(scores, k, id_base, ids)
+            my_s.copy_(loc_s)
+            my_i.copy_(loc_i)
+    cand_s, cand_i = _gather_rows(scores.shape[0], k, 1, scores.device, max(world, 1), dist, group, fill)
+    return select(cand_s, k, 0, cand_i)
 
 
-def _query_format(queries) -> Tuple[torch.dtype, int]:
-    if isinstance(queries, PackedQueries):
-        return queries.dtype, int(queries.tokens.shape[1])
-    if isinstance(queries, torch.Tensor):
-        return queries.dtype, int(queries.shape[-1])
-    if len(queries) == 0:
-        raise ValueError("No queries provided")
-    return queries[0].dtype, int(queries[0].shape[-1])
+def _no_page(scores: torch.Tensor, *ids: torch.Tensor):
+    """-inf is "no page" (or no document), whatever filled the row: (scores, *ids with -1 wherever the score is -inf)"""
+    none = scores == float("-inf")
+    return (scores, *(torch.where(none, torch.full_like(i, -1), i) for i in ids))
 
 
 def rerank_scores(queries, corpus: PackedCorpus, candidates: torch.Tensor, *, ref_rounding: bool = False,
@@ -145,36 +153,21 @@ def rerank_scores(queries, corpus: PackedCorpus, candidates: torch.Tensor, *, re
     `ShardedRetriever` calls per shard (its `rerank_fn`).  bfloat16 / float16, width 128 or 320 (ColQwen3), queries of at most
     128 tokens; anything else raises NotImplementedError."""
     dev = _require_gpu(corpus.device)
-    q_dtype, dim = _query_format(queries)
+    q_dtype, dim = _dtype_width(queries)
     if q_dtype != corpus.blob.dtype:        # as maxsim_scores: torch.einsum raises on mixed dtypes too
         raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {corpus.blob.dtype}")
     if q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or corpus.blob.shape[1] != dim:
         raise NotImplementedError(f"rerank takes bfloat16 / float16 embeddings of width 128 or 320 (got {q_dtype}, width {dim}, "
                                   f"corpus width {corpus.blob.shape[1]})")
-    if not isinstance(queries, PackedQueries):
-        dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-        queries = pack_queries(queries, dev, layout="flat", compact=not dense_on_device)
+    queries = _as_packed(queries, dev, layout="flat")
     if queries.device != dev:
         raise ValueError("queries and corpus live on different devices")
-    n_q = len(queries)
-    if (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2
-            or candidates.shape[0] != n_q or candidates.device != dev):
-        raise ValueError(f"candidates must be an int64 [n_q={n_q}, m] tensor on {dev}")
-    if (candidates.shape[1] > 1 and candidates.stride(1) != 1) or (n_q > 1 and candidates.stride(0) < candidates.shape[1]):
-        candidates = candidates.contiguous()          # e.g. one shared list broadcast to every query (row stride 0)
-    m = int(candidates.shape[1])
-    ld_cand = candidates.stride(0) if n_q > 1 else max(m, 1)
-    if out is None:
-        out = torch.empty((n_q, m), dtype=torch.float32, device=dev)
-    elif out.shape != (n_q, m) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise ValueError("out must be a contiguous fp32 [n_q, m] tensor on the corpus' device")
-    ids = torch.empty((n_q, m), dtype=torch.int64, device=dev)
+    n_q, n = len(queries), len(corpus)
     L = _lib.lib()
-    n = len(corpus)
     with torch.cuda.device(dev):
-        nbytes = (L.msim_fwd_candidates_workspace_bytes(n_q, m, n) if dim == 128
-                  else L.msim_fwd_candidates_wide_workspace_bytes(n_q, m, n, dim))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        candidates, m, ld_cand, out, ids, ws = _rerank_args(
+            n_q, dev, candidates, out, lambda m: (L.msim_fwd_candidates_workspace_bytes(n_q, m, n) if dim == 128
+                                                  else L.msim_fwd_candidates_wide_workspace_bytes(n_q, m, n, dim)))
         entry = L.msim_fwd_candidates if dim == 128 else L.msim_fwd_candidates_wide
         rc = entry(_lib.dtype_code(q_dtype), _lib.ptr(queries.tokens), _lib.ptr(queries.offsets),
                    queries.offsets_host.data_ptr(), n_q, _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets),
@@ -201,17 +194,19 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
     allocation inside the library call).
     `corpus` may be a `ResidualCorpus`: the listed pages are then scored straight from their compressed rows
     (`residual_rerank_scores`; width 128, no `ref_rounding`), with the bits `rerank` gives over `corpus.decompress()`."""
+    scorer = partial(rerank_scores, ref_rounding=ref_rounding)
     if isinstance(corpus, ResidualCorpus):
         if ref_rounding:
             raise NotImplementedError("ref_rounding over a ResidualCorpus: the residual rerank has no reference-rounding form")
-        if k is None:
-            return residual_rerank_scores(queries, corpus, candidates, out=out)[0]
-        scores, ids = residual_rerank_scores(queries, corpus, candidates)
-        return topk(scores, k, 0, ids, out=out)
+        scorer = residual_rerank_scores
     if k is None:
-        return rerank_scores(queries, corpus, candidates, ref_rounding=ref_rounding, out=out)[0]
-    scores, ids = rerank_scores(queries, corpus, candidates, ref_rounding=ref_rounding)
+        return scorer(queries, corpus, candidates, out=out)[0]
+    scores, ids = scorer(queries, corpus, candidates)
     return topk(scores, k, 0, ids, out=out)
+
+
+# the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
+_KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, align)
 
 
 class ShardedRetriever:
@@ -234,7 +229,7 @@ class ShardedRetriever:
         if isinstance(shard, ResidualCorpus) and rerank_fn is rerank_scores:
             rerank_fn = residual_rerank_scores
         self.shard, self.world, self.rank = shard, world, rank
-        self.dist, self.group = dist, group
+        self.dist, self.group = (_dist(dist) if world > 1 else dist), group
         self._score, self._select = score_fn, select
         # a compressed shard is scanned on request only: a scorer of its own must be handed in (residual_scores)
         self._res_refuses = isinstance(shard, ResidualCorpus) and score_fn is maxsim_scores
@@ -251,10 +246,6 @@ class ShardedRetriever:
         self._group_reduce = group_reduce_fn  # (scores, PageGroups) -> (fp32 [n_q, G], int64 [n_q, G]): every document's best page
         self._group_select = group_select_fn  # (scores, gids, pages, k) -> the k best documents of every candidate row
         self.force_collective = force_collective
-        if world > 1 and dist is None:
-            import torch.distributed as dist_mod
-
-            self.dist = dist_mod
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None,
                prefilter=None, n_candidates: Optional[int] = None, filter: Optional[PageFilter] = None,
@@ -336,14 +327,32 @@ class ShardedRetriever:
             raise ValueError("filter_route goes with filter=")
         if candidates is not None or prefilter is not None:
             return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, groups=groups)
-        if self._score in (maxsim_scores, residual_scores) and not isinstance(queries, PackedQueries):
-            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-            queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
-        scores = self._score(queries, self.shard)
+        scores = self._score(self._pack(queries, compact, self._score), self.shard)
         if groups is not None:
             return self._group_scan(scores, k, groups)
-        return shard_topk(scores, k, self.shard.id_base, self.world, self.dist, self.group, self._select,
-                          force_collective=self.force_collective)
+        return self._topk(scores, k, self.shard.id_base)
+
+    def _pack(self, queries, compact: bool, *fns: Callable, layout: str = "auto"):
+        """The queries as the hooks in play (`fns`) take them: packed (`_as_packed`) when one of them is a kernel of ours; an injected
+        stand-in receives the caller's queries untouched and packs them itself if it has to."""
+        if any(f in _KERNELS for f in fns):
+            return _as_packed(queries, self.shard.device, layout=layout, compact=compact)
+        return queries
+
+    def _topk(self, scores: torch.Tensor, k: int, id_base: int, ids: Optional[torch.Tensor] = None):
+        """this shard's top-k, then the merge across the ranks (`shard_topk`)"""
+        return shard_topk(scores, k, id_base, self.world, self.dist, self.group, self._select, force_collective=self.force_collective,
+                          ids=ids)
+
+    def _check_covers(self, what: str, x, noun: str = "pages", lives: Optional[str] = None):
+        """`x` -- group_by, filter or prefilter -- must cover the shard: same count, same id_base and, for what the kernels read
+        next to the scores (`lives` words that message), the same device"""
+        shard = self.shard
+        if len(x) != len(shard) or x.id_base != shard.id_base:
+            raise ValueError(f"{what} {len(x)} {noun} from id {x.id_base}; the shard holds {len(shard)} from id {shard.id_base}: "
+                             f"it must cover the same {noun}")
+        if lives is not None and x.device != shard.device:
+            raise ValueError(f"the {lives} on {x.device}, the shard on {shard.device}")
 
     def _no_rows(self, what: str):
         raise NotImplementedError(f"{what} over a ResidualCorpus: the shard keeps no full-precision rows and only candidate lists are "
@@ -358,23 +367,12 @@ class ShardedRetriever:
             return None
         if not isinstance(groups, PageGroups):
             raise ValueError("group_by must be a PageGroups")
-        shard = self.shard
-        if len(groups) != len(shard) or groups.id_base != shard.id_base:
-            raise ValueError(f"group_by covers {len(groups)} pages from id {groups.id_base}; the shard holds {len(shard)} from id "
-                             f"{shard.id_base}: it must cover the same pages")
-        if groups.device != shard.device:
-            raise ValueError(f"the groups live on {groups.device}, the shard on {shard.device}")
+        self._check_covers("group_by covers", groups, lives="groups live")
         collective = self.world > 1 or self.force_collective
         if collective and max(self.world, 1) * int(k) > SELECT_MAX_M:
             raise ValueError(f"group_by with world={max(self.world, 1)} and k={k}: the merge selects among world x k gathered "
                              f"entries, at most {SELECT_MAX_M}")
         return groups.prepare()
-
-    @staticmethod
-    def _group_result(top_s, gid, page):
-        """-inf is "no document", whatever filled the row"""
-        none = top_s == float("-inf")
-        return top_s, torch.where(none, torch.full_like(gid, -1), gid), torch.where(none, torch.full_like(page, -1), page)
 
     def _group_scan(self, scores: torch.Tensor, k: int, groups: PageGroups):
         """a score matrix over the shard's pages -> this shard's best k documents, then the merge"""
@@ -389,7 +387,7 @@ class ShardedRetriever:
             c = col.clamp(0, g - 1)
             gid = torch.where(col >= 0, groups.group_ids[c], torch.full_like(col, -1))
             page = torch.where(col >= 0, torch.gather(doc_p, 1, c), torch.full_like(col, -1))
-        return self._group_merge(*self._group_result(top_s, gid, page), k)
+        return self._group_merge(*_no_page(top_s, gid, page), k)
 
     def _group_list(self, scores: torch.Tensor, ids: torch.Tensor, k: int, groups: PageGroups):
         """reranked (scores, page ids) rows -> this shard's best k documents, then the merge"""
@@ -400,28 +398,13 @@ class ShardedRetriever:
     def _group_merge(self, top_s, gid, page, k: int):
         """(world > 1) ONE all-gather of every rank's k best documents, and the grouped selection over the world x k entries"""
         if self.world <= 1 and not self.force_collective:
-            return self._group_result(top_s, gid, page)
-        world = max(self.world, 1)
-        dist = self.dist
-        if dist is None:
-            import torch.distributed as dist  # noqa: PLW0642 - the default collective library
-        # one message per rank: [scores fp32 n_q*k | pad to 8 | document ids int64 n_q*k | page ids int64 n_q*k]: 20 bytes per entry
-        n_q = top_s.shape[0]
-        sb, ib = n_q * k * 4, n_q * k * 8
-        sbp = (sb + 7) // 8 * 8
-        nbytes = sbp + 2 * ib
-        mine = torch.empty((nbytes,), dtype=torch.uint8, device=top_s.device)
-        mine[:sb].view(torch.float32).view(n_q, k).copy_(top_s)
-        mine[sbp:sbp + ib].view(torch.int64).view(n_q, k).copy_(gid)
-        mine[sbp + ib:].view(torch.int64).view(n_q, k).copy_(page)
-        flat = torch.empty((world * nbytes,), dtype=torch.uint8, device=top_s.device)
-        dist.all_gather_into_tensor(flat, mine, group=self.group)
-        gathered = flat.view(world, nbytes)
+            return _no_page(top_s, gid, page)
 
-        def rows(part, dtype):
-            return part.view(dtype).view(world, n_q, k).permute(1, 0, 2).reshape(n_q, world * k).contiguous()
-        return self._group_result(*self._group_select(rows(gathered[:, :sb], torch.float32), rows(gathered[:, sbp:sbp + ib], torch.int64),
-                                                      rows(gathered[:, sbp + ib:], torch.int64), k))
+        def fill(*views):
+            for view, mine in zip(views, (top_s, gid, page)):
+                view.copy_(mine)
+        gathered = _gather_rows(top_s.shape[0], k, 2, top_s.device, max(self.world, 1), self.dist, self.group, fill)
+        return _no_page(*self._group_select(*gathered, k))
 
     def align(self, queries, ids: torch.Tensor, maps: bool = False) -> Alignment:
         """Explain hits (`align`): for every entry of `ids` -- int64 [n_q, m] GLOBAL ids, the same on every rank, e.g. what `search`
@@ -434,10 +417,7 @@ class ShardedRetriever:
         if maps and self.world > 1:
             raise ValueError("maps=True with world > 1: similarity maps are made by the rank that holds the page; call align() on "
                              "its shard")
-        if self._align is align and not isinstance(queries, PackedQueries):
-            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-            queries = pack_queries(queries, self.shard.device, layout="flat", compact=not dense_on_device)
-        out = self._align(queries, self.shard, ids, maps=maps)
+        out = self._align(self._pack(queries, False, self._align, layout="flat"), self.shard, ids, maps=maps)
         if self.world > 1:
             for t in (out.best_sim, out.best_row, out.ids):
                 self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
@@ -455,10 +435,7 @@ class ShardedRetriever:
         if self._res_refuses:
             self._no_rows("mine")
         n_neg, skip_top, max_ratio = check_mine_args(n_neg, skip_top, max_ratio)
-        if self._score in (maxsim_scores, residual_scores) and not isinstance(queries, PackedQueries):
-            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-            queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
-        scores = self._score(queries, self.shard)
+        scores = self._score(self._pack(queries, compact, self._score), self.shard)
         if alive is not None and alive.device != scores.device:
             raise ValueError("alive and the shard live on different devices")
         reduce_max = None
@@ -466,22 +443,12 @@ class ShardedRetriever:
             def reduce_max(t):
                 self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX, group=self.group)
         masked = mine_masked(scores, positives, int(self.shard.id_base), max_ratio, alive, self._mine_bounds, self._mine_mask, reduce_max)
-
-        def shard_select(s, k, id_base):
-            return shard_topk(s, k, id_base, self.world, self.dist, self.group, self._select, force_collective=self.force_collective)
-        return select_window(masked, int(self.shard.id_base), n_neg, skip_top, shard_select)
-
-    def _shard_format(self) -> Tuple[torch.dtype, int]:
-        """(dtype, width) of the shard's pages; a residual shard stores its centroids' dtype at width 128"""
-        if isinstance(self.shard, ResidualCorpus):
-            return self.shard.dtype, 128
-        return self.shard.blob.dtype, int(self.shard.blob.shape[1])
+        return select_window(masked, int(self.shard.id_base), n_neg, skip_top, self._topk)
 
     def _list_formats_fit(self, queries) -> bool:
         """what `rerank_scores` takes: bfloat16 / float16, width 128 or 320, at most 128 tokens per query (host metadata only)"""
-        q_dtype, dim = _query_format(queries)
-        s_dtype, s_dim = self._shard_format()
-        if q_dtype != s_dtype or q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or s_dim != dim:
+        q_dtype, dim = _dtype_width(queries)
+        if q_dtype != self.shard.dtype or q_dtype not in (torch.bfloat16, torch.float16) or dim not in (128, 320) or self.shard.width != dim:
             return False
         if isinstance(queries, PackedQueries):
             return len(queries) == 0 or int(queries.lengths.max()) <= 128
@@ -495,11 +462,7 @@ class ShardedRetriever:
         if not isinstance(flt, PageFilter):
             raise ValueError("filter must be a PageFilter")
         shard = self.shard
-        if len(flt) != len(shard) or flt.id_base != shard.id_base:
-            raise ValueError(f"filter covers {len(flt)} pages from id {flt.id_base}; the shard holds {len(shard)} from id "
-                             f"{shard.id_base}: it must cover the same pages")
-        if flt.device != shard.device:
-            raise ValueError(f"the filter lives on {flt.device}, the shard on {shard.device}")
+        self._check_covers("filter covers", flt, lives="filter lives")
         two_stage = candidates is not None or prefilter is not None
         if two_stage:
             if route == "list":
@@ -508,19 +471,16 @@ class ShardedRetriever:
                 return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt, groups)
             top_s, top_i = self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt)
         else:
-            if self._score in (maxsim_scores, residual_scores) and not isinstance(queries, PackedQueries):
-                dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-                queries = pack_queries(queries, shard.device, compact=compact or not dense_on_device)
+            queries = self._pack(queries, compact, self._score)
             n_q = len(queries)
             self._check_filter_rows(flt, n_q)
             flt.prepare()
             fits = self._list_formats_fit(queries)
             if route == "list" and not fits:
-                q_dtype, dim = _query_format(queries)
-                s_dtype, s_dim = self._shard_format()
+                q_dtype, dim = _dtype_width(queries)
                 raise NotImplementedError(f"filter_route='list' reranks the listed pages: rerank takes bfloat16 / float16 embeddings of "
                                           f"width 128 or 320 and queries of at most 128 tokens (got {q_dtype}, width {dim}, corpus "
-                                          f"{s_dtype} of width {s_dim})")
+                                          f"{shard.dtype} of width {shard.width})")
             if route == "list" and groups is not None and flt.max_allowed > SELECT_MAX_M:
                 raise NotImplementedError(f"filter_route='list' with group_by: a query is allowed {flt.max_allowed} pages, group_select "
                                           f"takes lists of at most {SELECT_MAX_M}")
@@ -533,15 +493,13 @@ class ShardedRetriever:
                 scores, ids = self._rerank(queries, shard, cand)
                 if groups is not None:
                     return self._group_list(scores, ids, k, groups)
-                top_s, top_i = shard_topk(scores, k, 0, self.world, self.dist, self.group, self._select,
-                                          force_collective=self.force_collective, ids=ids)
+                top_s, top_i = self._topk(scores, k, 0, ids)
             else:
                 scores = self._filter_mask(self._score(queries, shard), flt, None)
                 if groups is not None:
                     return self._group_scan(scores, k, groups)
-                top_s, top_i = shard_topk(scores, k, shard.id_base, self.world, self.dist, self.group, self._select,
-                                          force_collective=self.force_collective)
-        return top_s, torch.where(top_s == float("-inf"), torch.full_like(top_i, -1), top_i)     # -inf is "no page", whatever filled the row
+                top_s, top_i = self._topk(scores, k, shard.id_base)
+        return _no_page(top_s, top_i)
 
     @staticmethod
     def _check_filter_rows(flt, n_q):
@@ -559,38 +517,44 @@ class ShardedRetriever:
         if prefilter is not None:
             if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex)):
                 raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index or a CentroidIndex")
-            if len(prefilter) != len(self.shard) or prefilter.id_base != self.shard.id_base:
-                raise ValueError(f"prefilter holds {len(prefilter)} documents from id {prefilter.id_base}; the shard holds "
-                                 f"{len(self.shard)} from id {self.shard.id_base}: it must cover the same documents")
+            self._check_covers("prefilter holds", prefilter, "documents")
             if n_candidates is None or int(n_candidates) < 1:
                 raise ValueError("prefilter= needs n_candidates >= 1")
         stage1 = (self._fde_score if isinstance(prefilter, FdeIndex) else self._int8_score if isinstance(prefilter, Int8Index)
                   else self._centroid_score if isinstance(prefilter, CentroidIndex) else self._score)
-        uses_kernels = self._rerank in (rerank_scores, residual_rerank_scores) or (prefilter is not None and
-                                                         stage1 in (maxsim_scores, fde_scores, int8_scores, centroid_scores))
-        if uses_kernels and not isinstance(queries, PackedQueries):
-            dense_on_device = isinstance(queries, torch.Tensor) and queries.device.type == "cuda"
-            queries = pack_queries(queries, self.shard.device, compact=compact or not dense_on_device)
+        queries = self._pack(queries, compact, self._rerank, *((stage1,) if prefilter is not None else ()))
         if flt is not None:
             self._check_filter_rows(flt, len(queries))
         if prefilter is not None:
             coarse = stage1(queries, prefilter)                          # stage 1: the cheap corpus, or the encodings
             if flt is not None:
                 coarse = self._filter_mask(coarse, flt, None)            # all n_candidates are allowed pages
-            cand_s, candidates = shard_topk(coarse, int(n_candidates), prefilter.id_base, self.world, self.dist, self.group, self._select,
-                                            force_collective=self.force_collective)
+            cand_s, candidates = self._topk(coarse, int(n_candidates), prefilter.id_base)
             if flt is not None:                                          # a masked column that filled a short list is not reranked
-                candidates = torch.where(cand_s == float("-inf"), torch.full_like(candidates, -1), candidates)
+                candidates = _no_page(cand_s, candidates)[1]
         elif flt is not None:
-            if (not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2
-                    or candidates.shape[0] != len(queries) or candidates.device != self.shard.device):
-                raise ValueError(f"candidates must be an int64 [n_q={len(queries)}, m] tensor on {self.shard.device}")
-            candidates = self._filter_ids(candidates.clone(memory_format=torch.contiguous_format), flt, None)
+            mine = _id_list(candidates, len(queries), self.shard.device, "candidates")[0]
+            if mine is candidates:                                       # filter_ids writes in place: never into the caller's list
+                mine = mine.clone(memory_format=torch.contiguous_format)
+            candidates = self._filter_ids(mine, flt, None)
         scores, ids = self._rerank(queries, self.shard, candidates)      # stage 2: exact, this shard's candidates only
         if groups is not None:
             return self._group_list(scores, ids, k, groups)
-        return shard_topk(scores, k, 0, self.world, self.dist, self.group, self._select, force_collective=self.force_collective,
-                          ids=ids)
+        return self._topk(scores, k, 0, ids)
+
+
+def _query_box(queries_embeddings: torch.Tensor, shard) -> torch.Tensor:
+    """the [n, Lq, dim] box an index's `search` is handed, on the shard's device and in its dtype"""
+    q = queries_embeddings.to(device=shard.device, dtype=shard.dtype).contiguous()
+    if q.dim() != 3:
+        raise ValueError("queries_embeddings must be [n_queries, query_length, dim]")
+    return q
+
+
+def _hit_rows(top_s: torch.Tensor, top_i: torch.Tensor):
+    """FastPlaid's result shape: per query a list of (document id, score) tuples, best first; the (-inf, -1) padding is dropped"""
+    top_s, top_i = top_s.cpu().tolist(), top_i.cpu().tolist()
+    return [[(int(i), float(s)) for s, i in zip(row_s, row_i) if i >= 0] for row_s, row_i in zip(top_s, top_i)]
 
 
 class ExactMaxSimIndex:
@@ -605,13 +569,8 @@ class ExactMaxSimIndex:
         self.retriever = ShardedRetriever(corpus, world, rank, dist, group)
 
     def search(self, queries_embeddings: torch.Tensor, top_k: int = 10):
-        dev = self.retriever.shard.device
-        q = queries_embeddings.to(device=dev, dtype=self.retriever.shard.blob.dtype).contiguous()
-        if q.dim() != 3:
-            raise ValueError("queries_embeddings must be [n_queries, query_length, dim]")
-        top_s, top_i = self.retriever.search(q, k=top_k, compact=True)     # padded blocks from get_topk_plaid: the result is read back anyway
-        top_s, top_i = top_s.cpu().tolist(), top_i.cpu().tolist()
-        return [[(int(i), float(s)) for s, i in zip(row_s, row_i) if i >= 0] for row_s, row_i in zip(top_s, top_i)]
+        q = _query_box(queries_embeddings, self.retriever.shard)
+        return _hit_rows(*self.retriever.search(q, k=top_k, compact=True))     # padded blocks from get_topk_plaid: the result is read back anyway
 
 
 class ResidualMaxSimIndex:
@@ -629,14 +588,10 @@ class ResidualMaxSimIndex:
 
     def search(self, queries_embeddings: torch.Tensor, top_k: int = 10):
         rc = self.retriever.shard
-        q = queries_embeddings.to(device=rc.device, dtype=rc.dtype).contiguous()
-        if q.dim() != 3:
-            raise ValueError("queries_embeddings must be [n_queries, query_length, dim]")
+        q = _query_box(queries_embeddings, rc)
         # one shard: no more candidates than pages (with world > 1 the list is global, and a short one is padded with -1)
         m = self.n_candidates if self.retriever.world > 1 else max(min(self.n_candidates, len(rc)), 1)
-        top_s, top_i = self.retriever.search(q, k=top_k, compact=True, prefilter=rc.index, n_candidates=m)
-        top_s, top_i = top_s.cpu().tolist(), top_i.cpu().tolist()
-        return [[(int(i), float(s)) for s, i in zip(row_s, row_i) if i >= 0] for row_s, row_i in zip(top_s, top_i)]
+        return _hit_rows(*self.retriever.search(q, k=top_k, compact=True, prefilter=rc.index, n_candidates=m))
 
 
 def create_plaid_index(ps, device=None, *, nbits: Optional[int] = None, n_centroids: int = 1024, n_candidates: int = 1024):

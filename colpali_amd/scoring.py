@@ -115,13 +115,6 @@ def _score_on_host(qs, ps, batch_size: int, ref_rounding: bool) -> torch.Tensor:
     return out
 
 
-def _fwd_workspace(nbytes: int, device: torch.device) -> Optional[torch.Tensor]:
-    """msim_fwd's scratch (include/maxsim.h: one per launch in flight; the call initialises what it uses).  Allocated per
-    call from torch's caching allocator -- stream-ordered reuse, capturable, nothing shared between streams, threads or
-    graph replays."""
-    return torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None
-
-
 _MAX_FWD_SCRATCH = 1 << 30        # bytes of msim_fwd scratch per launch (long queries: see maxsim_scores)
 
 
@@ -171,7 +164,7 @@ def maxsim_scores(queries: Union[torch.Tensor, PackedQueries], corpus: PackedCor
     if flat:
         with torch.cuda.device(queries.device):
             oh = queries.offsets_host
-            ws = _fwd_workspace(L.msim_fwd_ragged_workspace_bytes(dt, oh.data_ptr(), n_q, n, dim), queries.device)
+            ws = _lib.workspace(L.msim_fwd_ragged_workspace_bytes(dt, oh.data_ptr(), n_q, n, dim), queries.device)
             rc = L.msim_fwd_ragged(dt, _lib.ptr(queries.tokens), _lib.ptr(queries.offsets), oh.data_ptr(), n_q, _lib.ptr(corpus.blob),
                                    _lib.ptr(corpus.offsets), _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(out), ld, flags, _lib.ptr(ws),
                                    _lib.current_stream_handle(queries.device))
@@ -185,7 +178,7 @@ def maxsim_scores(queries: Union[torch.Tensor, PackedQueries], corpus: PackedCor
     with torch.cuda.device(queries.device):
         for q0 in range(0, n_q, group):
             nq = min(group, n_q - q0)
-            ws = _fwd_workspace(L.msim_fwd_workspace_bytes(dt, nq, Lq, n, dim), queries.device)
+            ws = _lib.workspace(L.msim_fwd_workspace_bytes(dt, nq, Lq, n, dim), queries.device)
             rc = L.msim_fwd(dt, _lib.ptr(queries[q0:q0 + nq]), nq, Lq, _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets),
                             _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(out[q0:q0 + nq]), ld,
                             flags, _lib.ptr(ws), _lib.current_stream_handle(queries.device))

@@ -353,6 +353,43 @@ def test_routing_rule_of_auto_with_the_cap_and_argument_errors():
         amd.ShardedRetriever(corpus, world=5, rank=0, dist=dist, **Hooks().kw()).search(q, 820, group_by=groups)
 
 
+# ------------------------------------------------------------------------------------------------- the message of the collective
+class RecordingDist:
+    """a one-rank stand-in for torch.distributed: records every message, and the gathered buffer is the rank's own"""
+
+    def __init__(self):
+        self.messages = []
+
+    def all_gather_into_tensor(self, out, mine, group=None):
+        assert mine.dtype == torch.uint8 and mine.dim() == 1 and out.dtype == torch.uint8 and out.numel() == mine.numel()
+        self.messages.append(int(mine.numel()))
+        out.copy_(mine)
+
+
+def test_one_all_gather_per_merge_and_the_size_of_its_message():
+    from oracle import topk_oracle
+
+    n_q, k = 3, 1                                                        # 12 bytes of scores: the padding to 8 is not zero
+    amd, g, pages, labels, corpus, q = _case(n_q=n_q)
+    pad8 = (4 * n_q * k + 7) // 8 * 8
+    assert pad8 == 16
+    s = _score_fn(q, corpus)
+    fake = RecordingDist()
+    got = amd.shard_topk(s, k, 100, 1, fake, None, topk_oracle.torch_select, force_collective=True)
+    assert fake.messages == [pad8 + 8 * n_q * k]                         # ONE all-gather: [scores | pad | ids]
+    for a, b in zip(got, amd.shard_topk(s, k, 100, select=topk_oracle.torch_select)):
+        assert torch.equal(a, b)
+    groups = amd.PageGroups.from_labels(labels, 100)
+    cand = torch.stack([torch.randperm(len(corpus) + 10, generator=g)[:25] + 95 for _ in range(n_q)])
+    alone = amd.ShardedRetriever(corpus, **Hooks().kw())
+    for kw in (dict(), dict(candidates=cand)):
+        fake = RecordingDist()
+        forced = amd.ShardedRetriever(corpus, dist=fake, force_collective=True, **Hooks().kw())
+        got = forced.search(q, k, group_by=groups, **kw)
+        assert fake.messages == [pad8 + 16 * n_q * k], kw                # ONE all-gather: [scores | pad | document ids | page ids]
+        _check(got, [x.numpy() for x in alone.search(q, k, group_by=groups, **kw)], f"forced {sorted(kw)}")
+
+
 # --------------------------------------------------------------------------------------------- LiveCorpus.search(group_by=), host logic
 def test_live_corpus_scores_documents_by_their_surviving_pages():
     import colpali_amd as amd

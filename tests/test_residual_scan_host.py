@@ -150,7 +150,7 @@ def test_an_injected_scorer_opens_the_routes_that_need_the_score_matrix():
               f"{spec[0]} candidates")
     assert h.calls["mask"] >= 3 and h.calls["list"] >= 3 and h.calls["ids"] >= 3
     # the list route asks the shard for its format: a residual shard is its centroids' dtype at width 128
-    assert r._shard_format() == (torch.bfloat16, 128) and r._list_formats_fit(q) and not r._list_formats_fit(q.float())
+    assert (rc.dtype, rc.width) == (torch.bfloat16, 128) and r._list_formats_fit(q) and not r._list_formats_fit(q.float())
     with pytest.raises(NotImplementedError, match="bfloat16 of width 128"):
         r.search(q.float(), 5, filter=_filter(amd, ("shared", shared), 100), filter_route="list")
     _same(r.search(q, 4, group_by=groups), ref.search(q, 4, group_by=groups), "grouped scan")
