@@ -94,6 +94,17 @@ def lib() -> ctypes.CDLL:
     L.msim_fwd_ragged_workspace_bytes.restype = sz
     L.msim_fwd_ragged.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i64, u32, vp, vp]
     L.msim_fwd_ragged.restype = i32
+    # the 13-bit image of a bf16 corpus (corpus.py: PackedCorpus.pack13) and the forward entries that scan it
+    L.msim_pack13_image_bytes.argtypes = [i64]
+    L.msim_pack13_image_bytes.restype = sz
+    L.msim_pack13_encode.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, vp, vp]
+    L.msim_pack13_encode.restype = i32
+    L.msim_pack13_decode.argtypes = [vp, vp, vp, i32, i64, vp, vp]
+    L.msim_pack13_decode.restype = i32
+    L.msim_fwd_pack13.argtypes = [i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i64, u32, vp, vp]
+    L.msim_fwd_pack13.restype = i32
+    L.msim_fwd_ragged_pack13.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i64, u32, vp, vp]
+    L.msim_fwd_ragged_pack13.restype = i32
     L.msim_query_compact.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
     L.msim_query_compact.restype = i32
     L.msim_host_count_nonzero_rows.argtypes = [vp, vp, i64, i64, vp, i32]

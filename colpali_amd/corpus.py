@@ -16,7 +16,7 @@ import ctypes
 import operator
 import os
 import threading
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -57,6 +57,30 @@ def block_clamp0(lengths: torch.Tensor, batch_size: int) -> torch.Tensor:
     return torch.from_numpy(flags.astype(np.uint8))
 
 
+# ---- the 13-bit image of a bf16 corpus (csrc/pack13.hip; DESIGN.md sections 2 and 3)
+PACK13_SLAB_BYTES = 6656            # 32 rows x 128 values: 4096 low bytes + 2048 nibbles + 512 signs
+PACK13_MAX_FLAGGED = 0.05           # more flagged documents than this share of the corpus: the image is not worth its memory
+PACK13_RESERVE_BYTES = 2 << 30      # device memory that must stay free after the image is allocated, or it is not built
+
+
+def _pack13_env() -> Optional[bool]:
+    """COLPALI_AMD_PACK13: "0" = never build or use an image, "1" = build it on a corpus' first K1s scan; unset = on the second."""
+    v = os.environ.get("COLPALI_AMD_PACK13", "")
+    return None if v == "" else v != "0"
+
+
+@dataclass
+class Pack13Image:
+    """What the packed K1s reads beside the blob.  Private to the library: the layout may change with it."""
+    key: tuple                         # what the image was made from (PackedCorpus._pack13_key)
+    image: torch.Tensor                # uint8 [n_slabs * 6656]
+    slab_off: torch.Tensor             # int32 [n + 1]: document c owns slabs slab_off[c] .. slab_off[c+1]-1
+    flagged: torch.Tensor              # uint8 [n]: 1 = holds a value the code cannot represent; scored from the blob
+    ids: Optional[torch.Tensor]        # int32 [n_flagged]: the flagged documents in ascending order, or None
+    n_flagged: int
+    n_slabs: int
+
+
 @dataclass
 class PackedCorpus:
     blob: torch.Tensor                 # bf16 | f16 | f32 [rows, width], on the GPU
@@ -65,9 +89,71 @@ class PackedCorpus:
     lengths: torch.Tensor              # int64 [n], on the host
     id_base: int = 0                   # global id of passage 0 (sharded corpora)
     avg_rows: Optional[int] = None     # average passage length (launch-shape hint); None: derived once from `lengths` and kept
+    # the 13-bit image (pack13) and what the automatic rule remembers: (key, "seen" | "declined")
+    _pack13: Optional[Pack13Image] = field(default=None, compare=False, repr=False)
+    _pack13_note: Optional[tuple] = field(default=None, compare=False, repr=False)
 
     def __len__(self) -> int:
         return int(self.lengths.numel())
+
+    # ---- the 13-bit image: a resident bf16 corpus of L2-normalised rows re-coded once, scanned at 0.8125 x the bytes, same score bits
+    def _pack13_key(self) -> tuple:
+        b, o = self.blob, self.offsets
+        return (b.data_ptr(), b._version, o.data_ptr(), o._version, tuple(b.shape), tuple(o.shape))
+
+    def _pack13_eligible(self) -> bool:
+        return (self.blob.dtype == torch.bfloat16 and self.blob.dim() == 2 and self.blob.shape[1] == EMBED_DIM
+                and self.blob.device.type == "cuda" and len(self) > 0)
+
+    def pack13(self) -> bool:
+        """Build the 13-bit image now (one pass over the blob, about two scans' time, 0.8125 x the blob's bytes of device memory) so
+        that few-query scans (`maxsim_scores` on the K1s plan: at most 8 queries and 128 tokens in all) read it instead of the
+        blob.  The scores do not change by a bit.  Returns whether the corpus holds an image afterwards: the library declines --
+        and scans the blob as before -- for anything but bf16 rows of width 128 on the GPU, when more than 5 % of the documents
+        hold a value the code cannot represent (exact zeros, |x| < 2^-31, |x| >= 2, inf, NaN), when less than
+        PACK13_RESERVE_BYTES of device memory would stay free, when the allocation fails, and under COLPALI_AMD_PACK13=0.
+        An in-place change of `blob` or `offsets` drops the image at the next scan."""
+        key = self._pack13_key()
+        if self._pack13 is not None and self._pack13.key == key:
+            return True
+        self._pack13 = None
+        if _pack13_env() is False or not self._pack13_eligible():
+            return False
+        self._pack13 = _pack13_build(self, key)
+        self._pack13_note = None if self._pack13 is not None else (key, "declined")
+        return self._pack13 is not None
+
+    def drop_pack13(self) -> None:
+        """Release the image; the automatic rule starts over (the next scan counts as the first)."""
+        self._pack13 = None
+        self._pack13_note = None
+
+    def _pack13_for_scan(self) -> Optional[Pack13Image]:
+        """The image a K1s scan of this corpus should read, or None.  Called by `maxsim_scores` once per K1s scan: a corpus OBJECT
+        that takes this path a second time unchanged is taken to be resident and is packed then -- a drop-in corpus is scanned once
+        and never pays for an encoding that costs about two scans.  Stale images (the key differs) are dropped here."""
+        env = _pack13_env()
+        if env is False:
+            self._pack13 = None
+            return None
+        key = self._pack13_key()
+        img = self._pack13
+        if img is not None:
+            if img.key == key:
+                return img
+            self._pack13 = None
+            self._pack13_note = None
+        if not self._pack13_eligible() or torch.cuda.is_current_stream_capturing():
+            return None
+        note = self._pack13_note
+        if note is not None and note[0] == key:
+            if note[1] == "declined":
+                return None
+        elif not env:                                  # the first scan of this state of the corpus
+            self._pack13_note = (key, "seen")
+            return None
+        self.pack13()
+        return self._pack13
 
     def average_rows(self) -> int:
         """The launch-shape hint of include/maxsim.h (MSIM_FLAG_AVG_ROWS), computed ONCE per corpus and with numpy: a torch CPU
@@ -98,6 +184,58 @@ class PackedCorpus:
     @property
     def nbytes(self) -> int:
         return self.blob.numel() * self.blob.element_size()
+
+
+def _pack13_build(corpus: "PackedCorpus", key: tuple) -> Optional[Pack13Image]:
+    """Encode the corpus (msim_pack13_encode), or None where the library declines (PackedCorpus.pack13)."""
+    L = _lib_mod.lib()
+    n = len(corpus)
+    dev = corpus.blob.device
+    ln = corpus.lengths.detach().to("cpu").numpy().astype(np.int64, copy=False)
+    slab_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum((ln + 31) // 32, out=slab_off[1:])
+    n_slabs = int(slab_off[-1])
+    if n_slabs == 0 or n_slabs >= 2**31:
+        return None
+    with torch.cuda.device(dev):
+        # the kernel walks slab_off and the device offsets side by side: they must describe the same documents
+        if not np.array_equal(np.diff(corpus.offsets.detach().to("cpu").numpy().astype(np.int64)), ln):
+            return None
+        need = int(L.msim_pack13_image_bytes(n_slabs))
+        free, _total = torch.cuda.mem_get_info(dev)
+        free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)     # what torch's allocator holds unused
+        if free - need < PACK13_RESERVE_BYTES:
+            return None
+        try:
+            image = torch.empty((need,), dtype=torch.uint8, device=dev)
+        except RuntimeError:                          # torch.OutOfMemoryError is one
+            return None
+        slab_off_d = torch.from_numpy(slab_off.astype(np.int32)).to(dev)
+        flagged = torch.empty((n,), dtype=torch.uint8, device=dev)
+        ids = torch.empty((n,), dtype=torch.int32, device=dev)
+        count = torch.empty((1,), dtype=torch.int32, device=dev)
+        _lib_mod.check(L.msim_pack13_encode(_lib_mod.ptr(corpus.blob), _lib_mod.ptr(corpus.offsets), _lib_mod.ptr(slab_off_d), n, n_slabs,
+                                            _lib_mod.ptr(image), _lib_mod.ptr(flagged), _lib_mod.ptr(ids), _lib_mod.ptr(count),
+                                            _lib_mod.current_stream_handle(dev)), "msim_pack13_encode")
+        n_flagged = int(count.item())
+    if n_flagged > PACK13_MAX_FLAGGED * n:
+        return None
+    return Pack13Image(key=key, image=image, slab_off=slab_off_d, flagged=flagged,
+                       ids=ids[:n_flagged].clone() if n_flagged else None, n_flagged=n_flagged, n_slabs=n_slabs)
+
+
+def pack13_decode(corpus: "PackedCorpus") -> torch.Tensor:
+    """Test aid: the corpus' image decoded back into a [rows, 128] bf16 blob (msim_pack13_decode).  Rows of unflagged documents
+    carry the blob's bits; rows no document owns are zero."""
+    img = corpus._pack13
+    if img is None:
+        raise ValueError("the corpus holds no 13-bit image")
+    out = torch.zeros_like(corpus.blob)
+    with torch.cuda.device(corpus.blob.device):
+        _lib_mod.check(_lib_mod.lib().msim_pack13_decode(_lib_mod.ptr(img.image), _lib_mod.ptr(corpus.offsets), _lib_mod.ptr(img.slab_off),
+                                                         len(corpus), img.n_slabs, _lib_mod.ptr(out),
+                                                         _lib_mod.current_stream_handle(corpus.blob.device)), "msim_pack13_decode")
+    return out
 
 
 def _check_embeddings(x: torch.Tensor, what: str) -> None:

@@ -1,5 +1,5 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the forward scorers -- msim_fwd, msim_fwd_ragged and their plans and
-// workspace sizes, the plain similarity matrix, msim_query_compact and candidate reranking (msim_fwd_candidates, both widths).
+// workspace sizes (and their forms over the 13-bit image of a bf16 corpus: msim_fwd_pack13, msim_fwd_ragged_pack13), the plain similarity matrix, msim_query_compact and candidate reranking (msim_fwd_candidates, both widths).
 // Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
 // frees or synchronises, so every entry point is hipGraph-capturable.  The other families of entry points live in abi_train.hip,
 // abi_head_pool.hip, abi_search.hip and abi_index.hip, the state they share in abi_core.cpp; the kernels included below are
@@ -16,6 +16,7 @@
 #include "abi_common.hpp"
 #include "abi_shapes.hpp"
 #include "maxsim_stream.hip"
+#include "maxsim_stream13.hip"
 #include "maxsim_batch.hip"
 #if defined(MSIM_AB) || defined(MSIM_TRACE)
 #include "maxsim_batch_packed.hip"     // K1bK: several short documents per chunk -- measured, slower than K1b, measurement builds only
@@ -29,6 +30,15 @@
 using namespace msim_abi;
 
 namespace {
+
+// the 13-bit image of the corpus (pack13.hip) beside the blob: K1s plans of bf16 calls scan it instead
+struct Pack13View {
+    const uint8_t *image;
+    const int32_t *slab_off;
+    const uint8_t *flagged;
+    const int32_t *list;         // the flagged ids, n_list of them: scored from the blob
+    int n_list;
+};
 
 struct FwdCall {
     const uint16_t *Q, *D;       // Q: the [n_q, Lq, 128] box (uniform queries: also a flat token matrix) or the flat token matrix (q_off)
@@ -46,6 +56,7 @@ struct FwdCall {
     const int32_t *q_off_host = nullptr;   // the same numbers on the host: the plan below is made from them
     int seg = 0, n_seg = 1;                // uniform long queries: n_q counts PIECES of `seg` tokens (FlatQ::n_seg)
     int avg_rows = 0;                      // the caller's hint: average rows per document (MSIM_FLAG_AVG_ROWS), 0 = unknown
+    const Pack13View *p13 = nullptr;       // bf16 only
 };
 
 constexpr size_t kFwdWorkspaceBytes = 4096;   // K1b's convoy counters: n_ranges * n_qblocks <= 8 * 64 ints
@@ -75,9 +86,10 @@ int stream_nt() {
     return v;
 }
 
-template <int NU, bool F16, int AUX, bool IL, int RING = kStreamRing>
-int launch_stream_aux(const FwdCall &c) {
-    auto kern = msim::maxsim_stream_kernel<NU, RING, F16, AUX, IL>;
+// LIST: the documents doc_list[0 .. c.n_d) instead of 0 .. c.n_d-1
+template <int NU, bool F16, int AUX, bool IL, int RING = kStreamRing, bool LIST = false>
+int launch_stream_aux(const FwdCall &c, const int32_t *doc_list = nullptr) {
+    auto kern = msim::maxsim_stream_kernel<NU, RING, F16, AUX, IL, LIST>;
     constexpr int lds = 4 * (RING * msim::kSlabBytes + msim::kStreamTokBytes);
     static std::atomic<int> configured[kMaxDevices];
     if (int rc = allow_lds(kern, lds, configured)) return rc;
@@ -90,7 +102,7 @@ int launch_stream_aux(const FwdCall &c) {
     const int wg_needed = (c.n_d + 3) / 4;
     const int wg_cap = c.di->cus * (c.di->lds_per_cu / lds);
     hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), lds, c.st, c.Q, c.D, c.d_off,
-                       c.clamp0, c.scores, a);
+                       c.clamp0, c.scores, a, doc_list);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_stream_kernel<%d> launch: %s", NU, hipGetErrorString(e));
     return MSIM_OK;
@@ -121,6 +133,36 @@ int launch_stream(const FwdCall &c) {
     }
 #endif
     return launch_stream_aux<NU, F16, 2, true, ring_default>(c);     // nt stream, interleaved DMA issue
+}
+
+// K1s over the 13-bit image (maxsim_stream13.hip): the same ring depths and grid rule as launch_stream -- 2 slabs of 6.5 KiB for 5-8
+// units (60.25 KiB per workgroup: two per CU), 4 slabs below.  The documents the encoder flagged are skipped there and scored
+// from the blob by the raw K1s over their id list, into the same score columns; that launch exists only when the list is not empty.
+template <int NU>
+int launch_stream13(const FwdCall &c) {
+    constexpr int RING = NU >= 5 ? 2 : kStreamRing;
+    auto kern = msim::maxsim_stream13_kernel<NU, RING, 2>;
+    constexpr int lds = 4 * (RING * msim::kSlab13Bytes + msim::kStreamTokBytes);
+    static std::atomic<int> configured[kMaxDevices];
+    if (int rc = allow_lds(kern, lds, configured)) return rc;
+    msim::StreamArgs a;
+    a.ld = c.ld;
+    a.fq = flat_q(c);
+    a.n_q = c.n_q;
+    a.n_d = c.n_d;
+    a.flags = c.flags;
+    const int wg_needed = (c.n_d + 3) / 4;
+    const int wg_cap = c.di->cus * (c.di->lds_per_cu / lds);
+    hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), lds, c.st, c.Q, c.d_off, c.clamp0, c.scores, a,
+                       c.p13->image, c.p13->slab_off, c.p13->flagged);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_stream13_kernel<%d> launch: %s", NU, hipGetErrorString(e));
+    if (c.p13->n_list > 0) {
+        FwdCall l = c;
+        l.n_d = c.p13->n_list;
+        return launch_stream_aux<NU, false, 2, true, RING, true>(l, c.p13->list);
+    }
+    return MSIM_OK;
 }
 
 // ---- the plan of one tuned forward call, made on the host from the queries' lengths -- ONE definition, shared by the dispatch and
@@ -406,6 +448,20 @@ int fwd_dispatch(const FwdCall &c) {
     thread_local FlatPlan plan;
     if (int rc = flat_plan(host_q(c), c.n_q, plan)) return rc;
     if (plan.stream) {
+        if constexpr (!F16) {
+            if (c.p13 != nullptr) {
+                switch (plan.nu) {
+                    case 1: return launch_stream13<1>(c);
+                    case 2: return launch_stream13<2>(c);
+                    case 3: return launch_stream13<3>(c);
+                    case 4: return launch_stream13<4>(c);
+                    case 5: return launch_stream13<5>(c);
+                    case 6: return launch_stream13<6>(c);
+                    case 7: return launch_stream13<7>(c);
+                    default: return launch_stream13<8>(c);
+                }
+            }
+        }
         switch (plan.nu) {
             case 1: return launch_stream<1, F16>(c);
             case 2: return launch_stream<2, F16>(c);
@@ -695,9 +751,52 @@ bool box_on_panels_flat(int dtype, int dim, int n_q, int Lq) {
     return tpq > 2 || (Lq % msim::kTokTile) != 0;
 }
 
+int fwd_ragged_impl(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+                    const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, float *scores, int64_t ld_scores,
+                    uint32_t flags, void *workspace, void *stream, const Pack13View *p13);
+int fwd_impl(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, const uint8_t *d_clamp0,
+             int n_d, int dim, float *scores, int64_t ld_scores, uint32_t flags, void *workspace, void *stream, const Pack13View *p13);
+
+// the image arguments of the *_pack13 entries
+int check_pack13(const char *who, const void *image, const int32_t *slab_off, const uint8_t *flagged, const int32_t *list, int n_list,
+                 Pack13View *v) {
+    if (!image || !slab_off || !flagged || n_list < 0 || (n_list > 0 && !list)) return fail(MSIM_EINVAL, "%s: bad image arguments", who);
+    if (reinterpret_cast<uintptr_t>(image) & 15) return fail(MSIM_EINVAL, "%s: the image must be 16-byte aligned", who);
+    *v = Pack13View{static_cast<const uint8_t *>(image), slab_off, flagged, list, n_list};
+    return MSIM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int msim_fwd_pack13(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, const uint8_t *d_clamp0, int n_d,
+                    int dim, const void *image, const int32_t *slab_off, const uint8_t *flagged, const int32_t *list, int n_list,
+                    float *scores, int64_t ld_scores, uint32_t flags, void *workspace, void *stream) {
+    Pack13View v;
+    if (int rc = check_pack13("msim_fwd_pack13", image, slab_off, flagged, list, n_list, &v)) return rc;
+    return fwd_impl(dtype, Q, n_q, Lq, D, d_off, d_clamp0, n_d, dim, scores, ld_scores, flags, workspace, stream, &v);
+}
+
+int msim_fwd_ragged_pack13(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+                           const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, const void *image, const int32_t *slab_off,
+                           const uint8_t *flagged, const int32_t *list, int n_list, float *scores, int64_t ld_scores, uint32_t flags,
+                           void *workspace, void *stream) {
+    Pack13View v;
+    if (int rc = check_pack13("msim_fwd_ragged_pack13", image, slab_off, flagged, list, n_list, &v)) return rc;
+    return fwd_ragged_impl(dtype, Qt, q_off, q_off_host, n_q, D, d_off, d_clamp0, n_d, dim, scores, ld_scores, flags, workspace, stream, &v);
+}
+
+int msim_fwd_ragged(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+                    const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, float *scores, int64_t ld_scores,
+                    uint32_t flags, void *workspace, void *stream) {
+    return fwd_ragged_impl(dtype, Qt, q_off, q_off_host, n_q, D, d_off, d_clamp0, n_d, dim, scores, ld_scores, flags, workspace, stream, nullptr);
+}
+
+int msim_fwd(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, const uint8_t *d_clamp0,
+             int n_d, int dim, float *scores, int64_t ld_scores, uint32_t flags, void *workspace, void *stream) {
+    return fwd_impl(dtype, Q, n_q, Lq, D, d_off, d_clamp0, n_d, dim, scores, ld_scores, flags, workspace, stream, nullptr);
+}
 
 size_t msim_fwd_workspace_bytes(int dtype, int n_q, int Lq, int n_d, int dim) {
     // the only scratch msim_fwd uses: the progress counters of K1b's convoy, needed once more than one query block streams a
@@ -733,9 +832,13 @@ size_t msim_fwd_ragged_workspace_bytes(int dtype, const int32_t *q_off_host, int
     return flat_workspace_bytes(HostQ{q_off_host, 0, 0, 1}, n_q);
 }
 
-int msim_fwd_ragged(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+}  // extern "C"
+
+namespace {
+
+int fwd_ragged_impl(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
                     const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, float *scores, int64_t ld_scores,
-                    uint32_t flags, void *workspace, void *stream) {
+                    uint32_t flags, void *workspace, void *stream, const Pack13View *p13) {
     if (n_q < 0 || n_d < 0) return fail(MSIM_EINVAL, "negative size (n_q=%d n_d=%d)", n_q, n_d);
     if (n_q == 0 || n_d == 0) return MSIM_OK;
     if (!scores || !Qt || !D || !d_off || !q_off || !q_off_host) return fail(MSIM_EINVAL, "null pointer argument");
@@ -783,11 +886,12 @@ int msim_fwd_ragged(int dtype, const void *Qt, const int32_t *q_off, const int32
         }
         return dtype == MSIM_DTYPE_F16 ? launch_batch_panels_flat<true>(c) : launch_batch_panels_flat<false>(c);
     }
+    c.p13 = p13;                      // width 128; fwd_dispatch uses it for bf16 K1s plans only
     return dtype == MSIM_DTYPE_F16 ? fwd_dispatch<true>(c) : fwd_dispatch<false>(c);
 }
 
-int msim_fwd(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, const uint8_t *d_clamp0,
-             int n_d, int dim, float *scores, int64_t ld_scores, uint32_t flags, void *workspace, void *stream) {
+int fwd_impl(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, const uint8_t *d_clamp0,
+             int n_d, int dim, float *scores, int64_t ld_scores, uint32_t flags, void *workspace, void *stream, const Pack13View *p13) {
     if (n_q < 0 || n_d < 0 || Lq <= 0) return fail(MSIM_EINVAL, "negative size (n_q=%d n_d=%d Lq=%d)", n_q, n_d, Lq);
     if (n_q == 0 || n_d == 0) return MSIM_OK;
     if (!scores) return fail(MSIM_EINVAL, "null pointer argument");
@@ -895,8 +999,13 @@ int msim_fwd(int dtype, const void *Q, int n_q, int Lq, const void *D, const int
     c.avg_rows = avg_rows;
     c.st = static_cast<hipStream_t>(stream);
     c.workspace = workspace;
+    c.p13 = p13;
     return dtype == MSIM_DTYPE_F16 ? fwd_dispatch<true>(c) : fwd_dispatch<false>(c);
 }
+
+}  // namespace
+
+extern "C" {
 
 // ---------------------------------------------------------------- plain similarity matrix entry point
 int msim_sim_matrix(int dtype, const void *A, int n_a, const void *B, int n_b, int dim, float *out, int64_t ld_out,

@@ -57,15 +57,18 @@ __device__ __forceinline__ void wait_vmcnt() {
 // AUX : cache-policy bits of the LDS-DMA loads (0 = default, 2 = nt: streamed once, do not keep in L2 / MALL)
 // IL  : issue the 8 LDS-DMA pieces of the next slab BETWEEN the MFMAs of the current one instead of in a block in
 //       front of them (the matrix pipe idles while a block of DMA instructions issues; one piece per NU MFMAs hides)
+// LIST: the launch scores the documents doc_list[0 .. a.n_d) instead of 0 .. a.n_d-1 (the flagged documents behind the packed form,
+//       maxsim_stream13.hip); doc_list is null and unread without it
 // At most 8 units (4 token tiles of 32): launch bounds ask for two waves per SIMD (<= 256 registers), which the 2-slab ring needs to
 // put two workgroups on a CU; without the bound hipcc gives every unit an accumulator of its own and lands at 290 registers.
-template <int NU, int RING, bool F16, int AUX = 0, bool IL = false>
+template <int NU, int RING, bool F16, int AUX = 0, bool IL = false, bool LIST = false>
 __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *__restrict__ Qt,      // [T, 128] flat query tokens
                                                             const uint16_t *__restrict__ D,       // [rows, 128] bf16
                                                             const int32_t *__restrict__ d_off,    // [n_d + 1]
                                                             const uint8_t *__restrict__ clamp0,   // [n_d] or null
                                                             float *__restrict__ scores,           // [n_q, ld]
-                                                            StreamArgs a) {
+                                                            StreamArgs a,
+                                                            const int32_t *__restrict__ doc_list = nullptr) {   // [a.n_d] (LIST)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -73,6 +76,10 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
     char *tokmax = smem + 4 * (RING * kSlabBytes) + wave * kStreamTokBytes;
     const int gw = blockIdx.x * 4 + wave;  // global wave id: this wave owns documents gw, gw+GW, ...
     const int GW = gridDim.x * 4;
+    auto doc_id = [&](int i) -> int {      // the document behind position i of this launch (wave-uniform)
+        if constexpr (LIST) return doc_list[i];
+        else return i;
+    };
 
     // ---- query fragments: B operands, resident for the whole kernel (16 VGPRs per 16-token unit)
     const int n_tok = flat_qoff(a.fq, a.n_q);
@@ -112,7 +119,8 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
     __amdgpu_buffer_rsrc_t p_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)D, 0, 0, 0x00020000);
     auto p_open = [&]() {  // position on the next non-empty document at or after p_idx
         while (p_idx < a.n_d) {
-            const int r0 = d_off[p_idx], r1 = d_off[p_idx + 1];
+            const int p_doc = doc_id(p_idx);
+            const int r0 = d_off[p_doc], r1 = d_off[p_doc + 1];
             p_len = r1 - r0;
             if (p_len > 0) {
                 p_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(D + (size_t)r0 * kDim), 0,
@@ -175,7 +183,8 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
 
     const bool ref_bf16 = (a.flags & kFlagRefBf16) != 0;
     int c_slot = 0;
-    for (int c_idx = gw; c_idx < a.n_d; c_idx += GW) {
+    for (int c_pos = gw; c_pos < a.n_d; c_pos += GW) {
+        const int c_idx = doc_id(c_pos);
         const int len = d_off[c_idx + 1] - d_off[c_idx];
         float m[NU];
 #pragma unroll

@@ -136,6 +136,12 @@ def maxsim_scores(queries: Union[torch.Tensor, PackedQueries], corpus: PackedCor
     Asynchronous on torch's current stream.  `ref_rounding=True` reproduces the rounding the reference
     applies when torch evaluates processing_utils.py:179 in the embeddings' own 16-bit dtype
     (`ref_bf16` is the older name of the same switch).
+
+    A few-query scan (at most 8 queries and 128 tokens in all: the stream kernel K1s) of a bf16 corpus of width 128 reads the
+    corpus' 13-bit image when it has one (`PackedCorpus.pack13`): 0.8125 x the bytes, the same score bits.  A corpus object that
+    takes this path a SECOND time unchanged is taken to be resident and its image is built then (one pass over the blob, about
+    two scans' time, 0.8125 x the blob's bytes of device memory) -- a one-off drop-in corpus is scanned once and never pays.
+    COLPALI_AMD_PACK13=1 builds on the first scan, =0 never; `PackedCorpus.pack13` lists when the library declines.
     """
     if ref_bf16 is not None:
         ref_rounding = ref_bf16
@@ -161,10 +167,23 @@ def maxsim_scores(queries: Union[torch.Tensor, PackedQueries], corpus: PackedCor
     if n:       # launch-shape hint (include/maxsim.h: MSIM_FLAG_AVG_ROWS): the average document length, which the host side knows
         flags |= min(65535, max(1, corpus.average_rows())) << 8
     ld = out.stride(0) if n_q > 1 else max(n, 1)
+    img = None                      # the corpus' 13-bit image: K1s plans (maxsim_abi.hip: flat_plan) of bf16 / width-128 scans only
+    if n and n_q <= 8 and dim == 128 and queries.dtype == torch.bfloat16 and queries.device.type == "cuda":
+        tokens = int(queries.offsets_host[-1]) if flat else n_q * queries.shape[1]
+        if tokens <= 128:
+            img = corpus._pack13_for_scan()
     if flat:
         with torch.cuda.device(queries.device):
             oh = queries.offsets_host
             ws = _lib.workspace(L.msim_fwd_ragged_workspace_bytes(dt, oh.data_ptr(), n_q, n, dim), queries.device)
+            if img is not None:
+                rc = L.msim_fwd_ragged_pack13(dt, _lib.ptr(queries.tokens), _lib.ptr(queries.offsets), oh.data_ptr(), n_q,
+                                              _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets), _lib.ptr(corpus.clamp0), n, dim,
+                                              _lib.ptr(img.image), _lib.ptr(img.slab_off), _lib.ptr(img.flagged), _lib.ptr(img.ids),
+                                              img.n_flagged, _lib.ptr(out), ld, flags, _lib.ptr(ws),
+                                              _lib.current_stream_handle(queries.device))
+                _lib.check(rc, "msim_fwd_ragged_pack13")
+                return out
             rc = L.msim_fwd_ragged(dt, _lib.ptr(queries.tokens), _lib.ptr(queries.offsets), oh.data_ptr(), n_q, _lib.ptr(corpus.blob),
                                    _lib.ptr(corpus.offsets), _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(out), ld, flags, _lib.ptr(ws),
                                    _lib.current_stream_handle(queries.device))
@@ -179,6 +198,13 @@ def maxsim_scores(queries: Union[torch.Tensor, PackedQueries], corpus: PackedCor
         for q0 in range(0, n_q, group):
             nq = min(group, n_q - q0)
             ws = _lib.workspace(L.msim_fwd_workspace_bytes(dt, nq, Lq, n, dim), queries.device)
+            if img is not None:
+                rc = L.msim_fwd_pack13(dt, _lib.ptr(queries[q0:q0 + nq]), nq, Lq, _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets),
+                                       _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(img.image), _lib.ptr(img.slab_off),
+                                       _lib.ptr(img.flagged), _lib.ptr(img.ids), img.n_flagged, _lib.ptr(out[q0:q0 + nq]), ld,
+                                       flags, _lib.ptr(ws), _lib.current_stream_handle(queries.device))
+                _lib.check(rc, "msim_fwd_pack13")
+                continue
             rc = L.msim_fwd(dt, _lib.ptr(queries[q0:q0 + nq]), nq, Lq, _lib.ptr(corpus.blob), _lib.ptr(corpus.offsets),
                             _lib.ptr(corpus.clamp0), n, dim, _lib.ptr(out[q0:q0 + nq]), ld,
                             flags, _lib.ptr(ws), _lib.current_stream_handle(queries.device))

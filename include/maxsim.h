@@ -165,6 +165,37 @@ int msim_fwd_ragged(int dtype, const void *Qt, const int32_t *q_off, const int32
                     uint32_t flags, void *workspace, void *stream);
 
 /*
+ * THE 13-BIT IMAGE of a resident bf16 corpus of width 128.  Rows the scorers see are L2-normalised, so the exponent field of (all
+ * but a handful of) their values lies in [96, 127] and bits 14..12 of the 16-bit pattern are the constant 011: the image keeps the
+ * other 13 bits -- 0.8125 x the bytes, lossless -- in 6656-byte slabs of 32 rows laid out in the order a wave of the few-query stream
+ * kernel (K1s) consumes them.  The format is private to the library (csrc/pack13.hip) and may change with it: build the image with
+ * the library that scans it.  A document that holds ONE value outside the range (zero, denormal, |x| < 2^-31, |x| >= 2, inf, NaN)
+ * is FLAGGED; the forward entries below score flagged documents from the blob, so every score carries the bits msim_fwd /
+ * msim_fwd_ragged return.
+ *   slab_off  int32 [n_d + 1]  made by the caller: slab_off[0] = 0, slab_off[c + 1] = slab_off[c] + ceil(rows of document c / 32)
+ *   image     msim_pack13_image_bytes(slab_off[n_d]) bytes, 16-byte aligned
+ *   flagged   uint8 [n_d], list int32 [n_d] (the flagged ids, ascending), count int32 [1]      -- written by the encoder
+ * msim_pack13_encode is one pass over the blob (asynchronous on `stream`; read `count` after synchronising).  msim_pack13_decode
+ * is a test aid: the image back as [rows, 128] bf16 rows (those of flagged documents decode to other values).
+ * msim_fwd_pack13 / msim_fwd_ragged_pack13 take the image beside the arguments of msim_fwd / msim_fwd_ragged and return the same
+ * bits: calls whose plan is K1s (msim_fwd_plan: at most 8 queries and 128 tokens in all) on bf16 rows of width 128 scan the image
+ * -- plus one list-driven launch of K1s over the blob when n_list > 0 --, every other call ignores the image and runs as without it.
+ * `list` holds the n_list = *count flagged ids (NULL when n_list is 0).
+ */
+size_t msim_pack13_image_bytes(int64_t n_slabs);
+int msim_pack13_encode(const void *D, const int32_t *d_off, const int32_t *slab_off, int n_d, int64_t n_slabs, void *image,
+                       uint8_t *flagged, int32_t *list, int32_t *count, void *stream);
+int msim_pack13_decode(const void *image, const int32_t *d_off, const int32_t *slab_off, int n_d, int64_t n_slabs, void *out,
+                       void *stream);
+int msim_fwd_pack13(int dtype, const void *Q, int n_q, int Lq, const void *D, const int32_t *d_off, const uint8_t *d_clamp0,
+                    int n_d, int dim, const void *image, const int32_t *slab_off, const uint8_t *flagged, const int32_t *list,
+                    int n_list, float *scores, int64_t ld_scores, uint32_t flags, void *workspace, void *stream);
+int msim_fwd_ragged_pack13(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const void *D,
+                           const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int dim, const void *image,
+                           const int32_t *slab_off, const uint8_t *flagged, const int32_t *list, int n_list, float *scores,
+                           int64_t ld_scores, uint32_t flags, void *workspace, void *stream);
+
+/*
  * RERANKING: the same scores for a LIST of candidate documents per query -- the exact second stage behind a cheap first one (pooled
  * pages, BM25, a bi-encoder, a metadata filter, hard-negative mining).  For every entry (q, j) of cand [n_q, m] (row stride
  * ld_cand >= m, int64 GLOBAL ids; the shard's document c has id id_base + c):
