@@ -80,40 +80,41 @@ msim::FlatQ flat_q(const FwdCall &c) { return msim::FlatQ{c.q_off, c.Lq, c.seg, 
 
 // Cache policy of K1s's document stream: every byte is read once by one CU, so the LDS-DMA loads carry `nt`
 // (do not allocate in L2 / MALL).  Measured on MI355X, 16 GiB shard: 6.31 -> 7.02 TB/s at 1 query, 6.08 -> 6.45 TB/s
-// at 4 queries.  MSIM_STREAM_NT=0 switches it off for A/B measurements (tuning knob, not part of the ABI).
+// at 4 queries.  MSIM_STREAM_NT=0 switches it off (AUX = 0) for A/B measurements (tuning knob, not part of the ABI).
 int stream_nt() {
     static const int v = ab_env("MSIM_STREAM_NT", 1) != 0;
     return v;
 }
 
-// LIST: the documents doc_list[0 .. c.n_d) instead of 0 .. c.n_d-1
-template <int NU, bool F16, int AUX, bool IL, int RING = kStreamRing, bool LIST = false>
-int launch_stream_aux(const FwdCall &c, const int32_t *doc_list = nullptr) {
-    auto kern = msim::maxsim_stream_kernel<NU, RING, F16, AUX, IL, LIST>;
-    constexpr int lds = 4 * (RING * msim::kSlabBytes + msim::kStreamTokBytes);
-    static std::atomic<int> configured[kMaxDevices];
-    if (int rc = allow_lds(kern, lds, configured)) return rc;
+// what the launches of the K1s family share: the kernel arguments taken from the call, and the grid -- one wave per document, four
+// waves per workgroup, never more workgroups than are resident at once (the waves walk the documents grid-stride)
+msim::StreamArgs stream_args(const FwdCall &c) {
     msim::StreamArgs a;
     a.ld = c.ld;
     a.fq = flat_q(c);
     a.n_q = c.n_q;
     a.n_d = c.n_d;
     a.flags = c.flags;
+    return a;
+}
+dim3 stream_grid(const FwdCall &c, int lds) {
     const int wg_needed = (c.n_d + 3) / 4;
     const int wg_cap = c.di->cus * (c.di->lds_per_cu / lds);
-    hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), lds, c.st, c.Q, c.D, c.d_off,
-                       c.clamp0, c.scores, a, doc_list);
+    return dim3(wg_needed < wg_cap ? wg_needed : wg_cap);
+}
+
+// LIST: the documents doc_list[0 .. c.n_d) instead of 0 .. c.n_d-1
+template <int NU, bool F16, int AUX, int RING = kStreamRing, bool LIST = false>
+int launch_stream_aux(const FwdCall &c, const int32_t *doc_list = nullptr) {
+    auto kern = msim::maxsim_stream_kernel<NU, RING, F16, AUX, LIST>;
+    constexpr int lds = 4 * (RING * msim::kSlabBytes + msim::kStreamTokBytes);
+    static std::atomic<int> configured[kMaxDevices];
+    if (int rc = allow_lds(kern, lds, configured)) return rc;
+    hipLaunchKernelGGL(kern, stream_grid(c, lds), dim3(256), lds, c.st, c.Q, c.D, c.d_off, c.clamp0, c.scores, stream_args(c),
+                       doc_list);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_stream_kernel<%d> launch: %s", NU, hipGetErrorString(e));
     return MSIM_OK;
-}
-
-// LDS-DMA pieces of the next slab issued between the MFMAs of the current one (default).  Interleaved A/B on a 16 GiB
-// shard (profiles/r01_logs/ab_stream_il.log): 4 queries 6.37-6.43 -> 6.52-6.55 TB/s, 6-8 queries +1 %, 1-2 queries unchanged.
-// MSIM_STREAM_IL=0 selects the block-issue variant (tuning knob, not part of the ABI).
-int stream_il() {
-    static const int v = ab_env("MSIM_STREAM_IL", 1) != 0;
-    return v;
 }
 
 template <int NU, bool F16>
@@ -127,12 +128,11 @@ int launch_stream(const FwdCall &c) {
     {
         static const int ring_env = ab_env("MSIM_STREAM_RING", 0);
         const int ring = ring_env ? ring_env : ring_default;
-        if (ring == 2) return launch_stream_aux<NU, F16, 2, true, 2>(c);
-        if (stream_il() && stream_nt()) return launch_stream_aux<NU, F16, 2, true>(c);
-        return stream_nt() ? launch_stream_aux<NU, F16, 2, false>(c) : launch_stream_aux<NU, F16, 0, false>(c);
+        if (ring == 2) return launch_stream_aux<NU, F16, 2, 2>(c);
+        return stream_nt() ? launch_stream_aux<NU, F16, 2>(c) : launch_stream_aux<NU, F16, 0>(c);
     }
 #endif
-    return launch_stream_aux<NU, F16, 2, true, ring_default>(c);     // nt stream, interleaved DMA issue
+    return launch_stream_aux<NU, F16, 2, ring_default>(c);     // nt stream
 }
 
 // K1s over the 13-bit image (maxsim_stream13.hip): the same ring depths and grid rule as launch_stream -- 2 slabs of 6.5 KiB for 5-8
@@ -145,24 +145,31 @@ int launch_stream13(const FwdCall &c) {
     constexpr int lds = 4 * (RING * msim::kSlab13Bytes + msim::kStreamTokBytes);
     static std::atomic<int> configured[kMaxDevices];
     if (int rc = allow_lds(kern, lds, configured)) return rc;
-    msim::StreamArgs a;
-    a.ld = c.ld;
-    a.fq = flat_q(c);
-    a.n_q = c.n_q;
-    a.n_d = c.n_d;
-    a.flags = c.flags;
-    const int wg_needed = (c.n_d + 3) / 4;
-    const int wg_cap = c.di->cus * (c.di->lds_per_cu / lds);
-    hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), lds, c.st, c.Q, c.d_off, c.clamp0, c.scores, a,
+    hipLaunchKernelGGL(kern, stream_grid(c, lds), dim3(256), lds, c.st, c.Q, c.d_off, c.clamp0, c.scores, stream_args(c),
                        c.p13->image, c.p13->slab_off, c.p13->flagged);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_stream13_kernel<%d> launch: %s", NU, hipGetErrorString(e));
     if (c.p13->n_list > 0) {
         FwdCall l = c;
         l.n_d = c.p13->n_list;
-        return launch_stream_aux<NU, false, 2, true, RING, true>(l, c.p13->list);
+        return launch_stream_aux<NU, false, 2, RING, true>(l, c.p13->list);
     }
     return MSIM_OK;
+}
+
+// K1s holds 1..8 units: launch(std::integral_constant<int, NU>) for the plan's count
+template <class Launch>
+int dispatch_units(int nu, Launch &&launch) {
+    switch (nu) {
+        case 1: return launch(std::integral_constant<int, 1>{});
+        case 2: return launch(std::integral_constant<int, 2>{});
+        case 3: return launch(std::integral_constant<int, 3>{});
+        case 4: return launch(std::integral_constant<int, 4>{});
+        case 5: return launch(std::integral_constant<int, 5>{});
+        case 6: return launch(std::integral_constant<int, 6>{});
+        case 7: return launch(std::integral_constant<int, 7>{});
+        default: return launch(std::integral_constant<int, 8>{});
+    }
 }
 
 // ---- the plan of one tuned forward call, made on the host from the queries' lengths -- ONE definition, shared by the dispatch and
@@ -449,29 +456,10 @@ int fwd_dispatch(const FwdCall &c) {
     if (int rc = flat_plan(host_q(c), c.n_q, plan)) return rc;
     if (plan.stream) {
         if constexpr (!F16) {
-            if (c.p13 != nullptr) {
-                switch (plan.nu) {
-                    case 1: return launch_stream13<1>(c);
-                    case 2: return launch_stream13<2>(c);
-                    case 3: return launch_stream13<3>(c);
-                    case 4: return launch_stream13<4>(c);
-                    case 5: return launch_stream13<5>(c);
-                    case 6: return launch_stream13<6>(c);
-                    case 7: return launch_stream13<7>(c);
-                    default: return launch_stream13<8>(c);
-                }
-            }
+            if (c.p13 != nullptr)
+                return dispatch_units(plan.nu, [&](auto nu) { return launch_stream13<decltype(nu)::value>(c); });
         }
-        switch (plan.nu) {
-            case 1: return launch_stream<1, F16>(c);
-            case 2: return launch_stream<2, F16>(c);
-            case 3: return launch_stream<3, F16>(c);
-            case 4: return launch_stream<4, F16>(c);
-            case 5: return launch_stream<5, F16>(c);
-            case 6: return launch_stream<6, F16>(c);
-            case 7: return launch_stream<7, F16>(c);
-            default: return launch_stream<8, F16>(c);
-        }
+        return dispatch_units(plan.nu, [&](auto nu) { return launch_stream<decltype(nu)::value, F16>(c); });
     }
     // one query block = every corpus byte is read once by one workgroup: stream it past L2 / MALL (nt), like K1s does.
     // MSIM_BATCH_NT=0 switches that off for A/B measurements (tuning knob, not part of the ABI).
@@ -620,10 +608,7 @@ int launch_stream_panels(const FwdCall &c) {
     a.Lq = c.Lq;
     a.n_d = c.n_d;
     a.flags = c.flags;
-    const int wg_needed = (c.n_d + 3) / 4;
-    const int wg_cap = c.di->cus * (c.di->lds_per_cu / lds);
-    hipLaunchKernelGGL(kern, dim3(wg_needed < wg_cap ? wg_needed : wg_cap), dim3(256), lds, c.st, c.Q, c.D, c.d_off, c.clamp0,
-                       c.scores, a);
+    hipLaunchKernelGGL(kern, stream_grid(c, lds), dim3(256), lds, c.st, c.Q, c.D, c.d_off, c.clamp0, c.scores, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_stream_panels_kernel<%d,%d> launch: %s", QT, TPQ, hipGetErrorString(e));
     return MSIM_OK;

@@ -228,7 +228,7 @@ __device__ __forceinline__ void cand_item(const uint16_t *__restrict__ Qt, const
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(D + (size_t)r0 * kDim), 0, len * kRowBytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t null_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)D, 0, 0, 0x00020000);
 
-    // every request is 8 loads, real or through an empty descriptor: the number of loads in flight is a constant (K1s's IL form)
+    // every request is 8 loads, real or through an empty descriptor: the number of loads in flight is a constant (as in K1s)
     int p = 0, p_slot = 0;
     auto request_piece = [&](int slab, int slot, int i) {
         const bool live = slab < n_slabs;

@@ -55,13 +55,13 @@ __device__ __forceinline__ void wait_vmcnt() {
 // RING: slabs in the wave-private LDS ring
 // F16 : embeddings are IEEE half instead of bfloat16
 // AUX : cache-policy bits of the LDS-DMA loads (0 = default, 2 = nt: streamed once, do not keep in L2 / MALL)
-// IL  : issue the 8 LDS-DMA pieces of the next slab BETWEEN the MFMAs of the current one instead of in a block in
-//       front of them (the matrix pipe idles while a block of DMA instructions issues; one piece per NU MFMAs hides)
 // LIST: the launch scores the documents doc_list[0 .. a.n_d) instead of 0 .. a.n_d-1 (the flagged documents behind the packed form,
 //       maxsim_stream13.hip); doc_list is null and unread without it
+// The 8 LDS-DMA pieces of the next slab are issued BETWEEN the MFMAs of the current one, one piece per NU MFMAs: the matrix pipe idles
+// while a block of DMA instructions issues in front of them (that form measured behind this one in round 1 and is gone).
 // At most 8 units (4 token tiles of 32): launch bounds ask for two waves per SIMD (<= 256 registers), which the 2-slab ring needs to
 // put two workgroups on a CU; without the bound hipcc gives every unit an accumulator of its own and lands at 290 registers.
-template <int NU, int RING, bool F16, int AUX = 0, bool IL = false, bool LIST = false>
+template <int NU, int RING, bool F16, int AUX = 0, bool LIST = false>
 __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *__restrict__ Qt,      // [T, 128] flat query tokens
                                                             const uint16_t *__restrict__ D,       // [rows, 128] bf16
                                                             const int32_t *__restrict__ d_off,    // [n_d + 1]
@@ -133,24 +133,8 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
     };
     p_open();
     int p_slot = 0;
-    auto produce = [&]() -> bool {  // returns false when the stream is exhausted (nothing issued)
-        if (p_idx >= a.n_d) return false;
-        char *dst = ring + p_slot * kSlabBytes;
-        const int soff = p_row * kRowBytes;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(p_rsrc, MSIM_LDS(dst + i * 1024), 16, src_off[i & 3],
-                                                     soff + i * 1024, 0, AUX);
-        p_slot = (p_slot + 1 == RING) ? 0 : p_slot + 1;
-        p_row += kSlabRows;
-        if (p_row >= p_len) {
-            p_idx += GW;
-            p_open();
-        }
-        return true;
-    };
 
-    // IL: every request is 8 loads, real or through an empty descriptor (out-of-range lanes fetch nothing and count like any
+    // every request is 8 loads, real or through an empty descriptor (out-of-range lanes fetch nothing and count like any
     // other load), so the number of outstanding loads is a constant and the instruction stream has no branches
     const __amdgpu_buffer_rsrc_t null_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)D, 0, 0, 0x00020000);
     auto advance = [&](bool live) {
@@ -164,21 +148,16 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
         }
     };
     // prologue: RING-1 slabs in flight
-    if constexpr (IL) {
 #pragma unroll
-        for (int k = 0; k < RING - 1; ++k) {
-            const bool live = p_idx < a.n_d;
-            const __amdgpu_buffer_rsrc_t rs = live ? p_rsrc : null_rsrc;
-            char *dst = ring + p_slot * kSlabBytes;
-            const int soff = live ? p_row * kRowBytes : 0;
+    for (int k = 0; k < RING - 1; ++k) {
+        const bool live = p_idx < a.n_d;
+        const __amdgpu_buffer_rsrc_t rs = live ? p_rsrc : null_rsrc;
+        char *dst = ring + p_slot * kSlabBytes;
+        const int soff = live ? p_row * kRowBytes : 0;
 #pragma unroll
-            for (int i = 0; i < 8; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, MSIM_LDS(dst + i * 1024), 16, src_off[i & 3], soff + i * 1024, 0, AUX);
-            advance(live);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < RING - 1; ++i) produce();
+        for (int i = 0; i < 8; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, MSIM_LDS(dst + i * 1024), 16, src_off[i & 3], soff + i * 1024, 0, AUX);
+        advance(live);
     }
 
     const bool ref_bf16 = (a.flags & kFlagRefBf16) != 0;
@@ -190,30 +169,23 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
 #pragma unroll
         for (int u = 0; u < NU; ++u) m[u] = -INFINITY;
 
-        // one slab: request the next one (IL: its 8 pieces go out between the MFMAs), fetch the 8 operand fragments once, then the
+        // one slab: request the next one (its 8 pieces go out between the MFMAs), fetch the 8 operand fragments once, then the
         // MFMAs of all units (maxsim_common.hpp: slab_units, folds one group late).  kTail (rows past the document end masked to
         // -inf) is a compile-time variant so that the full-slab body has no branch in it.
         auto slab = [&](auto tail_c, int rows_left) {
             constexpr bool kTail = decltype(tail_c)::value;
             // next slab to request (its slot is the one consumed in the previous iteration: free again)
+            // DO NOT REORDER: these four are declared in front of the wait and assigned behind it.  Declared behind it, hipcc swaps two
+            // scalar selects in every slab step of every instantiation; check any change here with tools/kernel_diff.py.
             bool nx_live = false;
             char *nx_dst = ring;
             int nx_soff = 0;
             __amdgpu_buffer_rsrc_t nx_rsrc = p_rsrc;
-            if constexpr (IL) {
-                wait_vmcnt<8 * (RING - 2)>();     // RING - 1 requests are outstanding: all but the oldest may stay in flight
-                nx_live = p_idx < a.n_d;
-                nx_dst = ring + p_slot * kSlabBytes;
-                nx_soff = nx_live ? p_row * kRowBytes : 0;
-                nx_rsrc = nx_live ? p_rsrc : null_rsrc;
-            } else {
-                // the slot consumed in the previous iteration is free again: refill it, then wait for this slab
-                const bool issued = produce();
-                if (issued)
-                    wait_vmcnt<8 * (RING - 1)>();
-                else
-                    wait_vmcnt<0>();
-            }
+            wait_vmcnt<8 * (RING - 2)>();     // RING - 1 requests are outstanding: all but the oldest may stay in flight
+            nx_live = p_idx < a.n_d;
+            nx_dst = ring + p_slot * kSlabBytes;
+            nx_soff = nx_live ? p_row * kRowBytes : 0;
+            nx_rsrc = nx_live ? p_rsrc : null_rsrc;
 
             const char *src = ring + c_slot * kSlabBytes;
             c_slot = (c_slot + 1 == RING) ? 0 : c_slot + 1;
@@ -223,15 +195,13 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
 #pragma unroll
                 for (int ks = 0; ks < kKSteps16; ++ks) af[g][ks] = *reinterpret_cast<const bf16x8 *>(src + rd_off[g][ks]);
             slab_units<F16, NU, kTail, true>(m, af, qu, rows_left, lane, [&](int mf) {
-                if constexpr (IL) {                 // one DMA piece per NU MFMAs: 8 per slab (a slab is 8 * NU MFMAs)
-                    if (mf % NU == 0) {
-                        const int i = mf / NU;
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(nx_rsrc, MSIM_LDS(nx_dst + i * 1024), 16, src_off[i & 3],
-                                                                 nx_soff + i * 1024, 0, AUX);
-                    }
+                if (mf % NU == 0) {                 // one DMA piece per NU MFMAs: 8 per slab (a slab is 8 * NU MFMAs)
+                    const int i = mf / NU;
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(nx_rsrc, MSIM_LDS(nx_dst + i * 1024), 16, src_off[i & 3],
+                                                             nx_soff + i * 1024, 0, AUX);
                 }
             });
-            if constexpr (IL) advance(nx_live);                                  // the 8 pieces are out: advance the cursor
+            advance(nx_live);                                  // the 8 pieces are out: advance the cursor
         };
         const int n_full = len / kSlabRows, rem = len - n_full * kSlabRows;
         for (int s = 0; s < n_full; ++s) slab(std::false_type{}, kSlabRows);

@@ -140,7 +140,8 @@ def test_fewer_documents_than_waves_and_an_empty_document(amd, monkeypatch):
             assert _same_bits(_packed(amd, q, corpus), _plain(amd, monkeypatch, q, corpus)), lens
 
 
-@pytest.mark.parametrize("n_q,lq", [(4, 32), (2, 16)])
+# the only test that reaches the list-driven launch of the raw K1s: every unit count it is built for (1..8), and the headline plan
+@pytest.mark.parametrize("n_q,lq", [(4, 32)] + [(n, 16) for n in range(1, 9)])
 def test_flagged_documents_are_scored_from_the_blob(amd, monkeypatch, n_q, lq):
     g = torch.Generator().manual_seed(99)
     lens = ([64, 33, 200] * 60)[: 160]
