@@ -22,6 +22,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      dimension (34 / 66 bytes per row instead of 256), candidate lists reranked straight from them
   * residual_scores               -- the full scan of such a shard, a page decoded once per group of queries: the score matrix
                                      behind ShardedRetriever(rc, score_fn=residual_scores) -- search, filter=, group_by=, mine
+  * LiveResidualCorpus           -- such a shard filled incrementally from pages that are never kept: add (one fused encode pass),
+                                     delete, compact in place; the lifecycle LiveCorpus gives the bf16 shard
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
@@ -37,6 +39,7 @@ from .filter import PageFilter
 from .group import PageGroups, group_reduce, group_select
 from .int8_index import Int8Index, int8_scores, quantize_queries
 from .live import LiveCorpus
+from .live_residual import LiveResidualCorpus
 from .mine import gather_pages, mine_hard_negatives
 from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPairwiseCELoss,
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
@@ -71,6 +74,7 @@ __all__ = [
     "residual_scores",
     "train_residual_codec",
     "LiveCorpus",
+    "LiveResidualCorpus",
     "PageFilter",
     "PageGroups",
     "group_reduce",

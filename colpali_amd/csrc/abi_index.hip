@@ -1,5 +1,6 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the first-stage indexes -- fixed dimensional encodings, the int8
-// token-level index and the centroid-code index -- and the residual-compressed corpus built on the centroid codes.
+// token-level index and the centroid-code index -- and the residual-compressed corpus built on the centroid codes, with the fused
+// append-encode of its live form.
 // Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
 // frees or synchronises, so every entry point is hipGraph-capturable.  The kernels included below are defined and launched in
 // this translation unit and in no other.
@@ -15,6 +16,7 @@
 #include "centroid_index.hip"
 #include "residual_codec.hip"
 #include "residual_scan.hip"
+#include "residual_live.hip"
 
 using namespace msim_abi;
 
@@ -530,6 +532,43 @@ int msim_res_scores(int dtype, const void *Qt, const int32_t *q_off, const int32
     hipLaunchKernelGGL(msim::res_scan_poison_kernel, dim3((unsigned)(pblocks < wg_cap * 4 ? pblocks : wg_cap * 4)), dim3(256), 0, st, status,
                        n_q, n_d, out_scores, (long long)ld_scores);
     return launch_failed("res_scan_kernel");
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the live compressed shard: fused append-encode (residual_live.hip)
+extern "C" {
+
+int msim_res_append(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows, const void *C,
+                    int K, const float *cutoffs, int bits, uint16_t *codes, uint8_t *residuals, int64_t dst_row0, int64_t dst_rows,
+                    int32_t *status, void *stream) {
+    const char *who = "msim_res_append";
+    if (n_d < 0 || n_rows < 0 || max_doc_rows < 0 || dst_row0 < 0 || dst_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_d=%d rows=%lld max_doc_rows=%d dst_row0=%lld dst_rows=%lld)", who, n_d,
+                    (long long)n_rows, max_doc_rows, (long long)dst_row0, (long long)dst_rows);
+    if (dim != msim::kDim) return fail(MSIM_EINVAL, "%s: rows of width %d; the residual codec takes width %d", who, dim, msim::kDim);
+    if (int rc = res_check_format(who, dtype, dim, K, bits)) return rc;
+    if (n_rows > dst_rows - dst_row0)
+        return fail(MSIM_EINVAL, "%s: rows %lld .. %lld do not fit the %lld destination rows", who, (long long)dst_row0,
+                    (long long)(dst_row0 + n_rows), (long long)dst_rows);
+    if (n_d == 0 || max_doc_rows == 0) return MSIM_OK;
+    if ((!D && n_rows > 0) || !d_off || !C || !cutoffs || ((!codes || !residuals) && n_rows > 0))
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(D, 16) || misaligned(C, 16) || misaligned(codes, 16) || misaligned(residuals, 16) || misaligned(d_off, 4) ||
+        misaligned(status, 4) || misaligned(cutoffs, 4))
+        return fail(MSIM_EINVAL, "%s: rows, centroids, codes and residuals must be 16-byte aligned; offsets, status and cutoffs 4-byte aligned",
+                    who);
+    const long long gy = ((long long)max_doc_rows + msim::kCentEncRows - 1) / msim::kCentEncRows;
+    if (gy > 65535) return fail(MSIM_EUNSUPPORTED, "%s: max_doc_rows=%d above %d", who, max_doc_rows, 65535 * msim::kCentEncRows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = bits == 2 ? (f16 ? msim::res_append_kernel<true, 2> : msim::res_append_kernel<false, 2>)
+                          : (f16 ? msim::res_append_kernel<true, 4> : msim::res_append_kernel<false, 4>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_d, (unsigned)gy), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint16_t *>(D), d_off, n_d, (long long)n_rows, max_doc_rows, static_cast<const uint16_t *>(C), K,
+                       cutoffs, codes, residuals, (long long)dst_row0, (long long)dst_rows, status);
+    return launch_failed("res_append_kernel");
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@
 //                           A workgroup owns a run of consecutive destination rows: two binary searches over the new offsets give
 //                           the slots of its first and last row, each row then finds its slot between them (a page boundary or
 //                           two), and the rows move as 16-byte pieces, four in flight per lane, read once with non-temporal loads.
+//   live_move_codes_kernel the same two launches for an array of 2-byte rows (the centroid codes of a compressed shard,
+//                           msim_res_live_compact), one row per lane: a 16-byte piece of it would span eight rows.
 // Every row index the device derives is checked against rows_bound before it becomes an address; a broken invariant sets the
 // status word and every later kernel of the call returns at once.
 //
@@ -206,6 +208,41 @@ __global__ __launch_bounds__(kLiveMoveThreads) void live_move_kernel(uint8_t *__
                 if (TO_BOUNCE) *reinterpret_cast<live_u32x4 *>(bounce_base + dst[u]) = v[u];
                 else *reinterpret_cast<live_u32x4 *>(rows + dst[u]) = v[u];
             }
+        }
+    }
+}
+
+// The same move for an array of 2-byte rows (the uint16 centroid codes of a compressed shard, msim_res_live_compact): a 16-byte
+// piece of such an array spans eight rows, page boundaries and alignments, so this one works per row -- one lane per destination
+// row, kLiveCodeRows rows per lane; consecutive lanes read and write consecutive 2-byte elements inside a page.
+constexpr int kLiveCodeRows = 4;            // destination rows per lane: 1024 per workgroup
+
+template <bool TO_BOUNCE>
+__global__ __launch_bounds__(kLiveMoveThreads) void live_move_codes_kernel(uint16_t *__restrict__ codes, long long rows_bound,
+                                                                           const int32_t *__restrict__ new_off,
+                                                                           const int32_t *__restrict__ old_off, int n_slots,
+                                                                           int32_t *__restrict__ hdr, uint16_t *__restrict__ bounce,
+                                                                           long long chunk0, int chunk_rows) {
+    if (hdr[kLiveStatus]) return;                        // uniform
+    constexpr int block_rows = kLiveMoveThreads * kLiveCodeRows;
+    const long long total = hdr[kLiveTotal], first = hdr[kLiveFirst];
+    const long long r0 = chunk0 + (long long)blockIdx.x * block_rows;
+    long long r1 = r0 + block_rows;
+    if (r1 > chunk0 + chunk_rows) r1 = chunk0 + chunk_rows;
+    if (r1 > total) r1 = total;
+    if (r0 >= r1 || r1 <= first) return;                 // past the live rows, or wholly below the first row that moves
+    const int s_lo = live_slot_of(new_off, 0, n_slots, (int)r0);
+    const int s_hi = live_slot_of(new_off, s_lo, n_slots, (int)(r1 - 1));
+#pragma unroll
+    for (int u = 0; u < kLiveCodeRows; ++u) {
+        const long long d = r0 + u * kLiveMoveThreads + threadIdx.x;
+        if (d >= r1) continue;
+        const int c = live_slot_of(new_off, s_lo, s_hi + 1, (int)d);
+        const long long src = (long long)old_off[c] + (d - new_off[c]);
+        if (src < d || src >= rows_bound || d >= rows_bound) atomicOr(&hdr[kLiveStatus], kLiveBadRow);
+        else if (src != d) {
+            if (TO_BOUNCE) bounce[d - chunk0] = codes[src];
+            else codes[d] = bounce[d - chunk0];
         }
     }
 }

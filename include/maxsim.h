@@ -815,6 +815,48 @@ int msim_live_compact(void *rows, int64_t row_bytes, int64_t rows_bound, int32_t
 int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const uint8_t *alive, void *stream);
 
 /*
+ * LIVE COMPRESSED SHARD (residual_live.hip, live_corpus.hip; additions to ABI 22): a residual-compressed corpus that is filled from
+ * bf16 / f16 pages which are never kept, and whose deleted pages hand their rows back in place.  Formats as the residual-compressed
+ * corpus above: bf16 / f16, width 128, bits 2 or 4, K a multiple of 256 in 256 .. 2048.
+ *
+ * msim_res_append encodes the pages D [n_rows, 128] with offsets d_off int32 [n_d + 1] in one pass and writes row r of D to row
+ * dst_row0 + r of codes (uint16 [dst_rows]) and of residuals (uint8 [dst_rows, 16 * bits]).  codes and residuals are the BASE
+ * pointers of the arrays, 16-byte aligned; dst_row0 is arbitrary, so a code may land on any 2-byte boundary.  Bit identity with the
+ * two-call composition: the code of a row is what msim_cent_encode_docs gives (the same fp32 MFMA chain, k ascending, the lowest k
+ * on equal values), and its residual bytes are what msim_res_encode_docs gives for that row and that code (one fp32 subtraction
+ * per dimension, a value equal to a cutoff goes to the upper bucket, the same little-endian packing).  A row is read from memory
+ * once.  max_doc_rows and status (int32 [n_d] or NULL) as msim_cent_encode_docs: a page whose offsets fall outside 0 .. n_rows, or
+ * that is longer than max_doc_rows, gets status 1 and not one byte of either array is written for it; every other page gets 0.
+ * Bytes outside rows dst_row0 .. dst_row0 + n_rows - 1 are never written: every destination row the device derives is checked
+ * against dst_rows before it becomes an address.  MSIM_EINVAL for a negative size, dst_row0 + n_rows > dst_rows, dim != 128, K
+ * outside the rule, a null pointer or a misaligned one (D, C, codes, residuals: 16 bytes; d_off, status, cutoffs: 4);
+ * MSIM_EUNSUPPORTED for fp32 rows, bits other than 2 or 4 and max_doc_rows above 65535 * 256.  n_d == 0 or max_doc_rows == 0
+ * returns 0 before it looks at a pointer.
+ *
+ * msim_res_live_compact is msim_live_compact for the two arrays of such a shard: ONE offset plan (one rewrite of off, the rule,
+ * status word, `first` row below which nothing is read or written, idempotence and bounds checks of msim_live_compact), against
+ * which both codes (uint16 [rows_bound]) and residuals (uint8 [rows_bound, 16 * bits]) move.  The 2-byte codes move per row (a
+ * 16-byte piece of them would span eight rows and cross page boundaries and alignments), the residual rows as 16-byte pieces.
+ * Both go through `bounce` (16-byte aligned, caller-owned) in chunks of
+ *     chunk rows = floor(bounce_bytes / (16 * bits + 2))      destination rows (at least 1: MSIM_EINVAL otherwise),
+ * the chunk's residual rows first and its codes behind them, with the two-launch discipline of msim_live_compact per array
+ * (source -> bounce, then bounce -> destination).  ceil(rows_bound / chunk rows) must not exceed 65536 (MSIM_EUNSUPPORTED).
+ * workspace: msim_res_live_compact_workspace_bytes(n_slots, bounce_bytes) bytes, 16-byte aligned, initialised by the call (by a
+ * kernel); its first int32 is the status word of msim_live_compact: non-zero means an invariant was broken, nothing further was
+ * moved and *rows_used_out = the old off[n_slots].  codes, residuals, bounce and workspace 16-byte aligned, off 4-byte,
+ * rows_used_out 8-byte (MSIM_EINVAL); bits other than 2 or 4 and rows_bound > 2^31 - 1 are MSIM_EUNSUPPORTED.  n_slots == 0 returns
+ * 0 before it looks at a pointer.
+ *
+ * Both are asynchronous on `stream`, allocate nothing, never synchronise with the host and are hipGraph-capturable.
+ */
+int msim_res_append(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows, const void *C,
+                    int K, const float *cutoffs, int bits, uint16_t *codes, uint8_t *residuals, int64_t dst_row0, int64_t dst_rows,
+                    int32_t *status /* or NULL */, void *stream);
+size_t msim_res_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes);
+int msim_res_live_compact(uint16_t *codes, uint8_t *residuals, int bits, int64_t rows_bound, int32_t *off, const uint8_t *alive,
+                          int n_slots, int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream);
+
+/*
  * HARD-NEGATIVE MINING AND THE PAGE GATHER (mine.hip; additions to ABI 22).  Mining is "mask the score matrix of the full scan, then
  * msim_topk_f32": no scorer and no selection kernel changes.
  *
