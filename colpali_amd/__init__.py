@@ -22,6 +22,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      dimension (34 / 66 bytes per row instead of 256), candidate lists reranked straight from them
   * residual_scores               -- the full scan of such a shard, a page decoded once per group of queries: the score matrix
                                      behind ShardedRetriever(rc, score_fn=residual_scores) -- search, filter=, group_by=, mine
+  * residual_align / residual_gather_pages -- align and gather_pages over such a shard, the listed pages decoded inside the kernel
+                                     (align and gather_pages dispatch to them on a ResidualCorpus)
   * LiveResidualCorpus           -- such a shard filled incrementally from pages that are never kept: add (one fused encode pass),
                                      delete, compact in place; the lifecycle LiveCorpus gives the bf16 shard
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
@@ -45,7 +47,8 @@ from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPai
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
 from .patch import patch_colpali_engine, unpatch_colpali_engine
-from .residual import ResidualCorpus, residual_rerank_scores, residual_scores, train_residual_codec
+from .residual import (ResidualCorpus, residual_align, residual_gather_pages, residual_rerank_scores, residual_scores,
+                       train_residual_codec)
 from .retrieval import (ExactMaxSimIndex, ResidualMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered, rerank, shard_range,
                         shard_topk, topk)
 from .scoring import (get_similarity_maps_from_embeddings, get_torch_device, maxsim_scores, score_multi_vector,
@@ -70,6 +73,8 @@ __all__ = [
     "train_centroids",
     "ResidualCorpus",
     "ResidualMaxSimIndex",
+    "residual_align",
+    "residual_gather_pages",
     "residual_rerank_scores",
     "residual_scores",
     "train_residual_codec",

@@ -89,7 +89,13 @@ def align(queries, corpus: PackedCorpus, ids: torch.Tensor, *, maps: bool = Fals
     (default: the corpus' longest page, known on the host); a longer page comes back NaN / -1.
     The bits of a similarity depend on its token row and page row alone: the same (query, page) gives the same bits at any list
     position, in any batch and under any m.  Asynchronous on torch's current stream; with a `PackedQueries` there is no host
-    synchronisation and the call is hipGraph-capturable."""
+    synchronisation and the call is hipGraph-capturable.
+    A `ResidualCorpus` goes to `residual_align` (width 128; the bits of this call over `corpus.decompress()`, the pages decoded
+    inside the kernel)."""
+    from .residual import ResidualCorpus, residual_align      # residual imports this module's Alignment
+
+    if isinstance(corpus, ResidualCorpus):
+        return residual_align(queries, corpus, ids, maps=maps, max_rows=max_rows)
     dev = _require_gpu(corpus.device)
     q_dtype, dim = _dtype_width(queries)
     if q_dtype != corpus.blob.dtype:

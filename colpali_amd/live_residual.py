@@ -32,7 +32,8 @@ from .filter import PageFilter, filter_ids, filter_list, filter_mask
 from .group import PageGroups, group_reduce, group_select
 from .live import DEFAULT_BOUNCE_BYTES, mask_scores
 from .mine import mine_bounds, mine_mask
-from .residual import DIM, ResidualCorpus, _check_bits, _check_codec, residual_rerank_scores
+from .align import Alignment
+from .residual import DIM, ResidualCorpus, _check_bits, _check_codec, residual_align, residual_rerank_scores
 from .retrieval import ShardedRetriever, _no_page, topk
 from .scoring import maxsim_scores
 
@@ -72,8 +73,8 @@ class LiveResidualCorpus:
     are fixed at construction, and everything a later call needs -- the ingest buffer, the bounce buffer, the workspace -- is
     allocated there: no later call allocates in the library.
 
-    `score_fn`, `rerank_fn`, `centroid_score_fn`, `select`, the `filter_*_fn`, `group_*_fn`, `mine_*_fn` and `mask_fn` are the hooks of
-    `ShardedRetriever` plus the tombstone mask; `encode_fn(live, rows, offsets, n_pages, max_rows, dst_row0)` and
+    `score_fn`, `rerank_fn`, `centroid_score_fn`, `align_fn`, `select`, the `filter_*_fn`, `group_*_fn`, `mine_*_fn` and `mask_fn` are
+    the hooks of `ShardedRetriever` plus the tombstone mask; `encode_fn(live, rows, offsets, n_pages, max_rows, dst_row0)` and
     `compact_fn(live, rows_bound)` write the arrays.  The defaults are the gfx950 kernels; host-logic tests inject reference
     functions and run on the CPU.  As over a `ResidualCorpus`, the routes that scan the shard are refused unless a scorer of the
     compressed rows is handed in: `score_fn=residual_scores`."""
@@ -84,7 +85,8 @@ class LiveResidualCorpus:
                  centroid_score_fn: Callable = centroid_scores, select: Callable = topk, mask_fn: Callable = mask_scores,
                  mine_bounds_fn: Callable = mine_bounds, mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask,
                  filter_list_fn: Callable = filter_list, filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce,
-                 group_select_fn: Callable = group_select, encode_fn: Callable = append_encode, compact_fn: Callable = compact_arrays):
+                 group_select_fn: Callable = group_select, encode_fn: Callable = append_encode, compact_fn: Callable = compact_arrays,
+                 align_fn: Callable = residual_align):
         bits = _check_bits(bits)
         _check_centroids(centroids)
         _check_codec(cutoffs, weights, bits)
@@ -115,6 +117,7 @@ class LiveResidualCorpus:
         self._filter_fns = dict(filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
                                 group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn)
         self._encode_fn, self._compact_fn = encode_fn, compact_fn
+        self._align_fn = align_fn         # (queries, ResidualCorpus, ids, maps=) -> Alignment
         self._compactions = 0
         self._rows_compacted = 0                                     # rows in use right after the last compaction (check())
         self.ingest_rows = min(DEFAULT_INGEST_ROWS if ingest_rows is None else int(ingest_rows), capacity_rows)
@@ -378,6 +381,12 @@ class LiveResidualCorpus:
         r._res_refuses = self._score_fn is maxsim_scores        # the rule of a ResidualCorpus: scanned on request only
         return r
 
+    def align(self, queries, ids: torch.Tensor, maps: bool = False) -> Alignment:
+        """`residual_align` over the live pages, as `LiveCorpus.align`: a deleted id is treated as -1 (no page: (-inf, -1)), as
+        `search(candidates=)` treats it; a surviving page's result has the bits of `residual_align(queries, self.view(), ids)`, before
+        and after `compact()`.  The listed pages are decoded inside the kernel: nothing is decompressed."""
+        return self._align_fn(queries, self.view(), self._live_ids(ids), maps=maps)
+
     def mine(self, queries, positives, n_neg: int, *, max_ratio: Optional[float] = None, skip_top: int = 0, compact: bool = False,
              world: int = 1, rank: int = 0, dist=None, group=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """`ShardedRetriever.mine` over the live pages, as `LiveCorpus.mine`: the tombstone mask goes into the mining mask.  It scans
@@ -394,7 +403,7 @@ class LiveResidualCorpus:
         ids (they become -1 before the residual rerank); `prefilter` is `self.index`, or a `PackedCorpus` over the same slots; its
         scores are masked.  The full scan, the mask route of `filter=`, `group_by=` on the scan and `mine` read every row of the
         shard: a default instance refuses them with `ShardedRetriever`'s NotImplementedError, `score_fn=residual_scores` opens them
-        (the matrix is masked too).  Rows for `align`: `self.view().decompress(ids)`."""
+        (the matrix is masked too).  `align` is a method of its own."""
         shard = self.view()
         if self.device.type == "cuda":     # an injected hook packs host queries itself
             queries = _as_packed(queries, self.device, compact=compact)

@@ -18,6 +18,11 @@ registers into LDS and never written to memory); every score has the bits `reran
 the `[n_q, len(rc)]` matrix with the bits of `maxsim_scores(queries, rc.decompress())`.  It decodes every row of the shard, so the
 retriever only scans on request: `ShardedRetriever(rc, score_fn=residual_scores)` opens the full scan, `filter=`, `group_by=` and
 `mine`.
+
+`residual_align` and `residual_gather_pages` are the two operations that return rows -- `align` and `gather_pages` -- with the
+listed pages decoded inside the kernel that consumes them (colpali_amd/csrc/residual_align.hip): the bits of the same call over
+`rc.decompress()`, no decoded copy in memory, no host read of the list.  `align(queries, rc, ids)` and `gather_pages(rc, ids)`
+dispatch to them; `ShardedRetriever(rc, align_fn=residual_align)` opens the retriever's `align`.
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ import torch
 
 from . import _lib
 from .centroid import CentroidIndex
-from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _rerank_args
+from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .scoring import _require_gpu
 
 DIM = 128
@@ -214,16 +219,21 @@ class ResidualCorpus:
                             lengths=torch.from_numpy(sel.copy()), id_base=0)
 
 
-def _flat_queries(queries, rc: ResidualCorpus, what: str) -> Tuple[torch.device, PackedQueries]:
-    """the query forms and checks the residual kernels share: a `PackedQueries`, a host list, or a dense device box"""
-    if not isinstance(rc, ResidualCorpus):
-        raise ValueError("rc must be a ResidualCorpus")
-    dev = _require_gpu(rc.device)
+def _check_query_format(queries, rc: ResidualCorpus, what: str) -> None:
+    """the formats the residual kernels take, in whatever form the queries came (no device work)"""
     q_dtype, dim = _dtype_width(queries)
     if q_dtype != rc.dtype:
         raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {rc.dtype}")
     if q_dtype not in (torch.bfloat16, torch.float16) or dim != DIM:
         raise NotImplementedError(f"the residual {what} takes bfloat16 / float16 embeddings of width {DIM} (got {q_dtype}, width {dim})")
+
+
+def _flat_queries(queries, rc: ResidualCorpus, what: str) -> Tuple[torch.device, PackedQueries]:
+    """the query forms and checks the residual kernels share: a `PackedQueries`, a host list, or a dense device box"""
+    if not isinstance(rc, ResidualCorpus):
+        raise ValueError("rc must be a ResidualCorpus")
+    dev = _require_gpu(rc.device)
+    _check_query_format(queries, rc, what)
     queries = _as_packed(queries, dev, layout="flat")
     if queries.device != dev:
         raise ValueError("queries and corpus live on different devices")
@@ -280,3 +290,98 @@ def residual_rerank_scores(queries, rc: ResidualCorpus, candidates: torch.Tensor
                                       _lib.current_stream_handle(dev))
     _lib.check(rcode, "msim_res_candidates")
     return out, ids
+
+
+def residual_align(queries, rc: ResidualCorpus, ids: torch.Tensor, *, maps: bool = False, max_rows: Optional[int] = None):
+    """`align` over the compressed shard (include/maxsim.h: msim_res_align_candidates): the `Alignment` of every entry (q, j) of `ids`
+    (int64 [n_q, m] GLOBAL ids on the shard's device, -1 = none), with the signature, the query forms and the checks of `align`.
+    best_sim, best_row, ids and sims have the bits `align(queries, rc.decompress(), ids, maps=, max_rows=)` gives: every listed page
+    is decoded chunk by chunk in the registers of the kernel that multiplies it, and no decoded row is written to memory.
+    bfloat16 / float16, width 128, queries of at most 128 tokens (NotImplementedError otherwise; RuntimeError when queries and
+    shard differ in dtype; ValueError for ids of the wrong shape, dtype or device).  `max_rows` bounds the rows of a listed page
+    (default: the shard's longest page, known on the host); a longer page comes back NaN / -1.  Asynchronous on torch's current
+    stream; with a `PackedQueries` there is no host synchronisation and the call is hipGraph-capturable.
+    What can be refused without the device is refused before it is asked for: the formats and `max_rows` always, the token count
+    and `ids` for queries that come packed."""
+    from .align import MAX_QUERY_TOKENS, Alignment, resolve_ids          # align dispatches here
+
+    if not isinstance(rc, ResidualCorpus):
+        raise ValueError("rc must be a ResidualCorpus")
+    _check_query_format(queries, rc, "align")
+    n = len(rc)
+    if max_rows is None:
+        max_rows = int(rc.lengths.max()) if n else 0
+    max_rows = int(max_rows)
+    if max_rows < 0:
+        raise ValueError(f"max_rows={max_rows} is negative")
+    if not isinstance(queries, PackedQueries):                           # packing is device work
+        queries = _as_packed(queries, _require_gpu(rc.device), layout="flat")
+    if queries.device != rc.device:
+        raise ValueError("queries and corpus live on different devices")
+    n_q = len(queries)
+    ids, m, ld = _id_list(ids, n_q, rc.device, "ids")
+    q_lens = queries.lengths.to(torch.int64)
+    T = int(q_lens.max()) if n_q else 0
+    if T > MAX_QUERY_TOKENS:
+        raise NotImplementedError(f"align takes queries of at most {MAX_QUERY_TOKENS} tokens (got one of {T})")
+    dev = _require_gpu(rc.device)
+    best_sim = torch.empty((n_q, m, T), dtype=torch.float32, device=dev)
+    best_row = torch.empty((n_q, m, T), dtype=torch.int32, device=dev)
+    sims = torch.empty((n_q, m, T, max_rows), dtype=torch.float32, device=dev) if maps else None
+    tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
+    with torch.cuda.device(dev):
+        rcode = _lib.lib().msim_res_align_candidates(
+            _lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets), n_q, int(tokens.shape[0]), T, _lib.ptr(rc.codes),
+            _lib.ptr(rc.residuals), _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets),
+            _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM, _lib.ptr(ids), m, ld, int(rc.id_base), _lib.ptr(best_sim),
+            _lib.ptr(best_row), _lib.ptr(sims), max_rows, _lib.current_stream_handle(dev))
+    _lib.check(rcode, "msim_res_align_candidates")
+    return Alignment(best_sim, best_row, resolve_ids(ids, int(rc.id_base), n), sims, q_lens, page_lengths=rc.lengths,
+                     id_base=int(rc.id_base))
+
+
+def residual_gather_pages(rc: ResidualCorpus, ids: torch.Tensor, pad_to: Optional[int] = None,
+                          out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`gather_pages` over the compressed shard (include/maxsim.h: msim_res_gather_pages): (box [*ids.shape, L_pad, 128] of the
+    shard's dtype, lengths int32 [*ids.shape]) with the bytes `gather_pages(rc.decompress(), ids, pad_to)` gives -- the listed pages
+    are decoded straight into the box, so `mine_hard_negatives(q, rc, ...)` -> `gather_pages(rc, neg_ids)` feeds the
+    explicit-negative losses without a decoded shard.  ids: int64 GLOBAL ids of any shape; L_pad = `pad_to`, or the shard's longest
+    page.  Rows past a page's length, and the whole page for id -1 or an id outside the shard, are exactly zero and `lengths` is 0
+    for such a slot.  A page longer than `pad_to`: host ids raise ValueError, device ids TRUNCATE (`lengths` reports the truncated
+    count), as `gather_pages`.  out: a contiguous [*ids.shape, L_pad, 128] tensor to write into (every byte of it is written).
+    Asynchronous on torch's current stream; with device ids there is no host synchronisation and the call is hipGraph-capturable."""
+    if not isinstance(rc, ResidualCorpus):
+        raise ValueError("rc must be a ResidualCorpus")
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
+        raise ValueError("ids must be an int64 tensor")
+    n = len(rc)
+    if pad_to is None:
+        pad_to = int(rc.lengths.max()) if n else 0
+    pad_to = int(pad_to)
+    if pad_to < 0:
+        raise ValueError(f"pad_to={pad_to} is negative")
+    if ids.device.type == "cpu":
+        idx = ids.reshape(-1).numpy() - int(rc.id_base)
+        inside = idx[(ids.reshape(-1).numpy() >= 0) & (idx >= 0) & (idx < n)]
+        lens = rc.lengths.numpy()[inside]
+        if lens.size and int(lens.max()) > pad_to:
+            bad = int(inside[int(np.argmax(lens))]) + int(rc.id_base)
+            raise ValueError(f"page {bad} has {int(lens.max())} rows, pad_to={pad_to}")
+    elif ids.device != rc.device:
+        raise ValueError("ids and corpus live on different devices")
+    dev = _require_gpu(rc.device)
+    flat = ids.to(dev).reshape(-1).contiguous()
+    shape = tuple(ids.shape) + (pad_to, DIM)
+    if out is None:
+        out = torch.empty(shape, dtype=rc.dtype, device=dev)
+    elif out.shape != shape or out.dtype != rc.dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {rc.dtype} tensor of shape {shape} on {dev}")
+    lengths = torch.empty(tuple(ids.shape), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rcode = _lib.lib().msim_res_gather_pages(_lib.dtype_code(rc.dtype), _lib.ptr(rc.codes), _lib.ptr(rc.residuals),
+                                                 _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, DIM,
+                                                 int(rc.codes.shape[0]), _lib.ptr(rc.offsets), n, int(rc.id_base), _lib.ptr(flat),
+                                                 flat.numel(), pad_to, _lib.ptr(out), _lib.ptr(lengths),
+                                                 _lib.current_stream_handle(dev))
+    _lib.check(rcode, "msim_res_gather_pages")
+    return out, lengths

@@ -26,7 +26,7 @@ from .group import SELECT_MAX_M, PageGroups, group_reduce, group_select
 from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
-from .residual import ResidualCorpus, residual_rerank_scores, residual_scores
+from .residual import ResidualCorpus, residual_align, residual_rerank_scores, residual_scores
 from .scoring import _require_gpu, maxsim_scores
 
 
@@ -206,7 +206,8 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 
 
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
-_KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, align)
+_KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, align,
+            residual_align)
 
 
 class ShardedRetriever:
@@ -217,8 +218,9 @@ class ShardedRetriever:
     shard decodes every row of it and is opt-in: with `score_fn=residual_scores` (or any other scorer over a `ResidualCorpus`; the
     default `maxsim_scores` is not one) the routes that need only the score matrix or the rerank open -- the full scan, `filter=`
     on the mask, list and auto routes (the list route runs the residual rerank), `group_by=` on every route, `filter=` with
-    `candidates=` / `prefilter=`, and `mine` -- each with the bits of the same call over `shard.decompress()`.  `align` keeps
-    raising: it returns rows."""
+    `candidates=` / `prefilter=`, and `mine` -- each with the bits of the same call over `shard.decompress()`.  `align` is opened
+    the same way, by its own hook: `align_fn=residual_align` decodes the listed pages inside the alignment kernel; with the default
+    `align_fn` it keeps raising."""
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
@@ -359,7 +361,8 @@ class ShardedRetriever:
                                   "scored from the compressed ones -- use search(candidates=) or search(prefilter=shard.index, "
                                   "n_candidates=), or shard.decompress() for a PackedCorpus; ShardedRetriever(shard, "
                                   "score_fn=residual_scores) opts in to scanning the compressed rows (the full scan, filter=, "
-                                  "group_by= and mine; align needs rows either way)")
+                                  "group_by= and mine; align needs rows either way: ShardedRetriever(shard, "
+                                  "align_fn=residual_align) decodes the listed pages inside the alignment kernel)")
 
     # ------------------------------------------------------------------------------------------------- document-level search
     def _check_groups(self, groups, k) -> Optional[PageGroups]:
@@ -411,8 +414,10 @@ class ShardedRetriever:
         returned -- the best-matching page row of every query token and its similarity.  Every rank aligns the ids it holds; with
         world > 1 one element-wise MAX all-reduce of (best_sim, best_row, ids) follows: a rank that does not hold an id contributes
         (-inf, -1, -1), so every rank ends up with the holder's result (best_row is relative to the page, whichever rank holds it).
-        `maps=True` is for a single shard: the maps of a sharded corpus stay on the rank that holds the page (ValueError)."""
-        if isinstance(self.shard, ResidualCorpus):
+        `maps=True` is for a single shard: the maps of a sharded corpus stay on the rank that holds the page (ValueError).
+        Over a `ResidualCorpus` the default `align_fn` refuses (NotImplementedError); `align_fn=residual_align` decodes the listed
+        pages inside the kernel and gives the bits of the same call over `shard.decompress()`."""
+        if isinstance(self.shard, ResidualCorpus) and self._align is align:        # opt-in, as the scan: align_fn=residual_align
             self._no_rows("align")
         if maps and self.world > 1:
             raise ValueError("maps=True with world > 1: similarity maps are made by the rank that holds the page; call align() on "

@@ -1,7 +1,7 @@
 """The residual-compressed corpus (msim_res_*, colpali_amd.ResidualCorpus) on the headline shard; one JSON object on stdout (not part
 of bench.py).
 
-    python tools/bench_residual.py [--out FILE] [--steps 10 --warmup 3] [--docs 125000 --doc-len 1024] [--legs build,rerank,two_stage,recall,scan]
+    python tools/bench_residual.py [--out FILE] [--steps 10 --warmup 3] [--docs 125000 --doc-len 1024] [--legs build,rerank,two_stage,recall,scan,align,gather]
 
 Legs, each timed with device events after a warm-up, for 2 and 4 residual bits (K = 1024 centroids):
   * build: `train_residual_codec` on the residuals of 2^18 sampled rows, and `ResidualCorpus.build` with a given index, cutoffs
@@ -19,6 +19,14 @@ Legs, each timed with device events after a warm-up, for 2 and 4 residual bits (
     scan such a shard without it: every page decoded once per query).  The variants of one batch ALTERNATE step by step inside one
     timing loop, and the outputs' bit-equality at those sizes is recorded.  `--scan-ref 0` times `residual_scores` alone (A/B runs
     of a measurement build).
+  * align (not in the default legs): `residual_align` (msim_res_align_candidates) at 1000 x 32 queries x k = 10 hits, with and
+    without `maps`, beside the only way there was before it: read the ids back, `rc.decompress(local ids)`, `align` over that copy
+    (the read-back, the per-page decode launches and the bf16 copy are all inside the timed region), and beside `align` over a
+    RESIDENT `rc.decompress()` (K1a itself: what the in-kernel decode costs).  Variants alternate step by step; bit-equality of the
+    outputs is recorded.
+  * gather (not in the default legs): `residual_gather_pages` (msim_res_gather_pages) on `[1000, 8]` ids beside `gather_pages` over a
+    RESIDENT `rc.decompress()` (whose 256 bytes per row are what the compressed shard exists to avoid), alternating, with the bytes
+    compared.
 """
 from __future__ import annotations
 
@@ -118,6 +126,55 @@ def scan_leg(amd, rc, dec, q_len, dev, steps, warmup):
     return out
 
 
+ALIGN_SHAPE = (1000, 10)                    # (queries, hits per query)
+GATHER_SHAPE = (1000, 8)                    # the ids of a mined batch
+
+
+def align_leg(amd, rc, dec, q_len, dev, steps, warmup):
+    n_q, k = ALIGN_SHAPE
+    pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
+    ids = uniform_candidates(n_q, len(rc), k, dev, 7) + rc.id_base
+    listed = torch.arange(n_q * k, device=dev).reshape(n_q, k)
+    R = int(rc.lengths.max())
+    out = {}
+    for maps in (False, True):
+        def via_decompress():
+            part = rc.decompress((ids - rc.id_base).reshape(-1))       # reads the ids back: one synchronisation per call
+            return amd.align(pq, part, listed, maps=maps, max_rows=R)
+
+        fns = {"residual_align": lambda: amd.residual_align(pq, rc, ids, maps=maps, max_rows=R), "decompress_then_align": via_decompress,
+               "align_resident_bf16": lambda: amd.align(pq, dec, ids, maps=maps, max_rows=R)}       # K1a itself: what the decode costs
+        leg = timed_alternating(fns, steps, warmup)
+        leg["residual_over_resident_bf16"] = leg["residual_align"]["median_ms"] / leg["align_resident_bf16"]["median_ms"]
+        leg["residual_over_decompress"] = leg["residual_align"]["median_ms"] / leg["decompress_then_align"]["median_ms"]
+        got, want = fns["residual_align"](), via_decompress()
+        torch.cuda.synchronize()
+        same = torch.equal(got.best_sim.view(torch.int32), want.best_sim.view(torch.int32)) and torch.equal(got.best_row, want.best_row)
+        if maps:
+            same = same and torch.equal(got.sims.view(torch.int32), want.sims.view(torch.int32))
+        leg["bit_identical"] = bool(same)
+        rows = int(rc.lengths[(ids - rc.id_base).reshape(-1).cpu()].sum())
+        leg["rows_decoded_per_s"] = rows / (leg["residual_align"]["median_ms"] * 1e-3)
+        out["maps" if maps else "no_maps"] = leg
+        del got, want
+        torch.cuda.empty_cache()
+    return out
+
+
+def gather_leg(amd, rc, dec, dev, steps, warmup):
+    n_q, n_neg = GATHER_SHAPE
+    ids = uniform_candidates(n_q, len(rc), n_neg, dev, 11) + rc.id_base
+    pad = int(rc.lengths.max())
+    box = torch.empty((n_q, n_neg, pad, 128), dtype=rc.dtype, device=dev)
+    ref = torch.empty_like(box)
+    leg = timed_alternating({"residual_gather_pages": lambda: amd.residual_gather_pages(rc, ids, pad, out=box),
+                             "gather_pages_resident_bf16": lambda: amd.gather_pages(dec, ids, pad, out=ref)}, steps, warmup)
+    leg["residual_over_bf16"] = leg["residual_gather_pages"]["median_ms"] / leg["gather_pages_resident_bf16"]["median_ms"]
+    leg["bit_identical"] = bool(torch.equal(box.view(torch.int16), ref.view(torch.int16)))
+    leg["bytes_written_per_s"] = box.numel() * 2 / (leg["residual_gather_pages"]["median_ms"] * 1e-3)
+    return leg
+
+
 def recall_leg(amd, dev, n_docs, k=10):
     pages, q = planted_pages(dev, n_docs=n_docs)
     full = amd.pack_passages(pages, dev, batch_size=None)
@@ -165,7 +222,7 @@ def main():
     legs = set(args.legs.split(","))
     t0 = time.perf_counter()
     res = {"tool": "bench_residual", "docs": args.docs, "doc_len": args.doc_len, "q_len": args.q_len, "n_centroids": K}
-    if legs & {"build", "rerank", "two_stage", "scan"}:
+    if legs & {"build", "rerank", "two_stage", "scan", "align", "gather"}:
         corpus = make_shard(args.docs, args.doc_len, dev, seed=1234)
         index = amd.CentroidIndex.build(corpus, n_centroids=K)
         res["corpus_bytes"] = corpus.nbytes
@@ -196,6 +253,13 @@ def main():
             if "scan" in legs:
                 dec = rc.decompress() if args.scan_ref else None
                 leg["scan"] = scan_leg(amd, rc, dec, args.q_len, dev, args.steps, args.warmup)
+                del dec
+            if legs & {"align", "gather"}:
+                dec = rc.decompress()
+                if "align" in legs:
+                    leg["align"] = align_leg(amd, rc, dec, args.q_len, dev, args.steps, args.warmup)
+                if "gather" in legs:
+                    leg["gather"] = gather_leg(amd, rc, dec, dev, args.steps, args.warmup)
                 del dec
             res[f"bits{bits}"] = leg
             del rc
