@@ -339,3 +339,151 @@ def token_sums(M, q_lens, clamp0=None):
         out.append(M[o : o + int(n)].sum(dim=0))
         o += int(n)
     return torch.stack(out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Large-offset fixtures (tests/test_gpu_large_offsets.py, tests/test_large_offsets_host.py).  A shard is ONE block of P pages of random
+# unit rows (R0 rows in all, R0 odd) repeated T times, so that the truth of the block, tiled, is the truth of the shard, and the shard
+# crosses byte 2^31 / 2^32 and element 2^31 / 2^32.  R0 is odd and every wrap distance, taken modulo the block, lies at least one
+# longest page away from 0 and from R0: a row index, element offset or byte offset that lost its high bits lands in ANOTHER page of
+# the block (other random rows), never on an equal copy.  test_large_offsets_host.py asserts exactly that for the parameters below.
+
+LARGE_EDGE_LENS = [1, 31, 32, 33, 64, 96, 129, 500, 1000, 1030, 0]
+LARGE_PAGES = 60
+LARGE_SEED = 1
+# kind -> (torch dtype name, width, bytes per element, the row count the shard must exceed)
+LARGE_SHARDS = {
+    "bf16_128": ("bfloat16", 128, 2, 2**25),                 # 8.6 GB: byte 2^31 at row 2^23, byte 2^32 = element 2^31 at 2^24, element 2^32 at 2^25
+    "bf16_320": ("bfloat16", 320, 2, 2**32 // 640 + 1),      # 4.3 GB: byte 2^31, byte 2^32 = element 2^31 (no whole row: 2^32 / 640 is no integer)
+    "f32_128": ("float32", 128, 4, 2**24),                   # 8.6 GB: byte 2^31 at row 2^22, byte 2^32 at 2^23, element 2^31 at 2^24
+}
+# score matrices of more than 2^31 entries: n_q rows that repeat a 7-row block; ld = 4 x odd (the vector paths) and ld odd (the scalar ones)
+LARGE_MATRIX_ROWS = 2049
+LARGE_MATRIX_BLOCK = 7
+LARGE_MATRIX_LD = {"vec": 4 * 262145, "odd": 4 * 262145 - 1}
+
+
+def large_block_lens(seed=LARGE_SEED, n_pages=LARGE_PAGES):
+    """The page lengths of the block: every edge length once (an empty page among them) and lengths of 2 .. 300 rows, shuffled; the
+    total is odd and greater than 1."""
+    rng = np.random.default_rng(seed)
+    rand = rng.integers(2, 301, n_pages - len(LARGE_EDGE_LENS)).tolist()
+    if (sum(LARGE_EDGE_LENS) + sum(rand)) % 2 == 0:
+        rand[0] += 1
+    lens = LARGE_EDGE_LENS + rand
+    return [int(lens[i]) for i in rng.permutation(n_pages)]
+
+
+def large_shard_spec(kind):
+    """dict: dtype (name), width, row_bytes, elem_bytes, lens, offsets (int64 [P + 1] of the block), R0, P, T, rows, n and `bounds`:
+    name -> the first ROW INDEX at or past the boundary, for the boundaries the shard reaches."""
+    dtype, width, es, min_rows = LARGE_SHARDS[kind]
+    lens = large_block_lens()
+    off = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    R0 = int(off[-1])
+    T = min_rows // R0 + 2                                  # at least one whole tile past the last boundary
+    rb = width * es
+    bounds = {}
+    for name, nbytes in large_wrap_bytes(es).items():
+        row = -(-nbytes // rb)
+        if row < T * R0:
+            bounds[name] = row
+    return dict(kind=kind, dtype=dtype, width=width, elem_bytes=es, row_bytes=rb, lens=lens, offsets=off, R0=R0, P=len(lens), T=T,
+                rows=T * R0, n=T * len(lens), bounds=bounds)
+
+
+def large_wrap_bytes(elem_bytes):
+    """name -> the distance in BYTES an address moves when an offset loses bit 31 / 32 as a byte count or as an element count"""
+    return {"byte 2^31": 2**31, "byte 2^32": 2**32, "element 2^31": 2**31 * elem_bytes, "element 2^32": 2**32 * elem_bytes}
+
+
+def large_page_at(spec, byte_addr):
+    """the page of the BLOCK that owns byte `byte_addr` of the shard (any tile: the address is taken modulo the block)"""
+    row = (int(byte_addr) % (spec["R0"] * spec["row_bytes"])) // spec["row_bytes"]
+    return int(np.searchsorted(spec["offsets"], row, side="right")) - 1
+
+
+def large_tiles_of_interest(spec):
+    """sorted tile indices: tile 0, the last tile and, for every boundary the shard reaches, the tile that holds the boundary's row
+    with the tile before it and the tile after it"""
+    R0, T = spec["R0"], spec["T"]
+    tiles = {0, T - 1}
+    for row in spec["bounds"].values():
+        t = row // R0
+        tiles.update(x for x in (t - 1, t, t + 1) if 0 <= x < T)
+    return sorted(tiles)
+
+
+def large_block_rows(spec, seed=LARGE_SEED):
+    """the block's rows: random unit rows [R0, width] as a CPU tensor of the shard's dtype, every value one the 13-bit image holds"""
+    import torch
+
+    g = torch.Generator().manual_seed(1000 + seed)
+    rows = torch.nn.functional.normalize(torch.randn(spec["R0"], spec["width"], generator=g), dim=-1)
+    rows = rows.to(getattr(torch, spec["dtype"]))
+    rows[rows == 0] = 2.0**-10            # no exact zero: the 13-bit image of the corpus cannot hold one, and the block is to carry no flagged page
+    return rows
+
+
+def large_shard_tensors(spec, block, device):
+    """(blob [T * R0, width] on `device`, offsets int32 [n + 1] on `device`, lengths int64 [n] on the host): the block written T
+    times with one expanding copy, the block's offsets plus t * R0."""
+    import torch
+
+    T, R0, P, w = spec["T"], spec["R0"], spec["P"], spec["width"]
+    blob = torch.empty((T * R0, w), dtype=block.dtype, device=device)
+    blob.view(T, R0, w).copy_(block.to(device).unsqueeze(0).expand(T, R0, w))
+    off = spec["offsets"][None, :-1] + (np.arange(T, dtype=np.int64) * R0)[:, None]
+    off = np.concatenate([off.reshape(-1), [T * R0]])
+    assert off[-1] < 2**31
+    lengths = torch.from_numpy(np.tile(np.asarray(spec["lens"], dtype=np.int64), T))
+    return blob, torch.from_numpy(off.astype(np.int32)).to(device), lengths
+
+
+def large_matrix_block(ld, seed=7):
+    """fp32 [7, ld] on the host: random scores drawn from 4096 distinct values (so every row is full of exact ties) with -inf, +0.0
+    and -0.0 sprinkled in, and the largest value of a row repeated at both ends and in the middle"""
+    rng = np.random.default_rng(seed)
+    vals = rng.standard_normal(4096).astype(np.float32)
+    blk = vals[rng.integers(0, 4096, (LARGE_MATRIX_BLOCK, ld))]
+    kind = rng.integers(0, 64, blk.shape)
+    blk[kind == 0] = -np.inf
+    blk[kind == 1] = 0.0
+    blk[kind == 2] = -0.0
+    for r in range(LARGE_MATRIX_BLOCK):
+        blk[r, [0, ld // 2 + r, ld - 1]] = np.float32(5.0 + r)
+    return blk
+
+
+def large_matrix_probe_rows(ld, n_q=LARGE_MATRIX_ROWS):
+    """the rows checked element by element on the host: the first, the first one wholly past element 2^30 and 2^31, the last"""
+    return sorted({0, -(-2**30 // ld), -(-2**31 // ld), n_q - 1})
+
+
+def large_matrix_group_labels(ld):
+    """int64 [ld] document ids: runs of 37 consecutive pages in the first half, pages strided by 1001 in the second (a document's
+    pages need not be contiguous); the ids themselves are large and not contiguous"""
+    col = np.arange(ld, dtype=np.int64)
+    return np.where(col < ld // 2, 10 * (col // 37), 10**12 + col % 1001)
+
+
+def group_reduce_truth_fast(scores, page_groups, id_base=0):
+    """group_truth.reduce_truth, vectorised for a million columns (test_large_offsets_host.py holds the two equal): per document the
+    page with the highest score (-0.0 and +0.0 tie, the lower page wins a tie, the winner keeps its bits; all -inf: (-inf, -1))."""
+    scores = np.asarray(scores, dtype=np.float32)
+    labels = np.asarray(page_groups, dtype=np.int64)
+    group_ids, inv = np.unique(labels, return_inverse=True)
+    n_q, n = scores.shape
+    out_s = np.full((n_q, group_ids.size), -np.inf, dtype=np.float32)
+    out_p = np.full((n_q, group_ids.size), -1, dtype=np.int64)
+    cols = np.arange(n, dtype=np.int64)
+    for q in range(n_q):
+        key = scores[q].astype(np.float64) + 0.0                      # folds -0.0 onto +0.0
+        order = np.lexsort((cols, -key, inv))                         # by document, then score descending, then page ascending
+        first = order[np.concatenate([[True], inv[order][1:] != inv[order][:-1]])]
+        win = ~np.isneginf(scores[q, first])
+        g = inv[first]
+        out_s[q, g[win]] = scores[q, first[win]]
+        out_p[q, g[win]] = first[win] + id_base
+    return group_ids, out_s, out_p
