@@ -156,141 +156,140 @@ LiveWorkspace live_workspace(int n_slots) {
     return w;
 }
 
+// What msim_live_compact and msim_res_live_compact share.  An entry refuses its own row format between the two checks (the second
+// takes what it found on its own row arrays), returns MSIM_OK after them where there are no slots, and refuses a small bounce buffer itself.
+int live_check_sizes(const char *who, int n_slots, int64_t rows_bound, int64_t bounce_bytes) {
+    if (n_slots >= 0 && rows_bound >= 0 && bounce_bytes >= 0) return MSIM_OK;
+    return fail(MSIM_EINVAL, "%s: negative size (n_slots=%d rows_bound=%lld bounce_bytes=%lld)", who, n_slots, (long long)rows_bound,
+                (long long)bounce_bytes);
+}
+
+int live_check_args(const char *who, int n_slots, int64_t rows_bound, const int32_t *off, const uint8_t *alive, const int64_t *rows_used_out,
+                    const void *workspace, const void *bounce, bool arrays_null, bool arrays_misaligned, const char *arrays) {
+    if (rows_bound > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: rows_bound=%lld above 2^31 - 1", who, (long long)rows_bound);
+    if (n_slots == 0) return MSIM_OK;
+    if (!off || !alive || !rows_used_out || !workspace || ((arrays_null || !bounce) && rows_bound > 0))
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (arrays_misaligned || misaligned(bounce, 16) || misaligned(workspace, 16) || misaligned(off, 4) || misaligned(rows_used_out, 8))
+        return fail(MSIM_EINVAL, "%s: %s, bounce and workspace must be 16-byte aligned, off 4-byte and rows_used_out 8-byte aligned", who,
+                    arrays);
+    return MSIM_OK;
+}
+
+// What the move loops of both run against, in two steps.  The chunking rule: a chunk is the destination rows that fit the bounce buffer
+// at `unit_bytes` each.  The offset plan: carve the workspace, launch reset / lens / scan / apply; `off` then holds the new offsets.
+struct LivePlan {
+    int64_t chunk_rows, n_chunks;
+    int32_t *hdr, *old_off;          // the status words that the move kernels obey; the offsets as they were
+};
+
+int live_plan(const char *who, hipStream_t st, void *workspace, int32_t *off, const uint8_t *alive, int n_slots, int64_t rows_bound,
+              int64_t *rows_used_out, int64_t bounce_bytes, int64_t unit_bytes, LivePlan *p) {
+    p->chunk_rows = rows_bound > 0 ? bounce_bytes / unit_bytes : 1;
+    if (p->chunk_rows > (1 << 30)) p->chunk_rows = 1 << 30;
+    p->n_chunks = (rows_bound + p->chunk_rows - 1) / p->chunk_rows;
+    if (p->n_chunks > kLiveMaxChunks)
+        return fail(MSIM_EUNSUPPORTED, "%s: %lld rows through a bounce buffer of %lld rows are %lld chunks (at most %lld)", who,
+                    (long long)rows_bound, (long long)p->chunk_rows, (long long)p->n_chunks, (long long)kLiveMaxChunks);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const LiveWorkspace w = live_workspace(n_slots);
+    char *ws = static_cast<char *>(workspace);
+    int32_t *hdr = p->hdr = reinterpret_cast<int32_t *>(ws);
+    int32_t *old_off = p->old_off = reinterpret_cast<int32_t *>(ws + w.old_off);
+    long long *tile_sum = reinterpret_cast<long long *>(ws + w.tile_sum);
+    long long *tile_base = reinterpret_cast<long long *>(ws + w.tile_base);
+    hipLaunchKernelGGL(msim::live_reset_kernel, dim3(1), dim3(64), 0, st, hdr);
+    hipLaunchKernelGGL(msim::live_lens_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots,
+                       (long long)rows_bound, hdr, old_off, tile_sum);
+    hipLaunchKernelGGL(msim::live_scan_kernel, dim3(1), dim3(msim::kLiveTile), 0, st, w.n_tiles, n_slots, (long long)rows_bound, hdr,
+                       old_off, tile_sum, tile_base, reinterpret_cast<long long *>(rows_used_out));
+    hipLaunchKernelGGL(msim::live_apply_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots, hdr, old_off,
+                       tile_base);
+    return MSIM_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t msim_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes) {
     (void)bounce_bytes;                                // the bounce buffer is the caller's; the workspace holds the slot tables only
-    if (n_slots <= 0) return 0;
-    return live_workspace(n_slots).total;
+    return n_slots <= 0 ? 0 : live_workspace(n_slots).total;
 }
 
 int msim_live_compact(void *rows, int64_t row_bytes, int64_t rows_bound, int32_t *off, const uint8_t *alive, int n_slots,
                       int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream) {
     const char *who = "msim_live_compact";
-    if (n_slots < 0 || rows_bound < 0 || bounce_bytes < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_slots=%d rows_bound=%lld bounce_bytes=%lld)", who, n_slots, (long long)rows_bound,
-                    (long long)bounce_bytes);
+    if (int rc = live_check_sizes(who, n_slots, rows_bound, bounce_bytes)) return rc;
     if (row_bytes <= 0 || row_bytes % 16 != 0)
         return fail(MSIM_EINVAL, "%s: row_bytes=%lld must be a positive multiple of 16", who, (long long)row_bytes);
     if (row_bytes > kLiveMaxRowBytes)
         return fail(MSIM_EUNSUPPORTED, "%s: rows of %lld bytes (at most %lld)", who, (long long)row_bytes, (long long)kLiveMaxRowBytes);
-    if (rows_bound > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: rows_bound=%lld above 2^31 - 1", who, (long long)rows_bound);
+    if (int rc = live_check_args(who, n_slots, rows_bound, off, alive, rows_used_out, workspace, bounce, !rows, misaligned(rows, 16), "rows"))
+        return rc;
     if (n_slots == 0) return MSIM_OK;
-    if (!off || !alive || !rows_used_out || !workspace || (!rows && rows_bound > 0) || (!bounce && rows_bound > 0))
-        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(rows, 16) || misaligned(bounce, 16) || misaligned(workspace, 16) || misaligned(off, 4) || misaligned(rows_used_out, 8))
-        return fail(MSIM_EINVAL, "%s: rows, bounce and workspace must be 16-byte aligned, off 4-byte and rows_used_out 8-byte aligned", who);
     if (rows_bound > 0 && bounce_bytes < row_bytes)
         return fail(MSIM_EINVAL, "%s: a bounce buffer of %lld bytes holds no row of %lld bytes", who, (long long)bounce_bytes,
                     (long long)row_bytes);
-    int64_t chunk_rows = rows_bound > 0 ? bounce_bytes / row_bytes : 1;
-    if (chunk_rows > (1 << 30)) chunk_rows = 1 << 30;
-    const int64_t n_chunks = (rows_bound + chunk_rows - 1) / chunk_rows;
-    if (n_chunks > kLiveMaxChunks)
-        return fail(MSIM_EUNSUPPORTED, "%s: %lld rows through a bounce buffer of %lld rows are %lld chunks (at most %lld)", who,
-                    (long long)rows_bound, (long long)chunk_rows, (long long)n_chunks, (long long)kLiveMaxChunks);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const LiveWorkspace w = live_workspace(n_slots);
-    char *ws = static_cast<char *>(workspace);
-    int32_t *hdr = reinterpret_cast<int32_t *>(ws);
-    int32_t *old_off = reinterpret_cast<int32_t *>(ws + w.old_off);
-    long long *tile_sum = reinterpret_cast<long long *>(ws + w.tile_sum);
-    long long *tile_base = reinterpret_cast<long long *>(ws + w.tile_base);
-    hipLaunchKernelGGL(msim::live_reset_kernel, dim3(1), dim3(64), 0, st, hdr);
-    hipLaunchKernelGGL(msim::live_lens_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots,
-                       (long long)rows_bound, hdr, old_off, tile_sum);
-    hipLaunchKernelGGL(msim::live_scan_kernel, dim3(1), dim3(msim::kLiveTile), 0, st, w.n_tiles, n_slots, (long long)rows_bound, hdr,
-                       old_off, tile_sum, tile_base, reinterpret_cast<long long *>(rows_used_out));
-    hipLaunchKernelGGL(msim::live_apply_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots, hdr, old_off,
-                       tile_base);
+    LivePlan p;
+    if (int rc = live_plan(who, st, workspace, off, alive, n_slots, rows_bound, rows_used_out, bounce_bytes, row_bytes, &p)) return rc;
     int block_rows = (int)(msim::kLiveBlockBytes / row_bytes);
     block_rows = block_rows < 1 ? 1 : block_rows > msim::kLiveMaxBlockRows ? msim::kLiveMaxBlockRows : block_rows;
     const int lpr = (int)(row_bytes / 16);
-    for (int64_t k = 0; k < n_chunks; ++k) {
-        const long long chunk0 = k * chunk_rows;
-        const int rows_here = (int)(rows_bound - chunk0 < chunk_rows ? rows_bound - chunk0 : chunk_rows);
+    for (int64_t k = 0; k < p.n_chunks; ++k) {
+        const long long chunk0 = k * p.chunk_rows;
+        const int rows_here = (int)(rows_bound - chunk0 < p.chunk_rows ? rows_bound - chunk0 : p.chunk_rows);
         const unsigned blocks = (unsigned)((rows_here + block_rows - 1) / block_rows);
         hipLaunchKernelGGL(msim::live_move_kernel<true>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, static_cast<uint8_t *>(rows),
-                           lpr, (long long)rows_bound, off, old_off, n_slots, hdr, static_cast<uint8_t *>(bounce), chunk0, rows_here,
-                           block_rows);
+                           lpr, (long long)rows_bound, off, p.old_off, n_slots, p.hdr, static_cast<uint8_t *>(bounce), chunk0,
+                           rows_here, block_rows);
         hipLaunchKernelGGL(msim::live_move_kernel<false>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, static_cast<uint8_t *>(rows),
-                           lpr, (long long)rows_bound, off, old_off, n_slots, hdr, static_cast<uint8_t *>(bounce), chunk0, rows_here,
-                           block_rows);
+                           lpr, (long long)rows_bound, off, p.old_off, n_slots, p.hdr, static_cast<uint8_t *>(bounce), chunk0,
+                           rows_here, block_rows);
     }
     return launch_failed("live compaction");
 }
 
-size_t msim_res_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes) {
-    (void)bounce_bytes;                                // as msim_live_compact_workspace_bytes: the slot tables only
-    if (n_slots <= 0) return 0;
-    return live_workspace(n_slots).total;
-}
+size_t msim_res_live_compact_workspace_bytes(int n_slots, int64_t b) { return msim_live_compact_workspace_bytes(n_slots, b); }
 
 // One offset plan, two arrays moved against it.  A chunk is floor(bounce_bytes / (16 bits + 2)) destination rows: the bounce buffer
 // holds the chunk's residual rows first (16 bits bytes each, so the codes behind them start 16-byte aligned) and its codes after them.
 int msim_res_live_compact(uint16_t *codes, uint8_t *residuals, int bits, int64_t rows_bound, int32_t *off, const uint8_t *alive,
                           int n_slots, int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream) {
     const char *who = "msim_res_live_compact";
-    if (n_slots < 0 || rows_bound < 0 || bounce_bytes < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_slots=%d rows_bound=%lld bounce_bytes=%lld)", who, n_slots, (long long)rows_bound,
-                    (long long)bounce_bytes);
+    if (int rc = live_check_sizes(who, n_slots, rows_bound, bounce_bytes)) return rc;
     if (!(bits == 2 || bits == 4)) return fail(MSIM_EUNSUPPORTED, "%s: %d residual bits; the codec stores 2 or 4 per dimension", who, bits);
-    if (rows_bound > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: rows_bound=%lld above 2^31 - 1", who, (long long)rows_bound);
+    if (int rc = live_check_args(who, n_slots, rows_bound, off, alive, rows_used_out, workspace, bounce, !codes || !residuals,
+                                 misaligned(codes, 16) || misaligned(residuals, 16), "codes, residuals"))
+        return rc;
     if (n_slots == 0) return MSIM_OK;
-    if (!off || !alive || !rows_used_out || !workspace || ((!codes || !residuals || !bounce) && rows_bound > 0))
-        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(codes, 16) || misaligned(residuals, 16) || misaligned(bounce, 16) || misaligned(workspace, 16) || misaligned(off, 4) ||
-        misaligned(rows_used_out, 8))
-        return fail(MSIM_EINVAL, "%s: codes, residuals, bounce and workspace must be 16-byte aligned, off 4-byte and rows_used_out 8-byte aligned",
-                    who);
     const int64_t res_bytes = 16 * bits, both_bytes = res_bytes + 2;
     if (rows_bound > 0 && bounce_bytes < both_bytes)
         return fail(MSIM_EINVAL, "%s: a bounce buffer of %lld bytes holds no row of %lld + 2 bytes", who, (long long)bounce_bytes,
                     (long long)res_bytes);
-    int64_t chunk_rows = rows_bound > 0 ? bounce_bytes / both_bytes : 1;
-    if (chunk_rows > (1 << 30)) chunk_rows = 1 << 30;
-    const int64_t n_chunks = (rows_bound + chunk_rows - 1) / chunk_rows;
-    if (n_chunks > kLiveMaxChunks)
-        return fail(MSIM_EUNSUPPORTED, "%s: %lld rows through a bounce buffer of %lld rows are %lld chunks (at most %lld)", who,
-                    (long long)rows_bound, (long long)chunk_rows, (long long)n_chunks, (long long)kLiveMaxChunks);
-    const DeviceInfo *di = nullptr;
-    if (int rc = device_info(&di)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const LiveWorkspace w = live_workspace(n_slots);
-    char *ws = static_cast<char *>(workspace);
-    int32_t *hdr = reinterpret_cast<int32_t *>(ws);
-    int32_t *old_off = reinterpret_cast<int32_t *>(ws + w.old_off);
-    long long *tile_sum = reinterpret_cast<long long *>(ws + w.tile_sum);
-    long long *tile_base = reinterpret_cast<long long *>(ws + w.tile_base);
-    hipLaunchKernelGGL(msim::live_reset_kernel, dim3(1), dim3(64), 0, st, hdr);
-    hipLaunchKernelGGL(msim::live_lens_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots,
-                       (long long)rows_bound, hdr, old_off, tile_sum);
-    hipLaunchKernelGGL(msim::live_scan_kernel, dim3(1), dim3(msim::kLiveTile), 0, st, w.n_tiles, n_slots, (long long)rows_bound, hdr,
-                       old_off, tile_sum, tile_base, reinterpret_cast<long long *>(rows_used_out));
-    hipLaunchKernelGGL(msim::live_apply_kernel, dim3((unsigned)w.n_tiles), dim3(msim::kLiveTile), 0, st, off, alive, n_slots, hdr, old_off,
-                       tile_base);
+    LivePlan p;
+    if (int rc = live_plan(who, st, workspace, off, alive, n_slots, rows_bound, rows_used_out, bounce_bytes, both_bytes, &p)) return rc;
     const int block_rows = msim::kLiveMaxBlockRows;      // 256 rows of 32 / 64 bytes: 8 / 16 KiB per workgroup
     constexpr int code_block_rows = msim::kLiveMoveThreads * msim::kLiveCodeRows;
     const int lpr = bits;                                // 16-byte pieces per residual row
     uint8_t *bounce_res = static_cast<uint8_t *>(bounce);
-    uint16_t *bounce_codes = reinterpret_cast<uint16_t *>(bounce_res + chunk_rows * res_bytes);
-    for (int64_t k = 0; k < n_chunks; ++k) {
-        const long long chunk0 = k * chunk_rows;
-        const int rows_here = (int)(rows_bound - chunk0 < chunk_rows ? rows_bound - chunk0 : chunk_rows);
+    uint16_t *bounce_codes = reinterpret_cast<uint16_t *>(bounce_res + p.chunk_rows * res_bytes);
+    for (int64_t k = 0; k < p.n_chunks; ++k) {
+        const long long chunk0 = k * p.chunk_rows;
+        const int rows_here = (int)(rows_bound - chunk0 < p.chunk_rows ? rows_bound - chunk0 : p.chunk_rows);
         const unsigned blocks = (unsigned)((rows_here + block_rows - 1) / block_rows);
         const unsigned cblocks = (unsigned)((rows_here + code_block_rows - 1) / code_block_rows);
         hipLaunchKernelGGL(msim::live_move_kernel<true>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, residuals, lpr,
-                           (long long)rows_bound, off, old_off, n_slots, hdr, bounce_res, chunk0, rows_here, block_rows);
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_res, chunk0, rows_here, block_rows);
         hipLaunchKernelGGL(msim::live_move_codes_kernel<true>, dim3(cblocks), dim3(msim::kLiveMoveThreads), 0, st, codes,
-                           (long long)rows_bound, off, old_off, n_slots, hdr, bounce_codes, chunk0, rows_here);
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_codes, chunk0, rows_here);
         hipLaunchKernelGGL(msim::live_move_kernel<false>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, residuals, lpr,
-                           (long long)rows_bound, off, old_off, n_slots, hdr, bounce_res, chunk0, rows_here, block_rows);
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_res, chunk0, rows_here, block_rows);
         hipLaunchKernelGGL(msim::live_move_codes_kernel<false>, dim3(cblocks), dim3(msim::kLiveMoveThreads), 0, st, codes,
-                           (long long)rows_bound, off, old_off, n_slots, hdr, bounce_codes, chunk0, rows_here);
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_codes, chunk0, rows_here);
     }
     return launch_failed("live compaction of a compressed shard");
 }

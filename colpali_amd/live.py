@@ -12,6 +12,10 @@ kept in step.  No scoring kernel changes: every scorer reads page c through `off
 A page's id is its slot: `id_base + slot`, assigned in order of arrival, never reused, never renumbered -- the rule every kernel
 and `shard_topk` already follow.  After any history, `search` returns the scores (bit for bit) of a `ShardedRetriever` over
 `pack_passages(surviving pages in slot order, batch_size=None)`, with that corpus' positions mapped back to slots.
+
+`_LiveShard` below is the half that does not depend on what a row is: the slot table and its rules, and `add` / `delete` /
+`compact` / `search` / `mine` / `align` up to the few methods that touch the rows.  `LiveCorpus` supplies those for a bf16 / f16 /
+f32 blob, `LiveResidualCorpus` (colpali_amd/live_residual.py) for a residual-compressed shard.
 """
 from __future__ import annotations
 
@@ -51,77 +55,80 @@ def mask_scores(scores: torch.Tensor, alive: torch.Tensor) -> torch.Tensor:
     return scores
 
 
-class LiveCorpus:
-    """One mutable resident shard (see the module docstring).  `capacity_rows` and `capacity_docs` are fixed at construction.
+class _LiveShard:
+    """The half `LiveCorpus` and `LiveResidualCorpus` share: the slot table (offsets, `alive`, the host mirrors), its rules -- ids
+    are never reused, a device-side delete is read back before the host decides anything, a refusal leaves the shard as it was,
+    `check()` compares the device's row count with the host's -- and every search route over the tombstones.  A subclass owns the
+    storage and supplies `view`, `_write_rows`, `_move_rows`, `_widths` and the names below."""
 
-    `score_fn`, `rerank_fn`, `int8_score_fn`, `select`, the `filter_*_fn` and `mask_fn` are the hooks of `ShardedRetriever` plus the tombstone mask
-    (`mask_fn(scores, alive) -> scores`); the defaults are the gfx950 kernels.  Host-logic tests inject reference scorers and run on the CPU."""
+    _entry = ""                # the compaction entry behind `_move_rows` (its workspace size, the messages of `check()`)
+    _stage1_kw = ""            # the stage-1 hook of `ShardedRetriever` that `stage1_fn` is
 
-    def __init__(self, capacity_rows: int, capacity_docs: int, device, dtype: torch.dtype = torch.bfloat16, width: int = 128,
-                 id_base: int = 0, *, bounce_bytes: Optional[int] = None, score_fn: Callable = maxsim_scores,
-                 rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, select: Callable = topk,
-                 mask_fn: Callable = mask_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
-                 mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
-                 filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
+    @staticmethod
+    def _capacity(capacity_rows, capacity_docs) -> Tuple[int, int]:
         capacity_rows, capacity_docs = int(capacity_rows), int(capacity_docs)
         if capacity_rows < 1 or capacity_docs < 1:
             raise ValueError("capacity_rows and capacity_docs must be positive")
         if capacity_rows >= 2**31:
             raise NotImplementedError("more than 2^31 patch rows in one shard")
-        _lib.dtype_code(dtype)                                   # raises for anything but bf16 / f16 / f32
-        self.device = torch.device(device)
-        self.dtype, self.dim, self.id_base = dtype, int(width), int(id_base)
-        self.width = _lib.kernel_width(self.dim, dtype)          # physical row width (zero columns appended, as pack_passages)
+        return capacity_rows, capacity_docs
+
+    def _init_slots(self, capacity_rows: int, capacity_docs: int, device, id_base: int, *, score_fn, rerank_fn, stage1_fn, select, mask_fn,
+                    align_fn, mine_bounds_fn, mine_mask_fn, filter_mask_fn, filter_list_fn, filter_ids_fn, group_reduce_fn,
+                    group_select_fn) -> None:
+        """the slot table and the hooks; the subclass has allocated its rows"""
+        self.id_base = int(id_base)
         self.capacity_rows, self.capacity_docs = capacity_rows, capacity_docs
-        self.blob = torch.zeros((capacity_rows, self.width), dtype=dtype, device=self.device)
-        self.offsets = torch.zeros((capacity_docs + 1,), dtype=torch.int32, device=self.device)
-        self.alive = torch.zeros((capacity_docs + 1,), dtype=torch.uint8, device=self.device)   # [capacity_docs]: where ids outside the corpus land
+        self.offsets = torch.zeros((capacity_docs + 1,), dtype=torch.int32, device=device)
+        self.alive = torch.zeros((capacity_docs + 1,), dtype=torch.uint8, device=device)   # [capacity_docs]: where ids outside the shard land
         self._lengths = np.zeros((capacity_docs,), dtype=np.int64)   # host: rows each slot owns now (0 once compacted away)
         self._alive_h = np.zeros((capacity_docs,), dtype=bool)       # host mirror of `alive` (stale while _dirty)
         self._dirty = False                                          # a device-side delete has not been read back yet
         self.n_slots = 0
         self._rows_used = 0
-        self._score_fn, self._rerank_fn, self._int8_score_fn = score_fn, rerank_fn, int8_score_fn
+        self._score_fn, self._rerank_fn, self._stage1_fn = score_fn, rerank_fn, stage1_fn
         self._select, self._mask_fn = select, mask_fn
-        self._align_fn = align_fn
+        self._align_fn = align_fn         # (queries, view(), ids, maps=) -> Alignment
         self._mine_bounds_fn, self._mine_mask_fn = mine_bounds_fn, mine_mask_fn
         self._filter_fns = dict(filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
                                 group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn)
-        self._i8_codes: Optional[torch.Tensor] = None
-        self._i8_scales: Optional[torch.Tensor] = None
         self._compactions = 0
         self._rows_compacted = 0                                     # rows in use right after the last compaction (check())
-        row_bytes = self.width * self.blob.element_size()
+
+    @staticmethod
+    def _bounce_want(bounce_bytes: Optional[int], row_bytes: int) -> int:
         want = DEFAULT_BOUNCE_BYTES if bounce_bytes is None else int(bounce_bytes)
         if want < row_bytes:
             raise ValueError(f"bounce_bytes={want} holds no row of {row_bytes} bytes")
-        self.bounce_bytes = min(want, capacity_rows * row_bytes) // 16 * 16
-        if self.device.type == "cuda":                   # everything a compaction needs exists up front: no allocation later
-            ws_bytes = _lib.lib().msim_live_compact_workspace_bytes(capacity_docs, self.bounce_bytes)
-            self._bounce = torch.empty((self.bounce_bytes,), dtype=torch.uint8, device=self.device)
-            self._ws = [torch.zeros((ws_bytes,), dtype=torch.uint8, device=self.device) for _ in range(2)]   # rows, int8 codes
-            self._rows_used_dev = torch.zeros((2,), dtype=torch.int64, device=self.device)
-            self._off_tmp = torch.zeros((capacity_docs + 1,), dtype=torch.int32, device=self.device)
+        return want
 
-    # ------------------------------------------------------------------------------------------------------------ construction
-    @classmethod
-    def from_packed(cls, corpus: PackedCorpus, spare_rows: int, spare_docs: int, **kw) -> "LiveCorpus":
-        """A live corpus holding the pages of `corpus` (one device copy) plus room for `spare_rows` rows and `spare_docs` pages."""
-        if corpus.clamp0 is not None:
-            raise ValueError("a live corpus has no block zero-padding semantics: pack with batch_size=None (clamp0 must be None)")
-        lens = corpus.lengths.numpy().astype(np.int64)
+    def _alloc_compaction(self, n_plans: int) -> list:
+        """everything a compaction needs exists up front (no allocation later): the bounce buffer, a workspace and a row count per
+        offset plan; returns the workspaces"""
+        ws_bytes = getattr(_lib.lib(), self._entry + "_workspace_bytes")(self.capacity_docs, self.bounce_bytes)
+        self._bounce = torch.empty((self.bounce_bytes,), dtype=torch.uint8, device=self.device)
+        ws = [torch.zeros((ws_bytes,), dtype=torch.uint8, device=self.device) for _ in range(n_plans)]
+        self._rows_used_dev = torch.zeros((n_plans,), dtype=torch.int64, device=self.device)
+        return ws
+
+    @staticmethod
+    def _source_lengths(src) -> np.ndarray:
+        """the page lengths of a packed / compressed corpus a live shard can start from"""
+        if src.clamp0 is not None:
+            raise ValueError("a live shard has no block zero-padding semantics: pack with batch_size=None (clamp0 must be None)")
+        lens = src.lengths.numpy().astype(np.int64)
         if (lens <= 0).any():
-            raise ValueError("a live corpus holds no page of 0 rows: -inf means 'not there'")
-        n, rows = int(lens.size), int(lens.sum())
-        live = cls(rows + int(spare_rows), n + int(spare_docs), corpus.device, corpus.blob.dtype, int(corpus.blob.shape[1]),
-                   corpus.id_base, **kw)
-        live.blob[:rows].copy_(corpus.blob[:rows])
-        live.offsets[:n + 1].copy_(corpus.offsets)
-        live.alive[:n].fill_(1)
-        live._lengths[:n] = lens
-        live._alive_h[:n] = True
-        live.n_slots, live._rows_used = n, rows
-        return live
+            raise ValueError("a live shard holds no page of 0 rows: -inf means 'not there'")
+        return lens
+
+    def _adopt(self, offsets: torch.Tensor, lens: np.ndarray) -> None:
+        """slots 0 .. n - 1 are the pages whose rows the subclass has just copied in"""
+        n = int(lens.size)
+        self.offsets[:n + 1].copy_(offsets)
+        self.alive[:n].fill_(1)
+        self._lengths[:n] = lens
+        self._alive_h[:n] = True
+        self.n_slots, self._rows_used = n, int(lens.sum())
 
     # ------------------------------------------------------------------------------------------------------------------ state
     def __len__(self) -> int:
@@ -153,31 +160,24 @@ class LiveCorpus:
         if self.device.type != "cuda" or not self._compactions:
             return
         self._sync_host()
-        status = [int(w[:4].view(torch.int32)[0].item()) for w in self._ws]
+        status = [int(w[:4].view(torch.int32)[0].item()) for w in (self._ws if isinstance(self._ws, list) else [self._ws])]
         if any(status):
-            raise _lib.MaxSimLibraryError(f"msim_live_compact found broken offsets (status words {status}): nothing further was moved")
+            raise _lib.MaxSimLibraryError(f"{self._entry} found broken offsets (status words {status}): nothing further was moved")
         got = int(self._rows_used_dev[0].item())
         if got != self._rows_compacted:
-            raise _lib.MaxSimLibraryError(f"msim_live_compact left {got} rows in use, the host expected {self._rows_compacted}")
-
-    def view(self) -> PackedCorpus:
-        """The used prefix as a `PackedCorpus` (zero-copy slices), valid until the next `add` / `compact`.  Every slot is a
-        document: a deleted one keeps its rows until `compact()` and is an empty document afterwards."""
-        n = self.n_slots
-        return PackedCorpus(blob=self.blob[:max(self._rows_used, 1)], offsets=self.offsets[:n + 1], clamp0=None,
-                            lengths=torch.from_numpy(self._lengths[:n].copy()), id_base=self.id_base)
+            raise _lib.MaxSimLibraryError(f"{self._entry} left {got} rows in use, the host expected {self._rows_compacted}")
 
     # -------------------------------------------------------------------------------------------------------------------- add
     def add(self, pages: Union[torch.Tensor, Sequence[torch.Tensor]]) -> torch.Tensor:
-        """Append pages; returns their ids (int64, host).  `pages`: a list of [rows_i, width] tensors (host tensors go through
-        the pinned staging upload) or one [n, rows, width] tensor (on the device: rows and offsets are written there, nothing
-        synchronises).  Running out of rows or slots raises RuntimeError and leaves the corpus as it was."""
+        """Append pages; returns their ids (int64, host).  `pages`: a list of [rows_i, width] tensors or one [n, rows, width] tensor
+        (on the device: rows and offsets are written there, nothing synchronises).  Running out of rows or slots raises
+        RuntimeError and leaves the shard as it was."""
         if isinstance(pages, torch.Tensor):
             if pages.dim() != 3:
                 raise ValueError("a page tensor must be 3-D (n_pages, rows, width)")
             n, per, dim = (int(s) for s in pages.shape)
             if n and per == 0:
-                raise ValueError("a page of 0 rows cannot be added: in a live corpus -inf means 'not there'")
+                raise ValueError("a page of 0 rows cannot be added: in a live shard -inf means 'not there'")
             lens = np.full((n,), per, dtype=np.int64)
             first = pages
         else:
@@ -187,58 +187,48 @@ class LiveCorpus:
                 if p.dim() != 2:
                     raise ValueError("each page must be 2-D (rows, width)")
                 if p.shape[0] == 0:
-                    raise ValueError("a page of 0 rows cannot be added: in a live corpus -inf means 'not there'")
+                    raise ValueError("a page of 0 rows cannot be added: in a live shard -inf means 'not there'")
             lens = np.fromiter((p.shape[0] for p in pages), dtype=np.int64, count=n)
             first = pages[0] if n else None
-            dim = int(first.shape[1]) if n else self.dim
+            dim = int(first.shape[1]) if n else 0
             for p in pages:
                 if p.dtype != first.dtype or p.shape[1] != dim:
                     raise RuntimeError("expected pages of one dtype and one embedding width")
         if n == 0:
             return torch.empty((0,), dtype=torch.int64)
-        if first.dtype != self.dtype or dim not in (self.dim, self.width):
-            raise RuntimeError(f"this corpus holds {self.dtype} pages of width {self.dim}, got {first.dtype} of width {dim}")
+        if first.dtype != self.dtype or dim not in self._widths:
+            raise RuntimeError(f"this shard holds {self.dtype} pages of width {self._widths[0]}, got {first.dtype} of width {dim}")
         self._sync_host()
         total, n0, r0 = int(lens.sum()), self.n_slots, self._rows_used
         if n0 + n > self.capacity_docs:
-            raise RuntimeError(f"live corpus is full: {n0} of capacity_docs={self.capacity_docs} slots are taken, {n} more were asked for")
+            raise RuntimeError(f"live shard is full: {n0} of capacity_docs={self.capacity_docs} slots are taken, {n} more were asked for")
         if r0 + total > self.capacity_rows:
-            raise RuntimeError(f"live corpus is full: {r0} of capacity_rows={self.capacity_rows} rows are in use, {total} more were "
+            raise RuntimeError(f"live shard is full: {r0} of capacity_rows={self.capacity_rows} rows are in use, {total} more were "
                                "asked for (compact() hands back the rows of deleted pages)")
-        dst = self.blob[r0:r0 + total]
-        if isinstance(pages, torch.Tensor):
-            src = pages.reshape(total, dim).to(self.device, non_blocking=True)
-            dst[:, :dim].copy_(src)
-            if dim < self.width:
-                dst[:, dim:].zero_()
-            ends = torch.arange(1, n + 1, dtype=torch.int32, device=self.device) * int(lens[0]) + self.offsets[n0]
-            self.offsets[n0 + 1:n0 + n + 1].copy_(ends)
-        else:
-            image = host_list_image(pages, "pages") if self.device.type == "cuda" and dim == self.width else None
-            if image is not None:
-                keep, srcs, rows, _, _ = image
-                prefix = np.zeros(n + 1, dtype=np.int64)
-                np.cumsum(rows * (dim * first.element_size()), out=prefix[1:])
-                _staging.of(self.device).upload_image(srcs, prefix, n, dst.view(torch.uint8).view(-1),
-                                                      torch.cuda.current_stream(self.device))
-                del keep
-            else:
-                dst.copy_(_widen(torch.cat([p.to(self.device) for p in pages], dim=0)))
+        ends = self._write_rows(pages, lens, dim, n0, r0)
+        if ends is None:                   # a list: the new offsets come from the host
             ends = torch.from_numpy((r0 + np.cumsum(lens)).astype(np.int32))
-            self.offsets[n0 + 1:n0 + n + 1].copy_(ends)
+        self.offsets[n0 + 1:n0 + n + 1].copy_(ends)
         self.alive[n0:n0 + n].fill_(1)
         self._lengths[n0:n0 + n] = lens
         self._alive_h[n0:n0 + n] = True
         self.n_slots, self._rows_used = n0 + n, r0 + total
-        if self._i8_codes is not None:
-            self._encode_i8(n0, n0 + n)
+        self._added(n0, n0 + n)
         return torch.arange(self.id_base + n0, self.id_base + n0 + n, dtype=torch.int64)
+
+    def _write_rows(self, pages, lens: np.ndarray, dim: int, n0: int, r0: int) -> Optional[torch.Tensor]:
+        """Write the rows of the validated `pages` (they fit) from row `r0` on.  For a page tensor, return the new offsets
+        (int32 [n], computed on its device); for a list, None."""
+        raise NotImplementedError
+
+    def _added(self, lo: int, hi: int) -> None:
+        """slots lo .. hi - 1 have just been committed"""
 
     # ----------------------------------------------------------------------------------------------------------------- delete
     def delete(self, ids) -> None:
         """Clear `alive` for `ids`; every search sees it at once, the rows stay until `compact()`.  A host list (or host tensor):
         unknown, out-of-range or already-deleted ids raise KeyError and nothing is deleted.  An int64 tensor on the device is
-        applied without a synchronisation and ids outside the corpus are ignored."""
+        applied without a synchronisation and ids outside the shard are ignored."""
         if isinstance(ids, torch.Tensor) and ids.device.type != "cpu":
             if ids.dtype != torch.int64 or ids.device != self.device:
                 raise ValueError(f"device ids must be an int64 tensor on {self.device}")
@@ -269,17 +259,171 @@ class LiveCorpus:
         dead = ~self._alive_h[:n] & (self._lengths[:n] > 0)
         if not dead.any():
             return
-        if self.device.type != "cuda":
-            raise RuntimeError("compaction is a gfx950 kernel (msim_live_compact): this corpus lives on " + str(self.device))
-        bound = self._rows_used
-        if self._i8_codes is not None:                   # the same moves on the code rows, against a copy of the old offsets
-            self._off_tmp[:n + 1].copy_(self.offsets[:n + 1])
-            self._compact_rows(self._i8_codes, I8_DIM, bound, self._off_tmp, 1)
-            self._i8_scales[:n].masked_fill_(self.alive[:n] == 0, 0.0)      # an empty page has scale 0 (msim_i8_encode_docs)
-        self._compact_rows(self.blob, self.width * self.blob.element_size(), bound, self.offsets, 0)
+        self._move_rows(self._rows_used)
         self._lengths[:n][dead] = 0
         self._rows_used = self._rows_compacted = int(self._lengths[:n].sum())
         self._compactions += 1
+
+    def _move_rows(self, rows_bound: int) -> None:
+        """Move every array of rows, and the offsets, on the device; raise (having changed nothing) where that cannot be done."""
+        raise NotImplementedError
+
+    # ----------------------------------------------------------------------------------------------------------------- search
+    def _masked(self, scores: torch.Tensor) -> torch.Tensor:
+        return self._mask_fn(scores, self.alive[:self.n_slots])
+
+    def _score(self, queries, corpus):
+        return self._masked(self._score_fn(queries, corpus))
+
+    def _stage1_score(self, queries, index):
+        return self._masked(self._stage1_fn(queries, index))
+
+    def _live_ids(self, candidates: torch.Tensor) -> torch.Tensor:
+        """`candidates` with every id that is outside the shard or deleted replaced by -1 (on the device, no synchronisation)"""
+        n = self.n_slots
+        idx = candidates - self.id_base
+        inside = (idx >= 0) & (idx < n)
+        live = self.alive[:max(n, 1)][idx.clamp(0, max(n - 1, 0))] != 0
+        return torch.where(inside & live, candidates, torch.full_like(candidates, -1))
+
+    def _rerank(self, queries, corpus, candidates):
+        return self._rerank_fn(queries, corpus, self._live_ids(candidates))
+
+    def _retriever(self, shard, world, rank, dist, group, **hooks) -> ShardedRetriever:
+        return ShardedRetriever(shard, world, rank, dist, group, select=self._select, **hooks)
+
+    def align(self, queries, ids: torch.Tensor, maps: bool = False) -> Alignment:
+        """`align` (`residual_align` over a compressed shard, which decodes the listed pages inside the kernel) over the live pages:
+        a deleted id is treated as -1 (no page: (-inf, -1)), as `search(candidates=)` treats it; a surviving page's result has the
+        bits of the same call over `self.view()`, before and after `compact()`."""
+        return self._align_fn(queries, self.view(), self._live_ids(ids), maps=maps)
+
+    def mine(self, queries, positives, n_neg: int, *, max_ratio: Optional[float] = None, skip_top: int = 0, compact: bool = False,
+             world: int = 1, rank: int = 0, dist=None, group=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`ShardedRetriever.mine` (`mine_hard_negatives`) over the live pages: the tombstone mask goes into the mining mask, so a
+        deleted page is never mined and a deleted positive bounds nothing (it is not there).  The result has the bits of
+        `mine_hard_negatives` over a fresh pack of the surviving pages, positions mapped back to slots.  It scans the shard: a
+        compressed one needs `score_fn=residual_scores` (NotImplementedError otherwise)."""
+        r = self._retriever(self.view(), world, rank, dist, group, score_fn=self._score_fn, mine_bounds_fn=self._mine_bounds_fn,
+                            mine_mask_fn=self._mine_mask_fn)
+        return r.mine(queries, positives, n_neg, max_ratio=max_ratio, skip_top=skip_top, alive=self.alive[:self.n_slots], compact=compact)
+
+    def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None, prefilter=None,
+               n_candidates: Optional[int] = None, world: int = 1, rank: int = 0, dist=None, group=None,
+               filter: Optional[PageFilter] = None, filter_route: str = "auto", group_by: Optional[PageGroups] = None):
+        """`ShardedRetriever.search` over the live pages: the same arguments, rules and return value; a deleted page is never
+        returned, and where fewer than `k` live pages exist the tail is (-inf, -1).  `candidates=` lists may name deleted and foreign
+        ids (they become -1 before the rerank).  `prefilter` is the shard's own stage 1 (`LiveCorpus.int8_index()`,
+        `LiveResidualCorpus.index`), or a `PackedCorpus` over the same slots (e.g. pooled pages); its scores are masked too.
+        `filter` covers the slots (`len(filter) == len(self)`, deleted ones included) and is ANDed with the tombstones on both
+        routes: the scores of deleted slots are -inf before the filter masks the rest, and a listed id that is deleted is no page to
+        the rerank.  `group_by` covers the slots too (`len(group_by) == len(self)`, deleted ones included): a document is scored by
+        its surviving pages, and one whose every page is deleted is not returned.  A `PageGroups` is immutable: build a new one over
+        all slots after `add`.  Over a compressed shard the routes that read every row (the full scan, the mask route of `filter=`,
+        `group_by=` on the scan, `mine`) are refused with `ShardedRetriever`'s NotImplementedError unless `score_fn=residual_scores`."""
+        shard = self.view()
+        if self.device.type == "cuda":     # an injected hook packs host queries itself
+            queries = _as_packed(queries, self.device, compact=compact)
+        r = self._retriever(shard, world, rank, dist, group, score_fn=self._score, rerank_fn=self._rerank,
+                            **{self._stage1_kw: self._stage1_score}, **self._filter_fns)
+        if group_by is not None:                 # (-inf, -1, -1) is already the rule there
+            return r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates, filter=filter,
+                            filter_route=filter_route, group_by=group_by)
+        scores, ids = r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates,
+                               filter=filter, filter_route=filter_route)
+        return _no_page(scores, ids)             # a deleted slot that filled a short row
+
+
+class LiveCorpus(_LiveShard):
+    """One mutable resident shard (see the module docstring).  `capacity_rows` and `capacity_docs` are fixed at construction.
+
+    `score_fn`, `rerank_fn`, `int8_score_fn`, `select`, the `filter_*_fn` and `mask_fn` are the hooks of `ShardedRetriever` plus the tombstone mask
+    (`mask_fn(scores, alive) -> scores`); the defaults are the gfx950 kernels.  Host-logic tests inject reference scorers and run on the CPU."""
+
+    _entry = "msim_live_compact"
+    _stage1_kw = "int8_score_fn"
+
+    def __init__(self, capacity_rows: int, capacity_docs: int, device, dtype: torch.dtype = torch.bfloat16, width: int = 128,
+                 id_base: int = 0, *, bounce_bytes: Optional[int] = None, score_fn: Callable = maxsim_scores,
+                 rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, select: Callable = topk,
+                 mask_fn: Callable = mask_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
+                 mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
+                 filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
+        capacity_rows, capacity_docs = self._capacity(capacity_rows, capacity_docs)
+        _lib.dtype_code(dtype)                                   # raises for anything but bf16 / f16 / f32
+        self.device = torch.device(device)
+        self.dtype, self.dim = dtype, int(width)
+        self.width = _lib.kernel_width(self.dim, dtype)          # physical row width (zero columns appended, as pack_passages)
+        self.blob = torch.zeros((capacity_rows, self.width), dtype=dtype, device=self.device)
+        self._init_slots(capacity_rows, capacity_docs, self.device, id_base, score_fn=score_fn, rerank_fn=rerank_fn, stage1_fn=int8_score_fn,
+                         select=select, mask_fn=mask_fn, align_fn=align_fn, mine_bounds_fn=mine_bounds_fn, mine_mask_fn=mine_mask_fn,
+                         filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
+                         group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn)
+        self._i8_codes: Optional[torch.Tensor] = None
+        self._i8_scales: Optional[torch.Tensor] = None
+        row_bytes = self.width * self.blob.element_size()
+        self.bounce_bytes = min(self._bounce_want(bounce_bytes, row_bytes), capacity_rows * row_bytes) // 16 * 16
+        if self.device.type == "cuda":
+            self._ws = self._alloc_compaction(2)                 # one offset plan for the rows, one for the int8 codes
+            self._off_tmp = torch.zeros((capacity_docs + 1,), dtype=torch.int32, device=self.device)
+
+    @classmethod
+    def from_packed(cls, corpus: PackedCorpus, spare_rows: int, spare_docs: int, **kw) -> "LiveCorpus":
+        """A live corpus holding the pages of `corpus` (one device copy) plus room for `spare_rows` rows and `spare_docs` pages."""
+        lens = cls._source_lengths(corpus)
+        n, rows = int(lens.size), int(lens.sum())
+        live = cls(rows + int(spare_rows), n + int(spare_docs), corpus.device, corpus.blob.dtype, int(corpus.blob.shape[1]),
+                   corpus.id_base, **kw)
+        live.blob[:rows].copy_(corpus.blob[:rows])
+        live._adopt(corpus.offsets, lens)
+        return live
+
+    @property
+    def _widths(self) -> Tuple[int, ...]:
+        return (self.dim, self.width)
+
+    def view(self) -> PackedCorpus:
+        """The used prefix as a `PackedCorpus` (zero-copy slices), valid until the next `add` / `compact`.  Every slot is a
+        document: a deleted one keeps its rows until `compact()` and is an empty document afterwards."""
+        n = self.n_slots
+        return PackedCorpus(blob=self.blob[:max(self._rows_used, 1)], offsets=self.offsets[:n + 1], clamp0=None,
+                            lengths=torch.from_numpy(self._lengths[:n].copy()), id_base=self.id_base)
+
+    def _write_rows(self, pages, lens, dim, n0, r0):
+        """host pages go through the pinned staging upload; a page tensor is copied (on the device: from the caller's memory)"""
+        n, total = int(lens.size), int(lens.sum())
+        dst = self.blob[r0:r0 + total]
+        if isinstance(pages, torch.Tensor):
+            src = pages.reshape(total, dim).to(self.device, non_blocking=True)
+            dst[:, :dim].copy_(src)
+            if dim < self.width:
+                dst[:, dim:].zero_()
+            return torch.arange(1, n + 1, dtype=torch.int32, device=self.device) * int(lens[0]) + self.offsets[n0]
+        image = host_list_image(pages, "pages") if self.device.type == "cuda" and dim == self.width else None
+        if image is not None:
+            keep, srcs, rows, _, _ = image
+            prefix = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(rows * (dim * pages[0].element_size()), out=prefix[1:])
+            _staging.of(self.device).upload_image(srcs, prefix, n, dst.view(torch.uint8).view(-1),
+                                                  torch.cuda.current_stream(self.device))
+            del keep
+        else:
+            dst.copy_(_widen(torch.cat([p.to(self.device) for p in pages], dim=0)))
+        return None
+
+    def _added(self, lo, hi):
+        if self._i8_codes is not None:
+            self._encode_i8(lo, hi)
+
+    def _move_rows(self, rows_bound):
+        if self.device.type != "cuda":
+            raise RuntimeError("compaction is a gfx950 kernel (msim_live_compact): this corpus lives on " + str(self.device))
+        n = self.n_slots
+        if self._i8_codes is not None:                   # the same moves on the code rows, against a copy of the old offsets
+            self._off_tmp[:n + 1].copy_(self.offsets[:n + 1])
+            self._compact_rows(self._i8_codes, I8_DIM, rows_bound, self._off_tmp, 1)
+            self._i8_scales[:n].masked_fill_(self.alive[:n] == 0, 0.0)      # an empty page has scale 0 (msim_i8_encode_docs)
+        self._compact_rows(self.blob, self.width * self.blob.element_size(), rows_bound, self.offsets, 0)
 
     def _compact_rows(self, rows: torch.Tensor, row_bytes: int, bound: int, offsets: torch.Tensor, which: int) -> None:
         with torch.cuda.device(self.device):
@@ -315,60 +459,3 @@ class LiveCorpus:
         n = self.n_slots
         return Int8Index(self._i8_codes[:max(self._rows_used, 1)], self._i8_scales[:n], self.offsets[:n + 1], None,
                          torch.from_numpy(self._lengths[:n].copy()), self.id_base)
-
-    # ----------------------------------------------------------------------------------------------------------------- search
-    def _masked(self, scores: torch.Tensor) -> torch.Tensor:
-        return self._mask_fn(scores, self.alive[:self.n_slots])
-
-    def _score(self, queries, corpus):
-        return self._masked(self._score_fn(queries, corpus))
-
-    def _int8_score(self, queries, index):
-        return self._masked(self._int8_score_fn(queries, index))
-
-    def _live_ids(self, candidates: torch.Tensor) -> torch.Tensor:
-        """`candidates` with every id that is outside the corpus or deleted replaced by -1 (on the device, no synchronisation)"""
-        n = self.n_slots
-        idx = candidates - self.id_base
-        inside = (idx >= 0) & (idx < n)
-        live = self.alive[:max(n, 1)][idx.clamp(0, max(n - 1, 0))] != 0
-        return torch.where(inside & live, candidates, torch.full_like(candidates, -1))
-
-    def _rerank(self, queries, corpus, candidates):
-        return self._rerank_fn(queries, corpus, self._live_ids(candidates))
-
-    def align(self, queries, ids: torch.Tensor, maps: bool = False) -> Alignment:
-        """`align` over the live pages: a deleted id is treated as -1 (no page: (-inf, -1)), as `search(candidates=)` treats it; a
-        surviving page's result has the bits of `align(queries, self.view(), ids)`."""
-        return self._align_fn(queries, self.view(), self._live_ids(ids), maps=maps)
-
-    def mine(self, queries, positives, n_neg: int, *, max_ratio: Optional[float] = None, skip_top: int = 0, compact: bool = False,
-             world: int = 1, rank: int = 0, dist=None, group=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """`ShardedRetriever.mine` (`mine_hard_negatives`) over the live pages: the tombstone mask goes into the mining mask, so a
-        deleted page is never mined and a deleted positive bounds nothing (it is not there).  The result has the bits of
-        `mine_hard_negatives` over a fresh pack of the surviving pages, positions mapped back to slots."""
-        r = ShardedRetriever(self.view(), world, rank, dist, group, score_fn=self._score_fn, select=self._select,
-                             mine_bounds_fn=self._mine_bounds_fn, mine_mask_fn=self._mine_mask_fn)
-        return r.mine(queries, positives, n_neg, max_ratio=max_ratio, skip_top=skip_top, alive=self.alive[:self.n_slots], compact=compact)
-
-    def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None, prefilter=None,
-               n_candidates: Optional[int] = None, world: int = 1, rank: int = 0, dist=None, group=None,
-               filter: Optional[PageFilter] = None, filter_route: str = "auto", group_by: Optional[PageGroups] = None):
-        """`ShardedRetriever.search` over the live pages: the same arguments, rules and return value; a deleted page is never
-        returned, and where fewer than `k` live pages exist the tail is (-inf, -1).  `prefilter` is `self.int8_index()`, or a
-        `PackedCorpus` over the same slots (e.g. pooled pages; its deleted slots are masked too).  `filter` covers the slots
-        (`len(filter) == len(self)`, deleted ones included) and is ANDed with the tombstones on both routes: the scores of deleted
-        slots are -inf before the filter masks the rest, and a listed id that is deleted is no page to the rerank.  `group_by` covers
-        the slots too (`len(group_by) == len(self)`, deleted ones included): a document is scored by its surviving pages, and one
-        whose every page is deleted is not returned.  A `PageGroups` is immutable: build a new one over all slots after `add`."""
-        shard = self.view()
-        if self.device.type == "cuda":     # an injected hook packs host queries itself
-            queries = _as_packed(queries, self.device, compact=compact)
-        r = ShardedRetriever(shard, world, rank, dist, group, score_fn=self._score, select=self._select, rerank_fn=self._rerank,
-                             int8_score_fn=self._int8_score, **self._filter_fns)
-        if group_by is not None:                 # (-inf, -1, -1) is already the rule there
-            return r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates, filter=filter,
-                            filter_route=filter_route, group_by=group_by)
-        scores, ids = r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates,
-                               filter=filter, filter_route=filter_route)
-        return _no_page(scores, ids)             # a deleted slot that filled a short row

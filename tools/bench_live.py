@@ -11,6 +11,7 @@ Legs, each timed with device events (compact: one call per fresh set of deletion
   * search: LiveCorpus.search with nothing deleted against ShardedRetriever.search on the same rows, alternating, at 4 and 1000
     queries of 32 tokens; the mask's estimate is n_q x n x 8 B / 8 TB/s plus one launch.
   * add: add() of 1000 pages of --doc-len rows from a host list against the H2D floor of their bytes at 56 GB/s.
+search and add report the median over --steps and, as *_spread_ms, max - min of those identical calls.
 """
 from __future__ import annotations
 
@@ -101,7 +102,8 @@ def search_leg(amd, corpus, n_q, q_len, dev, steps):
     lv.sort(), rf.sort()
     est = n_q * len(corpus) * 8 / (HBM_PEAK_GBS * 1e9) * 1e3
     return {"live_ms": lv[len(lv) // 2], "static_ms": rf[len(rf) // 2], "difference_ms": lv[len(lv) // 2] - rf[len(rf) // 2],
-            "mask_alone_ms": mask["median_ms"], "mask_estimate_ms": est}
+            "live_spread_ms": lv[-1] - lv[0], "static_spread_ms": rf[-1] - rf[0], "mask_alone_ms": mask["median_ms"],
+            "mask_estimate_ms": est}
 
 
 def add_leg(amd, dev, n_pages, doc_len, steps):
@@ -116,7 +118,8 @@ def add_leg(amd, dev, n_pages, doc_len, steps):
         ms.append((time.perf_counter() - t0) * 1e3)
     ms = sorted(ms[2:])
     floor = nbytes / (H2D_GBS * 1e9) * 1e3
-    return {"pages": n_pages, "bytes": nbytes, "add_ms": ms[len(ms) // 2], "h2d_floor_ms": floor, "share_of_floor": floor / ms[len(ms) // 2]}
+    return {"pages": n_pages, "bytes": nbytes, "add_ms": ms[len(ms) // 2], "add_spread_ms": ms[-1] - ms[0], "h2d_floor_ms": floor,
+            "share_of_floor": floor / ms[len(ms) // 2]}
 
 
 def main():
