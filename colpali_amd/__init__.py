@@ -16,6 +16,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      grouped into documents, the top-k DOCUMENTS, each scored by (and returned with) its best page
   * FdeIndex / fde_scores         -- fixed dimensional encodings (MUVERA): a one-GEMM first stage for prefilter=
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
+  * BinaryIndex / binary_scores   -- one sign bit per dimension of every corpus row (16 bytes per row), scored against the int8
+                                     queries on int8 MFMAs: a token-level first stage for prefilter= at 1/16 of the bf16 shard
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
                                      centroid interaction): a first stage for prefilter= at 2 bytes per row
   * ResidualCorpus / residual_rerank_scores -- PLAID's second half: the shard itself as centroid codes + 2 / 4 residual bits per
@@ -32,6 +34,7 @@ The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
 colpali_amd/csrc/); this package is the thin host-side mirror of the reference interface.
 """
 from .align import Alignment, align
+from .binary_index import BinaryIndex, binary_scores, binary_scores_from_codes
 from .centroid import CentroidIndex, centroid_scores, train_centroids
 from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pack_queries
 from . import loss
@@ -68,6 +71,9 @@ __all__ = [
     "Int8Index",
     "int8_scores",
     "quantize_queries",
+    "BinaryIndex",
+    "binary_scores",
+    "binary_scores_from_codes",
     "CentroidIndex",
     "centroid_scores",
     "train_centroids",

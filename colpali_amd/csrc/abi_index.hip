@@ -1,6 +1,6 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the first-stage indexes -- fixed dimensional encodings, the int8
-// token-level index and the centroid-code index -- and the residual-compressed corpus built on the centroid codes, with the fused
-// append-encode of its live form.
+// token-level index, the 1-bit sign index and the centroid-code index -- and the residual-compressed corpus built on the centroid
+// codes, with the fused append-encode of its live form.
 // Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates,
 // frees or synchronises, so every entry point is hipGraph-capturable.  The kernels included below are defined and launched in
 // this translation unit and in no other.
@@ -13,6 +13,7 @@
 #include "abi_common.hpp"
 #include "fde.hip"
 #include "int8_index.hip"
+#include "binary_index.hip"
 #include "centroid_index.hip"
 #include "residual_codec.hip"
 #include "residual_scan.hip"
@@ -222,6 +223,115 @@ int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int 
                                           scores, ld_scores, st);
     return i8_scores_launch<NT, 4, 4>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, d8, sd, d_off, clamp0, n_d, d_rows, (int)ppw,
                                       (int)n_groups, scores, ld_scores, st);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the 1-bit sign index (binary_index.hip)
+namespace {
+
+// the launch form of a shape: the int8 scorer's query plan (every query gets TPQ 16-token tiles, QG queries fill one wave's NT
+// tiles, a longer query takes several passes) and GW = the waves that share a page range
+struct BinPlan {
+    static constexpr int NT = 8, D = 4;
+    int QG, TPQ, passes, GW, ppw;
+    long long n_groups;
+};
+
+BinPlan bin_plan(int n_q, int max_q_tokens, int n_d, int cus) {
+    BinPlan p;
+    const int tiles = max_q_tokens ? (max_q_tokens + msim::kI8Tile - 1) / msim::kI8Tile : 1;
+    p.QG = 1, p.TPQ = BinPlan::NT, p.passes = 1;
+    if (tiles <= BinPlan::NT) {
+        p.TPQ = tiles;
+        p.QG = BinPlan::NT / tiles;
+    } else {
+        p.passes = (tiles + BinPlan::NT - 1) / BinPlan::NT;
+    }
+    p.n_groups = ((long long)n_q + p.QG - 1) / p.QG;
+    p.GW = p.n_groups <= 1 ? 1 : p.n_groups == 2 ? 2 : 4;
+    // page ranges: enough waves to fill the chip (8 per CU, ~4 rounds); at most 16 pages a range when several query groups re-read it
+    const long long want = (long long)(cus > 0 ? cus : 1) * 32;
+    const long long work = p.n_groups * n_d;
+    const int cap = p.n_groups <= 1 ? msim::kI8MaxRange : 16;
+    long long ppw = (work + want - 1) / want;
+    p.ppw = (int)(ppw < 1 ? 1 : ppw > cap ? cap : ppw);
+    return p;
+}
+
+template <int GW>
+int bin_scores_launch(const BinPlan &p, const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows,
+                      const uint8_t *codes, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, float *scores,
+                      int64_t ld, hipStream_t st) {
+    const long long n_gb = (p.n_groups + GW - 1) / GW;
+    const long long n_ranges = ((long long)n_d + p.ppw - 1) / p.ppw, n_pb = (n_ranges + 4 / GW - 1) / (4 / GW);
+    if (n_gb * n_pb > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "msim_bin_scores: %lld workgroups exceed one launch", n_gb * n_pb);
+    hipLaunchKernelGGL((msim::bin_scores_kernel<BinPlan::NT, GW, BinPlan::D>), dim3((unsigned)(n_gb * n_pb)), dim3(256), 0, st, q8, sq,
+                       q_off, n_q, (long long)q_rows, p.QG, p.TPQ, p.passes, codes, d_off, clamp0, n_d, (long long)d_rows, p.ppw,
+                       (int)p.n_groups, (int)n_gb, scores, (long long)ld);
+    return launch_failed("bin_scores_kernel");
+}
+
+}  // namespace
+
+extern "C" {
+
+int msim_bin_encode_rows(int dtype, const void *X, int64_t n_rows, int dim, uint8_t *codes, void *stream) {
+    const char *who = "msim_bin_encode_rows";
+    if (n_rows < 0) return fail(MSIM_EINVAL, "%s: negative size (rows=%lld)", who, (long long)n_rows);
+    if (dim != msim::kDim) return fail(MSIM_EUNSUPPORTED, "%s: rows of width %d; the sign index takes width %d", who, dim, msim::kDim);
+    if (!(dtype == MSIM_DTYPE_BF16 || dtype == MSIM_DTYPE_F16))
+        return fail(MSIM_EUNSUPPORTED, "%s takes bfloat16 / float16 rows (dtype code %d)", who, dtype);
+    if (n_rows == 0) return MSIM_OK;
+    if (!X || !codes) return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(X, 16) || misaligned(codes, 16)) return fail(MSIM_EINVAL, "%s: rows and codes must be 16-byte aligned", who);
+    if ((n_rows + 15) / 16 > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld rows exceed one launch", who, (long long)n_rows);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto kern = dtype == MSIM_DTYPE_F16 ? msim::bin_encode_rows_kernel<true> : msim::bin_encode_rows_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n_rows + 15) / 16)), dim3(256), 0, st, static_cast<const uint16_t *>(X), (long long)n_rows,
+                       codes);
+    return launch_failed("bin_encode_rows_kernel");
+}
+
+int msim_bin_scores_plan(int n_q, int max_q_tokens, int n_d, int64_t d_rows, int32_t *plan) {
+    const char *who = "msim_bin_scores_plan";
+    if (n_q < 0 || n_d < 0 || d_rows < 0 || max_q_tokens < 0 || max_q_tokens > (1 << 20) || !plan)
+        return fail(MSIM_EINVAL, "%s: bad argument", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const BinPlan p = bin_plan(n_q, max_q_tokens, n_d, di->cus);
+    plan[0] = BinPlan::NT;
+    plan[1] = p.GW;
+    plan[2] = BinPlan::D;
+    plan[3] = p.ppw;
+    return MSIM_OK;
+}
+
+int msim_bin_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                    const uint8_t *codes, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int dim, float *scores,
+                    int64_t ld_scores, void *stream) {
+    const char *who = "msim_bin_scores";
+    if (n_q < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d,
+                    (long long)q_rows, (long long)d_rows, max_q_tokens);
+    if (dim != msim::kDim) return fail(MSIM_EUNSUPPORTED, "%s: rows of width %d; the sign index takes width %d", who, dim, msim::kDim);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if ((!q8 && q_rows > 0) || (!sq && q_rows > 0) || !q_off || (!codes && d_rows > 0) || !d_off || !scores)
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(q8, 16) || misaligned(codes, 16) || misaligned(sq, 4) || misaligned(q_off, 4) || misaligned(d_off, 4) ||
+        misaligned(scores, 4))
+        return fail(MSIM_EINVAL, "%s: codes must be 16-byte aligned; scales, offsets and scores 4-byte aligned", who);
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
+    if (max_q_tokens > (1 << 20)) return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, 1 << 20);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const BinPlan p = bin_plan(n_q, max_q_tokens, n_d, di->cus);
+    if (p.GW == 1) return bin_scores_launch<1>(p, q8, sq, q_off, n_q, q_rows, codes, d_off, clamp0, n_d, d_rows, scores, ld_scores, st);
+    if (p.GW == 2) return bin_scores_launch<2>(p, q8, sq, q_off, n_q, q_rows, codes, d_off, clamp0, n_d, d_rows, scores, ld_scores, st);
+    return bin_scores_launch<4>(p, q8, sq, q_off, n_q, q_rows, codes, d_off, clamp0, n_d, d_rows, scores, ld_scores, st);
 }
 
 }  // extern "C"

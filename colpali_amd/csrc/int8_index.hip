@@ -20,6 +20,8 @@
 //                             by one lane per query (through LDS) and stored once per (query, page).
 //                             GW waves of a workgroup take GW query groups of ONE page range (the rows are read once per workgroup
 //                             from L2, the others hit in L1), and consecutive workgroups of a page range run on one XCD.
+//                             Its body is token_scores<NT,GW,D,Rows> over I8Rows; binary_index.hip runs the same body over its
+//                             sign-bit rows.
 // Nothing allocates or synchronises.  Every address comes from a checked index: page offsets against the row count, query offsets
 // against the token count and the caller's bound on a query's length.  A page range or a query whose offsets break them is
 // written as NaN.
@@ -116,16 +118,38 @@ __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }   //
 
 __device__ __forceinline__ int lane_of(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 
-// NT: 16-token tiles per wave; GW: waves of a workgroup that share one page range (1, 2 or 4); D: chunks loaded ahead
+// The page rows of the int8 index, as the scorer below reads them: 128 code bytes per row, the lane's two 16-byte pieces ARE its A
+// operands, and a page's token sum is scaled by the page's fp32 scale.  (binary_index.hip has the sign-bit rows.)
+struct I8Rows {
+    const int8_t *__restrict__ d8;
+    const float *__restrict__ sd;
+    static constexpr int kRowBytes = kI8Row;
+    struct Chunk {
+        i32x4 v[2];
+    };
+    __device__ __forceinline__ const void *row(long long r) const { return d8 + r * kI8Row; }
+    __device__ __forceinline__ static void load(const __amdgpu_buffer_rsrc_t &rs, int row, int l4, Chunk &c) {
+        const int voff = row * kI8Row + l4 * 16;                     // past the stream's end: the descriptor returns zeros
+        c.v[0] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
+        c.v[1] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 64, 0, 0));
+    }
+    __device__ __forceinline__ static void operands(const Chunk &c, i32x4 &a0, i32x4 &a1) {
+        a0 = c.v[0];
+        a1 = c.v[1];
+    }
+    __device__ __forceinline__ float page_score(int p, float T) const { return sd[p] * T; }
+};
+
+// NT: 16-token tiles per wave; GW: waves of a workgroup that share one page range (1, 2 or 4); D: chunks loaded ahead; Rows: the
+// page rows (I8Rows, BinRows): their bytes per row, the chunk load, its expansion to the two A operands, and the page's scale
 // queries: group g = queries g * QG .. g * QG + QG - 1, query slot s owns tiles s * TPQ .. s * TPQ + TPQ - 1 (QG * TPQ <= NT);
 // with passes > 1 (QG = 1, TPQ = NT) the page range is streamed once per NT tiles and the sum carries on in token order.
-template <int NT, int GW, int D>
-__global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict__ q8, const float *__restrict__ sq,
-                                                        const int32_t *__restrict__ q_off, int n_q, long long q_rows, int QG, int TPQ,
-                                                        int passes, const int8_t *__restrict__ d8, const float *__restrict__ sd,
-                                                        const int32_t *__restrict__ d_off, const uint8_t *__restrict__ clamp0, int n_d,
-                                                        long long d_rows, int ppw, int n_groups, int n_gb, float *__restrict__ scores,
-                                                        long long ld) {
+template <int NT, int GW, int D, class Rows>
+__device__ __forceinline__ void token_scores(const int8_t *__restrict__ q8, const float *__restrict__ sq,
+                                             const int32_t *__restrict__ q_off, int n_q, long long q_rows, int QG, int TPQ, int passes,
+                                             const Rows rows, const int32_t *__restrict__ d_off, const uint8_t *__restrict__ clamp0,
+                                             int n_d, long long d_rows, int ppw, int n_groups, int n_gb, float *__restrict__ scores,
+                                             long long ld) {
     static_assert(GW == 1 || GW == 2 || GW == 4, "waves per page range");
     constexpr int RW = 4 / GW;                                         // page ranges per workgroup
     __shared__ float vals_all[4][NT * kI8Tile];
@@ -170,10 +194,10 @@ __global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict
             if (lane < nqs) scores[((long long)g * QG + lane) * ld + p0 + pl] = __builtin_nanf("");
         return;
     }
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(d8 + (long long)R0 * kI8Row), 0,
-                                                                        (R1 - R0) * kI8Row, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(rows.row(R0)), 0,
+                                                                        (R1 - R0) * Rows::kRowBytes, 0x00020000);
     const int nrows = R1 - R0, nch = (nrows + kI8Tile - 1) / kI8Tile;
-    const int lrow = lane & 15, kq = (lane >> 4) * 16;                // operand lane map: row lrow, bytes kq .. kq + 15 of each half
+    const int lrow = lane & 15, l4 = lane >> 4, kq = l4 * 16;         // operand lane map: row lrow, bytes kq .. kq + 15 of each half
 
     for (int pass = 0; pass < passes; ++pass) {
         // the query fragments (B) and token scales of this pass, in registers for the whole page range
@@ -193,11 +217,7 @@ __global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict
             }
         }
 
-        auto load = [&](int ch, i32x4 *dst) {
-            const int voff = (ch * kI8Tile + lrow) * kI8Row + kq;       // past the stream's end: the descriptor returns zeros
-            dst[0] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0));
-            dst[1] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + 64, 0, 0));
-        };
+        auto load = [&](int ch, typename Rows::Chunk &dst) { Rows::load(rs, ch * kI8Tile + lrow, l4, dst); };
 
         i32x4 runmax[NT];
 #pragma unroll
@@ -230,7 +250,7 @@ __global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict
                 if (pass + 1 < passes) {
                     part[pl] = T;
                 } else {
-                    const float s = empty ? -__builtin_inff() : qok ? sd[p] * T : __builtin_nanf("");
+                    const float s = empty ? -__builtin_inff() : qok ? rows.page_score(p, T) : __builtin_nanf("");
                     scores[((long long)g * QG + lane) * ld + p] = s;
                 }
             }
@@ -242,7 +262,7 @@ __global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict
             pend = pl < np ? lane_of(offl, pl + 1) - R0 : 0x7fffffff;
         };
 
-        i32x4 buf[D][2];
+        typename Rows::Chunk buf[D];
 #pragma unroll
         for (int d = 0; d < D; ++d) load(d, buf[d]);
         for (int ch0 = 0; ch0 < nch; ch0 += D) {
@@ -250,7 +270,8 @@ __global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict
             for (int d = 0; d < D; ++d) {
                 const int ch = ch0 + d;
                 if (ch >= nch) break;
-                const i32x4 a0 = buf[d][0], a1 = buf[d][1];
+                i32x4 a0, a1;
+                Rows::operands(buf[d], a0, a1);
                 load(ch + D, buf[d]);
                 i32x4 acc[NT];
 #pragma unroll
@@ -259,14 +280,16 @@ __global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict
                 for (int t = 0; t < NT; ++t) acc[t] = i8_mfma(a1, qb[t][1], acc[t]);
                 // D: lane holds token (lane & 15) of each tile against chunk rows 4 (lane >> 4) + {0..3}
                 const int cs = ch * kI8Tile, ce = cs + kI8Tile;
-                if (pstart <= cs && pend >= ce) {                         // the chunk lies inside one page: no mask
+                if (pstart <= cs && pend >= ce) {                         // the chunk lies inside one page: every row is real, no mask
 #pragma unroll
                     for (int t = 0; t < NT; ++t)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) runmax[t][r] = imax(runmax[t][r], acc[t][r]);
                     if (pend == ce && pl < np) finish();
                 } else {
-                    while (true) {                                        // a page boundary inside the chunk
+                    // a page boundary inside the chunk.  A range's last partial chunk always comes here (its last boundary is the
+                    // range's end), so the rows the descriptor made up past it stay outside [lo, hi) of every page that is stored
+                    while (true) {
                         const int lo = (pstart > cs ? pstart : cs) - cs, hi = (pend < ce ? pend : ce) - cs;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -286,6 +309,17 @@ __global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict
         }
         while (pl < np) finish();                                         // empty pages at the range's end (and a range of 0 rows)
     }
+}
+
+template <int NT, int GW, int D>
+__global__ __launch_bounds__(256) void i8_scores_kernel(const int8_t *__restrict__ q8, const float *__restrict__ sq,
+                                                        const int32_t *__restrict__ q_off, int n_q, long long q_rows, int QG, int TPQ,
+                                                        int passes, const int8_t *__restrict__ d8, const float *__restrict__ sd,
+                                                        const int32_t *__restrict__ d_off, const uint8_t *__restrict__ clamp0, int n_d,
+                                                        long long d_rows, int ppw, int n_groups, int n_gb, float *__restrict__ scores,
+                                                        long long ld) {
+    token_scores<NT, GW, D>(q8, sq, q_off, n_q, q_rows, QG, TPQ, passes, I8Rows{d8, sd}, d_off, clamp0, n_d, d_rows, ppw, n_groups, n_gb,
+                            scores, ld);
 }
 
 }  // namespace msim

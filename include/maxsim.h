@@ -678,6 +678,37 @@ int msim_i8_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int 
                    int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
 /*
+ * 1-BIT SIGN INDEX (binary_index.hip; additions to ABI 22): one sign bit per dimension of every corpus row -- 16 bytes per row, 1/16
+ * of the bf16 shard -- scored token by token against the UN-binarised query on int8 MFMAs: a first stage for two-stage search,
+ * reranked exactly by msim_fwd_candidates (or msim_res_candidates over a residual-compressed shard).
+ *   Encode (msim_bin_encode_rows): for a row x of a bf16 / f16 blob of width 128, s_k = -1 where the sign bit of the stored 16-bit
+ *     element is set (this includes -0.0 and negative NaNs), +1 otherwise: an integer operation on the sign bit, no arithmetic.
+ *     The row is stored as 16 bytes: dimension k is bit (k & 7) of byte (k >> 3), and a set bit means +1 (the residual codec's
+ *     little-endian bit string).  codes uint8 [n_rows, 16] in the input's row order.
+ *   Queries: quantized by msim_i8_encode_queries, unchanged: q8 int8 [T, 128], sq fp32 [T].
+ *   Score (msim_bin_scores): I_ij = sum_k q8_ik s_jk (exact int32, |I| <= 127 * 128); M_ic = max_j I_ij over the rows of page c,
+ *     then max(M_ic, 0) where clamp0[c] is set; scores[q, c] = the SEQUENTIAL fp32 sum in token order of fl32(float(M_ic) * sq_i)
+ *     (no fused multiply-add).  A page of 0 rows scores -inf; a query of 0 tokens scores 0 against every page that has rows.  A
+ *     score's bits depend on its query and page only (not on the batch, the tiling, the page's position or a rerun).  No row that
+ *     is not the page's takes part in M_ic -- in particular not the all-(-1) row that zero bits past the end of the codes would
+ *     decode to.  max_q_tokens, a query longer than its token slots or with offsets outside 0 .. q_rows (NaN), and a page whose
+ *     offsets fall outside 0 .. d_rows (NaN for every page scored by the same wave, a range of at most 63 consecutive pages): as
+ *     msim_i8_scores.  clamp0: uint8 [n_d] or NULL.  scores fp32 [n_q, ld_scores], ld_scores >= n_d.  No workspace.
+ *     msim_bin_scores_plan writes the launch form msim_bin_scores takes for the same arguments on the current device: plan[0] = NT
+ *     (16-token tiles a wave holds), plan[1] = GW (waves that share one page range: 1, 2 or 4), plan[2] = D (chunks read ahead),
+ *     plan[3] = pages per wave range (1 .. 63).  A query longer than 16 NT tokens takes ceil(tokens / (16 NT)) passes over its range.
+ * Width 128 and bf16 / f16 only (MSIM_EUNSUPPORTED otherwise); a null or misaligned pointer or a negative size is MSIM_EINVAL; both
+ * are decided before the device is touched.  Rows and codes 16-byte aligned; scales, offsets and scores 4-byte aligned.  A call with
+ * nothing to do returns 0 before it looks at a pointer.  Asynchronous on `stream`, no allocation, no host synchronisation:
+ * hipGraph-capturable.
+ */
+int msim_bin_encode_rows(int dtype, const void *X, int64_t n_rows, int dim, uint8_t *codes, void *stream);
+int msim_bin_scores_plan(int n_q, int max_q_tokens, int n_d, int64_t d_rows, int32_t *plan /* [4] */);
+int msim_bin_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                    const uint8_t *codes, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                    int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
+
+/*
  * CENTROID-CODE INDEX (centroid_index.hip; additions to ABI 22): every corpus row stored as the uint16 id of its nearest of K
  * centroids, pages scored by centroid interaction (PLAID's first stage) -- a first stage for two-stage search that reads 2 bytes
  * per row, reranked exactly by msim_fwd_candidates.  C: K centroid rows [K, 128] in the dtype of the rows they meet; K a multiple
