@@ -28,6 +28,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      (align and gather_pages dispatch to them on a ResidualCorpus)
   * LiveResidualCorpus           -- such a shard filled incrementally from pages that are never kept: add (one fused encode pass),
                                      delete, compact in place; the lifecycle LiveCorpus gives the bf16 shard
+  * save / load / verify_file     -- every shard and index class as one flat, versioned file (no pickle), streamed through the pinned
+                                     double buffer and verified chunk by chunk by a digest computed on the device (msim_digest)
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
                                      (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
@@ -48,6 +50,7 @@ from .live_residual import LiveResidualCorpus
 from .mine import gather_pages, mine_hard_negatives
 from .loss import (ColbertLoss, ColbertModule, ColbertNegativeCELoss, ColbertPairwiseCELoss,
                    ColbertPairwiseNegativeCELoss, ColbertSigmoidLoss, maxsim, maxsim_paired)
+from .persist import ShardFileError, digest, load, save, verify_file
 from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
 from .patch import patch_colpali_engine, unpatch_colpali_engine
 from .residual import (ResidualCorpus, residual_align, residual_gather_pages, residual_rerank_scores, residual_scores,
@@ -122,4 +125,9 @@ __all__ = [
     "score_single_vector",
     "similarity_matrix",
     "get_similarity_maps_from_embeddings",
+    "save",
+    "load",
+    "verify_file",
+    "digest",
+    "ShardFileError",
 ]

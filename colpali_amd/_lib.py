@@ -260,6 +260,10 @@ def lib() -> ctypes.CDLL:
     L.msim_topk_workspace_bytes.restype = sz
     L.msim_topk_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]
     L.msim_topk_f32.restype = i32
+    L.msim_digest.argtypes = [vp, sz, ctypes.c_uint64, vp, vp]
+    L.msim_digest.restype = i32
+    L.msim_digest_host.argtypes = [vp, sz, ctypes.c_uint64, vp]
+    L.msim_digest_host.restype = i32
     if L.msim_abi_version() != ABI_VERSION:
         raise MaxSimLibraryError(f"ABI version mismatch: library reports {L.msim_abi_version()}, binding expects {ABI_VERSION} "
                                  "(rebuild: make -C colpali_amd/csrc)")

@@ -71,6 +71,20 @@ class BinaryIndex:
         clamp0 = corpus.clamp0.clone() if corpus.clamp0 is not None else None
         return cls(codes, corpus.offsets.clone(), clamp0, corpus.lengths.clone(), corpus.id_base)
 
+    def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
+        """Write this index to `path` (colpali_amd/persist.py: one flat file, every chunk carrying its msim_digest)."""
+        from . import persist
+
+        persist.save(self, path, chunk_bytes=chunk_bytes)
+
+    @classmethod
+    def load(cls, path, device, *, verify: bool = True, pages=None) -> "BinaryIndex":
+        """The index saved at `path`, on `device`, every chunk verified where it landed; `pages=(lo, hi)`: those pages only
+        (`persist.load`)."""
+        from . import persist
+
+        return persist.load(path, device, verify=verify, pages=pages, expect=cls)
+
 
 def binary_scores_from_codes(q_codes: torch.Tensor, q_scales: torch.Tensor, q_offsets: torch.Tensor, max_q_tokens: int,
                              index: BinaryIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -169,6 +169,20 @@ class PackedCorpus:
                 self.avg_rows = int(self.lengths.sum()) // n
         return self.avg_rows
 
+    def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
+        """Write this corpus to `path` (colpali_amd/persist.py: one flat file, every chunk carrying its msim_digest)."""
+        from . import persist
+
+        persist.save(self, path, chunk_bytes=chunk_bytes)
+
+    @classmethod
+    def load(cls, path, device, *, verify: bool = True, pages=None) -> "PackedCorpus":
+        """The corpus saved at `path`, on `device`, every chunk verified where it landed; `pages=(lo, hi)`: those pages only
+        (`persist.load`)."""
+        from . import persist
+
+        return persist.load(path, device, verify=verify, pages=pages, expect=cls)
+
     @property
     def device(self) -> torch.device:
         return self.blob.device

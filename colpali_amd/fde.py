@@ -145,6 +145,20 @@ class FdeIndex:
             encode_corpus(corpus, config, Fd[lo:hi], lo=lo, hi=hi, params=params)
         return cls(Fd, corpus.id_base, config, params)
 
+    def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
+        """Write this index (its parameter tensors included) to `path` (colpali_amd/persist.py: one flat file, every chunk carrying its msim_digest)."""
+        from . import persist
+
+        persist.save(self, path, chunk_bytes=chunk_bytes)
+
+    @classmethod
+    def load(cls, path, device, *, verify: bool = True, pages=None) -> "FdeIndex":
+        """The index (its parameter tensors included) saved at `path`, on `device`, every chunk verified where it landed; `pages=(lo, hi)`: those pages only
+        (`persist.load`)."""
+        from . import persist
+
+        return persist.load(path, device, verify=verify, pages=pages, expect=cls)
+
 
 def encode_queries(queries, index: FdeIndex, out: Optional[torch.Tensor] = None, *,
                    codes: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -75,6 +75,20 @@ class Int8Index:
         clamp0 = corpus.clamp0.clone() if corpus.clamp0 is not None else None
         return cls(codes, scales, corpus.offsets.clone(), clamp0, corpus.lengths.clone(), corpus.id_base)
 
+    def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
+        """Write this index to `path` (colpali_amd/persist.py: one flat file, every chunk carrying its msim_digest)."""
+        from . import persist
+
+        persist.save(self, path, chunk_bytes=chunk_bytes)
+
+    @classmethod
+    def load(cls, path, device, *, verify: bool = True, pages=None) -> "Int8Index":
+        """The index saved at `path`, on `device`, every chunk verified where it landed; `pages=(lo, hi)`: those pages only
+        (`persist.load`)."""
+        from . import persist
+
+        return persist.load(path, device, verify=verify, pages=pages, expect=cls)
+
 
 def quantize_queries(queries, device: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-token codes int8 [T, 128] and scales fp32 [T] of `queries` (a `PackedQueries`, a host list of [len_i, 128] tensors or a

@@ -378,6 +378,20 @@ class LiveCorpus(_LiveShard):
         live._adopt(corpus.offsets, lens)
         return live
 
+    def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
+        """Write the used prefix of this shard -- rows, slot table, tombstones; the int8 index is rebuilt by `int8_index()` -- to `path` (colpali_amd/persist.py)."""
+        from . import persist
+
+        persist.save(self, path, chunk_bytes=chunk_bytes)
+
+    @classmethod
+    def load(cls, path, device, capacity_rows=None, capacity_docs=None, *, verify: bool = True, **kw) -> "LiveCorpus":
+        """The shard saved at `path`, on `device`, with its saved capacity or a larger one; slot ids, tombstones and the next id
+        handed out are the saved shard's; `**kw` go to the constructor (`persist.load`)."""
+        from . import persist
+
+        return persist.load(path, device, verify=verify, capacity_rows=capacity_rows, capacity_docs=capacity_docs, expect=cls, **kw)
+
     @property
     def _widths(self) -> Tuple[int, ...]:
         return (self.dim, self.width)

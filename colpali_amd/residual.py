@@ -218,6 +218,20 @@ class ResidualCorpus:
         return PackedCorpus(blob=blob, offsets=torch.from_numpy(off.astype(np.int32)).to(dev), clamp0=clamp0,
                             lengths=torch.from_numpy(sel.copy()), id_base=0)
 
+    def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
+        """Write this compressed corpus to `path` (colpali_amd/persist.py: one flat file, every chunk carrying its msim_digest)."""
+        from . import persist
+
+        persist.save(self, path, chunk_bytes=chunk_bytes)
+
+    @classmethod
+    def load(cls, path, device, *, verify: bool = True, pages=None) -> "ResidualCorpus":
+        """The compressed corpus saved at `path`, on `device`, every chunk verified where it landed; `pages=(lo, hi)`: those pages only
+        (`persist.load`)."""
+        from . import persist
+
+        return persist.load(path, device, verify=verify, pages=pages, expect=cls)
+
 
 def _check_query_format(queries, rc: ResidualCorpus, what: str) -> None:
     """the formats the residual kernels take, in whatever form the queries came (no device work)"""

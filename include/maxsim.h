@@ -1051,6 +1051,37 @@ int msim_group_reduce(const float *scores, int64_t ld, int n_q, int64_t n, const
 int msim_group_select(const float *scores, const int64_t *gids, const int64_t *pages, int n_q, int m, int64_t ld, int k,
                       float *out_scores, int64_t *out_gids, int64_t *out_pages, void *stream);
 
+/*
+ * PERSISTENCE (digest.hip; additions to ABI 22): the digest a saved shard or index is verified by (colpali_amd/persist.py,
+ * DESIGN.md section 3.23).  msim_digest sums over bytes in HBM -- what actually landed on the device --, msim_digest_host computes
+ * the same sum over host memory.  It detects corruption, truncation and misplacement.  It is NOT a cryptographic hash: anyone who
+ * can write the file can make any digest they like.
+ *
+ * The contract (tests/digest_truth.py restates it in numpy uint64; all arithmetic is mod 2^64):
+ *   - the nbytes bytes at `data` are read as little-endian 64-bit words w_0 .. w_{n-1}, n = ceil(nbytes / 8); the last word is
+ *     zero-padded past nbytes;
+ *   - word i has the absolute index g_i = pos / 8 + i (`pos`: the byte offset of `data` in the object it is a part of);
+ *   - acc[0] += sum_i mix(w_i + (g_i + 1) * MSIM_DIGEST_C0),    acc[1] += sum_i mix((w_i ^ MSIM_DIGEST_K) + (g_i + 1) * MSIM_DIGEST_C1)
+ *   - mix is the splitmix64 finaliser:  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31.
+ * The result is ADDED INTO acc (the caller zeroes it, or carries a running sum), hence
+ *   - it does not depend on the launch plan: integer addition commutes (rerun identity, bit for bit);
+ *   - chunks compose: the digest of a buffer is the sum of the digests of any cover of it by pieces that start on 8-byte boundaries,
+ *     each with its own `pos`;
+ *   - a trailing all-zero word still counts (mix(0 + k) != 0 for the k used): length and position are covered.
+ *
+ * msim_digest: `data` and `acc` (uint64 [2]) are device pointers; one kernel on `stream` (16-byte loads on the aligned body, one word
+ * on its own in front when `data` is 8- but not 16-byte aligned, the byte tail read by one lane; per-lane accumulators, a wave fold,
+ * two 64-bit integer atomics per workgroup).  No allocation, no synchronisation, hipGraph-capturable (a replay adds again).
+ * `pos` and `nbytes` may exceed 2^32.  msim_digest_host: both pointers are host pointers; one thread.
+ * MSIM_EINVAL, before any device work: acc == NULL; data == NULL with nbytes > 0; pos % 8 != 0; `data` not 8-byte aligned.
+ * nbytes == 0 is a successful no-op.
+ */
+#define MSIM_DIGEST_C0 0x9E3779B97F4A7C15ull /* lane 0's position multiplier (odd) */
+#define MSIM_DIGEST_C1 0xC2B2AE3D27D4EB4Full /* lane 1's position multiplier (odd) */
+#define MSIM_DIGEST_K 0xD6E8FEB86659FD93ull  /* lane 1 reads w ^ K (odd) */
+int msim_digest(const void *data, size_t nbytes, uint64_t pos, uint64_t *acc /* device, [2] */, void *stream);
+int msim_digest_host(const void *data, size_t nbytes, uint64_t pos, uint64_t acc[2]);
+
 #ifdef __cplusplus
 }
 #endif
