@@ -18,6 +18,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
   * Int8Index / int8_scores       -- an int8 copy of the corpus scored token by token on int8 MFMAs: a first stage for prefilter=
   * BinaryIndex / binary_scores   -- one sign bit per dimension of every corpus row (16 bytes per row), scored against the int8
                                      queries on int8 MFMAs: a token-level first stage for prefilter= at 1/16 of the bf16 shard
+  * Fp4Index / fp4_scores         -- every corpus row and query token as 128 e2m1 values and one power-of-two scale (65 bytes per
+                                     row), scored on the block-scaled FP4 MFMA: a token-level first stage for prefilter=
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
                                      centroid interaction): a first stage for prefilter= at 2 bytes per row
   * ResidualCorpus / residual_rerank_scores -- PLAID's second half: the shard itself as centroid codes + 2 / 4 residual bits per
@@ -41,6 +43,7 @@ from .centroid import CentroidIndex, centroid_scores, train_centroids
 from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pack_queries
 from . import loss
 from .embed import CorpusWriter, embedding_head
+from .fp4_index import Fp4Index, fp4_quantize_queries, fp4_scores, fp4_scores_from_codes
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .filter import PageFilter
 from .group import PageGroups, group_reduce, group_select
@@ -77,6 +80,10 @@ __all__ = [
     "BinaryIndex",
     "binary_scores",
     "binary_scores_from_codes",
+    "Fp4Index",
+    "fp4_scores",
+    "fp4_scores_from_codes",
+    "fp4_quantize_queries",
     "CentroidIndex",
     "centroid_scores",
     "train_centroids",

@@ -709,6 +709,46 @@ int msim_bin_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int
                     int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
 /*
+ * FP4 INDEX (fp4_index.hip; additions to ABI 22): every corpus row and every query token as 128 OCP e2m1 values and one power-of-two
+ * scale -- 65 bytes per row, half of the int8 index -- scored token by token on the block-scaled MFMA
+ * (v_mfma_scale_f32_16x16x128_f8f6f4, one instruction per 16 rows x 16 tokens): a first stage for two-stage search, reranked
+ * exactly by msim_fwd_candidates (or msim_res_candidates over a residual-compressed shard).
+ *   Row code (msim_f4_encode_rows; pages and query tokens alike): for a row x of a bf16 / f16 blob of width 128, on the stored values
+ *     in fp32: a = max_k |x_k|.  If a == 0 every nibble is 0 and the scale byte is 127.  Otherwise e = the smallest integer with
+ *     a <= 6 * 2^e, clamped to [-32, 32] (taken from a's exponent and mantissa fields, no logarithm); y_k = min(|x_k| * 2^-e, 6),
+ *     the scaling by a power of two being exact; the code is the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6} (codes 0 .. 7), a tie
+ *     going to the even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); the nibble is
+ *     sign << 3 | code with x's sign bit when the code is not 0, and 0 otherwise (so -0.0 and everything that rounds to 0 store
+ *     0).  Dimension k is nibble (k & 1) of byte (k >> 1), the low nibble holding the even k.  The scale byte is e + 127 (E8M0).
+ *     codes uint8 [n_rows, 64] and scales uint8 [n_rows] in the input's row order.  NaN elements are unspecified: the codes and
+ *     the scale of a row that holds one may be anything (nothing is read or written out of bounds).
+ *   Score (msim_f4_scores): with v() the decoded grid value, I_ij = sum_k v(q_ik) v(d_jk) -- a multiple of 1/4 with |I| <= 4608,
+ *     exact in fp32 in any order; Z_ij = I_ij * 2^(eq_i + ed_j), exact; M_ic = max_j Z_ij over the rows of page c, then
+ *     max(M_ic, 0) where clamp0[c] is set; scores[q, c] = the SEQUENTIAL fp32 sum of M_ic in token order.  A page of 0 rows scores
+ *     -inf; a query of 0 tokens scores 0 against every page that has rows.  A score's bits depend on its query and page only (not
+ *     on the batch, the tiling, the page's position or a rerun).  No row that is not the page's takes part in M_ic -- in particular
+ *     not the zero row that zero bytes past the end of the codes and scales decode to.  One scale per ROW, not per 32-element
+ *     block: with different block scales the four block sums of a row would no longer add exactly and the bits would depend on
+ *     the hardware's undocumented order.  Scale bytes outside 95 .. 159 never come out of msim_f4_encode_rows; with them Z may
+ *     round and the bits are unspecified.  max_q_tokens, a query longer than its token slots or with offsets outside 0 .. q_rows
+ *     (NaN), and a page whose offsets fall outside 0 .. d_rows (NaN for every page scored by the same wave, a range of at most 63
+ *     consecutive pages): as msim_i8_scores.  clamp0: uint8 [n_d] or NULL.  scores fp32 [n_q, ld_scores], ld_scores >= n_d.  No
+ *     workspace.
+ *     msim_f4_scores_plan writes the launch form msim_f4_scores takes for the same arguments on the current device: plan[0] = NT
+ *     (16-token tiles a wave holds), plan[1] = GW (waves that share one page range: 1, 2 or 4), plan[2] = D (chunks read ahead),
+ *     plan[3] = pages per wave range (1 .. 63).  A query longer than 16 NT tokens takes ceil(tokens / (16 NT)) passes over its range.
+ * Width 128 and bf16 / f16 only (MSIM_EUNSUPPORTED otherwise); a null or misaligned pointer or a negative size is MSIM_EINVAL; both
+ * are decided before the device is touched.  Rows and codes 16-byte aligned; offsets and scores 4-byte aligned; scale bytes
+ * unaligned.  A call with nothing to do returns 0 before it looks at a pointer.  Asynchronous on `stream`, no allocation, no host
+ * synchronisation: hipGraph-capturable.
+ */
+int msim_f4_encode_rows(int dtype, const void *X, int64_t n_rows, int dim, uint8_t *codes, uint8_t *scales, void *stream);
+int msim_f4_scores_plan(int n_q, int max_q_tokens, int n_d, int64_t d_rows, int32_t *plan /* [4] */);
+int msim_f4_scores(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                   const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                   int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
+
+/*
  * CENTROID-CODE INDEX (centroid_index.hip; additions to ABI 22): every corpus row stored as the uint16 id of its nearest of K
  * centroids, pages scored by centroid interaction (PLAID's first stage) -- a first stage for two-stage search that reads 2 bytes
  * per row, reranked exactly by msim_fwd_candidates.  C: K centroid rows [K, 128] in the dtype of the rows they meet; K a multiple
