@@ -95,6 +95,10 @@ msim::StreamArgs stream_args(const FwdCall &c) {
     a.n_q = c.n_q;
     a.n_d = c.n_d;
     a.flags = c.flags;
+#ifdef MSIM_TRACE
+    a.trace = nullptr;
+    if (const char *tp = getenv("MSIM_STREAM_TRACE_PTR")) a.trace = reinterpret_cast<unsigned long long *>(strtoull(tp, nullptr, 0));
+#endif
     return a;
 }
 dim3 stream_grid(const FwdCall &c, int lds) {
@@ -103,10 +107,30 @@ dim3 stream_grid(const FwdCall &c, int lds) {
     return dim3(wg_needed < wg_cap ? wg_needed : wg_cap);
 }
 
+// MSIM_STREAM_ORDER=0..4 / MSIM_STREAM_ORDER_RAW=0..4 (measurement builds): the slab body's request order of the 2-slot forms
+// (maxsim_stream.hip: hook, early, paced, split, paced half) in K1s13 / in raw K1s; the shipped library has DEFAULT and nothing else
+template <int RING, int DEFAULT, class Launch>
+int dispatch_order(int forced, Launch &&launch) {
+#if defined(MSIM_AB) || defined(MSIM_TRACE)
+    if constexpr (RING == 2) {
+        switch (forced) {
+            case msim::kOrderHook: return launch(std::integral_constant<int, msim::kOrderHook>{});
+            case msim::kOrderEarly: return launch(std::integral_constant<int, msim::kOrderEarly>{});
+            case msim::kOrderPaced: return launch(std::integral_constant<int, msim::kOrderPaced>{});
+            case msim::kOrderSplit: return launch(std::integral_constant<int, msim::kOrderSplit>{});
+            case msim::kOrderPacedHalf: return launch(std::integral_constant<int, msim::kOrderPacedHalf>{});
+            default: break;
+        }
+    }
+#endif
+    (void)forced;
+    return launch(std::integral_constant<int, DEFAULT>{});
+}
+
 // LIST: the documents doc_list[0 .. c.n_d) instead of 0 .. c.n_d-1
-template <int NU, bool F16, int AUX, int RING = kStreamRing, bool LIST = false>
-int launch_stream_aux(const FwdCall &c, const int32_t *doc_list = nullptr) {
-    auto kern = msim::maxsim_stream_kernel<NU, RING, F16, AUX, LIST>;
+template <int NU, bool F16, int AUX, int RING, bool LIST, int ORDER>
+int launch_stream_order(const FwdCall &c, const int32_t *doc_list) {
+    auto kern = msim::maxsim_stream_kernel<NU, RING, F16, AUX, LIST, ORDER>;
     constexpr int lds = 4 * (RING * msim::kSlabBytes + msim::kStreamTokBytes);
     static std::atomic<int> configured[kMaxDevices];
     if (int rc = allow_lds(kern, lds, configured)) return rc;
@@ -116,12 +140,19 @@ int launch_stream_aux(const FwdCall &c, const int32_t *doc_list = nullptr) {
     if (e != hipSuccess) return fail(MSIM_ELAUNCH, "maxsim_stream_kernel<%d> launch: %s", NU, hipGetErrorString(e));
     return MSIM_OK;
 }
+template <int NU, bool F16, int AUX, int RING = kStreamRing, bool LIST = false>
+int launch_stream_aux(const FwdCall &c, const int32_t *doc_list = nullptr) {
+    static const int forced = ab_env("MSIM_STREAM_ORDER_RAW", -1);
+    return dispatch_order<RING, msim::stream_order(RING)>(
+        forced, [&](auto order) { return launch_stream_order<NU, F16, AUX, RING, LIST, decltype(order)::value>(c, doc_list); });
+}
 
 template <int NU, bool F16>
 int launch_stream(const FwdCall &c) {
     // 5-8 units (3-4 token tiles of 32): a 2-slab ring (72 KiB per workgroup) lets TWO workgroups share a CU -- two waves per SIMD,
     // one covering the other's DMA issue / operand reads / max folds: 4 queries 6.51-6.55 -> 6.82 TB/s (85 % of spec); up to 4 units
-    // are at the stream ceiling either way and keep the deeper ring.
+    // are at the stream ceiling either way and keep the deeper ring.  In the compiled body the eight requests of the next slab stand
+    // in one block behind the last operand read (maxsim_stream.hip: ORDER, hook), not one per NU MFMAs; pinning them there is a tie.
     // MSIM_STREAM_RING=2|4 forces one of them (tuning knob, not part of the ABI).
     constexpr int ring_default = NU >= 5 ? 2 : kStreamRing;
 #ifdef MSIM_AB
@@ -136,12 +167,12 @@ int launch_stream(const FwdCall &c) {
 }
 
 // K1s over the 13-bit image (maxsim_stream13.hip): the same ring depths and grid rule as launch_stream -- 2 slabs of 6.5 KiB for 5-8
-// units (60.25 KiB per workgroup: two per CU), 4 slabs below.  The documents the encoder flagged are skipped there and scored
+// units (60.25 KiB per workgroup: two per CU; the next slab's requests pinned one per NU / 2 MFMAs: maxsim_stream.hip, ORDER, paced
+// half), 4 slabs below.  The documents the encoder flagged are skipped there and scored
 // from the blob by the raw K1s over their id list, into the same score columns; that launch exists only when the list is not empty.
-template <int NU>
-int launch_stream13(const FwdCall &c) {
-    constexpr int RING = NU >= 5 ? 2 : kStreamRing;
-    auto kern = msim::maxsim_stream13_kernel<NU, RING, 2>;
+template <int NU, int RING, int ORDER>
+int launch_stream13_order(const FwdCall &c) {
+    auto kern = msim::maxsim_stream13_kernel<NU, RING, 2, ORDER>;
     constexpr int lds = 4 * (RING * msim::kSlab13Bytes + msim::kStreamTokBytes);
     static std::atomic<int> configured[kMaxDevices];
     if (int rc = allow_lds(kern, lds, configured)) return rc;
@@ -155,6 +186,12 @@ int launch_stream13(const FwdCall &c) {
         return launch_stream_aux<NU, false, 2, RING, true>(l, c.p13->list);
     }
     return MSIM_OK;
+}
+template <int NU>
+int launch_stream13(const FwdCall &c) {
+    constexpr int RING = NU >= 5 ? 2 : kStreamRing;
+    static const int forced = ab_env("MSIM_STREAM_ORDER", -1);
+    return dispatch_order<RING, msim::stream13_order(RING)>(forced, [&](auto order) { return launch_stream13_order<NU, RING, decltype(order)::value>(c); });
 }
 
 // K1s holds 1..8 units: launch(std::integral_constant<int, NU>) for the plan's count

@@ -37,7 +37,52 @@ struct StreamArgs {
     int n_q;        // queries (<= 8: one 8-lane group of every wave per query)
     int n_d;
     unsigned flags;
+#ifdef MSIM_TRACE
+    unsigned long long *trace;   // tools/trace_stream.py: per wave of the first kStreamTraceWgs workgroups {s_memtime ticks in the wait, in the rest of the body, slabs, s_memrealtime ticks of the wave}; or null
+#endif
 };
+
+// ---- where a slab body puts the eight LDS-DMA pieces of the next request (ORDER of K1s and K1s13).  Every order drains the ring to
+// its depth at the top of the body unless it says otherwise; measured on MI355X in profiles/stream_request_order.md.
+//   hook      : the pieces are handed to slab_units' hook, "one per NU MFMAs" -- and hipcc does not keep them there: it gathers all
+//               eight behind the body's last ds_read (an LDS-DMA write and an LDS read may alias as far as it knows): in K1s13 at 8
+//               units behind MFMA 16, in raw K1s at MFMAs 33..37.  Raw K1s (a tie with the pinned orders at 5-8 units) and every
+//               4-slot form (three requests in flight whatever the order) keep it.
+//   paced half: one piece in front of every (NU / 2)th MFMA, each pinned between two scheduling barriers, so all eight are out by the
+//               middle of the body and each one's issue cost falls behind MFMAs.  K1s13 at 5-8 units: 4.41 -> 4.23 ms at the headline.
+//   paced     : the same, one piece per NU MFMAs -- the documented order made real (measurement builds; 0.03 ms behind paced half).
+//   early     : all eight in front of the wait, then vmcnt(8 more): the target slot is the one the PREVIOUS body consumed, free since
+//               that body's operand reads returned, so a wave has two slabs in flight while it waits (measurement builds: SLOWER
+//               than hook by 0.04-0.09 ms in K1s13 and in raw K1s -- the wait at the top is not where these waves lose their time).
+//   split     : four pieces in front of the wait, four behind the first row group's operand reads (measurement builds: as hook).
+constexpr int kOrderHook = 0, kOrderEarly = 1, kOrderPaced = 2, kOrderSplit = 3, kOrderPacedHalf = 4;
+constexpr int stream_order(int) { return kOrderHook; }                                                       // what the shipped library runs: raw K1s,
+constexpr int stream13_order(int ring) { return ring == 2 ? kOrderPacedHalf : kOrderHook; }                 // K1s13
+constexpr int stream_order_early(int order) { return order == kOrderEarly ? 8 : order == kOrderSplit ? 4 : 0; }   // pieces in front of the wait
+constexpr int stream_order_stride(int order, int nu) {                                                       // MFMAs from one pinned piece to the next (0: none pinned)
+    return order == kOrderPaced ? nu : order == kOrderPacedHalf ? (nu >= 2 ? nu / 2 : 1) : 0;
+}
+
+// MSIM_TRACE builds only: s_memtime stamps around the wait of every slab body (wave-uniform, SGPRs only)
+#ifdef MSIM_TRACE
+constexpr int kStreamTraceWgs = 64;
+#define MSIM_STREAM_TRACE_BEGIN() \
+    const bool tracing = a.trace != nullptr && blockIdx.x < kStreamTraceWgs; \
+    unsigned long long tr_wait = 0, tr_body = 0, tr_n = 0, tr_t0 = 0, tr_t1 = 0; \
+    const unsigned long long tr_r0 = tracing ? __builtin_amdgcn_s_memrealtime() : 0
+#define MSIM_STREAM_TRACE_TOP() do { if (tracing) tr_t0 = __builtin_amdgcn_s_memtime(); } while (0)
+#define MSIM_STREAM_TRACE_WAITED() do { if (tracing) tr_t1 = __builtin_amdgcn_s_memtime(); } while (0)
+#define MSIM_STREAM_TRACE_END() \
+    do { if (tracing) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); tr_wait += tr_t1 - tr_t0; tr_body += t2 - tr_t1; ++tr_n; } } while (0)
+#define MSIM_STREAM_TRACE_WRITE() \
+    do { if (tracing && lane == 0) { unsigned long long *t = a.trace + (size_t)gw * 4; t[0] = tr_wait; t[1] = tr_body; t[2] = tr_n; t[3] = __builtin_amdgcn_s_memrealtime() - tr_r0; } } while (0)
+#else
+#define MSIM_STREAM_TRACE_BEGIN() do {} while (0)
+#define MSIM_STREAM_TRACE_TOP() do {} while (0)
+#define MSIM_STREAM_TRACE_WAITED() do {} while (0)
+#define MSIM_STREAM_TRACE_END() do {} while (0)
+#define MSIM_STREAM_TRACE_WRITE() do {} while (0)
+#endif
 
 constexpr unsigned kFlagRefBf16 = 1u;
 constexpr unsigned kFlagPartial = 2u;     // internal (long queries scored in 128-token pieces): the token sum is a PARTIAL sum, not rounded here
@@ -57,11 +102,10 @@ __device__ __forceinline__ void wait_vmcnt() {
 // AUX : cache-policy bits of the LDS-DMA loads (0 = default, 2 = nt: streamed once, do not keep in L2 / MALL)
 // LIST: the launch scores the documents doc_list[0 .. a.n_d) instead of 0 .. a.n_d-1 (the flagged documents behind the packed form,
 //       maxsim_stream13.hip); doc_list is null and unread without it
-// The 8 LDS-DMA pieces of the next slab are issued BETWEEN the MFMAs of the current one, one piece per NU MFMAs: the matrix pipe idles
-// while a block of DMA instructions issues in front of them (that form measured behind this one in round 1 and is gone).
+// ORDER: where the body issues the 8 LDS-DMA pieces of the next slab (above; the shipped library has the hook order only).
 // At most 8 units (4 token tiles of 32): launch bounds ask for two waves per SIMD (<= 256 registers), which the 2-slab ring needs to
 // put two workgroups on a CU; without the bound hipcc gives every unit an accumulator of its own and lands at 290 registers.
-template <int NU, int RING, bool F16, int AUX = 0, bool LIST = false>
+template <int NU, int RING, bool F16, int AUX = 0, bool LIST = false, int ORDER = stream_order(RING)>
 __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *__restrict__ Qt,      // [T, 128] flat query tokens
                                                             const uint16_t *__restrict__ D,       // [rows, 128] bf16
                                                             const int32_t *__restrict__ d_off,    // [n_d + 1]
@@ -160,6 +204,12 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
         advance(live);
     }
 
+    constexpr int kOrd = ORDER;
+    constexpr int kEarly = stream_order_early(kOrd);     // pieces of the next request issued in front of the wait
+    static_assert(7 * stream_order_stride(kOrd, NU) < 8 * NU, "the eighth pinned piece must stand in front of an MFMA of the body");
+    auto piece = [&](const __amdgpu_buffer_rsrc_t &rs, char *dst, int soff, int i) {
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, MSIM_LDS(dst + i * 1024), 16, src_off[i & 3], soff + i * 1024, 0, AUX);
+    };
     const bool ref_bf16 = (a.flags & kFlagRefBf16) != 0;
     int c_slot = 0;
     for (int c_pos = gw; c_pos < a.n_d; c_pos += GW) {
@@ -169,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
 #pragma unroll
         for (int u = 0; u < NU; ++u) m[u] = -INFINITY;
 
-        // one slab: request the next one (its 8 pieces go out between the MFMAs), fetch the 8 operand fragments once, then the
+        // one slab: request the next one (ORDER says where its 8 pieces go out), fetch the 8 operand fragments once, then the
         // MFMAs of all units (maxsim_common.hpp: slab_units, folds one group late).  kTail (rows past the document end masked to
         // -inf) is a compile-time variant so that the full-slab body has no branch in it.
         auto slab = [&](auto tail_c, int rows_left) {
@@ -181,24 +231,52 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream_kernel(const uint16_t *_
             char *nx_dst = ring;
             int nx_soff = 0;
             __amdgpu_buffer_rsrc_t nx_rsrc = p_rsrc;
-            wait_vmcnt<8 * (RING - 2)>();     // RING - 1 requests are outstanding: all but the oldest may stay in flight
+            if constexpr (!kEarly) wait_vmcnt<8 * (RING - 2)>();     // RING - 1 requests are outstanding: all but the oldest may stay in flight
             nx_live = p_idx < a.n_d;
             nx_dst = ring + p_slot * kSlabBytes;
             nx_soff = nx_live ? p_row * kRowBytes : 0;
             nx_rsrc = nx_live ? p_rsrc : null_rsrc;
+            if constexpr (kEarly) {
+                // every ds_read of the target slot was waited on before the previous body's MFMAs used it: the request goes out in
+                // front of the wait for the current slab.  Loads retire in order, so behind the wait all but the kEarly youngest of
+                // this request and the RING - 2 requests before it have landed.  The barriers pin the order against the scheduler.
+#pragma unroll
+                for (int i = 0; i < kEarly; ++i) piece(nx_rsrc, nx_dst, nx_soff, i);
+                __builtin_amdgcn_sched_barrier(0);
+                wait_vmcnt<8 * (RING - 2) + kEarly>();
+                __builtin_amdgcn_sched_barrier(0);
+            }
 
             const char *src = ring + c_slot * kSlabBytes;
             c_slot = (c_slot + 1 == RING) ? 0 : c_slot + 1;
             bf16x8 af[2][kKSteps16];
 #pragma unroll
-            for (int g = 0; g < 2; ++g)
+            for (int g = 0; g < 2; ++g) {
 #pragma unroll
                 for (int ks = 0; ks < kKSteps16; ++ks) af[g][ks] = *reinterpret_cast<const bf16x8 *>(src + rd_off[g][ks]);
+                if constexpr (kOrd == kOrderSplit) {
+                    if (g == 0) {
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = kEarly; i < 8; ++i) piece(nx_rsrc, nx_dst, nx_soff, i);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
             slab_units<F16, NU, kTail, true>(m, af, qu, rows_left, lane, [&](int mf) {
-                if (mf % NU == 0) {                 // one DMA piece per NU MFMAs: 8 per slab (a slab is 8 * NU MFMAs)
-                    const int i = mf / NU;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(nx_rsrc, MSIM_LDS(nx_dst + i * 1024), 16, src_off[i & 3],
-                                                             nx_soff + i * 1024, 0, AUX);
+                if constexpr (kOrd == kOrderHook) {
+                    if (mf % NU == 0) {                 // one DMA piece per NU MFMAs: 8 per slab (a slab is 8 * NU MFMAs)
+                        const int i = mf / NU;
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(nx_rsrc, MSIM_LDS(nx_dst + i * 1024), 16, src_off[i & 3],
+                                                                 nx_soff + i * 1024, 0, AUX);
+                    }
+                } else if constexpr (stream_order_stride(kOrd, NU) > 0) {
+                    constexpr int kStride = stream_order_stride(kOrd, NU);
+                    if (mf % kStride == 0 && mf / kStride < 8) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        piece(nx_rsrc, nx_dst, nx_soff, mf / kStride);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
             });
             advance(nx_live);                                  // the 8 pieces are out: advance the cursor

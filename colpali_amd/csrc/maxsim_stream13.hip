@@ -6,7 +6,7 @@
 // What differs:
 //   * a slab request is 8 LDS-DMA instructions as before -- six of 1 KiB (16 bytes per lane: the low bytes and the nibbles) and two of
 //     256 B (one dword per lane: the signs of one row group each).  Every instruction is a full-wave linear copy, none writes past its
-//     slot, and the counted vmcnt stays 8 per request, one piece per NU MFMAs;
+//     slot, and the counted vmcnt stays 8 per request; where in the slab body they go out is K1s's ORDER (maxsim_stream.hip);
 //   * the image is lane-major (pack13.hip), so neither the DMA source nor the ds_reads are swizzled: per row group two ds_read_b128
 //     of low bytes, one of nibbles and one ds_read_b32 of signs, all at lane * 16 (lane * 4);
 //   * documents flagged by the encoder (a value the code cannot hold) are skipped; the host scores them from the blob with a
@@ -44,7 +44,7 @@ __device__ __forceinline__ void pack13_decode_group(bf16x8 (&af)[kKSteps16], con
     }
 }
 
-template <int NU, int RING, int AUX = 2>
+template <int NU, int RING, int AUX = 2, int ORDER = stream13_order(RING)>
 __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t *__restrict__ Qt,      // [T, 128] flat query tokens
                                                                  const int32_t *__restrict__ d_off,    // [n_d + 1]
                                                                  const uint8_t *__restrict__ clamp0,   // [n_d] or null
@@ -138,6 +138,10 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
         advance(live);
     }
 
+    constexpr int kOrd = ORDER;
+    constexpr int kEarly = stream_order_early(kOrd);     // pieces of the next request issued in front of the wait
+    static_assert(7 * stream_order_stride(kOrd, NU) < 8 * NU, "the eighth pinned piece must stand in front of an MFMA of the body");
+    MSIM_STREAM_TRACE_BEGIN();
     const bool ref_bf16 = (a.flags & kFlagRefBf16) != 0;
     int c_slot = 0;
     for (int c_idx = gw; c_idx < a.n_d; c_idx += GW) {
@@ -149,11 +153,23 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
 
         auto slab = [&](auto tail_c, int rows_left) {
             constexpr bool kTail = decltype(tail_c)::value;
-            wait_vmcnt<8 * (RING - 2)>();
+            MSIM_STREAM_TRACE_TOP();
+            if constexpr (!kEarly) wait_vmcnt<8 * (RING - 2)>();
             const bool nx_live = p_idx < a.n_d;
             char *nx_dst = ring + p_slot * kSlab13Bytes;
             const int nx_soff = nx_live ? p_s * kSlab13Bytes : 0;
             const __amdgpu_buffer_rsrc_t nx_rsrc = nx_live ? p_rsrc : null_rsrc;
+            if constexpr (kEarly) {
+                // measurement builds: the target slot is the one the previous body consumed -- every ds_read of it was waited on
+                // before that body's MFMAs used it -- so the request may go out BEFORE the wait for the current slab.  Loads retire
+                // in order: all but the kEarly youngest have landed behind the wait, i.e. the current slab.
+#pragma unroll
+                for (int i = 0; i < kEarly; ++i) piece(nx_rsrc, nx_dst, nx_soff, i);
+                __builtin_amdgcn_sched_barrier(0);
+                wait_vmcnt<8 * (RING - 2) + kEarly>();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            MSIM_STREAM_TRACE_WAITED();
 
             const char *src = ring + c_slot * kSlab13Bytes;
             c_slot = (c_slot + 1 == RING) ? 0 : c_slot + 1;
@@ -165,11 +181,29 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
                 const i32x4 nib = *reinterpret_cast<const i32x4 *>(src + kSlab13Nib + g * 1024 + off16);
                 const uint32_t sign = *reinterpret_cast<const uint32_t *>(src + kSlab13Sign + g * 256 + off4);
                 pack13_decode_group(af[g], lo01, lo23, nib, sign);
+                if constexpr (kOrd == kOrderSplit) {
+                    if (g == 0) {
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = kEarly; i < 8; ++i) piece(nx_rsrc, nx_dst, nx_soff, i);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
             }
             slab_units<false, NU, kTail, true>(m, af, qu, rows_left, lane, [&](int mf) {
-                if (mf % NU == 0) piece(nx_rsrc, nx_dst, nx_soff, mf / NU);
+                if constexpr (kOrd == kOrderHook) {
+                    if (mf % NU == 0) piece(nx_rsrc, nx_dst, nx_soff, mf / NU);
+                } else if constexpr (stream_order_stride(kOrd, NU) > 0) {
+                    constexpr int kStride = stream_order_stride(kOrd, NU);
+                    if (mf % kStride == 0 && mf / kStride < 8) {
+                        __builtin_amdgcn_sched_barrier(0);
+                        piece(nx_rsrc, nx_dst, nx_soff, mf / kStride);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
             });
             advance(nx_live);
+            MSIM_STREAM_TRACE_END();
         };
         const int n_full = len / kSlabRows, rem = len - n_full * kSlabRows;
         for (int s = 0; s < n_full; ++s) slab(std::false_type{}, kSlabRows);
@@ -188,6 +222,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
             if (ri == 0) scores[(size_t)rq * a.ld + c_idx] = tot;
         }
     }
+    MSIM_STREAM_TRACE_WRITE();
 }
 
 }  // namespace msim
