@@ -20,6 +20,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      queries on int8 MFMAs: a token-level first stage for prefilter= at 1/16 of the bf16 shard
   * Fp4Index / fp4_scores         -- every corpus row and query token as 128 e2m1 values and one power-of-two scale (65 bytes per
                                      row), scored on the block-scaled FP4 MFMA: a token-level first stage for prefilter=
+  * fp6_scores                    -- the same Fp4Index scored with e2m3 (FP6) query tokens, at the same MFMA rate: the better
+                                     first stage, ShardedRetriever(..., fp4_score_fn=fp6_scores)
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
                                      centroid interaction): a first stage for prefilter= at 2 bytes per row
   * ResidualCorpus / residual_rerank_scores -- PLAID's second half: the shard itself as centroid codes + 2 / 4 residual bits per
@@ -43,7 +45,7 @@ from .centroid import CentroidIndex, centroid_scores, train_centroids
 from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pack_queries
 from . import loss
 from .embed import CorpusWriter, embedding_head
-from .fp4_index import Fp4Index, fp4_quantize_queries, fp4_scores, fp4_scores_from_codes
+from .fp4_index import Fp4Index, fp4_quantize_queries, fp4_scores, fp4_scores_from_codes, fp6_quantize_queries, fp6_scores
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .filter import PageFilter
 from .group import PageGroups, group_reduce, group_select
@@ -84,6 +86,8 @@ __all__ = [
     "fp4_scores",
     "fp4_scores_from_codes",
     "fp4_quantize_queries",
+    "fp6_scores",
+    "fp6_quantize_queries",
     "CentroidIndex",
     "centroid_scores",
     "train_centroids",

@@ -6,6 +6,11 @@ byte.  `fp4_scores` codes the query tokens the same way and scores every page by
 every per-token maximum is exactly representable in fp32, so a score's bits are fixed.  Its top `n_candidates` are reranked
 exactly -- `ShardedRetriever.search(prefilter=index, n_candidates=m)` -- so every returned score is the exact one.  The index
 carries no trained parameter: stage-1 scores of different shards are comparable.
+
+`fp6_scores` scores the same index with the query tokens coded as OCP e2m3 (FP6: 96 code bytes and a scale byte per token,
+msim_f6_encode_rows / msim_f4_scores_q6).  The pages stay FP4 and the index is untouched; the instruction takes a format per
+operand and FP6 runs at the FP4 rate, so the first stage loses the query side's quantisation error for nothing stored.  It is the
+function to hand to a retriever: `ShardedRetriever(shard, fp4_score_fn=fp6_scores)`.
 """
 from __future__ import annotations
 
@@ -19,6 +24,8 @@ from .scoring import _require_gpu
 
 DIM = 128
 ROW_BYTES = DIM // 2
+Q6_ROW_BYTES = DIM * 6 // 8                       # an e2m3 query token: 128 6-bit fields
+QUERY_CODES = {"e2m1": ROW_BYTES, "e2m3": Q6_ROW_BYTES}   # query_code -> code bytes per token
 
 
 def _check_format(dtype: torch.dtype, width: int, what: str) -> None:
@@ -26,16 +33,25 @@ def _check_format(dtype: torch.dtype, width: int, what: str) -> None:
         raise NotImplementedError(f"the fp4 index takes bfloat16 / float16 {what} of width {DIM} (got {dtype}, width {width})")
 
 
-def _encode_rows(rows_t: torch.Tensor, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """codes uint8 [rows, 64] and scales uint8 [rows] of a [rows, 128] bf16 / f16 device tensor: one launch, asynchronous"""
+def _check_query_code(query_code: str) -> int:
+    """code bytes per token of a query code"""
+    if query_code not in QUERY_CODES:
+        raise ValueError(f"query_code must be 'e2m1' or 'e2m3' (got {query_code!r})")
+    return QUERY_CODES[query_code]
+
+
+def _encode_rows(rows_t: torch.Tensor, dev: torch.device, code: str = "e2m1") -> Tuple[torch.Tensor, torch.Tensor]:
+    """codes uint8 [rows, 64] (e2m1) or [rows, 96] (e2m3) and scales uint8 [rows] of a [rows, 128] bf16 / f16 device tensor: one
+    launch, asynchronous"""
     rows_t = rows_t if rows_t.is_contiguous() else rows_t.contiguous()
     rows = int(rows_t.shape[0])
-    codes = torch.empty((rows, ROW_BYTES), dtype=torch.uint8, device=dev)
+    name = "msim_f6_encode_rows" if code == "e2m3" else "msim_f4_encode_rows"
+    codes = torch.empty((rows, QUERY_CODES[code]), dtype=torch.uint8, device=dev)
     scales = torch.empty((rows,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.lib().msim_f4_encode_rows(_lib.dtype_code(rows_t.dtype), _lib.ptr(rows_t), rows, DIM, _lib.ptr(codes), _lib.ptr(scales),
-                                            _lib.current_stream_handle(dev))
-    _lib.check(rc, "msim_f4_encode_rows")
+        rc = getattr(_lib.lib(), name)(_lib.dtype_code(rows_t.dtype), _lib.ptr(rows_t), rows, DIM, _lib.ptr(codes), _lib.ptr(scales),
+                                       _lib.current_stream_handle(dev))
+    _lib.check(rc, name)
     return codes, scales
 
 
@@ -106,16 +122,32 @@ def fp4_quantize_queries(queries, device: Optional[torch.device] = None) -> Tupl
     return _quantize_packed(queries)
 
 
-def _quantize_packed(q: PackedQueries) -> Tuple[torch.Tensor, torch.Tensor]:
+def fp6_quantize_queries(queries, device: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-token e2m3 codes uint8 [T, 96] and scales uint8 [T] of `queries` (as `fp4_quantize_queries` takes them), in the packed
+    token order: dimension k is the 6-bit field (sign << 5 | code) at bit 6 (k mod 32) of the little-endian 24-byte group k // 32."""
+    if not isinstance(queries, PackedQueries):
+        if device is None:
+            device = queries.device if isinstance(queries, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        queries = _as_packed(queries, device, layout="flat")
+    return _quantize_packed(queries, "e2m3")
+
+
+def _quantize_packed(q: PackedQueries, code: str = "e2m1") -> Tuple[torch.Tensor, torch.Tensor]:
     dev = _require_gpu(q.device)
     _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
-    return _encode_rows(q.tokens, dev)
+    return _encode_rows(q.tokens, dev, code)
 
 
 def fp4_scores_from_codes(q_codes: torch.Tensor, q_scales: torch.Tensor, q_offsets: torch.Tensor, max_q_tokens: int,
-                          index: Fp4Index, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          index: Fp4Index, out: Optional[torch.Tensor] = None, *, query_code: str = "e2m1") -> torch.Tensor:
     """fp32 [n_q, len(index)] (msim_f4_scores) from coded queries (`fp4_quantize_queries`): codes uint8 [T, 64], scales uint8 [T],
-    offsets int32 [n_q + 1] on the device and a host bound on every query's token count."""
+    offsets int32 [n_q + 1] on the device and a host bound on every query's token count.  `query_code="e2m3"`: codes uint8 [T, 96]
+    from `fp6_quantize_queries` (msim_f4_scores_q6)."""
+    width = _check_query_code(query_code)
+    if q_codes.dtype != torch.uint8 or q_codes.dim() != 2 or q_codes.shape[1] != width or not q_codes.is_contiguous():
+        raise ValueError(f"{query_code} query codes must be a contiguous uint8 [tokens, {width}] tensor (got {q_codes.dtype} "
+                         f"{list(q_codes.shape)})")
+    name = "msim_f4_scores_q6" if query_code == "e2m3" else "msim_f4_scores"
     dev = _require_gpu(index.device)
     for t in (q_codes, q_scales, q_offsets):
         if t.device != dev:
@@ -126,19 +158,21 @@ def fp4_scores_from_codes(q_codes: torch.Tensor, q_scales: torch.Tensor, q_offse
     elif out.shape != (n_q, n) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"out must be a contiguous fp32 [{n_q}, {n}] tensor on {dev}")
     with torch.cuda.device(dev):
-        rc = _lib.lib().msim_f4_scores(_lib.ptr(q_codes), _lib.ptr(q_scales), _lib.ptr(q_offsets), n_q, int(q_codes.shape[0]),
+        rc = getattr(_lib.lib(), name)(_lib.ptr(q_codes), _lib.ptr(q_scales), _lib.ptr(q_offsets), n_q, int(q_codes.shape[0]),
                                        int(max_q_tokens), _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets),
                                        _lib.ptr(index.clamp0), n, int(index.codes.shape[0]), DIM, _lib.ptr(out), max(n, 1),
                                        _lib.current_stream_handle(dev))
-    _lib.check(rc, "msim_f4_scores")
+    _lib.check(rc, name)
     return out
 
 
-def fp4_scores(queries, index: Fp4Index, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def fp4_scores(queries, index: Fp4Index, out: Optional[torch.Tensor] = None, *, query_code: str = "e2m1") -> torch.Tensor:
     """Approximate MaxSim of every query against every page of the index: fp32 [n_q, len(index)], column j = page
     index.id_base + j.  A score's bits depend on its query and page only.  Asynchronous on torch's current stream.  Given a
     `PackedQueries` it never synchronises with the host and is hipGraph-capturable: its only allocations are torch tensors (the
-    query codes and scales, and `out` when it is None), made on the current stream before the library calls."""
+    query codes and scales, and `out` when it is None), made on the current stream before the library calls.  `query_code`: how the
+    query tokens are coded, "e2m1" (as the pages) or "e2m3" (`fp6_scores`)."""
+    _check_query_code(query_code)
     dev = index.device
     q = _as_packed(queries, dev, layout="flat")
     _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
@@ -146,5 +180,11 @@ def fp4_scores(queries, index: Fp4Index, out: Optional[torch.Tensor] = None) -> 
         raise ValueError("queries and index live on different devices")
     lens = q.lengths
     max_q = int(lens.max()) if lens.numel() else 0
-    codes, scales = _quantize_packed(q)
-    return fp4_scores_from_codes(codes, scales, q.offsets, max_q, index, out=out)
+    codes, scales = _quantize_packed(q, query_code)
+    return fp4_scores_from_codes(codes, scales, q.offsets, max_q, index, out=out, query_code=query_code)
+
+
+def fp6_scores(queries, index: Fp4Index, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`fp4_scores` with the query tokens coded as e2m3 (FP6) against the same FP4 pages: a better first stage from the same index,
+    bit for bit reproducible in the same way.  The stage-1 hook of a retriever: `ShardedRetriever(shard, fp4_score_fn=fp6_scores)`."""
+    return fp4_scores(queries, index, out, query_code="e2m3")

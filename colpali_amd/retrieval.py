@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .align import Alignment, align
 from .binary_index import BinaryIndex, binary_scores
-from .fp4_index import Fp4Index, fp4_scores
+from .fp4_index import Fp4Index, fp4_scores, fp6_scores
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .fde import FdeIndex, fde_scores
 from . import filter as _filter
@@ -209,7 +209,7 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
-            fp4_scores, align, residual_align)
+            fp4_scores, fp6_scores, align, residual_align)
 
 
 class ShardedRetriever:

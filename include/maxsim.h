@@ -737,6 +737,20 @@ int msim_bin_scores(const int8_t *q8, const float *sq, const int32_t *q_off, int
  *     msim_f4_scores_plan writes the launch form msim_f4_scores takes for the same arguments on the current device: plan[0] = NT
  *     (16-token tiles a wave holds), plan[1] = GW (waves that share one page range: 1, 2 or 4), plan[2] = D (chunks read ahead),
  *     plan[3] = pages per wave range (1 .. 63).  A query longer than 16 NT tokens takes ceil(tokens / (16 NT)) passes over its range.
+ *     The plan describes both scorers: msim_f4_scores_q6 takes the same launch form for the same arguments.
+ *   E2M3 QUERY TOKENS (msim_f6_encode_rows, msim_f4_scores_q6; additions to ABI 22): the pages stay FP4, the query tokens are coded
+ *   as OCP e2m3 (FP6), which the same instruction takes as its B operand at the FP4 rate.  The stored index is the same index.
+ *   Query row code (msim_f6_encode_rows; bf16 / f16, width 128; NaN elements unspecified, as above): a = max_k |x_k|.  If a == 0
+ *     every field is 0 and the scale byte is 127.  Otherwise e = the smallest integer with a <= 7.5 * 2^e, clamped to [-32, 32],
+ *     read from a's exponent and mantissa fields: a = m * 2^E (1 <= m < 2) gives e = E - 2 + (m > 1.875).  y_k = min(|x_k| * 2^-e,
+ *     7.5); the code is the nearest of the 32 e2m3 magnitudes -- codes 0 .. 7 the subnormals i/8, code 8 (j + 1) + i the normal
+ *     (1 + i/8) * 2^j for j = 0 .. 2, i = 0 .. 7 -- a tie going to the even code.  The 6-bit field is sign << 5 | code, and 0 when
+ *     the code is 0 (so -0.0 and everything that rounds to 0 store 0).  Scale byte = e + 127.  A token is 96 code bytes and 1 scale
+ *     byte: dimension k is the 6-bit field at bit 6 (k mod 32) of the little-endian 24-byte group k / 32.  codes uint8
+ *     [n_rows, 96], scales uint8 [n_rows].
+ *   Score (msim_f4_scores_q6): as msim_f4_scores with v(q) a multiple of 1/8: I_ij is a multiple of 1/16 with
+ *     |I| <= 128 * 7.5 * 6 = 5760 (92 160 sixteenths, below 2^24: exact in fp32 in any order); Z, M, clamp0, the sequential sum, the
+ *     0-row page (-inf), the 0-token query (0), broken offsets (NaN) and every argument but q6 [q_rows, 96] as msim_f4_scores.
  * Width 128 and bf16 / f16 only (MSIM_EUNSUPPORTED otherwise); a null or misaligned pointer or a negative size is MSIM_EINVAL; both
  * are decided before the device is touched.  Rows and codes 16-byte aligned; offsets and scores 4-byte aligned; scale bytes
  * unaligned.  A call with nothing to do returns 0 before it looks at a pointer.  Asynchronous on `stream`, no allocation, no host
@@ -747,6 +761,11 @@ int msim_f4_scores_plan(int n_q, int max_q_tokens, int n_d, int64_t d_rows, int3
 int msim_f4_scores(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
                    const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
                    int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
+int msim_f6_encode_rows(int dtype, const void *X, int64_t n_rows, int dim, uint8_t *codes /* [n_rows, 96] */, uint8_t *scales,
+                        void *stream);
+int msim_f4_scores_q6(const uint8_t *q6, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                      const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                      int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
 /*
  * CENTROID-CODE INDEX (centroid_index.hip; additions to ABI 22): every corpus row stored as the uint16 id of its nearest of K

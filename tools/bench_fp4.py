@@ -8,14 +8,15 @@ Legs, each timed with device events after a warm-up; the variants of a leg ALTER
 figure is the median with its range:
   * build: Fp4Index.build of the shard beside Int8Index.build and BinaryIndex.build; bound = (the shard's rows read once + the
     codes and scales written) / 8 TB/s.
-  * stage1: fp4_scores at 4 and 1000 queries of 32 tokens on the full shard, beside int8_scores, binary_scores and the exact scan
-    (maxsim_scores) of the same shard.  Bounds of fp4_scores: memory (rows x 65 + n_q n_d 4) B / 8 TB/s, matrix cores
+  * stage1: fp4_scores and fp6_scores (e2m3 query tokens against the same Fp4Index) at 4 and 1000 queries of 32 tokens on the full
+    shard, beside int8_scores, binary_scores and the exact scan (maxsim_scores) of the same shard.  Bounds of fp4_scores: memory (rows x 65 + n_q n_d 4) B / 8 TB/s, matrix cores
     2 n_q 32 rows 128 / 10 PFLOPS.
   * pooled: the stage1 leg on a shard of the same page count and 343 rows per page (a pool factor of 3).
   * two_stage: ShardedRetriever.search(prefilter=<Fp4Index>, n_candidates=m) at 1000 x 32 for m in {100, 400, 1000}, beside the
-    same search through the Int8Index and the BinaryIndex and the exact search.
+    same search with fp4_score_fn=fp6_scores, through the Int8Index and the BinaryIndex, and the exact search.
   * recall: recall@10 against the exact search on the planted 10 000-page set of tools/bench_fde.py:planted_pages, for the FP4
-    index of the full and the pooled pages beside the Int8Index and the BinaryIndex of the full pages.
+    index of the full and the pooled pages, scored with e2m1 and with e2m3 query tokens, beside the Int8Index and the BinaryIndex
+    of the full pages.
 """
 from __future__ import annotations
 
@@ -49,12 +50,17 @@ def stage1_leg(amd, corpus, f4idx, i8idx, bidx, n_q, q_len, dev, steps, warmup):
     pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
     out = torch.empty((n_q, len(f4idx)), dtype=torch.float32, device=dev)
     leg = alternating({"fp4_scores": lambda: amd.fp4_scores(pq, f4idx, out=out),
+                       "fp6_scores": lambda: amd.fp6_scores(pq, f4idx, out=out),
                        "int8_scores": lambda: amd.int8_scores(pq, i8idx, out=out),
                        "binary_scores": lambda: amd.binary_scores(pq, bidx, out=out),
                        "exact_scan": lambda: amd.maxsim_scores(pq, corpus)}, steps, warmup)
     leg["bounds"] = stage1_bounds_ms(n_q, q_len, len(f4idx), int(f4idx.codes.shape[0]))
     leg["fp4_share_of_memory_bound"] = leg["bounds"]["memory_ms"] / leg["fp4_scores"]["median_ms"]
     leg["fp4_share_of_matrix_bound"] = leg["bounds"]["matrix_ms"] / leg["fp4_scores"]["median_ms"]
+    leg["fp6_vs_fp4"] = leg["fp6_scores"]["median_ms"] / leg["fp4_scores"]["median_ms"]
+    # "equal" only when the gap of the medians is inside the larger of the two spreads of this loop
+    spread = max(leg[k]["max_ms"] - leg[k]["min_ms"] for k in ("fp4_scores", "fp6_scores"))
+    leg["fp6_equals_fp4"] = abs(leg["fp6_scores"]["median_ms"] - leg["fp4_scores"]["median_ms"]) <= spread
     leg["fp4_vs_int8"] = leg["int8_scores"]["median_ms"] / leg["fp4_scores"]["median_ms"]
     leg["fp4_vs_binary"] = leg["binary_scores"]["median_ms"] / leg["fp4_scores"]["median_ms"]
     leg["fp4_vs_exact"] = leg["exact_scan"]["median_ms"] / leg["fp4_scores"]["median_ms"]
@@ -76,8 +82,10 @@ def recall_leg(amd, dev, n_docs, k=10):
     _, exact = r.search(pq, k=k)
     exact = exact.tolist()
 
-    def recall(prefilter, m):
-        _, two = r.search(pq, k=k, prefilter=prefilter, n_candidates=m)
+    r6 = amd.ShardedRetriever(full, fp4_score_fn=amd.fp6_scores)
+
+    def recall(prefilter, m, retriever=r):
+        _, two = retriever.search(pq, k=k, prefilter=prefilter, n_candidates=m)
         return sum(len(set(a) & set(b)) for a, b in zip(exact, two.tolist())) / (len(pq) * k)
 
     stages = {"fp4_full": amd.Fp4Index.build(full), "fp4_pooled": amd.Fp4Index.build(pooled), "int8_full": amd.Int8Index.build(full),
@@ -85,7 +93,10 @@ def recall_leg(amd, dev, n_docs, k=10):
     out = {"docs": n_docs, "queries": len(pq), "k": k, "pooled_rows_per_doc": float(pooled.blob.shape[0]) / n_docs}
     for name, idx in stages.items():
         out[name] = {str(m): recall(idx, m) for m in MS}
+    for name in ("full", "pooled"):                       # the same two indexes, e2m3 query tokens
+        out[f"fp6_{name}"] = {str(m): recall(stages[f"fp4_{name}"], m, r6) for m in MS}
     out["bytes"] = {name: idx.nbytes for name, idx in stages.items()}
+    out["bytes"].update({"fp6_full": stages["fp4_full"].nbytes, "fp6_pooled": stages["fp4_pooled"].nbytes})
     out["bytes"]["shard"] = full.nbytes
     return out
 
@@ -95,13 +106,17 @@ def _ms(v):
 
 
 def _stage1_table(legs):
-    rows = ["| | `fp4_scores` | `int8_scores` | `binary_scores` | exact scan | memory bound (share) | matrix-core bound (share) |",
-            "|---|---|---|---|---|---|---|"]
+    rows = ["| | `fp4_scores` | `fp6_scores` | `int8_scores` | `binary_scores` | exact scan | memory bound (share) | matrix-core bound (share) |",
+            "|---|---|---|---|---|---|---|---|"]
     for n, leg in legs.items():
         b = leg["bounds"]
-        rows.append(f"| {n} × 32 | {_ms(leg['fp4_scores'])} | {_ms(leg['int8_scores'])} | {_ms(leg['binary_scores'])} | "
+        rows.append(f"| {n} × 32 | {_ms(leg['fp4_scores'])} | {_ms(leg['fp6_scores'])} | {_ms(leg['int8_scores'])} | {_ms(leg['binary_scores'])} | "
                     f"{_ms(leg['exact_scan'])} | {b['memory_ms']:.2f} ms ({leg['fp4_share_of_memory_bound']:.2f}) | "
                     f"{b['matrix_ms']:.2f} ms ({leg['fp4_share_of_matrix_bound']:.2f}) |")
+    for n, leg in legs.items():
+        rows.append("")
+        rows.append(f"{n} × 32: `fp6_scores` / `fp4_scores` = {leg['fp6_vs_fp4']:.3f}; the gap of the medians is "
+                    f"{'inside' if leg['fp6_equals_fp4'] else 'OUTSIDE'} the larger spread of the two in this loop.")
     return rows
 
 
@@ -129,7 +144,7 @@ def summary(res):
     if "two_stage" in res:
         t = res["two_stage"]
         per = lambda p: " / ".join(f"{t[f'{p}_m{m}']['median_ms']:.1f}" for m in MS)
-        L += [f"* Two-stage search at 1000 × 32, k = 10, m = 100 / 400 / 1000: fp4 {per('fp4')} ms; int8 {per('int8')} ms; binary "
+        L += [f"* Two-stage search at 1000 × 32, k = 10, m = 100 / 400 / 1000: fp4 {per('fp4')} ms; fp6 queries {per('fp6')} ms; int8 {per('int8')} ms; binary "
               f"{per('binary')} ms; exact search {t['exact_search']['median_ms']:.1f} ms, all alternating in one loop."]
     else:
         L += ["* Two-stage search: not measured in this run."]
@@ -137,7 +152,9 @@ def summary(res):
         r = res["recall"]
         L += [f"* Recall@10 against the exact search on the planted {r['docs']}-page set ({r['queries']} queries):", "",
               "| first stage | bytes | m = 100 | m = 400 | m = 1000 |", "|---|---|---|---|---|"]
-        names = {"fp4_full": "`Fp4Index`, full pages", "fp4_pooled": f"`Fp4Index`, pooled pages ({r['pooled_rows_per_doc']:.0f} rows)",
+        names = {"fp4_full": "`Fp4Index`, full pages", "fp6_full": "`Fp4Index`, full pages, e2m3 queries (`fp6_scores`)",
+                 "fp4_pooled": f"`Fp4Index`, pooled pages ({r['pooled_rows_per_doc']:.0f} rows)",
+                 "fp6_pooled": f"`Fp4Index`, pooled pages ({r['pooled_rows_per_doc']:.0f} rows), e2m3 queries",
                  "int8_full": "`Int8Index`, full pages", "binary_full": "`BinaryIndex`, full pages"}
         for key, name in names.items():
             L += [f"| {name} | {r['bytes'][key] / 1e6:.0f} MB | " + " | ".join(f"{r[key][str(m)]:.3f}" for m in MS) + " |"]
@@ -191,9 +208,11 @@ def main():
         if "two_stage" in legs:
             pq = amd.pack_queries(make_queries(1000, args.q_len, dev, seed=99), dev, compact=False)
             r = amd.ShardedRetriever(corpus)
+            r6 = amd.ShardedRetriever(corpus, fp4_score_fn=amd.fp6_scores)
             variants = {}
             for name, idx in (("fp4", f4idx), ("int8", i8idx), ("binary", bidx)):
                 variants.update({f"{name}_m{m}": (lambda m=m, idx=idx: r.search(pq, k=10, prefilter=idx, n_candidates=m)) for m in MS})
+            variants.update({f"fp6_m{m}": (lambda m=m: r6.search(pq, k=10, prefilter=f4idx, n_candidates=m)) for m in MS})
             variants["exact_search"] = lambda: r.search(pq, k=10)
             ts = alternating(variants, max(3, args.steps // 2), 1)
             ts["n_queries"] = 1000
