@@ -22,6 +22,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      row), scored on the block-scaled FP4 MFMA: a token-level first stage for prefilter=
   * fp6_scores                    -- the same Fp4Index scored with e2m3 (FP6) query tokens, at the same MFMA rate: the better
                                      first stage, ShardedRetriever(..., fp4_score_fn=fp6_scores)
+  * Fp4WideIndex / fp4_wide_scores -- the FP4 index of a 320-wide (ColQwen3) shard: 160 bytes of e2m1 nibbles and one scale byte
+                                     per row, three chained block-scaled MFMAs per 16 rows x 16 tokens: a first stage for prefilter=
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
                                      centroid interaction): a first stage for prefilter= at 2 bytes per row
   * ResidualCorpus / residual_rerank_scores -- PLAID's second half: the shard itself as centroid codes + 2 / 4 residual bits per
@@ -46,6 +48,7 @@ from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pa
 from . import loss
 from .embed import CorpusWriter, embedding_head
 from .fp4_index import Fp4Index, fp4_quantize_queries, fp4_scores, fp4_scores_from_codes, fp6_quantize_queries, fp6_scores
+from .fp4_wide_index import Fp4WideIndex, fp4_wide_quantize_queries, fp4_wide_scores, fp4_wide_scores_from_codes
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .filter import PageFilter
 from .group import PageGroups, group_reduce, group_select
@@ -88,6 +91,10 @@ __all__ = [
     "fp4_quantize_queries",
     "fp6_scores",
     "fp6_quantize_queries",
+    "Fp4WideIndex",
+    "fp4_wide_scores",
+    "fp4_wide_scores_from_codes",
+    "fp4_wide_quantize_queries",
     "CentroidIndex",
     "centroid_scores",
     "train_centroids",

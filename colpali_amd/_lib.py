@@ -200,6 +200,12 @@ def lib() -> ctypes.CDLL:
     L.msim_f4_scores_plan.restype = i32
     L.msim_f4_scores.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp]
     L.msim_f4_scores.restype = i32
+    L.msim_f4w_encode_rows.argtypes = [i32, vp, i64, i32, vp, vp, vp]
+    L.msim_f4w_encode_rows.restype = i32
+    L.msim_f4w_scores_plan.argtypes = [i32, i32, i32, i64, vp]
+    L.msim_f4w_scores_plan.restype = i32
+    L.msim_f4w_scores.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp]
+    L.msim_f4w_scores.restype = i32
     L.msim_f6_encode_rows.argtypes = [i32, vp, i64, i32, vp, vp, vp]
     L.msim_f6_encode_rows.restype = i32
     L.msim_f4_scores_q6.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp]

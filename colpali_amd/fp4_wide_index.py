@@ -1,0 +1,163 @@
+"""An FP4 index for 320-wide (ColQwen3) shards: a token-level first stage for two-stage search at 161 bytes per corpus row
+instead of 640.
+
+`Fp4WideIndex.build` keeps every row of a resident 320-wide `PackedCorpus` as 320 OCP e2m1 values (two per byte) and ONE
+power-of-two scale byte.  `fp4_wide_scores` codes the query tokens the same way and scores every page by MaxSim on the
+block-scaled MFMA (include/maxsim.h: msim_f4w_*, colpali_amd/csrc/fp4_wide_index.hip): a 320-wide row is 2 1/2 of the
+instruction's 128-wide K blocks, so one 16 rows x 16 tokens product is three instructions chained through the accumulator; with
+one scale per row every partial sum is exactly representable in fp32, so a score's bits are fixed.  Its top `n_candidates` are
+reranked exactly -- `ShardedRetriever.search(prefilter=index, n_candidates=m)` -- so every returned score is the exact one.  The
+index carries no trained parameter: stage-1 scores of different shards are comparable.
+
+It is the sibling of `Fp4Index` (width 128), which keeps refusing width 320 as this class refuses width 128.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from .corpus import PackedCorpus, PackedQueries, _as_packed
+from .scoring import _require_gpu
+
+DIM = 320
+ROW_BYTES = DIM // 2
+
+
+def _check_format(dtype: torch.dtype, width: int, what: str) -> None:
+    if dtype not in (torch.bfloat16, torch.float16) or width != DIM:
+        hint = "; a 128-wide corpus takes Fp4Index / fp4_scores" if width == 128 else ""
+        raise NotImplementedError(f"the wide fp4 index takes bfloat16 / float16 {what} of width {DIM} (got {dtype}, width {width})"
+                                  f"{hint}")
+
+
+def _encode_rows(rows_t: torch.Tensor, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """codes uint8 [rows, 160] and scales uint8 [rows] of a [rows, 320] bf16 / f16 device tensor: one launch, asynchronous"""
+    rows_t = rows_t if rows_t.is_contiguous() else rows_t.contiguous()
+    rows = int(rows_t.shape[0])
+    codes = torch.empty((rows, ROW_BYTES), dtype=torch.uint8, device=dev)
+    scales = torch.empty((rows,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().msim_f4w_encode_rows(_lib.dtype_code(rows_t.dtype), _lib.ptr(rows_t), rows, DIM, _lib.ptr(codes),
+                                             _lib.ptr(scales), _lib.current_stream_handle(dev))
+    _lib.check(rc, "msim_f4w_encode_rows")
+    return codes, scales
+
+
+class Fp4WideIndex:
+    """The FP4 rows of one resident 320-wide shard: `codes` uint8 [rows, 160] in the corpus's row order (dimension k is nibble
+    k & 1 of byte k >> 1, the low nibble the even k; a nibble is sign << 3 | e2m1 code), `scales` uint8 [rows] (E8M0: the row's
+    values are the decoded codes times 2^(scale - 127)), the corpus's page `offsets` (int32 [n + 1], device) and `clamp0` (uint8 [n]
+    or None), copied; `lengths` (int64 [n], host) and `id_base` as the corpus's."""
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor, offsets: torch.Tensor, clamp0: Optional[torch.Tensor],
+                 lengths: torch.Tensor, id_base: int = 0):
+        n = int(lengths.numel())
+        if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] != ROW_BYTES or not codes.is_contiguous():
+            raise ValueError(f"codes must be a contiguous uint8 [rows, {ROW_BYTES}] tensor")
+        if scales.dtype != torch.uint8 or scales.shape != (codes.shape[0],) or not scales.is_contiguous():
+            raise ValueError(f"scales must be a contiguous uint8 [{int(codes.shape[0])}] tensor")
+        if offsets.shape != (n + 1,) or offsets.dtype != torch.int32:
+            raise ValueError(f"offsets must be int32 [{n + 1}]")
+        if clamp0 is not None and (clamp0.dtype != torch.uint8 or clamp0.shape != (n,)):
+            raise ValueError(f"clamp0 must be uint8 [{n}] or None")
+        self.codes, self.scales, self.offsets, self.clamp0 = codes, scales, offsets, clamp0
+        self.lengths, self.id_base = lengths, int(id_base)
+
+    def __len__(self) -> int:
+        return int(self.lengths.numel())
+
+    @property
+    def device(self) -> torch.device:
+        return self.codes.device
+
+    @property
+    def nbytes(self) -> int:
+        n = sum(t.numel() * t.element_size() for t in (self.codes, self.scales, self.offsets))
+        return n + (self.clamp0.numel() if self.clamp0 is not None else 0)
+
+    @classmethod
+    def build(cls, corpus: PackedCorpus) -> "Fp4WideIndex":
+        """The FP4 code of every row of `corpus` (bf16 / f16, width 320): one launch over the blob.  Asynchronous on torch's
+        current stream."""
+        if not isinstance(corpus, PackedCorpus):
+            raise NotImplementedError(f"Fp4WideIndex.build takes a PackedCorpus (got {type(corpus).__name__})")
+        _check_format(corpus.blob.dtype, int(corpus.blob.shape[1]), "pages")
+        dev = _require_gpu(corpus.device)
+        codes, scales = _encode_rows(corpus.blob, dev)
+        clamp0 = corpus.clamp0.clone() if corpus.clamp0 is not None else None
+        return cls(codes, scales, corpus.offsets.clone(), clamp0, corpus.lengths.clone(), corpus.id_base)
+
+    def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
+        """Write this index to `path` (colpali_amd/persist.py: one flat file, every chunk carrying its msim_digest)."""
+        from . import persist
+
+        persist.save(self, path, chunk_bytes=chunk_bytes)
+
+    @classmethod
+    def load(cls, path, device, *, verify: bool = True, pages=None) -> "Fp4WideIndex":
+        """The index saved at `path`, on `device`, every chunk verified where it landed; `pages=(lo, hi)`: those pages only
+        (`persist.load`)."""
+        from . import persist
+
+        return persist.load(path, device, verify=verify, pages=pages, expect=cls)
+
+
+def fp4_wide_quantize_queries(queries, device: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-token codes uint8 [T, 160] and scales uint8 [T] of `queries` (a `PackedQueries`, a host list of [len_i, 320] tensors or
+    a [n_q, Lq, 320] tensor, packed into the flat layout first), in the packed token order: the page rows' code."""
+    if not isinstance(queries, PackedQueries):
+        if device is None:
+            device = queries.device if isinstance(queries, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        queries = _as_packed(queries, device, layout="flat")
+    return _quantize_packed(queries)
+
+
+def _quantize_packed(q: PackedQueries) -> Tuple[torch.Tensor, torch.Tensor]:
+    dev = _require_gpu(q.device)
+    _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
+    return _encode_rows(q.tokens, dev)
+
+
+def fp4_wide_scores_from_codes(q_codes: torch.Tensor, q_scales: torch.Tensor, q_offsets: torch.Tensor, max_q_tokens: int,
+                               index: Fp4WideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [n_q, len(index)] (msim_f4w_scores) from coded queries (`fp4_wide_quantize_queries`): codes uint8 [T, 160], scales
+    uint8 [T], offsets int32 [n_q + 1] on the device and a host bound on every query's token count."""
+    if q_codes.dtype != torch.uint8 or q_codes.dim() != 2 or q_codes.shape[1] != ROW_BYTES or not q_codes.is_contiguous():
+        raise ValueError(f"query codes must be a contiguous uint8 [tokens, {ROW_BYTES}] tensor (got {q_codes.dtype} "
+                         f"{list(q_codes.shape)})")
+    dev = _require_gpu(index.device)
+    for t in (q_codes, q_scales, q_offsets):
+        if t.device != dev:
+            raise ValueError("queries and index live on different devices")
+    n_q, n = int(q_offsets.numel()) - 1, len(index)
+    if out is None:
+        out = torch.empty((n_q, n), dtype=torch.float32, device=dev)
+    elif out.shape != (n_q, n) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous fp32 [{n_q}, {n}] tensor on {dev}")
+    with torch.cuda.device(dev):
+        rc = _lib.lib().msim_f4w_scores(_lib.ptr(q_codes), _lib.ptr(q_scales), _lib.ptr(q_offsets), n_q, int(q_codes.shape[0]),
+                                        int(max_q_tokens), _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets),
+                                        _lib.ptr(index.clamp0), n, int(index.codes.shape[0]), DIM, _lib.ptr(out), max(n, 1),
+                                        _lib.current_stream_handle(dev))
+    _lib.check(rc, "msim_f4w_scores")
+    return out
+
+
+def fp4_wide_scores(queries, index: Fp4WideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Approximate MaxSim of every query against every page of the index: fp32 [n_q, len(index)], column j = page
+    index.id_base + j.  A score's bits depend on its query and page only.  Asynchronous on torch's current stream.  Given a
+    `PackedQueries` it never synchronises with the host and is hipGraph-capturable: its only allocations are torch tensors (the
+    query codes and scales, and `out` when it is None), made on the current stream before the library calls."""
+    if not isinstance(index, Fp4WideIndex):
+        raise TypeError(f"fp4_wide_scores takes an Fp4WideIndex (got {type(index).__name__})")
+    dev = index.device
+    q = _as_packed(queries, dev, layout="flat")
+    _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
+    if q.device != dev:
+        raise ValueError("queries and index live on different devices")
+    lens = q.lengths
+    max_q = int(lens.max()) if lens.numel() else 0
+    codes, scales = _quantize_packed(q)
+    return fp4_wide_scores_from_codes(codes, scales, q.offsets, max_q, index, out=out)

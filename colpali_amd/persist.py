@@ -31,6 +31,7 @@ from .centroid import CentroidIndex
 from .corpus import PackedCorpus, _staging
 from .fde import FdeConfig, FdeIndex
 from .fp4_index import Fp4Index
+from .fp4_wide_index import Fp4WideIndex
 from .int8_index import Int8Index
 from .live import LiveCorpus
 from .live_residual import LiveResidualCorpus
@@ -54,6 +55,8 @@ _FROZEN = {
     "Int8Index": (Int8Index, (("codes", "rows"), ("scales", "pages"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
     "BinaryIndex": (BinaryIndex, (("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
     "Fp4Index": (Fp4Index, (("codes", "rows"), ("scales", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
+    "Fp4WideIndex": (Fp4WideIndex, (("codes", "rows"), ("scales", "rows"), ("offsets", "offsets"), ("clamp0", "pages"),
+                                    ("lengths", "pages"))),
     "CentroidIndex": (CentroidIndex, (("centroids", "whole"), ("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"),
                                       ("lengths", "pages"))),
     "FdeIndex": (FdeIndex, (("Fd", "rows"), ("G", "whole"), ("S", "whole"))),
@@ -247,7 +250,7 @@ def _kind_of(obj) -> str:
 
 
 def save(obj, path, *, chunk_bytes: int = DEFAULT_CHUNK_BYTES) -> None:
-    """Write `obj` -- a `PackedCorpus`, `Int8Index`, `BinaryIndex`, `Fp4Index`, `CentroidIndex`, `FdeIndex`, `ResidualCorpus`, `LiveCorpus` or
+    """Write `obj` -- a `PackedCorpus`, `Int8Index`, `BinaryIndex`, `Fp4Index`, `Fp4WideIndex`, `CentroidIndex`, `FdeIndex`, `ResidualCorpus`, `LiveCorpus` or
     `LiveResidualCorpus` -- to `path` (see the module docstring).  Written to `path + ".tmp"`, fsynced and renamed: a failed save
     leaves nothing under `path` and an older file there untouched.  Holds two pinned chunks of host memory at most, whatever the
     object's size.  Synchronises with the host; raises under stream capture."""
@@ -507,6 +510,8 @@ def _load_frozen(rd: _Reader, kind: str, device, pages):
             return BinaryIndex(got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind == "Fp4Index":
             return Fp4Index(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
+        if kind == "Fp4WideIndex":
+            return Fp4WideIndex(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind == "CentroidIndex":
             return CentroidIndex(got["centroids"], got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind == "FdeIndex":

@@ -20,6 +20,7 @@ from . import _lib
 from .align import Alignment, align
 from .binary_index import BinaryIndex, binary_scores
 from .fp4_index import Fp4Index, fp4_scores, fp6_scores
+from .fp4_wide_index import Fp4WideIndex, fp4_wide_scores
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .fde import FdeIndex, fde_scores
 from . import filter as _filter
@@ -209,7 +210,7 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
-            fp4_scores, fp6_scores, align, residual_align)
+            fp4_scores, fp6_scores, fp4_wide_scores, align, residual_align)
 
 
 class ShardedRetriever:
@@ -227,7 +228,7 @@ class ShardedRetriever:
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
                  rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores,
-                 int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, binary_score_fn: Callable = binary_scores, fp4_score_fn: Callable = fp4_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
+                 int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, binary_score_fn: Callable = binary_scores, fp4_score_fn: Callable = fp4_scores, fp4_wide_score_fn: Callable = fp4_wide_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
                  filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
         if isinstance(shard, ResidualCorpus) and rerank_fn is rerank_scores:
@@ -243,6 +244,7 @@ class ShardedRetriever:
         self._centroid_score = centroid_score_fn  # (queries, CentroidIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<CentroidIndex>
         self._binary_score = binary_score_fn  # (queries, BinaryIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<BinaryIndex>
         self._fp4_score = fp4_score_fn    # (queries, Fp4Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4Index>
+        self._fp4_wide_score = fp4_wide_score_fn  # (queries, Fp4WideIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4WideIndex>
         self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
         self._mine_bounds = mine_bounds_fn    # (scores, csr, id_base, local=, alive=) -> fp32 [n_q]: the best in-shard positive of each query
         self._mine_mask = mine_mask_fn        # (scores, csr, id_base, bounds, max_ratio, alive) -> scores, -inf where ineligible
@@ -275,7 +277,8 @@ class ShardedRetriever:
         different centroid sets are not comparable, and the global top `n_candidates` is taken across the shards.  Or a
         `BinaryIndex` of the shard or of its pooled pages: stage 1 is then the 1-bit sign scan (`binary_scores`); it has no trained
         parameter, so its scores are comparable across shards as they stand.  Or an `Fp4Index` of the shard or of its pooled
-        pages: stage 1 is then the FP4 scan (`fp4_scores`), comparable across shards in the same way.
+        pages: stage 1 is then the FP4 scan (`fp4_scores`), comparable across shards in the same way.  Or, over a 320-wide shard,
+        an `Fp4WideIndex` of it: stage 1 is then `fp4_wide_scores`, under the same rules, and stage 2 the 320-wide rerank.
 
         Filtered search: `filter` -- a `PageFilter` over this shard (same count, same id_base, same device; ValueError otherwise, and
         for a per-query filter whose rows differ from the number of queries) -- restricts every query to its allowed pages.  For each
@@ -527,15 +530,16 @@ class ShardedRetriever:
             if m > SELECT_MAX_M:
                 raise NotImplementedError(f"group_by over a list of {m} pages: group_select takes at most {SELECT_MAX_M}")
         if prefilter is not None:
-            if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex, BinaryIndex, Fp4Index)):
-                raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index, a CentroidIndex or a BinaryIndex, or an Fp4Index")
+            if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex, BinaryIndex, Fp4Index, Fp4WideIndex)):
+                raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index, a CentroidIndex or a BinaryIndex, or an Fp4Index or an Fp4WideIndex")
             self._check_covers("prefilter holds", prefilter, "documents")
             if n_candidates is None or int(n_candidates) < 1:
                 raise ValueError("prefilter= needs n_candidates >= 1")
         stage1 = (self._fde_score if isinstance(prefilter, FdeIndex) else self._int8_score if isinstance(prefilter, Int8Index)
                   else self._centroid_score if isinstance(prefilter, CentroidIndex)
                   else self._binary_score if isinstance(prefilter, BinaryIndex)
-                  else self._fp4_score if isinstance(prefilter, Fp4Index) else self._score)
+                  else self._fp4_score if isinstance(prefilter, Fp4Index)
+                  else self._fp4_wide_score if isinstance(prefilter, Fp4WideIndex) else self._score)
         queries = self._pack(queries, compact, self._rerank, *((stage1,) if prefilter is not None else ()))
         if flt is not None:
             self._check_filter_rows(flt, len(queries))

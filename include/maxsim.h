@@ -768,6 +768,45 @@ int msim_f4_scores_q6(const uint8_t *q6, const uint8_t *qs, const int32_t *q_off
                       int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
 /*
+ * FP4 INDEX AT WIDTH 320 (fp4_wide_index.hip; additions to ABI 22): the FP4 index for 320-wide (ColQwen3) shards, a sibling of
+ * msim_f4_* as msim_fwd_candidates_wide is of msim_fwd_candidates.  Every corpus row and every query token is 320 OCP e2m1 values and
+ * ONE power-of-two scale -- 161 bytes per row instead of 640.  A 320-wide row is 2 1/2 K blocks of
+ * v_mfma_scale_f32_16x16x128_f8f6f4: 16 rows x 16 tokens take three instructions, chained through the C operand, the third with
+ * half of its K block empty.  A first stage for two-stage search, reranked exactly by msim_fwd_candidates_wide.
+ *   Row code (msim_f4w_encode_rows; pages and query tokens alike): msim_f4_encode_rows' rule over 320 dimensions, for a row x of a
+ *     bf16 / f16 blob of width 320, on the stored values in fp32: a = max over all 320 |x_k|.  If a == 0 every nibble is 0 and the
+ *     scale byte is 127.  Otherwise e = the smallest integer with a <= 6 * 2^e, clamped to [-32, 32] (taken from a's exponent and
+ *     mantissa fields); y_k = min(|x_k| * 2^-e, 6); the code is the nearest of {0, 0.5, 1, 1.5, 2, 3, 4, 6} (codes 0 .. 7), a tie
+ *     going to the even code; the nibble is sign << 3 | code with x's sign bit when the code is not 0, and 0 otherwise.  Dimension k
+ *     is nibble (k & 1) of byte (k >> 1) of a 160-byte row, the low nibble holding the even k.  The scale byte is e + 127 (E8M0).
+ *     codes uint8 [n_rows, 160] and scales uint8 [n_rows] in the input's row order.  NaN elements are unspecified, as above.
+ *   Score (msim_f4w_scores): as msim_f4_scores.  I_ij = sum_{k<320} v(q_ik) v(d_jk) -- a multiple of 1/4 with
+ *     |I| <= 320 * 36 = 11 520 (46 080 quarters, below 2^24), and so is every partial sum: exact in fp32 in any order, which one
+ *     scale per ROW keeps true across the three K blocks; Z_ij = I_ij * 2^(eq_i + ed_j), exact; M_ic = max_j Z_ij over the rows of
+ *     page c, then max(M_ic, 0) where clamp0[c] is set; scores[q, c] = the SEQUENTIAL fp32 sum of M_ic in token order.  A page of 0
+ *     rows scores -inf; a query of 0 tokens scores 0 against every page that has rows.  A score's bits depend on its query and page
+ *     only.  No row that is not the page's takes part in M_ic.  Scale bytes outside 95 .. 159: unspecified bits, as above.
+ *     max_q_tokens, a query longer than its token slots or with offsets outside 0 .. q_rows (NaN over that query), and a page whose
+ *     offsets fall outside 0 .. d_rows (NaN for every page scored by the same wave, a range of at most 63 consecutive pages): as
+ *     msim_f4_scores.  A wave's range holds at most 2^23 rows, which keeps every 32-bit buffer offset below 2^31 at 160 bytes per
+ *     row (a longer range is written as NaN).  clamp0: uint8 [n_d] or NULL.  scores fp32 [n_q, ld_scores], ld_scores >= n_d.  No
+ *     workspace.
+ *     msim_f4w_scores_plan writes the launch form msim_f4w_scores takes for the same arguments on the current device: plan[0] = NT
+ *     (16-token tiles a wave holds), plan[1] = GW (waves that share one page range: 1, 2 or 4), plan[2] = D (chunks read ahead),
+ *     plan[3] = pages per wave range (1 .. 63).  A query longer than 16 NT tokens takes ceil(tokens / (16 NT)) passes over its range.
+ * Width 320 and bf16 / f16 only (MSIM_EUNSUPPORTED otherwise -- width 128 is msim_f4_*'s, which refuses 320 in turn); a null or
+ * misaligned pointer or a negative size is MSIM_EINVAL; both are decided before the device is touched.  Rows and codes 16-byte
+ * aligned; offsets and scores 4-byte aligned; scale bytes unaligned.  A call with nothing to do returns 0 before it looks at a
+ * pointer.  Asynchronous on `stream`, no allocation, no host synchronisation: hipGraph-capturable.
+ */
+int msim_f4w_encode_rows(int dtype, const void *X, int64_t n_rows, int dim, uint8_t *codes /* [n_rows, 160] */, uint8_t *scales,
+                         void *stream);
+int msim_f4w_scores_plan(int n_q, int max_q_tokens, int n_d, int64_t d_rows, int32_t *plan /* [4] */);
+int msim_f4w_scores(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                    const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                    int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
+
+/*
  * CENTROID-CODE INDEX (centroid_index.hip; additions to ABI 22): every corpus row stored as the uint16 id of its nearest of K
  * centroids, pages scored by centroid interaction (PLAID's first stage) -- a first stage for two-stage search that reads 2 bytes
  * per row, reranked exactly by msim_fwd_candidates.  C: K centroid rows [K, 128] in the dtype of the rows they meet; K a multiple

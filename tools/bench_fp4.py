@@ -3,6 +3,10 @@
 
     python tools/bench_fp4.py [--out FILE] [--summary profiles/fp4_summary.md] [--steps 10 --warmup 3] [--docs 125000 --doc-len 1024]
                               [--legs build,stage1,pooled,two_stage,recall]
+    python tools/bench_fp4.py --dim 320 [--out FILE] [--summary profiles/fp4_wide_summary.md] [--legs build,stage1,two_stage,recall]
+
+--dim 320 measures the 320-wide index (msim_f4w_*, colpali_amd.Fp4WideIndex) on the shard of tools/bench_rerank.py --dim 320
+(50 000 x 1024 x 320 bf16 by default): see `main_wide`.
 
 Legs, each timed with device events after a warm-up; the variants of a leg ALTERNATE call by call inside one timed loop, and every
 figure is the median with its range:
@@ -163,13 +167,170 @@ def summary(res):
     return "\n".join(L) + "\n"
 
 
+# ------------------------------------------------------------------------------------------------------------------ width 320
+WIDE_ROW_BYTES = 161           # 160 code bytes and one scale byte
+
+
+def wide_bounds_ms(n_q, q_len, n_d, rows):
+    """memory: the index read once and the scores written; matrix cores: three K = 128 instructions per 16 x 16 tile"""
+    return {"memory_ms": (rows * WIDE_ROW_BYTES + n_q * n_d * 4) / (HBM_PEAK_GBS * 1e9) * 1e3,
+            "matrix_ms": 2.0 * n_q * q_len * rows * 384 / (FP4_PEAK_TFLOPS * 1e12) * 1e3}
+
+
+def wide_planted(amd, dev, n_docs, dim=320, doc_len=1024, n_q=100, q_len=32, seed=5):
+    """the planted set of tools/bench_rerank.py:planted_recall at `dim`: (full shard, pooled shard, packed queries)"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    pages = []
+    for d0 in range(0, n_docs, 500):
+        n = min(500, n_docs - d0)
+        topics = torch.randn((n, 48, dim), generator=g, device=dev)
+        pick = torch.randint(0, 48, (n, doc_len), generator=g, device=dev)
+        rows = torch.gather(topics, 1, pick.unsqueeze(-1).expand(n, doc_len, dim)) + 0.6 * torch.randn((n, doc_len, dim), generator=g, device=dev)
+        pages.append(torch.nn.functional.normalize(rows, dim=-1).to(torch.bfloat16))
+    pages = torch.cat(pages)
+    full = amd.pack_passages(pages, dev, batch_size=None)
+    pooler = amd.HierarchicalTokenPooler()
+    pooled_list = []
+    for d0 in range(0, n_docs, 1000):
+        pooled_list += pooler.pool_embeddings(list(pages[d0:d0 + 1000].unbind(0)), pool_factor=3)
+    pooled = amd.pack_passages(pooled_list, dev, batch_size=None)
+    target = torch.randint(0, n_docs, (n_q,), generator=g, device=dev)
+    tok = torch.randint(0, doc_len, (n_q, q_len), generator=g, device=dev)
+    q = pages[target.unsqueeze(1), tok].float() + 0.8 * torch.randn((n_q, q_len, dim), generator=g, device=dev) / dim ** 0.5
+    return full, pooled, amd.pack_queries(torch.nn.functional.normalize(q, dim=-1).to(torch.bfloat16), dev, compact=False)
+
+
+def wide_recall_leg(amd, dev, n_docs, k=10):
+    full, pooled, pq = wide_planted(amd, dev, n_docs)
+    r = amd.ShardedRetriever(full)
+    exact = r.search(pq, k=k)[1].tolist()
+    idx = amd.Fp4WideIndex.build(full)
+
+    def recall(prefilter, m):
+        two = r.search(pq, k=k, prefilter=prefilter, n_candidates=m)[1].tolist()
+        return sum(len(set(a) & set(b)) for a, b in zip(exact, two)) / (len(pq) * k)
+
+    return {"docs": n_docs, "queries": len(pq), "k": k, "pooled_rows_per_doc": float(pooled.blob.shape[0]) / n_docs,
+            "fp4_wide_full": {str(m): recall(idx, m) for m in MS}, "pooled_corpus": {str(m): recall(pooled, m) for m in MS},
+            "bytes": {"fp4_wide_full": idx.nbytes, "pooled_corpus": pooled.nbytes, "shard": full.nbytes}}
+
+
+def wide_summary(res):
+    L = ["# FP4 index at width 320: measured on one MI355X", "",
+         f"`tools/bench_fp4.py --dim 320 --steps {res['steps']} --warmup {res['warmup']}` on the 320-wide shard ({res['docs']} pages × "
+         f"{res['doc_len']} rows, bf16), queries of 32 tokens.  The variants of a leg alternate call by call in one timed loop; median, "
+         "with the range in brackets.  The bounds are derived (8 TB/s; 10 PFLOPS dense FP4, three K = 128 instructions per 16 × 16 "
+         "tile), not measured; a share is bound / measured.", ""]
+    if "bytes" in res:
+        b = res["bytes"]
+        L += [f"Sizes: shard {b['shard'] / 1e9:.2f} GB, `Fp4WideIndex` {b['fp4_wide'] / 1e9:.2f} GB ({b['fp4_wide'] / b['shard']:.3f} of it).", ""]
+    if "build" in res:
+        b = res["build"]
+        L += [f"Build: `Fp4WideIndex.build` {_ms(b['fp4_wide_build'])} in one launch, {b['share_of_bound']:.2f} of its {b['bound_ms']:.2f} ms bound "
+              "(the shard read once, codes and scales written).", ""]
+    if "stage1" in res:
+        L += ["## Stage 1", "", "| | `fp4_wide_scores` | exact scan | ratio | memory bound (share) | matrix-core bound (share) |", "|---|---|---|---|---|---|"]
+        for n, leg in res["stage1"].items():
+            bd = leg["bounds"]
+            L += [f"| {n} × 32 | {_ms(leg['fp4_wide_scores'])} | {_ms(leg['exact_scan'])} | {leg['exact_vs_fp4_wide']:.2f} × | "
+                  f"{bd['memory_ms']:.2f} ms ({bd['memory_ms'] / leg['fp4_wide_scores']['median_ms']:.2f}) | "
+                  f"{bd['matrix_ms']:.2f} ms ({bd['matrix_ms'] / leg['fp4_wide_scores']['median_ms']:.2f}) |"]
+        L += [""]
+    if "two_stage" in res:
+        t = res["two_stage"]
+        L += ["## Two-stage search at 1000 × 32, k = 10", "", "| | time | exact search / this |", "|---|---|---|"]
+        ex = t["exact_search"]
+        for key, name in [(f"fp4_wide_m{m}", f"`prefilter=<Fp4WideIndex>`, m = {m}") for m in MS] + \
+                         [("pooled_m100", f"`prefilter=<PackedCorpus of {t['coarse_rows_per_doc']}-row pages>`, m = 100"), ("exact_search", "exact search")]:
+            L += [f"| {name} | {_ms(t[key])} | {ex['median_ms'] / t[key]['median_ms']:.2f} |"]
+        a = t["fp4_wide_m100"]
+        apart = a["max_ms"] < ex["min_ms"]
+        L += ["", f"Two-stage search at m = 100 against the exact search of the same shard in the same loop: {ex['median_ms'] / a['median_ms']:.2f} × "
+              f"faster; the two ranges {'do not overlap' if apart else 'OVERLAP: the claim does not hold in this run'}.", ""]
+    if "recall" in res:
+        r = res["recall"]
+        L += [f"## Recall@10 against the exact search, planted {r['docs']}-page set at width 320 ({r['queries']} queries)", "",
+              "| first stage | bytes | m = 100 | m = 400 | m = 1000 |", "|---|---|---|---|---|"]
+        for key, name in (("fp4_wide_full", "`Fp4WideIndex`, full pages"),
+                          ("pooled_corpus", f"pooled `PackedCorpus` ({r['pooled_rows_per_doc']:.0f} rows per page)")):
+            L += [f"| {name} | {r['bytes'][key] / 1e6:.0f} MB | " + " | ".join(f"{r[key][str(m)]:.3f}" for m in MS) + " |"]
+    return "\n".join(L) + "\n"
+
+
+def main_wide(args):
+    """--dim 320: index bytes, build, stage 1 beside the exact 320-wide scan, two-stage search beside the exact search and the
+    pooled-prefilter two-stage search, recall@10 on the planted set."""
+    import colpali_amd as amd
+    from tools.bench_rerank import make_queries_dim, make_shard_dim
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    amd._lib.lib()
+    legs = set(args.legs.split(","))
+    docs = 50_000 if args.docs is None else args.docs
+    t0 = time.perf_counter()
+    res = {"tool": "bench_fp4", "dim": 320, "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len, "steps": args.steps,
+           "warmup": args.warmup, "hbm_peak_GBps": HBM_PEAK_GBS, "fp4_peak_TFLOPs": FP4_PEAK_TFLOPS}
+    if legs & {"build", "stage1", "two_stage"}:
+        corpus = make_shard_dim(docs, args.doc_len, 320, dev, seed=1234)
+        idx = amd.Fp4WideIndex.build(corpus)
+        _progress("shard and index", t0)
+        res["bytes"] = {"shard": corpus.nbytes, "fp4_wide": idx.nbytes}
+        rows = int(idx.codes.shape[0])
+        if "build" in legs:
+            b = alternating({"fp4_wide_build": lambda: amd.Fp4WideIndex.build(corpus)}, max(3, args.steps // 2), 1)
+            b["bound_ms"] = (corpus.nbytes + rows * WIDE_ROW_BYTES) / (HBM_PEAK_GBS * 1e9) * 1e3
+            b["share_of_bound"] = b["bound_ms"] / b["fp4_wide_build"]["median_ms"]
+            res["build"] = b
+            _progress("build", t0)
+        if "stage1" in legs:
+            res["stage1"] = {}
+            for n in (4, 1000):
+                pq = amd.pack_queries(make_queries_dim(n, args.q_len, 320, dev, seed=99), dev, compact=False)
+                out = torch.empty((n, len(idx)), dtype=torch.float32, device=dev)
+                leg = alternating({"fp4_wide_scores": lambda: amd.fp4_wide_scores(pq, idx, out=out),
+                                   "exact_scan": lambda: amd.maxsim_scores(pq, corpus)},
+                                  args.steps if n == 4 else max(3, args.steps // 2), args.warmup if n == 4 else 1)
+                leg["bounds"] = wide_bounds_ms(n, args.q_len, len(idx), rows)
+                leg["exact_vs_fp4_wide"] = leg["exact_scan"]["median_ms"] / leg["fp4_wide_scores"]["median_ms"]
+                res["stage1"][str(n)] = leg
+                del out
+            _progress("stage1", t0)
+        if "two_stage" in legs:
+            pq = amd.pack_queries(make_queries_dim(1000, args.q_len, 320, dev, seed=99), dev, compact=False)
+            coarse = make_shard_dim(docs, POOLED_LEN, 320, dev, seed=4321)
+            r = amd.ShardedRetriever(corpus)
+            variants = {f"fp4_wide_m{m}": (lambda m=m: r.search(pq, k=10, prefilter=idx, n_candidates=m)) for m in MS}
+            variants["pooled_m100"] = lambda: r.search(pq, k=10, prefilter=coarse, n_candidates=100)
+            variants["exact_search"] = lambda: r.search(pq, k=10)
+            ts = alternating(variants, max(3, args.steps // 2), 1)
+            ts["n_queries"], ts["coarse_rows_per_doc"] = 1000, POOLED_LEN
+            res["two_stage"] = ts
+            del coarse
+            _progress("two_stage", t0)
+        del corpus, idx
+        torch.cuda.empty_cache()
+    if "recall" in legs:
+        res["recall"] = wide_recall_leg(amd, dev, args.recall_docs)
+    res["wall_s"] = time.perf_counter() - t0
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    if args.summary:
+        with open(args.summary, "w") as f:
+            f.write(wide_summary(res))
+    print(line)
+
+
 def _progress(what, t0):
     print(f"[bench_fp4] {what} at {time.perf_counter() - t0:.0f} s", file=sys.stderr, flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--docs", type=int, default=125_000)
+    ap.add_argument("--dim", type=int, default=128, choices=(128, 320), help="320: the Fp4WideIndex on the 320-wide shard")
+    ap.add_argument("--docs", type=int, default=None, help="default: 125 000 at width 128, 50 000 at width 320 (the same bytes)")
     ap.add_argument("--doc-len", type=int, default=1024)
     ap.add_argument("--q-len", type=int, default=32)
     ap.add_argument("--steps", type=int, default=10)
@@ -181,6 +342,10 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_fp4.py needs an MI355X (there is no CPU fallback)")
+    if args.dim == 320:
+        return main_wide(args)
+    if args.docs is None:
+        args.docs = 125_000
     import colpali_amd as amd
 
     dev = torch.device("cuda:0")
