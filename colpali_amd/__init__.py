@@ -24,6 +24,9 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      first stage, ShardedRetriever(..., fp4_score_fn=fp6_scores)
   * Fp4WideIndex / fp4_wide_scores -- the FP4 index of a 320-wide (ColQwen3) shard: 160 bytes of e2m1 nibbles and one scale byte
                                      per row, three chained block-scaled MFMAs per 16 rows x 16 tokens: a first stage for prefilter=
+  * LiveCorpus.fp4_index / drop_fp4_index -- the FP4 index of a shard that changes (width 128 and 320), kept in step: add encodes
+                                     the new rows, compact moves code rows and scale bytes (msim_f4_live_compact); its stage-1
+                                     scores, and those of any Fp4Index / Fp4WideIndex passed as prefilter=, are tombstone-masked
   * CentroidIndex / centroid_scores -- rows stored as the id of their nearest centroid, pages scored by table lookups (PLAID's
                                      centroid interaction): a first stage for prefilter= at 2 bytes per row
   * ResidualCorpus / residual_rerank_scores -- PLAID's second half: the shard itself as centroid codes + 2 / 4 residual bits per

@@ -250,6 +250,10 @@ def lib() -> ctypes.CDLL:
     L.msim_res_live_compact_workspace_bytes.restype = sz
     L.msim_res_live_compact.argtypes = [vp, vp, i32, i64, vp, vp, i32, vp, vp, vp, i64, vp]
     L.msim_res_live_compact.restype = i32
+    L.msim_f4_live_compact_workspace_bytes.argtypes = [i32, i64]
+    L.msim_f4_live_compact_workspace_bytes.restype = sz
+    L.msim_f4_live_compact.argtypes = [vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, i64, vp]
+    L.msim_f4_live_compact.restype = i32
     L.msim_mine_bounds.argtypes = [vp, i64, i32, i64, vp, vp, i64, i64, vp, i32, vp, vp]
     L.msim_mine_bounds.restype = i32
     L.msim_mine_mask.argtypes = [vp, i64, i32, i64, vp, f32, vp, vp, vp, i64, i64, vp]

@@ -294,6 +294,52 @@ int msim_res_live_compact(uint16_t *codes, uint8_t *residuals, int bits, int64_t
     return launch_failed("live compaction of a compressed shard");
 }
 
+size_t msim_f4_live_compact_workspace_bytes(int n_slots, int64_t b) { return msim_live_compact_workspace_bytes(n_slots, b); }
+
+// One offset plan, two arrays moved against it: the FP4 code rows (64 or 160 bytes) and the scale bytes of a live FP4 index.  A chunk is
+// floor(bounce_bytes / (code_row_bytes + 1)) destination rows: the bounce buffer holds the chunk's code rows first (a multiple of 16
+// bytes each, so the scale bytes behind them start 16-byte aligned; they need no alignment) and its scale bytes after them.
+int msim_f4_live_compact(uint8_t *codes, int64_t code_row_bytes, uint8_t *scales, int64_t rows_bound, int32_t *off, const uint8_t *alive,
+                         int n_slots, int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream) {
+    const char *who = "msim_f4_live_compact";
+    if (int rc = live_check_sizes(who, n_slots, rows_bound, bounce_bytes)) return rc;
+    if (!(code_row_bytes == 64 || code_row_bytes == 160))
+        return fail(MSIM_EUNSUPPORTED, "%s: code rows of %lld bytes; an fp4 index stores 64 (width 128) or 160 (width 320)", who,
+                    (long long)code_row_bytes);
+    if (int rc = live_check_args(who, n_slots, rows_bound, off, alive, rows_used_out, workspace, bounce, !codes || !scales,
+                                 misaligned(codes, 16), "codes"))
+        return rc;
+    if (n_slots == 0) return MSIM_OK;
+    const int64_t both_bytes = code_row_bytes + 1;
+    if (rows_bound > 0 && bounce_bytes < both_bytes)
+        return fail(MSIM_EINVAL, "%s: a bounce buffer of %lld bytes holds no row of %lld + 1 bytes", who, (long long)bounce_bytes,
+                    (long long)code_row_bytes);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    LivePlan p;
+    if (int rc = live_plan(who, st, workspace, off, alive, n_slots, rows_bound, rows_used_out, bounce_bytes, both_bytes, &p)) return rc;
+    int block_rows = (int)(msim::kLiveBlockBytes / code_row_bytes);          // 256 rows of 64 bytes, 102 of 160: 16 KiB per workgroup
+    block_rows = block_rows > msim::kLiveMaxBlockRows ? msim::kLiveMaxBlockRows : block_rows;
+    constexpr int scale_block_rows = msim::kLiveMoveThreads * msim::kLiveCodeRows;
+    const int lpr = (int)(code_row_bytes / 16);
+    uint8_t *bounce_codes = static_cast<uint8_t *>(bounce);
+    uint8_t *bounce_scales = bounce_codes + p.chunk_rows * code_row_bytes;
+    for (int64_t k = 0; k < p.n_chunks; ++k) {
+        const long long chunk0 = k * p.chunk_rows;
+        const int rows_here = (int)(rows_bound - chunk0 < p.chunk_rows ? rows_bound - chunk0 : p.chunk_rows);
+        const unsigned blocks = (unsigned)((rows_here + block_rows - 1) / block_rows);
+        const unsigned sblocks = (unsigned)((rows_here + scale_block_rows - 1) / scale_block_rows);
+        hipLaunchKernelGGL(msim::live_move_kernel<true>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, codes, lpr,
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_codes, chunk0, rows_here, block_rows);
+        hipLaunchKernelGGL(msim::live_move_bytes_kernel<true>, dim3(sblocks), dim3(msim::kLiveMoveThreads), 0, st, scales,
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_scales, chunk0, rows_here);
+        hipLaunchKernelGGL(msim::live_move_kernel<false>, dim3(blocks), dim3(msim::kLiveMoveThreads), 0, st, codes, lpr,
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_codes, chunk0, rows_here, block_rows);
+        hipLaunchKernelGGL(msim::live_move_bytes_kernel<false>, dim3(sblocks), dim3(msim::kLiveMoveThreads), 0, st, scales,
+                           (long long)rows_bound, off, p.old_off, n_slots, p.hdr, bounce_scales, chunk0, rows_here);
+    }
+    return launch_failed("live compaction of an fp4 index");
+}
+
 int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const uint8_t *alive, void *stream) {
     const char *who = "msim_live_mask_scores";
     if (n_q < 0 || n < 0) return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n=%lld)", who, n_q, (long long)n);

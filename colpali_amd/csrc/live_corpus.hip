@@ -19,6 +19,7 @@
 //                           two), and the rows move as 16-byte pieces, four in flight per lane, read once with non-temporal loads.
 //   live_move_codes_kernel the same two launches for an array of 2-byte rows (the centroid codes of a compressed shard,
 //                           msim_res_live_compact), one row per lane: a 16-byte piece of it would span eight rows.
+//   live_move_bytes_kernel the same for an array of 1-byte rows (the scale bytes of a live FP4 index, msim_f4_live_compact).
 // Every row index the device derives is checked against rows_bound before it becomes an address; a broken invariant sets the
 // status word and every later kernel of the call returns at once.
 //
@@ -243,6 +244,38 @@ __global__ __launch_bounds__(kLiveMoveThreads) void live_move_codes_kernel(uint1
         else if (src != d) {
             if (TO_BOUNCE) bounce[d - chunk0] = codes[src];
             else codes[d] = bounce[d - chunk0];
+        }
+    }
+}
+
+// ... and for an array of 1-byte rows (the E8M0 scale bytes of a live FP4 index, msim_f4_live_compact): the same shape, the same
+// early exits and status word; consecutive lanes read and write consecutive bytes inside a page.
+template <bool TO_BOUNCE>
+__global__ __launch_bounds__(kLiveMoveThreads) void live_move_bytes_kernel(uint8_t *__restrict__ bytes, long long rows_bound,
+                                                                           const int32_t *__restrict__ new_off,
+                                                                           const int32_t *__restrict__ old_off, int n_slots,
+                                                                           int32_t *__restrict__ hdr, uint8_t *__restrict__ bounce,
+                                                                           long long chunk0, int chunk_rows) {
+    if (hdr[kLiveStatus]) return;                        // uniform
+    constexpr int block_rows = kLiveMoveThreads * kLiveCodeRows;
+    const long long total = hdr[kLiveTotal], first = hdr[kLiveFirst];
+    const long long r0 = chunk0 + (long long)blockIdx.x * block_rows;
+    long long r1 = r0 + block_rows;
+    if (r1 > chunk0 + chunk_rows) r1 = chunk0 + chunk_rows;
+    if (r1 > total) r1 = total;
+    if (r0 >= r1 || r1 <= first) return;                 // past the live rows, or wholly below the first row that moves
+    const int s_lo = live_slot_of(new_off, 0, n_slots, (int)r0);
+    const int s_hi = live_slot_of(new_off, s_lo, n_slots, (int)(r1 - 1));
+#pragma unroll
+    for (int u = 0; u < kLiveCodeRows; ++u) {
+        const long long d = r0 + u * kLiveMoveThreads + threadIdx.x;
+        if (d >= r1) continue;
+        const int c = live_slot_of(new_off, s_lo, s_hi + 1, (int)d);
+        const long long src = (long long)old_off[c] + (d - new_off[c]);
+        if (src < d || src >= rows_bound || d >= rows_bound) atomicOr(&hdr[kLiveStatus], kLiveBadRow);
+        else if (src != d) {
+            if (TO_BOUNCE) bounce[d - chunk0] = bytes[src];
+            else bytes[d] = bounce[d - chunk0];
         }
     }
 }

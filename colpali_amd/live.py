@@ -1,10 +1,11 @@
 """A live resident shard: pages are added, deleted and compacted in place, and every search sees the change at once.
 
 `LiveCorpus` owns one row blob with spare capacity, the page offsets, a tombstone mask (`alive`) and, on request, an int8 index
-kept in step.  No scoring kernel changes: every scorer reads page c through `offsets[c] .. offsets[c + 1]`, so
+(`int8_index()`) and an FP4 index (`fp4_index()`: width 128 and width 320) kept in step.  No scoring kernel changes: every scorer
+reads page c through `offsets[c] .. offsets[c + 1]`, so
 
   * `add` appends rows at the tail of the blob and slots at the tail of the offsets (no reallocation, ever);
-  * `delete` clears `alive`; the scores of deleted slots are overwritten with -inf behind the full scan and the int8 stage 1
+  * `delete` clears `alive`; the scores of deleted slots are overwritten with -inf behind the full scan and the int8 / FP4 stage 1
     (msim_live_mask_scores), and deleted candidate ids become -1 before the rerank;
   * `compact` moves the rows of live pages down over the deleted ones (msim_live_compact, colpali_amd/csrc/live_corpus.hip) and turns
     every deleted slot into an empty page.
@@ -28,6 +29,10 @@ from . import _lib
 from .corpus import PackedCorpus, _as_packed, _staging, _widen, host_list_image
 from .int8_index import DIM as I8_DIM
 from .int8_index import Int8Index, int8_scores
+from .fp4_index import DIM as F4_DIM
+from .fp4_index import Fp4Index, fp4_scores
+from .fp4_wide_index import DIM as F4W_DIM
+from .fp4_wide_index import Fp4WideIndex, fp4_wide_scores
 from .align import Alignment, align
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
 from .group import PageGroups, group_reduce, group_select
@@ -62,7 +67,6 @@ class _LiveShard:
     storage and supplies `view`, `_write_rows`, `_move_rows`, `_widths` and the names below."""
 
     _entry = ""                # the compaction entry behind `_move_rows` (its workspace size, the messages of `check()`)
-    _stage1_kw = ""            # the stage-1 hook of `ShardedRetriever` that `stage1_fn` is
 
     @staticmethod
     def _capacity(capacity_rows, capacity_docs) -> Tuple[int, int]:
@@ -73,7 +77,7 @@ class _LiveShard:
             raise NotImplementedError("more than 2^31 patch rows in one shard")
         return capacity_rows, capacity_docs
 
-    def _init_slots(self, capacity_rows: int, capacity_docs: int, device, id_base: int, *, score_fn, rerank_fn, stage1_fn, select, mask_fn,
+    def _init_slots(self, capacity_rows: int, capacity_docs: int, device, id_base: int, *, score_fn, rerank_fn, stage1_fns, select, mask_fn,
                     align_fn, mine_bounds_fn, mine_mask_fn, filter_mask_fn, filter_list_fn, filter_ids_fn, group_reduce_fn,
                     group_select_fn) -> None:
         """the slot table and the hooks; the subclass has allocated its rows"""
@@ -86,7 +90,8 @@ class _LiveShard:
         self._dirty = False                                          # a device-side delete has not been read back yet
         self.n_slots = 0
         self._rows_used = 0
-        self._score_fn, self._rerank_fn, self._stage1_fn = score_fn, rerank_fn, stage1_fn
+        self._score_fn, self._rerank_fn = score_fn, rerank_fn
+        self._stage1_fns = dict(stage1_fns)   # the stage-1 hooks of `ShardedRetriever` whose scores the tombstones mask, by keyword
         self._select, self._mask_fn = select, mask_fn
         self._align_fn = align_fn         # (queries, view(), ids, maps=) -> Alignment
         self._mine_bounds_fn, self._mine_mask_fn = mine_bounds_fn, mine_mask_fn
@@ -275,8 +280,9 @@ class _LiveShard:
     def _score(self, queries, corpus):
         return self._masked(self._score_fn(queries, corpus))
 
-    def _stage1_score(self, queries, index):
-        return self._masked(self._stage1_fn(queries, index))
+    def _stage1_hooks(self) -> dict:
+        """every stage-1 hook this class masks, wrapped: (queries, index) -> its scores with -inf in the deleted slots"""
+        return {kw: (lambda queries, index, fn=fn: self._masked(fn(queries, index))) for kw, fn in self._stage1_fns.items()}
 
     def _live_ids(self, candidates: torch.Tensor) -> torch.Tensor:
         """`candidates` with every id that is outside the shard or deleted replaced by -1 (on the device, no synchronisation)"""
@@ -314,7 +320,8 @@ class _LiveShard:
         """`ShardedRetriever.search` over the live pages: the same arguments, rules and return value; a deleted page is never
         returned, and where fewer than `k` live pages exist the tail is (-inf, -1).  `candidates=` lists may name deleted and foreign
         ids (they become -1 before the rerank).  `prefilter` is the shard's own stage 1 (`LiveCorpus.int8_index()`,
-        `LiveResidualCorpus.index`), or a `PackedCorpus` over the same slots (e.g. pooled pages); its scores are masked too.
+        `LiveCorpus.fp4_index()`, `LiveResidualCorpus.index`), any `Int8Index` / `Fp4Index` / `Fp4WideIndex` over the same slots, or a
+        `PackedCorpus` over them (e.g. pooled pages); its scores are masked too, so all `n_candidates` are live pages.
         `filter` covers the slots (`len(filter) == len(self)`, deleted ones included) and is ANDed with the tombstones on both
         routes: the scores of deleted slots are -inf before the filter masks the rest, and a listed id that is deleted is no page to
         the rerank.  `group_by` covers the slots too (`len(group_by) == len(self)`, deleted ones included): a document is scored by
@@ -325,7 +332,7 @@ class _LiveShard:
         if self.device.type == "cuda":     # an injected hook packs host queries itself
             queries = _as_packed(queries, self.device, compact=compact)
         r = self._retriever(shard, world, rank, dist, group, score_fn=self._score, rerank_fn=self._rerank,
-                            **{self._stage1_kw: self._stage1_score}, **self._filter_fns)
+                            **self._stage1_hooks(), **self._filter_fns)
         if group_by is not None:                 # (-inf, -1, -1) is already the rule there
             return r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates, filter=filter,
                             filter_route=filter_route, group_by=group_by)
@@ -337,15 +344,17 @@ class _LiveShard:
 class LiveCorpus(_LiveShard):
     """One mutable resident shard (see the module docstring).  `capacity_rows` and `capacity_docs` are fixed at construction.
 
-    `score_fn`, `rerank_fn`, `int8_score_fn`, `select`, the `filter_*_fn` and `mask_fn` are the hooks of `ShardedRetriever` plus the tombstone mask
-    (`mask_fn(scores, alive) -> scores`); the defaults are the gfx950 kernels.  Host-logic tests inject reference scorers and run on the CPU."""
+    `score_fn`, `rerank_fn`, `int8_score_fn`, `fp4_score_fn`, `fp4_wide_score_fn`, `select`, the `filter_*_fn` and `mask_fn` are the hooks of
+    `ShardedRetriever` plus the tombstone mask (`mask_fn(scores, alive) -> scores`); the defaults are the gfx950 kernels
+    (`fp4_score_fn=fp6_scores` scores e2m3 query tokens against the FP4 pages, as on `ShardedRetriever`).  The scores of all three
+    stage-1 hooks are masked, whichever index is passed as `prefilter=`.  Host-logic tests inject reference scorers and run on the CPU."""
 
     _entry = "msim_live_compact"
-    _stage1_kw = "int8_score_fn"
 
     def __init__(self, capacity_rows: int, capacity_docs: int, device, dtype: torch.dtype = torch.bfloat16, width: int = 128,
                  id_base: int = 0, *, bounce_bytes: Optional[int] = None, score_fn: Callable = maxsim_scores,
-                 rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, select: Callable = topk,
+                 rerank_fn: Callable = rerank_scores, int8_score_fn: Callable = int8_scores, fp4_score_fn: Callable = fp4_scores,
+                 fp4_wide_score_fn: Callable = fp4_wide_scores, select: Callable = topk,
                  mask_fn: Callable = mask_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
                  filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
@@ -355,16 +364,19 @@ class LiveCorpus(_LiveShard):
         self.dtype, self.dim = dtype, int(width)
         self.width = _lib.kernel_width(self.dim, dtype)          # physical row width (zero columns appended, as pack_passages)
         self.blob = torch.zeros((capacity_rows, self.width), dtype=dtype, device=self.device)
-        self._init_slots(capacity_rows, capacity_docs, self.device, id_base, score_fn=score_fn, rerank_fn=rerank_fn, stage1_fn=int8_score_fn,
+        self._init_slots(capacity_rows, capacity_docs, self.device, id_base, score_fn=score_fn, rerank_fn=rerank_fn,
+                         stage1_fns=dict(int8_score_fn=int8_score_fn, fp4_score_fn=fp4_score_fn, fp4_wide_score_fn=fp4_wide_score_fn),
                          select=select, mask_fn=mask_fn, align_fn=align_fn, mine_bounds_fn=mine_bounds_fn, mine_mask_fn=mine_mask_fn,
                          filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
                          group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn)
         self._i8_codes: Optional[torch.Tensor] = None
         self._i8_scales: Optional[torch.Tensor] = None
+        self._f4_codes: Optional[torch.Tensor] = None
+        self._f4_scales: Optional[torch.Tensor] = None
         row_bytes = self.width * self.blob.element_size()
         self.bounce_bytes = min(self._bounce_want(bounce_bytes, row_bytes), capacity_rows * row_bytes) // 16 * 16
         if self.device.type == "cuda":
-            self._ws = self._alloc_compaction(2)                 # one offset plan for the rows, one for the int8 codes
+            self._ws = self._alloc_compaction(3)                 # one offset plan for the rows, one for the int8 codes, one for the FP4 index
             self._off_tmp = torch.zeros((capacity_docs + 1,), dtype=torch.int32, device=self.device)
 
     @classmethod
@@ -379,7 +391,8 @@ class LiveCorpus(_LiveShard):
         return live
 
     def save(self, path, *, chunk_bytes: int = 64 << 20) -> None:
-        """Write the used prefix of this shard -- rows, slot table, tombstones; the int8 index is rebuilt by `int8_index()` -- to `path` (colpali_amd/persist.py)."""
+        """Write the used prefix of this shard -- rows, slot table, tombstones; the int8 index is rebuilt by `int8_index()` and the FP4
+        index by `fp4_index()` after `load`, neither is written -- to `path` (colpali_amd/persist.py)."""
         from . import persist
 
         persist.save(self, path, chunk_bytes=chunk_bytes)
@@ -428,6 +441,8 @@ class LiveCorpus(_LiveShard):
     def _added(self, lo, hi):
         if self._i8_codes is not None:
             self._encode_i8(lo, hi)
+        if self._f4_codes is not None:                   # the new pages own the tail of the rows in use
+            self._encode_f4(self._rows_used - int(self._lengths[lo:hi].sum()), self._rows_used)
 
     def _move_rows(self, rows_bound):
         if self.device.type != "cuda":
@@ -437,6 +452,14 @@ class LiveCorpus(_LiveShard):
             self._off_tmp[:n + 1].copy_(self.offsets[:n + 1])
             self._compact_rows(self._i8_codes, I8_DIM, rows_bound, self._off_tmp, 1)
             self._i8_scales[:n].masked_fill_(self.alive[:n] == 0, 0.0)      # an empty page has scale 0 (msim_i8_encode_docs)
+        if self._f4_codes is not None:                   # ... and on the FP4 code rows and scale bytes, against a fresh copy of them
+            self._off_tmp[:n + 1].copy_(self.offsets[:n + 1])
+            with torch.cuda.device(self.device):
+                rc = _lib.lib().msim_f4_live_compact(_lib.ptr(self._f4_codes), int(self._f4_codes.shape[1]), _lib.ptr(self._f4_scales),
+                                                     rows_bound, _lib.ptr(self._off_tmp), _lib.ptr(self.alive), n,
+                                                     _lib.ptr(self._rows_used_dev[2:]), _lib.ptr(self._ws[2]), _lib.ptr(self._bounce),
+                                                     self.bounce_bytes, _lib.current_stream_handle(self.device))
+            _lib.check(rc, "msim_f4_live_compact")
         self._compact_rows(self.blob, self.width * self.blob.element_size(), rows_bound, self.offsets, 0)
 
     def _compact_rows(self, rows: torch.Tensor, row_bytes: int, bound: int, offsets: torch.Tensor, which: int) -> None:
@@ -473,3 +496,39 @@ class LiveCorpus(_LiveShard):
         n = self.n_slots
         return Int8Index(self._i8_codes[:max(self._rows_used, 1)], self._i8_scales[:n], self.offsets[:n + 1], None,
                          torch.from_numpy(self._lengths[:n].copy()), self.id_base)
+
+    # -------------------------------------------------------------------------------------------------------------- fp4 index
+    def _encode_f4(self, r0: int, r1: int) -> None:
+        """FP4 code rows and scale bytes of blob rows r0 .. r1 - 1, written where they belong (the scale pointer may be unaligned)"""
+        if r1 <= r0:
+            return
+        name = "msim_f4w_encode_rows" if self.width == F4W_DIM else "msim_f4_encode_rows"
+        with torch.cuda.device(self.device):
+            rc = getattr(_lib.lib(), name)(_lib.dtype_code(self.dtype), _lib.ptr(self.blob[r0:]), r1 - r0, self.width,
+                                           _lib.ptr(self._f4_codes[r0:]), _lib.ptr(self._f4_scales[r0:]),
+                                           _lib.current_stream_handle(self.device))
+        _lib.check(rc, name)
+
+    def fp4_index(self) -> Union[Fp4Index, Fp4WideIndex]:
+        """The FP4 token-level index of this corpus -- an `Fp4Index` at width 128, an `Fp4WideIndex` at width 320 -- kept in step
+        from the first call on: `add` encodes the new rows only, `compact` moves the code rows and scale bytes as it moves the
+        embedding rows (msim_f4_live_compact).  The first call allocates 65 / 161 bytes per capacity row and encodes the rows in
+        use; nothing is allocated later.  Its bits equal `Fp4Index.build(self.view())` / `Fp4WideIndex.build(self.view())`.  Like
+        `view()`, the returned object is valid until the next `add` / `compact`."""
+        if self._f4_codes is None:
+            if self.device.type != "cuda":
+                raise RuntimeError("the fp4 index is built by gfx950 kernels: this corpus lives on " + str(self.device))
+            if self.dtype not in (torch.bfloat16, torch.float16) or self.width not in (F4_DIM, F4W_DIM):
+                raise NotImplementedError(f"the fp4 index takes bfloat16 / float16 pages of width {F4_DIM} or {F4W_DIM} "
+                                          f"(got {self.dtype}, width {self.width})")
+            self._f4_codes = torch.zeros((self.capacity_rows, self.width // 2), dtype=torch.uint8, device=self.device)
+            self._f4_scales = torch.zeros((self.capacity_rows,), dtype=torch.uint8, device=self.device)
+            self._encode_f4(0, self._rows_used)
+        n, rows = self.n_slots, max(self._rows_used, 1)
+        cls = Fp4WideIndex if self.width == F4W_DIM else Fp4Index
+        return cls(self._f4_codes[:rows], self._f4_scales[:rows], self.offsets[:n + 1], None, torch.from_numpy(self._lengths[:n].copy()),
+                   self.id_base)
+
+    def drop_fp4_index(self) -> None:
+        """Release the FP4 index (65 / 161 bytes per capacity row); a later `fp4_index()` rebuilds it from the rows."""
+        self._f4_codes = self._f4_scales = None

@@ -83,7 +83,6 @@ class LiveResidualCorpus(_LiveShard):
     compressed rows is handed in: `score_fn=residual_scores`."""
 
     _entry = "msim_res_live_compact"
-    _stage1_kw = "centroid_score_fn"
     _widths = (DIM,)
 
     def __init__(self, centroids: torch.Tensor, cutoffs: torch.Tensor, weights: torch.Tensor, bits: int, capacity_rows: int,
@@ -105,7 +104,8 @@ class LiveResidualCorpus(_LiveShard):
         self.centroids, self.cutoffs, self.weights, self.bits = centroids, cutoffs, weights, bits
         self.codes = torch.zeros((capacity_rows,), dtype=torch.int16, device=dev).view(torch.uint16)
         self.residuals = torch.zeros((capacity_rows, 16 * bits), dtype=torch.uint8, device=dev)
-        self._init_slots(capacity_rows, capacity_docs, dev, id_base, score_fn=score_fn, rerank_fn=rerank_fn, stage1_fn=centroid_score_fn,
+        self._init_slots(capacity_rows, capacity_docs, dev, id_base, score_fn=score_fn, rerank_fn=rerank_fn,
+                         stage1_fns=dict(centroid_score_fn=centroid_score_fn),       # the single stage-1 hook this class masks
                          select=select, mask_fn=mask_fn, align_fn=align_fn, mine_bounds_fn=mine_bounds_fn, mine_mask_fn=mine_mask_fn,
                          filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
                          group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn)

@@ -1009,7 +1009,22 @@ int msim_live_mask_scores(float *scores, int64_t ld, int n_q, int64_t n, const u
  * rows_used_out 8-byte (MSIM_EINVAL); bits other than 2 or 4 and rows_bound > 2^31 - 1 are MSIM_EUNSUPPORTED.  n_slots == 0 returns
  * 0 before it looks at a pointer.
  *
- * Both are asynchronous on `stream`, allocate nothing, never synchronise with the host and are hipGraph-capturable.
+ * msim_f4_live_compact (an addition to ABI 22) is msim_live_compact for the two arrays of a live FP4 index (msim_f4_encode_rows,
+ * msim_f4w_encode_rows): ONE offset plan, with the semantics of msim_live_compact -- the new offsets in place, *rows_used_out, the
+ * status word, nothing at or past rows_bound touched, a second call a no-op -- against which both codes (uint8 [rows_bound,
+ * code_row_bytes], code_row_bytes 64 for width 128 or 160 for width 320) and scales (uint8 [rows_bound], one E8M0 byte per row)
+ * move.  The code rows move as 16-byte pieces, the scale bytes per row.  Both go through `bounce` (16-byte aligned, caller-owned)
+ * in chunks of
+ *     chunk rows = floor(bounce_bytes / (code_row_bytes + 1))      destination rows (at least 1: MSIM_EINVAL otherwise),
+ * the chunk's code rows first and its scale bytes behind them, with the two-launch discipline of msim_live_compact per array.
+ * ceil(rows_bound / chunk rows) must not exceed 65536 (MSIM_EUNSUPPORTED).  workspace:
+ * msim_f4_live_compact_workspace_bytes(n_slots, bounce_bytes) bytes (the size msim_live_compact_workspace_bytes gives), 16-byte
+ * aligned, initialised by the call; its first int32 is the status word of msim_live_compact.  Refused before the device is
+ * touched: a negative size or a null pointer (MSIM_EINVAL); codes, bounce or workspace not 16-byte aligned, off not 4-byte,
+ * rows_used_out not 8-byte aligned (MSIM_EINVAL; scales may have any alignment, as in msim_f4_encode_rows); code_row_bytes other
+ * than 64 or 160 and rows_bound > 2^31 - 1 (MSIM_EUNSUPPORTED).  n_slots == 0 returns 0 before it looks at a pointer.
+ *
+ * All three are asynchronous on `stream`, allocate nothing, never synchronise with the host and are hipGraph-capturable.
  */
 int msim_res_append(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows, const void *C,
                     int K, const float *cutoffs, int bits, uint16_t *codes, uint8_t *residuals, int64_t dst_row0, int64_t dst_rows,
@@ -1017,6 +1032,10 @@ int msim_res_append(int dtype, const void *D, const int32_t *d_off, int n_d, int
 size_t msim_res_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes);
 int msim_res_live_compact(uint16_t *codes, uint8_t *residuals, int bits, int64_t rows_bound, int32_t *off, const uint8_t *alive,
                           int n_slots, int64_t *rows_used_out, void *workspace, void *bounce, int64_t bounce_bytes, void *stream);
+size_t msim_f4_live_compact_workspace_bytes(int n_slots, int64_t bounce_bytes);
+int msim_f4_live_compact(uint8_t *codes, int64_t code_row_bytes /* 64 or 160 */, uint8_t *scales, int64_t rows_bound, int32_t *off,
+                         const uint8_t *alive, int n_slots, int64_t *rows_used_out, void *workspace, void *bounce,
+                         int64_t bounce_bytes, void *stream);
 
 /*
  * HARD-NEGATIVE MINING AND THE PAGE GATHER (mine.hip; additions to ABI 22).  Mining is "mask the score matrix of the full scan, then

@@ -12,6 +12,17 @@ Legs, each timed with device events (compact: one call per fresh set of deletion
     queries of 32 tokens; the mask's estimate is n_q x n x 8 B / 8 TB/s plus one launch.
   * add: add() of 1000 pages of --doc-len rows from a host list against the H2D floor of their bytes at 56 GB/s.
 search and add report the median over --steps and, as *_spread_ms, max - min of those identical calls.
+
+    python tools/bench_live.py --fp4 [--dim 320] [--out FILE] [--summary FILE] [--docs N] [--steps 5] [--bounce-mb 256]
+
+The live FP4 index (LiveCorpus.fp4_index, msim_f4_live_compact) instead of the legs above; every comparison alternates its two
+variants in one loop and reports the median with min and max:
+  * compact() with the index on after deleting 1 %, 10 % and 50 % of the pages, beside compact() with no index followed by
+    Fp4Index.build(live.view()) (Fp4WideIndex at --dim 320): what keeping the same state took before the index was kept in step.
+    The first trial is checked (the index against a build over the view), not timed.
+  * add() of 1000 host pages with the index on and off.
+  * search(prefilter=live.fp4_index(), n_candidates=100) with nothing deleted against ShardedRetriever.search over the same rows
+    and a built index, at 4 and 1000 queries of 32 tokens; the results are compared first.
 """
 from __future__ import annotations
 
@@ -122,9 +133,139 @@ def add_leg(amd, dev, n_pages, doc_len, steps):
             "share_of_floor": floor / ms[len(ms) // 2]}
 
 
+def _stats(ms):
+    ms = sorted(ms)
+    return {"median_ms": ms[len(ms) // 2], "min_ms": ms[0], "max_ms": ms[-1]}
+
+
+def fp4_compact_leg(amd, corpus, cls, frac, bounce_bytes, steps, seed):
+    """compact() with the FP4 index on, beside what the parent commit needs for the same state: compact() with no index, then a
+    build over the view.  Alternating in one loop; every trial starts from a fresh copy of the shard with the same deletions."""
+    n = len(corpus)
+    g = torch.Generator().manual_seed(seed)
+    gone = torch.randperm(n, generator=g)[:max(1, int(n * frac))].sort().values.tolist()
+
+    def fresh(index):
+        live = amd.LiveCorpus.from_packed(corpus, 0, 0, bounce_bytes=bounce_bytes)
+        if index:
+            live.fp4_index()
+        live.delete(gone)
+        return live
+
+    kept, rebuilt = [], []
+    for s in range(steps + 1):                           # trial 0 warms both variants up and is checked, not timed
+        live = fresh(True)
+        ms = once_ms(live.compact)
+        live.check()
+        if s == 0:
+            idx, want = live.fp4_index(), cls.build(live.view())
+            r = live.rows_used
+            assert torch.equal(idx.codes[:r], want.codes[:r]) and torch.equal(idx.scales[:r], want.scales[:r]), "index differs from a build"
+            del idx, want
+        else:
+            kept.append(ms)
+        del live
+        live = fresh(False)
+        ms = once_ms(lambda: (live.compact(), cls.build(live.view())))
+        if s:
+            rebuilt.append(ms)
+        del live
+    return {"deleted": len(gone), "first_deleted": gone[0], "kept_in_step": _stats(kept), "compact_then_build": _stats(rebuilt)}
+
+
+def fp4_add_leg(amd, dev, dim, n_pages, doc_len, steps):
+    """add() of host pages with the FP4 index on and off, alternating"""
+    pages = [torch.empty((doc_len, dim), dtype=torch.bfloat16).normal_() for _ in range(n_pages)]
+    lives = {"index_on": amd.LiveCorpus((steps + 2) * n_pages * doc_len, (steps + 2) * n_pages, dev, width=dim),
+             "index_off": amd.LiveCorpus((steps + 2) * n_pages * doc_len, (steps + 2) * n_pages, dev, width=dim)}
+    lives["index_on"].fp4_index()
+    ms = {name: [] for name in lives}
+    for _ in range(steps + 2):
+        for name, live in lives.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            live.add(pages)
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    out = {name: _stats(v[2:]) for name, v in ms.items()}
+    out["pages"], out["bytes"] = n_pages, n_pages * doc_len * dim * 2
+    return out
+
+
+def fp4_search_leg(amd, corpus, cls, pq, steps):
+    """search(prefilter=live.fp4_index()) with nothing deleted against the frozen two-stage search on the same rows, alternating"""
+    from tools.bench_binary import alternating
+
+    live = amd.LiveCorpus.from_packed(corpus, 0, 0, bounce_bytes=1 << 20)
+    live.fp4_index()
+    ref, ref_idx = amd.ShardedRetriever(corpus), cls.build(corpus)
+    a = live.search(pq, 10, prefilter=live.fp4_index(), n_candidates=100)
+    b = ref.search(pq, 10, prefilter=ref_idx, n_candidates=100)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    return alternating({"live": lambda: live.search(pq, 10, prefilter=live.fp4_index(), n_candidates=100),
+                        "frozen": lambda: ref.search(pq, 10, prefilter=ref_idx, n_candidates=100)}, steps, 1)
+
+
+def _mmm(t):
+    return f"{t['median_ms']:.2f} ms ({t['min_ms']:.2f}–{t['max_ms']:.2f})"
+
+
+def fp4_summary(res):
+    """the markdown section of profiles/live_summary.md for one --fp4 run"""
+    L = [f"`tools/bench_live.py --fp4 --dim {res['dim']}` on {res['docs']} pages × {res['doc_len']} rows × {res['dim']} bf16 "
+         f"({res['shard_bytes'] / 2**30:.1f} GiB, FP4 index {res['index_bytes'] / 2**30:.1f} GiB), bounce {res['bounce_mb']} MiB; "
+         f"medians of {res['steps']} alternating trials with min–max.", "",
+         "| deleted | `compact()` with the index kept in step | `compact()` then a build over the view |", "|---|---|---|"]
+    for f, r in res["compact"].items():
+        L.append(f"| {f} ({r['deleted']}) | {_mmm(r['kept_in_step'])} | {_mmm(r['compact_then_build'])} |")
+    a = res["add"]
+    L += ["", f"`add` of {a['pages']} host pages ({a['bytes'] / 1e6:.0f} MB): {_mmm(a['index_on'])} with the index on, "
+          f"{_mmm(a['index_off'])} with it off.", "",
+          "| queries | `live.search(prefilter=live.fp4_index(), n_candidates=100)` | frozen `ShardedRetriever` + built index |", "|---|---|---|"]
+    for n, r in res["search"].items():
+        L.append(f"| {n} × {res['q_len']} | {_mmm(r['live'])} | {_mmm(r['frozen'])} |")
+    return "\n".join(L) + "\n"
+
+
+def main_fp4(args, amd, dev):
+    """--fp4: the live FP4 index on the headline shard (--dim 320: 50 000 pages by default, the shard every other width-320
+    measurement uses -- tools/bench_fp4.py --dim 320 -- so that the shard, its live copy and both indexes fit beside each other)"""
+    from tools.bench_rerank import make_queries_dim, make_shard_dim
+
+    dim = args.dim
+    docs = args.docs if args.docs is not None else (125_000 if dim == 128 else 50_000)
+    cls = amd.Fp4WideIndex if dim == 320 else amd.Fp4Index
+    mb = int(args.bounce_mb.split(",")[0])
+    t0 = time.perf_counter()
+    res = {"tool": "bench_live", "leg": "fp4", "dim": dim, "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len, "steps": args.steps,
+           "bounce_mb": mb}
+    res["add"] = fp4_add_leg(amd, dev, dim, 1000, args.doc_len, args.steps)
+    torch.cuda.empty_cache()
+    corpus = make_shard_dim(docs, args.doc_len, dim, dev, seed=1234)
+    res["shard_bytes"], res["index_bytes"] = corpus.nbytes, docs * args.doc_len * (dim // 2 + 1)
+    res["search"] = {}
+    for n in (4, 1000):
+        pq = amd.pack_queries(make_queries_dim(n, args.q_len, dim, dev, seed=99), dev, compact=False)
+        res["search"][str(n)] = fp4_search_leg(amd, corpus, cls, pq, args.steps if n <= 8 else 3)
+        torch.cuda.empty_cache()
+    res["compact"] = {f"{int(f * 100)} %": fp4_compact_leg(amd, corpus, cls, f, mb << 20, args.steps, 7) for f in (0.01, 0.10, 0.50)}
+    res["wall_s"] = time.perf_counter() - t0
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    if args.summary:
+        with open(args.summary, "w") as f:
+            f.write(fp4_summary(res))
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--docs", type=int, default=125_000)
+    ap.add_argument("--fp4", action="store_true", help="the live FP4 index legs (compact, add, search) instead of --legs")
+    ap.add_argument("--dim", type=int, default=128, choices=(128, 320), help="with --fp4: the shard's width")
+    ap.add_argument("--summary", default=None, help="with --fp4: write the markdown section for profiles/live_summary.md here")
+    ap.add_argument("--docs", type=int, default=None, help="125 000; with --fp4 --dim 320: 50 000")
     ap.add_argument("--doc-len", type=int, default=1024)
     ap.add_argument("--q-len", type=int, default=32)
     ap.add_argument("--steps", type=int, default=5)
@@ -140,6 +281,9 @@ def main():
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     amd._lib.lib()
+    if args.fp4:
+        return main_fp4(args, amd, dev)
+    args.docs = 125_000 if args.docs is None else args.docs
     legs = set(args.legs.split(","))
     t0 = time.perf_counter()
     res = {"tool": "bench_live", "docs": args.docs, "doc_len": args.doc_len, "hbm_peak_GBps": HBM_PEAK_GBS}
