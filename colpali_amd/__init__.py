@@ -22,6 +22,9 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      row), scored on the block-scaled FP4 MFMA: a token-level first stage for prefilter=
   * fp6_scores                    -- the same Fp4Index scored with e2m3 (FP6) query tokens, at the same MFMA rate: the better
                                      first stage, ShardedRetriever(..., fp4_score_fn=fp6_scores)
+  * fp4_rerank_scores / fp6_rerank_scores -- the list form of the two: the FP4 score of the pages a candidate list names (65 bytes
+                                     per row read, the scan's bits); the middle stage of a three-stage search,
+                                     ShardedRetriever.search(prefilter=fde, n_candidates=m1, refine=fp4_index, n_refine=m2)
   * Fp4WideIndex / fp4_wide_scores -- the FP4 index of a 320-wide (ColQwen3) shard: 160 bytes of e2m1 nibbles and one scale byte
                                      per row, three chained block-scaled MFMAs per 16 rows x 16 tokens: a first stage for prefilter=
   * LiveCorpus.fp4_index / drop_fp4_index -- the FP4 index of a shard that changes (width 128 and 320), kept in step: add encodes
@@ -50,7 +53,8 @@ from .centroid import CentroidIndex, centroid_scores, train_centroids
 from .corpus import PackedCorpus, PackedQueries, block_clamp0, pack_passages, pack_queries
 from . import loss
 from .embed import CorpusWriter, embedding_head
-from .fp4_index import Fp4Index, fp4_quantize_queries, fp4_scores, fp4_scores_from_codes, fp6_quantize_queries, fp6_scores
+from .fp4_index import (Fp4Index, fp4_quantize_queries, fp4_rerank_scores, fp4_scores, fp4_scores_from_codes, fp6_quantize_queries,
+                        fp6_rerank_scores, fp6_scores)
 from .fp4_wide_index import Fp4WideIndex, fp4_wide_quantize_queries, fp4_wide_scores, fp4_wide_scores_from_codes
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .filter import PageFilter
@@ -94,6 +98,8 @@ __all__ = [
     "fp4_quantize_queries",
     "fp6_scores",
     "fp6_quantize_queries",
+    "fp4_rerank_scores",
+    "fp6_rerank_scores",
     "Fp4WideIndex",
     "fp4_wide_scores",
     "fp4_wide_scores_from_codes",

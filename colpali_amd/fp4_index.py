@@ -11,6 +11,12 @@ carries no trained parameter: stage-1 scores of different shards are comparable.
 msim_f6_encode_rows / msim_f4_scores_q6).  The pages stay FP4 and the index is untouched; the instruction takes a format per
 operand and FP6 runs at the FP4 rate, so the first stage loses the query side's quantisation error for nothing stored.  It is the
 function to hand to a retriever: `ShardedRetriever(shard, fp4_score_fn=fp6_scores)`.
+
+`fp4_rerank_scores` / `fp6_rerank_scores` are the LIST form of the two (msim_f4_candidates / msim_f4_candidates_q6,
+colpali_amd/csrc/fp4_candidates.hip): the FP4 score of the pages a candidate list names and of no other, bit for bit what the scan
+gives for the same query and page.  It is the middle stage of a three-stage search -- a cheap stage 1 makes a long list, the FP4
+rows cut it, the exact rerank orders the survivors: `ShardedRetriever.search(prefilter=fde, n_candidates=m1, refine=index,
+n_refine=m2)`.
 """
 from __future__ import annotations
 
@@ -19,7 +25,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .corpus import PackedCorpus, PackedQueries, _as_packed
+from .corpus import PackedCorpus, PackedQueries, _as_packed, _rerank_args
 from .scoring import _require_gpu
 
 DIM = 128
@@ -188,3 +194,53 @@ def fp6_scores(queries, index: Fp4Index, out: Optional[torch.Tensor] = None) -> 
     """`fp4_scores` with the query tokens coded as e2m3 (FP6) against the same FP4 pages: a better first stage from the same index,
     bit for bit reproducible in the same way.  The stage-1 hook of a retriever: `ShardedRetriever(shard, fp4_score_fn=fp6_scores)`."""
     return fp4_scores(queries, index, out, query_code="e2m3")
+
+
+MAX_RERANK_TOKENS = 128                            # the longest query of the list form (eight 16-token tiles in registers)
+
+
+def fp4_rerank_scores(queries, index: Fp4Index, candidates: torch.Tensor, *, query_code: str = "e2m1",
+                      out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The FP4 score of listed candidates (include/maxsim.h: msim_f4_candidates, msim_f4_candidates_q6): (scores fp32 [n_q, m], ids
+    int64 [n_q, m]).
+
+    Entry (q, j) is scored against page candidates[q, j] (a GLOBAL id, int64 [n_q, m] on the index's device) of `index`; its bits
+    are those of `fp4_scores(queries, index, query_code=query_code)[q, candidates[q, j] - index.id_base]`, whatever else the list
+    holds.  An id of -1 or outside [id_base, id_base + len(index)) comes back as (-inf, -1) and reads nothing; a page of 0 rows
+    scores -inf; an id listed twice is scored twice.  Only the listed pages are read: 65 bytes per row.  Lists are taken as
+    `rerank_scores` takes them (a broadcast row is copied).  Queries are packed and coded as `fp4_scores` does; more than 128
+    tokens in a query, or an index that is not an `Fp4Index`, raises NotImplementedError.  `out`: the fp32 [n_q, m] score tensor.
+    Asynchronous on torch's current stream; given a `PackedQueries` it never synchronises with the host, never reads the list on
+    the host, and is hipGraph-capturable (its allocations are torch tensors made before the library call; the list may be
+    rewritten in place between replays).  It is the `fp4_rerank_fn` hook of `ShardedRetriever` (`search(refine=)`)."""
+    width = _check_query_code(query_code)
+    if not isinstance(index, Fp4Index):
+        raise NotImplementedError(f"the fp4 rerank takes an Fp4Index of a 128-wide shard (got {type(index).__name__})")
+    dev = _require_gpu(index.device)
+    q = _as_packed(queries, dev, layout="flat")
+    _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
+    if q.device != dev:
+        raise ValueError("queries and index live on different devices")
+    lens = q.lengths
+    max_q = int(lens.max()) if lens.numel() else 0
+    if max_q > MAX_RERANK_TOKENS:
+        raise NotImplementedError(f"the fp4 rerank takes queries of at most {MAX_RERANK_TOKENS} tokens (got {max_q})")
+    n_q, n = len(q), len(index)
+    codes, scales = _quantize_packed(q, query_code)
+    assert int(codes.shape[1]) == width
+    name = "msim_f4_candidates_q6" if query_code == "e2m3" else "msim_f4_candidates"
+    with torch.cuda.device(dev):
+        candidates, m, ld_cand, out, ids, _ = _rerank_args(n_q, dev, candidates, out, lambda m: 0)
+        rc = getattr(_lib.lib(), name)(_lib.ptr(codes), _lib.ptr(scales), _lib.ptr(q.offsets), n_q, int(codes.shape[0]), max_q,
+                                       _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets), _lib.ptr(index.clamp0),
+                                       n, int(index.codes.shape[0]), DIM, _lib.ptr(candidates), m, ld_cand, int(index.id_base),
+                                       _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.current_stream_handle(dev))
+    _lib.check(rc, name)
+    return out, ids
+
+
+def fp6_rerank_scores(queries, index: Fp4Index, candidates: torch.Tensor, *, out: Optional[torch.Tensor] = None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`fp4_rerank_scores` with the query tokens coded as e2m3 (FP6): the bits of `fp6_scores` at the listed pages.  The refine hook
+    to hand to a retriever beside `fp4_score_fn=fp6_scores`: `ShardedRetriever(shard, fp4_rerank_fn=fp6_rerank_scores)`."""
+    return fp4_rerank_scores(queries, index, candidates, query_code="e2m3", out=out)

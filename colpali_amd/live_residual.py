@@ -33,6 +33,7 @@ from . import _lib
 from .centroid import CentroidIndex, _check_centroids, centroid_scores
 from .corpus import _staging, host_list_image
 from .filter import filter_ids, filter_list, filter_mask
+from .fp4_index import fp4_rerank_scores
 from .group import group_reduce, group_select
 from .live import _LiveShard, mask_scores
 from .mine import mine_bounds, mine_mask
@@ -76,7 +77,7 @@ class LiveResidualCorpus(_LiveShard):
     are fixed at construction, and everything a later call needs -- the ingest buffer, the bounce buffer, the workspace -- is
     allocated there: no later call allocates in the library.
 
-    `score_fn`, `rerank_fn`, `centroid_score_fn`, `align_fn`, `select`, the `filter_*_fn`, `group_*_fn`, `mine_*_fn` and `mask_fn` are
+    `score_fn`, `rerank_fn`, `centroid_score_fn`, `fp4_rerank_fn`, `align_fn`, `select`, the `filter_*_fn`, `group_*_fn`, `mine_*_fn` and `mask_fn` are
     the hooks of `ShardedRetriever` plus the tombstone mask; `encode_fn(live, rows, offsets, n_pages, max_rows, dst_row0)` and
     `compact_fn(live, rows_bound)` write the arrays.  The defaults are the gfx950 kernels; host-logic tests inject reference
     functions and run on the CPU.  As over a `ResidualCorpus`, the routes that scan the shard are refused unless a scorer of the
@@ -92,7 +93,7 @@ class LiveResidualCorpus(_LiveShard):
                  mine_bounds_fn: Callable = mine_bounds, mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask,
                  filter_list_fn: Callable = filter_list, filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce,
                  group_select_fn: Callable = group_select, encode_fn: Callable = append_encode, compact_fn: Callable = compact_arrays,
-                 align_fn: Callable = residual_align):
+                 align_fn: Callable = residual_align, fp4_rerank_fn: Callable = fp4_rerank_scores):
         bits = _check_bits(bits)
         _check_centroids(centroids)
         _check_codec(cutoffs, weights, bits)
@@ -108,7 +109,7 @@ class LiveResidualCorpus(_LiveShard):
                          stage1_fns=dict(centroid_score_fn=centroid_score_fn),       # the single stage-1 hook this class masks
                          select=select, mask_fn=mask_fn, align_fn=align_fn, mine_bounds_fn=mine_bounds_fn, mine_mask_fn=mine_mask_fn,
                          filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
-                         group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn)
+                         group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn, fp4_rerank_fn=fp4_rerank_fn)
         self._encode_fn, self._compact_fn = encode_fn, compact_fn
         self.ingest_rows = min(DEFAULT_INGEST_ROWS if ingest_rows is None else int(ingest_rows), capacity_rows)
         if self.ingest_rows < 1:

@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from .align import Alignment, align
 from .binary_index import BinaryIndex, binary_scores
-from .fp4_index import Fp4Index, fp4_scores, fp6_scores
+from .fp4_index import Fp4Index, fp4_rerank_scores, fp4_scores, fp6_rerank_scores, fp6_scores
 from .fp4_wide_index import Fp4WideIndex, fp4_wide_scores
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .fde import FdeIndex, fde_scores
@@ -210,7 +210,7 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
-            fp4_scores, fp6_scores, fp4_wide_scores, align, residual_align)
+            fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, align, residual_align)
 
 
 class ShardedRetriever:
@@ -230,7 +230,8 @@ class ShardedRetriever:
                  rerank_fn: Callable = rerank_scores, fde_score_fn: Callable = fde_scores,
                  int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, binary_score_fn: Callable = binary_scores, fp4_score_fn: Callable = fp4_scores, fp4_wide_score_fn: Callable = fp4_wide_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
-                 filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select):
+                 filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select,
+                 fp4_rerank_fn: Callable = fp4_rerank_scores):
         if isinstance(shard, ResidualCorpus) and rerank_fn is rerank_scores:
             rerank_fn = residual_rerank_scores
         self.shard, self.world, self.rank = shard, world, rank
@@ -245,6 +246,7 @@ class ShardedRetriever:
         self._binary_score = binary_score_fn  # (queries, BinaryIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<BinaryIndex>
         self._fp4_score = fp4_score_fn    # (queries, Fp4Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4Index>
         self._fp4_wide_score = fp4_wide_score_fn  # (queries, Fp4WideIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4WideIndex>
+        self._fp4_rerank = fp4_rerank_fn  # (queries, Fp4Index, candidates) -> (scores [n_q, m], ids [n_q, m]): the refine stage of refine=
         self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
         self._mine_bounds = mine_bounds_fn    # (scores, csr, id_base, local=, alive=) -> fp32 [n_q]: the best in-shard positive of each query
         self._mine_mask = mine_mask_fn        # (scores, csr, id_base, bounds, max_ratio, alive) -> scores, -inf where ineligible
@@ -257,7 +259,8 @@ class ShardedRetriever:
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None,
                prefilter=None, n_candidates: Optional[int] = None, filter: Optional[PageFilter] = None,
-               filter_route: str = "auto", group_by: Optional[PageGroups] = None):
+               filter_route: str = "auto", group_by: Optional[PageGroups] = None, refine: Optional[Fp4Index] = None,
+               n_refine: Optional[int] = None):
         """queries (replicated on every rank): a `PackedQueries`, a list of [len_i, 128] tensors, or a [n_q, Lq, 128] tensor.
         A host list is packed into the flat layout (ragged lengths, zero rows dropped on the way into the staging buffer).  A dense
         DEVICE tensor is scored as it stands unless `compact=True`: dropping its zero padding rows needs the per-query counts on the
@@ -324,9 +327,23 @@ class ShardedRetriever:
         globally as well, and there are fewer than k of those.  Its best entry therefore reaches the merge, which deduplicates
         documents that several ranks sent.  The answer does not depend on the number of shards, also where a document's pages
         straddle a boundary.  `search` calls `group_by.prepare()` on first use (one host synchronisation); with prepared groups
-        and a `PackedQueries` the call is hipGraph-capturable."""
+        and a `PackedQueries` the call is hipGraph-capturable.
+
+        Three-stage search: `refine` -- an `Fp4Index` over the shard's pages (same count, same id_base, same device; ValueError
+        otherwise) -- puts the FP4 rows between a cheap first stage and the exact rerank.  It needs exactly one of `candidates=` /
+        `prefilter=` (ValueError otherwise) and `n_refine` >= 1, at most `n_candidates` with `prefilter=` (ValueError otherwise;
+        `n_refine` without `refine` is a ValueError too).  Once the candidate list exists -- from stage 1, filtered, or the caller's
+        list behind `filter_ids` -- the refine hook (`fp4_rerank_fn`, default `fp4_rerank_scores`; `fp6_rerank_scores` codes the query
+        tokens as e2m3) scores the listed pages of this shard from their 65-byte FP4 rows, and the top `n_refine` of those scores
+        are kept through the same all-gather and merge as every other list: the refined list is identical on every rank and does
+        not depend on the number of shards.  An entry the refine stage scored -inf (no page, an empty page) becomes -1 and is not
+        reranked.  The exact rerank then runs on the `n_refine` survivors, unchanged, so every returned score is still the exact
+        one.  With `group_by=`, `n_refine` counts PAGES and the 4096-entry limit applies to `n_refine`, not to `n_candidates`.  A
+        `ResidualCorpus` shard works as it does with `prefilter=`: the last stage is its own rerank.  An `Fp4WideIndex`, or a
+        320-wide shard, raises NotImplementedError.  With `refine=None` every route runs exactly as it did."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
+        n_refine = self._check_refine(refine, n_refine, candidates, prefilter, n_candidates)
         if self._res_refuses:
             if filter is not None or group_by is not None:
                 self._no_rows("search(filter=) and search(group_by=)")
@@ -334,11 +351,13 @@ class ShardedRetriever:
                 self._no_rows("the full scan")
         groups = self._check_groups(group_by, k)
         if filter is not None:
-            return self._search_filtered(queries, k, compact, candidates, prefilter, n_candidates, filter, filter_route, groups)
+            return self._search_filtered(queries, k, compact, candidates, prefilter, n_candidates, filter, filter_route, groups,
+                                         refine, n_refine)
         if filter_route != "auto":
             raise ValueError("filter_route goes with filter=")
         if candidates is not None or prefilter is not None:
-            return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, groups=groups)
+            return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, groups=groups, refine=refine,
+                                           n_refine=n_refine)
         scores = self._score(self._pack(queries, compact, self._score), self.shard)
         if groups is not None:
             return self._group_scan(scores, k, groups)
@@ -365,6 +384,25 @@ class ShardedRetriever:
                              f"it must cover the same {noun}")
         if lives is not None and x.device != shard.device:
             raise ValueError(f"the {lives} on {x.device}, the shard on {shard.device}")
+
+    def _check_refine(self, refine, n_refine, candidates, prefilter, n_candidates) -> Optional[int]:
+        """the rules of `search(refine=, n_refine=)`; returns n_refine as an int (None without refine)"""
+        if refine is None:
+            if n_refine is not None:
+                raise ValueError("n_refine goes with refine=")
+            return None
+        if isinstance(refine, Fp4WideIndex) or getattr(self.shard, "width", 128) != 128:
+            raise NotImplementedError("refine takes an Fp4Index of a 128-wide shard")
+        if not isinstance(refine, Fp4Index):
+            raise ValueError("refine must be an Fp4Index")
+        if (candidates is None) == (prefilter is None):
+            raise ValueError("refine= cuts a candidate list: it needs exactly one of candidates= / prefilter=")
+        self._check_covers("refine covers", refine, lives="refine index lives")
+        if n_refine is None or int(n_refine) < 1:
+            raise ValueError("refine= needs n_refine >= 1")
+        if prefilter is not None and n_candidates is not None and int(n_refine) > int(n_candidates):
+            raise ValueError(f"n_refine={int(n_refine)} exceeds the list of n_candidates={int(n_candidates)} pages it is cut from")
+        return int(n_refine)
 
     def _no_rows(self, what: str):
         raise NotImplementedError(f"{what} over a ResidualCorpus: the shard keeps no full-precision rows and only candidate lists are "
@@ -471,7 +509,8 @@ class ShardedRetriever:
             return int(queries.shape[1]) <= 128
         return all(int(q.shape[0]) <= 128 for q in queries)
 
-    def _search_filtered(self, queries, k, compact, candidates, prefilter, n_candidates, flt, route, groups=None):
+    def _search_filtered(self, queries, k, compact, candidates, prefilter, n_candidates, flt, route, groups=None, refine=None,
+                         n_refine=None):
         if route not in ("auto", "mask", "list"):
             raise ValueError(f"filter_route={route!r}: 'auto', 'mask' or 'list'")
         if not isinstance(flt, PageFilter):
@@ -483,8 +522,9 @@ class ShardedRetriever:
             if route == "list":
                 raise ValueError("filter_route='list' lists the allowed pages itself: it does not go with candidates= / prefilter=")
             if groups is not None:
-                return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt, groups)
-            top_s, top_i = self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt)
+                return self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt, groups, refine, n_refine)
+            top_s, top_i = self._search_candidates(queries, k, compact, candidates, prefilter, n_candidates, flt, refine=refine,
+                                                   n_refine=n_refine)
         else:
             queries = self._pack(queries, compact, self._score)
             n_q = len(queries)
@@ -521,11 +561,12 @@ class ShardedRetriever:
         if flt.rows is not None and flt.rows != n_q:
             raise ValueError(f"a per-query filter of {flt.rows} rows was given for {n_q} queries")
 
-    def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates, flt=None, groups=None):
+    def _search_candidates(self, queries, k, compact, candidates, prefilter, n_candidates, flt=None, groups=None, refine=None,
+                           n_refine=None):
         if candidates is not None and prefilter is not None:
             raise ValueError("pass either candidates= or prefilter=, not both")
         if groups is not None:
-            m = int(n_candidates) if prefilter is not None and n_candidates is not None else (
+            m = int(n_refine) if refine is not None else int(n_candidates) if prefilter is not None and n_candidates is not None else (
                 int(candidates.shape[-1]) if isinstance(candidates, torch.Tensor) and candidates.dim() == 2 else 0)
             if m > SELECT_MAX_M:
                 raise NotImplementedError(f"group_by over a list of {m} pages: group_select takes at most {SELECT_MAX_M}")
@@ -540,7 +581,8 @@ class ShardedRetriever:
                   else self._binary_score if isinstance(prefilter, BinaryIndex)
                   else self._fp4_score if isinstance(prefilter, Fp4Index)
                   else self._fp4_wide_score if isinstance(prefilter, Fp4WideIndex) else self._score)
-        queries = self._pack(queries, compact, self._rerank, *((stage1,) if prefilter is not None else ()))
+        queries = self._pack(queries, compact, self._rerank, *((stage1,) if prefilter is not None else ()),
+                             *((self._fp4_rerank,) if refine is not None else ()))
         if flt is not None:
             self._check_filter_rows(flt, len(queries))
         if prefilter is not None:
@@ -555,7 +597,10 @@ class ShardedRetriever:
             if mine is candidates:                                       # filter_ids writes in place: never into the caller's list
                 mine = mine.clone(memory_format=torch.contiguous_format)
             candidates = self._filter_ids(mine, flt, None)
-        scores, ids = self._rerank(queries, self.shard, candidates)      # stage 2: exact, this shard's candidates only
+        if refine is not None:                                           # the FP4 rows cut the list: this shard's entries, then the merge
+            fine_s, fine_i = self._fp4_rerank(queries, refine, candidates)
+            candidates = _no_page(*self._topk(fine_s, n_refine, 0, fine_i))[1]
+        scores, ids = self._rerank(queries, self.shard, candidates)      # the last stage: exact, this shard's candidates only
         if groups is not None:
             return self._group_list(scores, ids, k, groups)
         return self._topk(scores, k, 0, ids)

@@ -3,6 +3,7 @@
 
     python tools/bench_fp4.py [--out FILE] [--summary profiles/fp4_summary.md] [--steps 10 --warmup 3] [--docs 125000 --doc-len 1024]
                               [--legs build,stage1,pooled,two_stage,recall]
+    python tools/bench_fp4.py --legs refine --summary profiles/fp4_summary.md      (rewrites only its own section of the summary)
     python tools/bench_fp4.py --dim 320 [--out FILE] [--summary profiles/fp4_wide_summary.md] [--legs build,stage1,two_stage,recall]
 
 --dim 320 measures the 320-wide index (msim_f4w_*, colpali_amd.Fp4WideIndex) on the shard of tools/bench_rerank.py --dim 320
@@ -21,6 +22,13 @@ figure is the median with its range:
   * recall: recall@10 against the exact search on the planted 10 000-page set of tools/bench_fde.py:planted_pages, for the FP4
     index of the full and the pooled pages, scored with e2m1 and with e2m3 query tokens, beside the Int8Index and the BinaryIndex
     of the full pages.
+  * refine (not in the default list): the list form and the three-stage search.  `fp4_rerank_scores` and `fp6_rerank_scores` at
+    1000 x 32 x m in {1000, 4000} and 4 x 32 x m = 4000 on uniform and clustered lists (the generators of tools/bench_rerank.py),
+    beside `rerank_scores` on the same lists and `fp4_scores` of the whole shard plus a gather; bound = n_q m rows 65 B / 8 TB/s.
+    The cascade search(prefilter=FdeIndex | CentroidIndex, n_candidates=m1, refine=Fp4Index, n_refine=100) at m1 in {1000, 4000}
+    beside the same FDE search without refine and search(prefilter=Fp4Index, n_candidates=100), all in one loop (m1 = 4000 is above
+    the top-k's 1024 per row: there the first-stage scores go through torch.topk and the list through candidates=).  Recall@10 of the
+    same configurations on the planted set, with e2m1 and e2m3 query tokens.
 """
 from __future__ import annotations
 
@@ -105,6 +113,135 @@ def recall_leg(amd, dev, n_docs, k=10):
     return out
 
 
+# ------------------------------------------------------------------------------------------------- the list form and the cascade
+REFINE_M1 = (1000, 4000)
+N_REFINE = 100
+REFINE_MARK = "## FP4 candidate rerank and three-stage search"
+
+
+def rerank_legs(amd, corpus, f4idx, q_len, doc_len, dev, steps):
+    """the list form alone: per (n_q, m, list distribution) the four variants alternating in one loop"""
+    from tools.bench_rerank import clustered_candidates, uniform_candidates
+
+    n = len(corpus)
+    out = {}
+    for n_q, m in ((1000, 1000), (1000, 4000), (4, 4000)):
+        pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
+        full = torch.empty((n_q, n), dtype=torch.float32, device=dev)
+        for dist_name, cand in (("uniform", uniform_candidates(n_q, n, m, dev, seed=7)),
+                                ("clustered", clustered_candidates(n_q, n, m, dev, seed=7, pool=min(2 * m, n)))):
+            s4, s6 = (torch.empty((n_q, m), dtype=torch.float32, device=dev) for _ in range(2))
+            leg = alternating({"fp4_rerank": lambda: amd.fp4_rerank_scores(pq, f4idx, cand, out=s4),
+                               "fp6_rerank": lambda: amd.fp6_rerank_scores(pq, f4idx, cand, out=s6),
+                               "exact_rerank": lambda: amd.rerank(pq, corpus, cand),
+                               "fp4_scan_gather": lambda: torch.gather(amd.fp4_scores(pq, f4idx, out=full), 1, cand)},
+                              steps if n_q == 4 else max(3, steps // 2), 1)
+            leg["bound_ms"] = n_q * m * doc_len * 65 / (HBM_PEAK_GBS * 1e9) * 1e3
+            for k in ("fp4", "fp6"):
+                leg[f"{k}_share_of_bound"] = leg["bound_ms"] / leg[f"{k}_rerank"]["median_ms"]
+            leg["distinct_pages"] = int(torch.unique(cand).numel())
+            leg["bits_equal_scan_gather"] = bool(torch.equal(s4.view(torch.int32), torch.gather(full, 1, cand).view(torch.int32)))
+            out[f"{n_q}x{q_len}_m{m}_{dist_name}"] = leg
+        del full
+    return out
+
+
+TOPK_MAX_K = 1024              # msim_topk_f32 selects at most 1024 per row: the longest list search(prefilter=) can make
+
+
+def staged_search(amd, r, pq, score_fn, index, m1, k=10, **refine):
+    """search behind a first stage of m1 pages: `prefilter=index, n_candidates=m1` where the top-k takes m1; above its limit of 1024
+    the same first-stage scores go through torch.topk and the list through `candidates=` (the order inside the list, and which of
+    two equal scores makes it, may differ from `topk`'s; the stages behind it are the same)"""
+    if m1 <= TOPK_MAX_K:
+        return r.search(pq, k=k, prefilter=index, n_candidates=m1, **refine)
+    cand = torch.topk(score_fn(pq, index), m1, dim=1).indices + index.id_base
+    return r.search(pq, k=k, candidates=cand, **refine)
+
+
+def cascade_leg(amd, corpus, f4idx, q_len, dev, steps):
+    pq = amd.pack_queries(make_queries(1000, q_len, dev, seed=99), dev, compact=False)
+    fde, cen = amd.FdeIndex.build(corpus), amd.CentroidIndex.build(corpus)
+    r = amd.ShardedRetriever(corpus)
+    refine = dict(refine=f4idx, n_refine=N_REFINE)
+    variants = {}
+    for m1 in REFINE_M1:
+        variants[f"fde_refine_m{m1}"] = lambda m1=m1: staged_search(amd, r, pq, amd.fde_scores, fde, m1, **refine)
+        variants[f"centroid_refine_m{m1}"] = lambda m1=m1: staged_search(amd, r, pq, amd.centroid_scores, cen, m1, **refine)
+        variants[f"fde_only_m{m1}"] = lambda m1=m1: staged_search(amd, r, pq, amd.fde_scores, fde, m1)
+    variants["fp4_m100"] = lambda: r.search(pq, k=10, prefilter=f4idx, n_candidates=100)
+    out = alternating(variants, max(3, steps // 2), 1)
+    out["n_queries"], out["n_refine"] = 1000, N_REFINE
+    return out
+
+
+def refine_recall_leg(amd, dev, n_docs, k=10):
+    pages, q = planted_pages(dev, n_docs=n_docs)
+    full = amd.pack_passages(pages, dev, batch_size=None)
+    del pages
+    pq = amd.pack_queries(q, dev, compact=False)
+    r4 = amd.ShardedRetriever(full)
+    r6 = amd.ShardedRetriever(full, fp4_score_fn=amd.fp6_scores, fp4_rerank_fn=amd.fp6_rerank_scores)
+    exact = r4.search(pq, k=k)[1].tolist()
+    f4idx, fde, cen = amd.Fp4Index.build(full), amd.FdeIndex.build(full), amd.CentroidIndex.build(full)
+
+    def hits(got):
+        return sum(len(set(a) & set(b)) for a, b in zip(exact, got[1].tolist())) / (len(pq) * k)
+
+    out = {"docs": n_docs, "queries": len(pq), "k": k, "n_refine": N_REFINE}
+    for code, r in (("e2m1", r4), ("e2m3", r6)):
+        for m1 in REFINE_M1:
+            out[f"fde_refine_m{m1}_{code}"] = hits(staged_search(amd, r, pq, amd.fde_scores, fde, m1, k, refine=f4idx, n_refine=N_REFINE))
+            out[f"centroid_refine_m{m1}_{code}"] = hits(staged_search(amd, r, pq, amd.centroid_scores, cen, m1, k, refine=f4idx,
+                                                                    n_refine=N_REFINE))
+        out[f"fp4_m100_{code}"] = hits(r.search(pq, k=k, prefilter=f4idx, n_candidates=100))
+    for m1 in REFINE_M1:
+        out[f"fde_only_m{m1}"] = hits(staged_search(amd, r4, pq, amd.fde_scores, fde, m1, k))
+        out[f"centroid_only_m{m1}"] = hits(staged_search(amd, r4, pq, amd.centroid_scores, cen, m1, k))
+    return out
+
+
+def refine_section(res):
+    """the summary's section of the refine leg: measured figures only"""
+    f = res["refine"]
+    L = [REFINE_MARK, "",
+         f"`tools/bench_fp4.py --legs refine --steps {res['steps']}` on the headline shard ({res['docs']} pages × {res['doc_len']} rows).  "
+         "The variants of a row alternate call by call in one timed loop; median, with the range in brackets.  The bound is n_q × m × "
+         "rows × 65 B at 8 TB/s (every listed page read once per entry: no page shared between queries); a share is bound / measured.  "
+         "`distinct pages` says how far that holds: where the lists of a batch name each page several times, the repeats come from the "
+         "caches, and `rerank_scores` reads a page once for all the queries that list it.", "",
+         "| shape, list | `fp4_rerank_scores` (share) | `fp6_rerank_scores` (share) | `rerank_scores` (exact) | `fp4_scores` + gather | bound | "
+         "distinct pages | bits = scan |", "|---|---|---|---|---|---|---|---|"]
+    for name, leg in f["rerank"].items():
+        L += [f"| {name.replace('_', ' ')} | {_ms(leg['fp4_rerank'])} ({leg['fp4_share_of_bound']:.2f}) | {_ms(leg['fp6_rerank'])} "
+              f"({leg['fp6_share_of_bound']:.2f}) | {_ms(leg['exact_rerank'])} | {_ms(leg['fp4_scan_gather'])} | {leg['bound_ms']:.2f} ms | "
+              f"{leg['distinct_pages']} | {'yes' if leg['bits_equal_scan_gather'] else 'NO'} |"]
+    c, rc = f["cascade"], f["recall"]
+    L += ["", f"Search at 1000 × 32, k = 10, n_refine = {c['n_refine']}, all alternating in one loop; recall@10 against the exact search on the "
+          f"planted {rc['docs']}-page set ({rc['queries']} queries), e2m1 / e2m3 query tokens in the FP4 stages:", "",
+          f"A first stage of more than {TOPK_MAX_K} pages cannot come from `prefilter=` (the top-k selects at most {TOPK_MAX_K} per row): "
+         "at n_candidates = 4000 the same first-stage scores go through `torch.topk` and the list through `candidates=`.", "",
+         "| search | time | recall@10 (e2m1 / e2m3) |", "|---|---|---|"]
+    for m1 in REFINE_M1:
+        for first, name in (("fde", "FdeIndex"), ("centroid", "CentroidIndex")):
+            key = f"{first}_refine_m{m1}"
+            L += [f"| `prefilter={name}, n_candidates={m1}, refine=Fp4Index, n_refine={c['n_refine']}` | {_ms(c[key])} | "
+                  f"{rc[key + '_e2m1']:.3f} / {rc[key + '_e2m3']:.3f} |"]
+        L += [f"| `prefilter=FdeIndex, n_candidates={m1}` (no refine) | {_ms(c[f'fde_only_m{m1}'])} | {rc[f'fde_only_m{m1}']:.3f} "
+              f"(CentroidIndex alone: {rc[f'centroid_only_m{m1}']:.3f}) |"]
+    L += [f"| `prefilter=Fp4Index, n_candidates=100` | {_ms(c['fp4_m100'])} | {rc['fp4_m100_e2m1']:.3f} / {rc['fp4_m100_e2m3']:.3f} |", ""]
+    return L
+
+
+def splice_refine_section(text, section):
+    """`text` (an earlier summary) with its refine section replaced by `section` (appended when it has none)"""
+    at = text.find(REFINE_MARK)
+    if at >= 0:
+        nxt = text.find("\n## ", at + 1)
+        text = text[:at] + (text[nxt + 1:] if nxt >= 0 else "")
+    return text.rstrip("\n") + "\n\n" + "\n".join(section)
+
+
 def _ms(v):
     return f"{v['median_ms']:.2f} ms ({v['min_ms']:.2f}–{v['max_ms']:.2f})"
 
@@ -164,6 +301,8 @@ def summary(res):
             L += [f"| {name} | {r['bytes'][key] / 1e6:.0f} MB | " + " | ".join(f"{r[key][str(m)]:.3f}" for m in MS) + " |"]
     else:
         L += ["* Recall: not measured in this run."]
+    if "refine" in res:
+        L += [""] + refine_section(res)
     return "\n".join(L) + "\n"
 
 
@@ -355,6 +494,18 @@ def main():
     t0 = time.perf_counter()
     res = {"tool": "bench_fp4", "docs": args.docs, "doc_len": args.doc_len, "q_len": args.q_len, "steps": args.steps,
            "warmup": args.warmup, "hbm_peak_GBps": HBM_PEAK_GBS, "fp4_peak_TFLOPs": FP4_PEAK_TFLOPS}
+    if "refine" in legs:
+        corpus = make_shard(args.docs, args.doc_len, dev, seed=1234)
+        f4idx = amd.Fp4Index.build(corpus)
+        _progress("shard and index", t0)
+        res["refine"] = {"rerank": rerank_legs(amd, corpus, f4idx, args.q_len, args.doc_len, dev, args.steps)}
+        _progress("refine: list form", t0)
+        res["refine"]["cascade"] = cascade_leg(amd, corpus, f4idx, args.q_len, dev, args.steps)
+        _progress("refine: cascade", t0)
+        del corpus, f4idx
+        torch.cuda.empty_cache()
+        res["refine"]["recall"] = refine_recall_leg(amd, dev, args.recall_docs)
+        _progress("refine: recall", t0)
     if legs & {"build", "stage1", "two_stage"}:
         corpus = make_shard(args.docs, args.doc_len, dev, seed=1234)
         f4idx, i8idx, bidx = amd.Fp4Index.build(corpus), amd.Int8Index.build(corpus), amd.BinaryIndex.build(corpus)
@@ -400,8 +551,12 @@ def main():
         with open(args.out, "w") as f:
             f.write(line + "\n")
     if args.summary:
+        text = summary(res)
+        if legs == {"refine"} and os.path.exists(args.summary):            # the other legs' recorded figures stay
+            with open(args.summary) as f:
+                text = splice_refine_section(f.read(), refine_section(res))
         with open(args.summary, "w") as f:
-            f.write(summary(res))
+            f.write(text)
     print(line)
 
 
