@@ -5,7 +5,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      (colpali_engine/utils/processing_utils.py:132-187)
   * ColbertPairwiseCELoss (+ ColbertLoss, ColbertSigmoidLoss, ColbertModule)
                                   <- colpali_engine/loss/late_interaction_losses.py:255-313 (:110-164, :401-465, :6-107)
-  * ShardedRetriever / topk       -- sharded-corpus top-k with an RCCL all-gather merge (no reference equivalent)
+  * ShardedRetriever / topk       -- sharded-corpus top-k with an RCCL all-gather merge (no reference equivalent); lists of up to
+                                     TOPK_MAX_K = 8192 entries per row, in one order (score desc, id asc) at every length
   * rerank                        -- exact MaxSim of per-query candidate lists; two-stage search (ShardedRetriever.search(prefilter=))
   * align / Alignment             -- which page row matched each query token of a search hit, and its similarity maps
   * mine_hard_negatives / gather_pages -- hard negatives by the model's own MaxSim score over the resident corpus, and the padded
@@ -70,8 +71,8 @@ from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
 from .patch import patch_colpali_engine, unpatch_colpali_engine
 from .residual import (ResidualCorpus, residual_align, residual_gather_pages, residual_rerank_scores, residual_scores,
                        train_residual_codec)
-from .retrieval import (ExactMaxSimIndex, ResidualMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered, rerank, shard_range,
-                        shard_topk, topk)
+from .retrieval import (TOPK_MAX_K, ExactMaxSimIndex, ResidualMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered,
+                        rerank, shard_range, shard_topk, topk)
 from .scoring import (get_similarity_maps_from_embeddings, get_torch_device, maxsim_scores, score_multi_vector,
                       score_single_vector, similarity_matrix)
 
@@ -141,6 +142,7 @@ __all__ = [
     "shard_range",
     "shard_topk",
     "topk",
+    "TOPK_MAX_K",
     "block_clamp0",
     "get_torch_device",
     "maxsim_scores",

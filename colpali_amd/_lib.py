@@ -285,6 +285,10 @@ def lib() -> ctypes.CDLL:
     L.msim_topk_workspace_bytes.restype = sz
     L.msim_topk_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]
     L.msim_topk_f32.restype = i32
+    L.msim_topk_deep_workspace_bytes.argtypes = [i32, i64, i32]
+    L.msim_topk_deep_workspace_bytes.restype = sz
+    L.msim_topk_deep_f32.argtypes = [vp, vp, i32, i64, i64, i32, i64, vp, vp, vp, vp]
+    L.msim_topk_deep_f32.restype = i32
     L.msim_digest.argtypes = [vp, sz, ctypes.c_uint64, vp, vp]
     L.msim_digest.restype = i32
     L.msim_digest_host.argtypes = [vp, sz, ctypes.c_uint64, vp]

@@ -14,28 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "topk_order.hpp"
+
 namespace msim {
 
 constexpr int kTopkSeg = 4096;      // most candidates one workgroup sorts (the host may choose a smaller power of two)
 constexpr int kTopkThreads = 256;
 constexpr int kTopkMaxK = 1024;     // k <= kTopkSeg / 4 keeps every level shrinking by >= 4x
 
-// order-preserving map float -> uint32 (ascending); -0.0 is folded onto +0.0 so that equal
-// floats always tie and the id decides
-__device__ __forceinline__ uint32_t score_key(float s) {
-    if (s == 0.0f) s = 0.0f;
-    uint32_t u = __float_as_uint(s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_score(uint32_t k) {
-    uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
-}
-
-// a ranks before b: higher score first, then lower id (ids compared unsigned so the -1 padding id ranks last)
-__device__ __forceinline__ bool ranks_before(uint32_t ka, uint64_t ia, uint32_t kb, uint64_t ib) {
-    return (ka > kb) || (ka == kb && ia < ib);
-}
+// score_key / key_score / ranks_before: topk_order.hpp (shared with topk_deep.hip, which lives in another translation unit)
 
 __global__ __launch_bounds__(kTopkThreads) void topk_segment_kernel(const float *__restrict__ scores,
                                                                     const int64_t *__restrict__ ids,  // or null

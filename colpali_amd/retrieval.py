@@ -42,9 +42,13 @@ def shard_range(n_total: int, world: int, rank: int) -> Tuple[int, int]:
     return lo, lo + q + (1 if rank < r else 0)
 
 
+TOPK_MAX_K = 8192                 # include/maxsim.h: MSIM_TOPK_DEEP_MAX_K -- the longest list `topk` (and every route through it) selects
+_TOPK_SEGMENT_MAX_K = 1024        # msim_topk_f32's own limit: up to here nothing changed
+
+
 def topk(scores: torch.Tensor, k: int, id_base: int = 0, ids: Optional[torch.Tensor] = None,
          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Row-wise top-k on the GPU, ordered by (score desc, id asc); pads with (-inf, -1).
+    """Row-wise top-k on the GPU, ordered by (score desc, id asc); pads with (-inf, -1).  1 <= k <= TOPK_MAX_K (8192).
 
     scores: fp32 [n_q, n] (device). ids: optional int64 [n_q, n] candidate ids (default id_base + column).
     out: optional preallocated contiguous (fp32 [n_q, k], int64 [n_q, k]) to write into.
@@ -72,11 +76,15 @@ def topk(scores: torch.Tensor, k: int, id_base: int = 0, ids: Optional[torch.Ten
     else:
         out_s = torch.empty((n_q, k), dtype=torch.float32, device=dev)
         out_i = torch.empty((n_q, k), dtype=torch.int64, device=dev)
-    ws = _lib.workspace(L.msim_topk_workspace_bytes(n_q, n, k), dev)
+    # k <= 1024: the chained-segment kernels; above, up to TOPK_MAX_K, the radix select (include/maxsim.h: msim_topk_deep_f32) --
+    # the same order bit for bit; beyond that the deep entry refuses (NotImplementedError through _lib.check)
+    name, entry, ws_bytes = (("msim_topk_f32", L.msim_topk_f32, L.msim_topk_workspace_bytes) if k <= _TOPK_SEGMENT_MAX_K else
+                             ("msim_topk_deep_f32", L.msim_topk_deep_f32, L.msim_topk_deep_workspace_bytes))
+    ws = _lib.workspace(ws_bytes(n_q, n, k), dev)
     with torch.cuda.device(dev):
-        rc = L.msim_topk_f32(_lib.ptr(scores), _lib.ptr(ids), n_q, n, ld, k, id_base, _lib.ptr(out_s), _lib.ptr(out_i),
-                             _lib.ptr(ws), _lib.current_stream_handle(dev))
-    _lib.check(rc, "msim_topk_f32")
+        rc = entry(_lib.ptr(scores), _lib.ptr(ids), n_q, n, ld, k, id_base, _lib.ptr(out_s), _lib.ptr(out_i),
+                   _lib.ptr(ws), _lib.current_stream_handle(dev))
+    _lib.check(rc, name)
     return out_s, out_i
 
 
@@ -340,7 +348,14 @@ class ShardedRetriever:
         reranked.  The exact rerank then runs on the `n_refine` survivors, unchanged, so every returned score is still the exact
         one.  With `group_by=`, `n_refine` counts PAGES and the 4096-entry limit applies to `n_refine`, not to `n_candidates`.  A
         `ResidualCorpus` shard works as it does with `prefilter=`: the last stage is its own rerank.  An `Fp4WideIndex`, or a
-        320-wide shard, raises NotImplementedError.  With `refine=None` every route runs exactly as it did."""
+        320-wide shard, raises NotImplementedError.  With `refine=None` every route runs exactly as it did.
+
+        How long a list may be: every selection here is `topk`, which takes 1 .. `TOPK_MAX_K` = 8192 entries (NotImplementedError
+        beyond) -- `k`, `n_candidates` and `n_refine` alike, on the scan, behind `candidates=` / `prefilter=` / `refine=`, on the
+        filter's mask route, on a live shard, and for the per-rank message and the world x k wide merge of a sharded search.  Up
+        to 1024 the kernels are the ones that always ran; above, the radix select (`msim_topk_deep_f32`) gives the same order bit
+        for bit.  Two limits are not `topk`'s and stay: `group_by=` selects documents with `group_select` (lists of at most 4096
+        pages, k <= 1024), and the filter's "list" route lists at most 4096 allowed pages per query."""
         if n_candidates is not None and prefilter is None:
             raise ValueError("n_candidates goes with prefilter=")
         n_refine = self._check_refine(refine, n_refine, candidates, prefilter, n_candidates)

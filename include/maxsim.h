@@ -614,6 +614,31 @@ size_t msim_topk_workspace_bytes(int n_q, int64_t n, int k);
 int msim_topk_f32(const float *scores, const int64_t *ids, int n_q, int64_t n, int64_t ld,
                   int k, int64_t id_base,
                   float *out_scores, int64_t *out_ids, void *workspace, void *stream);
+/*
+ * msim_topk_f32 takes 1 <= k <= 1024 (MSIM_EUNSUPPORTED beyond).  DEEP TOP-K: the same selection for 1 <= k <= MSIM_TOPK_DEEP_MAX_K,
+ * for the long lists a cheap first stage hands to a rerank (k <= 1024 is accepted so that the two entries can be compared bit for
+ * bit; callers send such a k to msim_topk_f32).  Arguments and result are those of msim_topk_f32:
+ *   ids NULL: id = id_base + column; else int64 [n_q, ld], and an entry whose id is negative is no entry;
+ *   the order is (score descending, id ascending); -0.0 and +0.0 tie and come back as +0.0; a -inf score with a valid id is an
+ *   entry and ranks last, by id; rows with fewer than k entries are padded with (-inf, -1); NaN is outside the contract.
+ * The result is a function of the row's (score, id) set only -- not of the launch shape, of n_q or of scheduling -- so lists can be
+ * merged across shards and are reproducible bit for bit.  (Two entries with the same score AND the same id are interchangeable.)
+ * out_scores / out_ids are contiguous [n_q, k]; rows of scores / ids may start at any 4- / 8-byte aligned address (odd ld).
+ * MSIM_EUNSUPPORTED: k > 8192, n >= 2^31.  MSIM_EINVAL: a negative size, k <= 0, a null pointer (scores may be NULL when n == 0),
+ * ld < n, scores / out_scores not 4-byte or ids / out_ids not 8-byte aligned, no (or a not 16-byte aligned) workspace when
+ * msim_topk_deep_workspace_bytes(n_q, n, k) > 0.  n_q == 0 returns MSIM_OK with nothing launched.  msim_topk_deep_workspace_bytes
+ * is 0 for arguments the entry refuses.
+ * Asynchronous on `stream`; allocates nothing and reads nothing back.  The launch sequence is fixed by (n_q, n, k, ids == NULL),
+ * never by the data, so the call can be captured in a hipGraph; what it counts into the workspace it zeroes itself, on the stream,
+ * in every call, so a replay is correct.  Method (colpali_amd/csrc/topk_deep.hip): a radix select on the 32-bit order-preserving
+ * image of the score, most significant byte first, finds the key of the k-th entry; ties at that key go to the smallest ids (the
+ * select continues into the id, or -- rows split over several workgroups -- an ordered count in column order); the survivors, at
+ * most k, are sorted in LDS at 12 B per entry: 96 KiB at k = 8192 of the CU's 160 KiB, which is where the limit comes from.
+ */
+#define MSIM_TOPK_DEEP_MAX_K 8192
+size_t msim_topk_deep_workspace_bytes(int n_q, int64_t n, int k);
+int msim_topk_deep_f32(const float *scores, const int64_t *ids, int n_q, int64_t n, int64_t ld, int k, int64_t id_base,
+                       float *out_scores, int64_t *out_ids, void *workspace, void *stream);
 
 /*
  * FIXED DIMENSIONAL ENCODINGS (FDE; Dhulipala et al., "MUVERA", NeurIPS 2024): one vector of F values per page and per query whose

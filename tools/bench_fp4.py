@@ -26,8 +26,8 @@ figure is the median with its range:
     1000 x 32 x m in {1000, 4000} and 4 x 32 x m = 4000 on uniform and clustered lists (the generators of tools/bench_rerank.py),
     beside `rerank_scores` on the same lists and `fp4_scores` of the whole shard plus a gather; bound = n_q m rows 65 B / 8 TB/s.
     The cascade search(prefilter=FdeIndex | CentroidIndex, n_candidates=m1, refine=Fp4Index, n_refine=100) at m1 in {1000, 4000}
-    beside the same FDE search without refine and search(prefilter=Fp4Index, n_candidates=100), all in one loop (m1 = 4000 is above
-    the top-k's 1024 per row: there the first-stage scores go through torch.topk and the list through candidates=).  Recall@10 of the
+    beside the same FDE search without refine and search(prefilter=Fp4Index, n_candidates=100), all in one loop (m1 = 4000 is the deep
+    top-k's range: the same prefilter= route).  Recall@10 of the
     same configurations on the planted set, with e2m1 and e2m3 query tokens.
 """
 from __future__ import annotations
@@ -146,17 +146,12 @@ def rerank_legs(amd, corpus, f4idx, q_len, doc_len, dev, steps):
     return out
 
 
-TOPK_MAX_K = 1024              # msim_topk_f32 selects at most 1024 per row: the longest list search(prefilter=) can make
-
-
 def staged_search(amd, r, pq, score_fn, index, m1, k=10, **refine):
-    """search behind a first stage of m1 pages: `prefilter=index, n_candidates=m1` where the top-k takes m1; above its limit of 1024
-    the same first-stage scores go through torch.topk and the list through `candidates=` (the order inside the list, and which of
-    two equal scores makes it, may differ from `topk`'s; the stages behind it are the same)"""
-    if m1 <= TOPK_MAX_K:
-        return r.search(pq, k=k, prefilter=index, n_candidates=m1, **refine)
-    cand = torch.topk(score_fn(pq, index), m1, dim=1).indices + index.id_base
-    return r.search(pq, k=k, candidates=cand, **refine)
+    """search behind a first stage of m1 pages: `prefilter=index, n_candidates=m1` for every m1 the top-k takes (amd.TOPK_MAX_K =
+    8192: above 1024 the deep selection, the same order); `score_fn` is the first stage's scorer, for the caller's reference"""
+    if m1 > amd.TOPK_MAX_K:
+        raise NotImplementedError(f"a first stage of {m1} pages: the top-k selects at most {amd.TOPK_MAX_K} per row")
+    return r.search(pq, k=k, prefilter=index, n_candidates=m1, **refine)
 
 
 def cascade_leg(amd, corpus, f4idx, q_len, dev, steps):
@@ -219,8 +214,6 @@ def refine_section(res):
     c, rc = f["cascade"], f["recall"]
     L += ["", f"Search at 1000 × 32, k = 10, n_refine = {c['n_refine']}, all alternating in one loop; recall@10 against the exact search on the "
           f"planted {rc['docs']}-page set ({rc['queries']} queries), e2m1 / e2m3 query tokens in the FP4 stages:", "",
-          f"A first stage of more than {TOPK_MAX_K} pages cannot come from `prefilter=` (the top-k selects at most {TOPK_MAX_K} per row): "
-         "at n_candidates = 4000 the same first-stage scores go through `torch.topk` and the list through `candidates=`.", "",
          "| search | time | recall@10 (e2m1 / e2m3) |", "|---|---|---|"]
     for m1 in REFINE_M1:
         for first, name in (("fde", "FdeIndex"), ("centroid", "CentroidIndex")):
