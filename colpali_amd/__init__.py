@@ -28,6 +28,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      ShardedRetriever.search(prefilter=fde, n_candidates=m1, refine=fp4_index, n_refine=m2)
   * Fp4WideIndex / fp4_wide_scores -- the FP4 index of a 320-wide (ColQwen3) shard: 160 bytes of e2m1 nibbles and one scale byte
                                      per row, three chained block-scaled MFMAs per 16 rows x 16 tokens: a first stage for prefilter=
+  * fp4_wide_rerank_scores        -- its list form: the FP4 score of the pages a candidate list names (161 bytes per row read, the
+                                     scan's bits); search(prefilter=pooled, n_candidates=m1, refine=fp4_wide_index, n_refine=m2)
   * LiveCorpus.fp4_index / drop_fp4_index -- the FP4 index of a shard that changes (width 128 and 320), kept in step: add encodes
                                      the new rows, compact moves code rows and scale bytes (msim_f4_live_compact); its stage-1
                                      scores, and those of any Fp4Index / Fp4WideIndex passed as prefilter=, are tombstone-masked
@@ -56,7 +58,8 @@ from . import loss
 from .embed import CorpusWriter, embedding_head
 from .fp4_index import (Fp4Index, fp4_quantize_queries, fp4_rerank_scores, fp4_scores, fp4_scores_from_codes, fp6_quantize_queries,
                         fp6_rerank_scores, fp6_scores)
-from .fp4_wide_index import Fp4WideIndex, fp4_wide_quantize_queries, fp4_wide_scores, fp4_wide_scores_from_codes
+from .fp4_wide_index import (Fp4WideIndex, fp4_wide_quantize_queries, fp4_wide_rerank_scores, fp4_wide_scores,
+                             fp4_wide_scores_from_codes)
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .filter import PageFilter
 from .group import PageGroups, group_reduce, group_select
@@ -103,6 +106,7 @@ __all__ = [
     "fp6_rerank_scores",
     "Fp4WideIndex",
     "fp4_wide_scores",
+    "fp4_wide_rerank_scores",
     "fp4_wide_scores_from_codes",
     "fp4_wide_quantize_queries",
     "CentroidIndex",

@@ -9,6 +9,11 @@ one scale per row every partial sum is exactly representable in fp32, so a score
 reranked exactly -- `ShardedRetriever.search(prefilter=index, n_candidates=m)` -- so every returned score is the exact one.  The
 index carries no trained parameter: stage-1 scores of different shards are comparable.
 
+`fp4_wide_rerank_scores` is the LIST form (msim_f4w_candidates, colpali_amd/csrc/fp4_wide_candidates.hip): the FP4 score of the
+pages a candidate list names and of no other, bit for bit what the scan gives for the same query and page.  It is the middle stage
+of a three-stage search on a 320-wide shard -- a cheap stage 1 makes a long list, the 161-byte FP4 rows cut it, the exact rerank
+orders the survivors: `ShardedRetriever.search(prefilter=pooled, n_candidates=m1, refine=index, n_refine=m2)`.
+
 It is the sibling of `Fp4Index` (width 128), which keeps refusing width 320 as this class refuses width 128.
 """
 from __future__ import annotations
@@ -18,7 +23,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .corpus import PackedCorpus, PackedQueries, _as_packed
+from .corpus import PackedCorpus, PackedQueries, _as_packed, _rerank_args
 from .scoring import _require_gpu
 
 DIM = 320
@@ -161,3 +166,46 @@ def fp4_wide_scores(queries, index: Fp4WideIndex, out: Optional[torch.Tensor] = 
     max_q = int(lens.max()) if lens.numel() else 0
     codes, scales = _quantize_packed(q)
     return fp4_wide_scores_from_codes(codes, scales, q.offsets, max_q, index, out=out)
+
+
+MAX_RERANK_TOKENS = 128                            # the longest query of the list form (eight 16-token tiles in registers)
+
+
+def fp4_wide_rerank_scores(queries, index: Fp4WideIndex, candidates: torch.Tensor, *, out: Optional[torch.Tensor] = None
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The FP4 score of listed candidates at width 320 (include/maxsim.h: msim_f4w_candidates): (scores fp32 [n_q, m], ids int64
+    [n_q, m]).
+
+    Entry (q, j) is scored against page candidates[q, j] (a GLOBAL id, int64 [n_q, m] on the index's device) of `index`; its bits
+    are those of `fp4_wide_scores(queries, index)[q, candidates[q, j] - index.id_base]`, whatever else the list holds.  An id of
+    -1 or outside [id_base, id_base + len(index)) comes back as (-inf, -1) and reads nothing; a page of 0 rows scores -inf; an id
+    listed twice is scored twice.  Only the listed pages are read: 161 bytes per row.  Lists are taken as `rerank_scores` takes
+    them (a broadcast row is copied).  Queries are packed and coded as `fp4_wide_scores` does; more than 128 tokens in a query, or
+    an index that is not an `Fp4WideIndex` (an `Fp4Index` of a 128-wide shard goes to `fp4_rerank_scores`), raises
+    NotImplementedError.  `out`: the fp32 [n_q, m] score tensor.  Asynchronous on torch's current stream; given a `PackedQueries`
+    it never synchronises with the host, never reads the list on the host, and is hipGraph-capturable (its allocations are torch
+    tensors made before the library call; the list may be rewritten in place between replays).  It is the `fp4_wide_rerank_fn`
+    hook of `ShardedRetriever` (`search(refine=)`)."""
+    if not isinstance(index, Fp4WideIndex):
+        hint = "; an Fp4Index of a 128-wide shard takes fp4_rerank_scores" if type(index).__name__ == "Fp4Index" else ""
+        raise NotImplementedError(f"the wide fp4 rerank takes an Fp4WideIndex of a 320-wide shard (got {type(index).__name__}){hint}")
+    dev = _require_gpu(index.device)
+    q = _as_packed(queries, dev, layout="flat")
+    _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
+    if q.device != dev:
+        raise ValueError("queries and index live on different devices")
+    lens = q.lengths
+    max_q = int(lens.max()) if lens.numel() else 0
+    if max_q > MAX_RERANK_TOKENS:
+        raise NotImplementedError(f"the wide fp4 rerank takes queries of at most {MAX_RERANK_TOKENS} tokens (got {max_q})")
+    n_q, n = len(q), len(index)
+    codes, scales = _quantize_packed(q)
+    with torch.cuda.device(dev):
+        candidates, m, ld_cand, out, ids, _ = _rerank_args(n_q, dev, candidates, out, lambda m: 0)
+        rc = _lib.lib().msim_f4w_candidates(_lib.ptr(codes), _lib.ptr(scales), _lib.ptr(q.offsets), n_q, int(codes.shape[0]), max_q,
+                                            _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets),
+                                            _lib.ptr(index.clamp0), n, int(index.codes.shape[0]), DIM, _lib.ptr(candidates), m,
+                                            ld_cand, int(index.id_base), _lib.ptr(out), max(m, 1), _lib.ptr(ids),
+                                            _lib.current_stream_handle(dev))
+    _lib.check(rc, "msim_f4w_candidates")
+    return out, ids

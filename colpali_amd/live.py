@@ -32,7 +32,7 @@ from .int8_index import Int8Index, int8_scores
 from .fp4_index import DIM as F4_DIM
 from .fp4_index import Fp4Index, fp4_rerank_scores, fp4_scores
 from .fp4_wide_index import DIM as F4W_DIM
-from .fp4_wide_index import Fp4WideIndex, fp4_wide_scores
+from .fp4_wide_index import Fp4WideIndex, fp4_wide_rerank_scores, fp4_wide_scores
 from .align import Alignment, align
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
 from .group import PageGroups, group_reduce, group_select
@@ -79,7 +79,7 @@ class _LiveShard:
 
     def _init_slots(self, capacity_rows: int, capacity_docs: int, device, id_base: int, *, score_fn, rerank_fn, stage1_fns, select, mask_fn,
                     align_fn, mine_bounds_fn, mine_mask_fn, filter_mask_fn, filter_list_fn, filter_ids_fn, group_reduce_fn,
-                    group_select_fn, fp4_rerank_fn=fp4_rerank_scores) -> None:
+                    group_select_fn, fp4_rerank_fn=fp4_rerank_scores, fp4_wide_rerank_fn=fp4_wide_rerank_scores) -> None:
         """the slot table and the hooks; the subclass has allocated its rows"""
         self.id_base = int(id_base)
         self.capacity_rows, self.capacity_docs = capacity_rows, capacity_docs
@@ -92,6 +92,7 @@ class _LiveShard:
         self._rows_used = 0
         self._score_fn, self._rerank_fn = score_fn, rerank_fn
         self._fp4_rerank_fn = fp4_rerank_fn   # (queries, Fp4Index, candidates) -> (scores, ids): the refine stage of search(refine=)
+        self._fp4_wide_rerank_fn = fp4_wide_rerank_fn   # the same for an Fp4WideIndex (a 320-wide shard)
         self._stage1_fns = dict(stage1_fns)   # the stage-1 hooks of `ShardedRetriever` whose scores the tombstones mask, by keyword
         self._select, self._mask_fn = select, mask_fn
         self._align_fn = align_fn         # (queries, view(), ids, maps=) -> Alignment
@@ -299,6 +300,9 @@ class _LiveShard:
     def _fp4_rerank(self, queries, index, candidates):
         return self._fp4_rerank_fn(queries, index, self._live_ids(candidates))
 
+    def _fp4_wide_rerank(self, queries, index, candidates):
+        return self._fp4_wide_rerank_fn(queries, index, self._live_ids(candidates))
+
     def _retriever(self, shard, world, rank, dist, group, **hooks) -> ShardedRetriever:
         return ShardedRetriever(shard, world, rank, dist, group, select=self._select, **hooks)
 
@@ -321,7 +325,7 @@ class _LiveShard:
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None, prefilter=None,
                n_candidates: Optional[int] = None, world: int = 1, rank: int = 0, dist=None, group=None,
                filter: Optional[PageFilter] = None, filter_route: str = "auto", group_by: Optional[PageGroups] = None,
-               refine: Optional[Fp4Index] = None, n_refine: Optional[int] = None):
+               refine: Union[Fp4Index, Fp4WideIndex, None] = None, n_refine: Optional[int] = None):
         """`ShardedRetriever.search` over the live pages: the same arguments, rules and return value; a deleted page is never
         returned, and where fewer than `k` live pages exist the tail is (-inf, -1).  `candidates=` lists may name deleted and foreign
         ids (they become -1 before the rerank).  `prefilter` is the shard's own stage 1 (`LiveCorpus.int8_index()`,
@@ -334,15 +338,17 @@ class _LiveShard:
         all slots after `add`.  Over a compressed shard the routes that read every row (the full scan, the mask route of `filter=`,
         `group_by=` on the scan, `mine`) are refused with `ShardedRetriever`'s NotImplementedError unless `score_fn=residual_scores`.
         `refine` / `n_refine`: the three-stage search of `ShardedRetriever.search`, under its rules (exactly one of `candidates=` /
-        `prefilter=`, `n_refine` >= 1 and at most `n_candidates`, ValueError otherwise; an `Fp4WideIndex` or a 320-wide shard raises
-        NotImplementedError) -- `refine=live.fp4_index()`, or any `Fp4Index` over the same slots (a `LiveResidualCorpus` takes one in
-        the same way).  The refine hook (`fp4_rerank_fn`) sees the list with every deleted or foreign id replaced by -1, as the
+        `prefilter=`, `n_refine` >= 1 and at most `n_candidates`, ValueError otherwise; an index of the other width than the
+        shard's raises NotImplementedError) -- `refine=live.fp4_index()` at width 128 and 320 alike, or any `Fp4Index` (320-wide shard:
+        `Fp4WideIndex`) over the same slots (a `LiveResidualCorpus` takes an `Fp4Index` in the same way).  The refine hook
+        (`fp4_rerank_fn`; for an `Fp4WideIndex` `fp4_wide_rerank_fn`) sees the list with every deleted or foreign id replaced by
+        -1, as the
         rerank does, so a deleted page is never refined, never counted among the `n_refine` survivors and never returned."""
         shard = self.view()
         if self.device.type == "cuda":     # an injected hook packs host queries itself
             queries = _as_packed(queries, self.device, compact=compact)
         r = self._retriever(shard, world, rank, dist, group, score_fn=self._score, rerank_fn=self._rerank,
-                            fp4_rerank_fn=self._fp4_rerank, **self._stage1_hooks(), **self._filter_fns)
+                            fp4_rerank_fn=self._fp4_rerank, fp4_wide_rerank_fn=self._fp4_wide_rerank, **self._stage1_hooks(), **self._filter_fns)
         if group_by is not None:                 # (-inf, -1, -1) is already the rule there
             return r.search(queries, k, compact, candidates=candidates, prefilter=prefilter, n_candidates=n_candidates, filter=filter,
                             filter_route=filter_route, group_by=group_by, refine=refine, n_refine=n_refine)
@@ -354,7 +360,7 @@ class _LiveShard:
 class LiveCorpus(_LiveShard):
     """One mutable resident shard (see the module docstring).  `capacity_rows` and `capacity_docs` are fixed at construction.
 
-    `score_fn`, `rerank_fn`, `int8_score_fn`, `fp4_score_fn`, `fp4_wide_score_fn`, `fp4_rerank_fn`, `select`, the `filter_*_fn` and `mask_fn` are the hooks of
+    `score_fn`, `rerank_fn`, `int8_score_fn`, `fp4_score_fn`, `fp4_wide_score_fn`, `fp4_rerank_fn`, `fp4_wide_rerank_fn`, `select`, the `filter_*_fn` and `mask_fn` are the hooks of
     `ShardedRetriever` plus the tombstone mask (`mask_fn(scores, alive) -> scores`); the defaults are the gfx950 kernels
     (`fp4_score_fn=fp6_scores` scores e2m3 query tokens against the FP4 pages, as on `ShardedRetriever`).  The scores of all three
     stage-1 hooks are masked, whichever index is passed as `prefilter=`.  Host-logic tests inject reference scorers and run on the CPU."""
@@ -368,7 +374,7 @@ class LiveCorpus(_LiveShard):
                  mask_fn: Callable = mask_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
                  filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select,
-                 fp4_rerank_fn: Callable = fp4_rerank_scores):
+                 fp4_rerank_fn: Callable = fp4_rerank_scores, fp4_wide_rerank_fn: Callable = fp4_wide_rerank_scores):
         capacity_rows, capacity_docs = self._capacity(capacity_rows, capacity_docs)
         _lib.dtype_code(dtype)                                   # raises for anything but bf16 / f16 / f32
         self.device = torch.device(device)
@@ -379,7 +385,7 @@ class LiveCorpus(_LiveShard):
                          stage1_fns=dict(int8_score_fn=int8_score_fn, fp4_score_fn=fp4_score_fn, fp4_wide_score_fn=fp4_wide_score_fn),
                          select=select, mask_fn=mask_fn, align_fn=align_fn, mine_bounds_fn=mine_bounds_fn, mine_mask_fn=mine_mask_fn,
                          filter_mask_fn=filter_mask_fn, filter_list_fn=filter_list_fn, filter_ids_fn=filter_ids_fn,
-                         group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn, fp4_rerank_fn=fp4_rerank_fn)
+                         group_reduce_fn=group_reduce_fn, group_select_fn=group_select_fn, fp4_rerank_fn=fp4_rerank_fn, fp4_wide_rerank_fn=fp4_wide_rerank_fn)
         self._i8_codes: Optional[torch.Tensor] = None
         self._i8_scales: Optional[torch.Tensor] = None
         self._f4_codes: Optional[torch.Tensor] = None

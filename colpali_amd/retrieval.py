@@ -12,7 +12,7 @@ depend on the number of shards.
 from __future__ import annotations
 
 from functools import partial
-from typing import Callable, Optional, Tuple
+from typing import Callable, Optional, Tuple, Union
 
 import torch
 
@@ -20,7 +20,7 @@ from . import _lib
 from .align import Alignment, align
 from .binary_index import BinaryIndex, binary_scores
 from .fp4_index import Fp4Index, fp4_rerank_scores, fp4_scores, fp6_rerank_scores, fp6_scores
-from .fp4_wide_index import Fp4WideIndex, fp4_wide_scores
+from .fp4_wide_index import Fp4WideIndex, fp4_wide_rerank_scores, fp4_wide_scores
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .fde import FdeIndex, fde_scores
 from . import filter as _filter
@@ -218,7 +218,8 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
-            fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, align, residual_align)
+            fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, fp4_wide_rerank_scores, align,
+            residual_align)
 
 
 class ShardedRetriever:
@@ -239,7 +240,7 @@ class ShardedRetriever:
                  int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, binary_score_fn: Callable = binary_scores, fp4_score_fn: Callable = fp4_scores, fp4_wide_score_fn: Callable = fp4_wide_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
                  filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select,
-                 fp4_rerank_fn: Callable = fp4_rerank_scores):
+                 fp4_rerank_fn: Callable = fp4_rerank_scores, fp4_wide_rerank_fn: Callable = fp4_wide_rerank_scores):
         if isinstance(shard, ResidualCorpus) and rerank_fn is rerank_scores:
             rerank_fn = residual_rerank_scores
         self.shard, self.world, self.rank = shard, world, rank
@@ -255,6 +256,7 @@ class ShardedRetriever:
         self._fp4_score = fp4_score_fn    # (queries, Fp4Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4Index>
         self._fp4_wide_score = fp4_wide_score_fn  # (queries, Fp4WideIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4WideIndex>
         self._fp4_rerank = fp4_rerank_fn  # (queries, Fp4Index, candidates) -> (scores [n_q, m], ids [n_q, m]): the refine stage of refine=
+        self._fp4_wide_rerank = fp4_wide_rerank_fn  # the same for an Fp4WideIndex: the refine stage on a 320-wide shard
         self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
         self._mine_bounds = mine_bounds_fn    # (scores, csr, id_base, local=, alive=) -> fp32 [n_q]: the best in-shard positive of each query
         self._mine_mask = mine_mask_fn        # (scores, csr, id_base, bounds, max_ratio, alive) -> scores, -inf where ineligible
@@ -267,7 +269,7 @@ class ShardedRetriever:
 
     def search(self, queries, k: int = 10, compact: bool = False, *, candidates: Optional[torch.Tensor] = None,
                prefilter=None, n_candidates: Optional[int] = None, filter: Optional[PageFilter] = None,
-               filter_route: str = "auto", group_by: Optional[PageGroups] = None, refine: Optional[Fp4Index] = None,
+               filter_route: str = "auto", group_by: Optional[PageGroups] = None, refine: Union[Fp4Index, Fp4WideIndex, None] = None,
                n_refine: Optional[int] = None):
         """queries (replicated on every rank): a `PackedQueries`, a list of [len_i, 128] tensors, or a [n_q, Lq, 128] tensor.
         A host list is packed into the flat layout (ragged lengths, zero rows dropped on the way into the staging buffer).  A dense
@@ -337,18 +339,21 @@ class ShardedRetriever:
         straddle a boundary.  `search` calls `group_by.prepare()` on first use (one host synchronisation); with prepared groups
         and a `PackedQueries` the call is hipGraph-capturable.
 
-        Three-stage search: `refine` -- an `Fp4Index` over the shard's pages (same count, same id_base, same device; ValueError
-        otherwise) -- puts the FP4 rows between a cheap first stage and the exact rerank.  It needs exactly one of `candidates=` /
+        Three-stage search: `refine` -- an `Fp4Index` over a 128-wide shard's pages or an `Fp4WideIndex` over a 320-wide shard's
+        (same count, same id_base, same device; ValueError otherwise) -- puts the FP4 rows between a cheap first stage and the
+        exact rerank.  It needs exactly one of `candidates=` /
         `prefilter=` (ValueError otherwise) and `n_refine` >= 1, at most `n_candidates` with `prefilter=` (ValueError otherwise;
         `n_refine` without `refine` is a ValueError too).  Once the candidate list exists -- from stage 1, filtered, or the caller's
         list behind `filter_ids` -- the refine hook (`fp4_rerank_fn`, default `fp4_rerank_scores`; `fp6_rerank_scores` codes the query
-        tokens as e2m3) scores the listed pages of this shard from their 65-byte FP4 rows, and the top `n_refine` of those scores
+        tokens as e2m3; for an `Fp4WideIndex` `fp4_wide_rerank_fn`, default `fp4_wide_rerank_scores`) scores the listed pages of
+        this shard from their 65-byte (width 320: 161-byte) FP4 rows, and the top `n_refine` of those scores
         are kept through the same all-gather and merge as every other list: the refined list is identical on every rank and does
         not depend on the number of shards.  An entry the refine stage scored -inf (no page, an empty page) becomes -1 and is not
         reranked.  The exact rerank then runs on the `n_refine` survivors, unchanged, so every returned score is still the exact
         one.  With `group_by=`, `n_refine` counts PAGES and the 4096-entry limit applies to `n_refine`, not to `n_candidates`.  A
-        `ResidualCorpus` shard works as it does with `prefilter=`: the last stage is its own rerank.  An `Fp4WideIndex`, or a
-        320-wide shard, raises NotImplementedError.  With `refine=None` every route runs exactly as it did.
+        `ResidualCorpus` shard works as it does with `prefilter=`: the last stage is its own rerank.  An index of the other width
+        -- an `Fp4WideIndex` on a 128-wide shard, an `Fp4Index` on a 320-wide one -- raises NotImplementedError.  With
+        `refine=None` every route runs exactly as it did.
 
         How long a list may be: every selection here is `topk`, which takes 1 .. `TOPK_MAX_K` = 8192 entries (NotImplementedError
         beyond) -- `k`, `n_candidates` and `n_refine` alike, on the scan, behind `candidates=` / `prefilter=` / `refine=`, on the
@@ -406,9 +411,12 @@ class ShardedRetriever:
             if n_refine is not None:
                 raise ValueError("n_refine goes with refine=")
             return None
-        if isinstance(refine, Fp4WideIndex) or getattr(self.shard, "width", 128) != 128:
+        width = getattr(self.shard, "width", 128)
+        if width == 320 and isinstance(refine, Fp4WideIndex):
+            pass                                                         # the wide pair: fp4_wide_rerank_fn
+        elif isinstance(refine, Fp4WideIndex) or width != 128:
             raise NotImplementedError("refine takes an Fp4Index of a 128-wide shard")
-        if not isinstance(refine, Fp4Index):
+        elif not isinstance(refine, Fp4Index):
             raise ValueError("refine must be an Fp4Index")
         if (candidates is None) == (prefilter is None):
             raise ValueError("refine= cuts a candidate list: it needs exactly one of candidates= / prefilter=")
@@ -596,8 +604,9 @@ class ShardedRetriever:
                   else self._binary_score if isinstance(prefilter, BinaryIndex)
                   else self._fp4_score if isinstance(prefilter, Fp4Index)
                   else self._fp4_wide_score if isinstance(prefilter, Fp4WideIndex) else self._score)
+        fine = self._fp4_wide_rerank if isinstance(refine, Fp4WideIndex) else self._fp4_rerank
         queries = self._pack(queries, compact, self._rerank, *((stage1,) if prefilter is not None else ()),
-                             *((self._fp4_rerank,) if refine is not None else ()))
+                             *((fine,) if refine is not None else ()))
         if flt is not None:
             self._check_filter_rows(flt, len(queries))
         if prefilter is not None:
@@ -613,7 +622,7 @@ class ShardedRetriever:
                 mine = mine.clone(memory_format=torch.contiguous_format)
             candidates = self._filter_ids(mine, flt, None)
         if refine is not None:                                           # the FP4 rows cut the list: this shard's entries, then the merge
-            fine_s, fine_i = self._fp4_rerank(queries, refine, candidates)
+            fine_s, fine_i = fine(queries, refine, candidates)
             candidates = _no_page(*self._topk(fine_s, n_refine, 0, fine_i))[1]
         scores, ids = self._rerank(queries, self.shard, candidates)      # the last stage: exact, this shard's candidates only
         if groups is not None:

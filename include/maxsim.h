@@ -868,6 +868,40 @@ int msim_f4w_scores(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, 
                     int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
 /*
+ * FP4 CANDIDATES AT WIDTH 320 (fp4_wide_candidates.hip; additions to ABI 22): the LIST form of msim_f4w_scores -- the FP4 score of
+ * the pages a candidate list names and of no other, the middle stage of a three-stage search on a 320-wide shard: a cheap stage 1
+ * makes a long list, the 161-byte FP4 rows cut it, msim_fwd_candidates_wide orders the survivors exactly.  The sibling of
+ * msim_f4_candidates, argument for argument.
+ *   cand int64 [n_q, m] GLOBAL ids with row stride ld_cand >= m; the index holds pages id_base .. id_base + n_d - 1.  Queries, index
+ *   and every other argument as msim_f4w_scores.
+ *   out_scores[q, j] (fp32 [n_q, ld_scores], ld_scores >= m) has EXACTLY the bits msim_f4w_scores writes at
+ *     [q, cand[q, j] - id_base] for the same coded queries and index: every partial sum is exact in fp32, the maxima are taken over
+ *     the page's own rows only and the sum runs in token order from 0.0f, so a score's bits depend on its query and page only.
+ *   out_ids[q, j] (int64 [n_q, ld_scores], or NULL) = cand[q, j].
+ *   Order of resolution per entry: an id of -1, or outside [id_base, id_base + n_d), is written as (-inf, -1) and reads nothing; a
+ *     page whose offsets break 0 <= d_off[c] <= d_off[c + 1] <= d_rows, or that is longer than msim_f4w_scores' range limit of 2^23
+ *     rows, scores NaN; a page of 0 rows scores -inf; a query whose offsets break 0 <= q_off[q] <= q_off[q + 1] <= q_rows, or that
+ *     holds more tokens than the launch has slots for (16 * plan[0], at most 128), scores NaN; a query of 0 tokens scores 0.  A
+ *     duplicate id is scored once per occurrence.  Every index is checked before it becomes an address; only the affected entries
+ *     become NaN; nothing is left unwritten.  Base addresses are formed in 64 bits: the code array may exceed 2 GiB.
+ *   max_q_tokens (0 .. 128): the caller's bound on a query's token count; it chooses the 16-token tiles a wave holds.  One wave
+ *     scores one entry, four waves a workgroup, one workgroup per four consecutive entries.  msim_f4w_candidates_plan writes that
+ *     launch form: plan[0] = NT (tiles a wave holds: 1, 2, 4 or 8), plan[1] = D (16-row chunks read ahead), plan[2] = waves per
+ *     workgroup, plan[3] = workgroups.  It touches no device.
+ * No workspace, no allocation, no host read of the list, no synchronisation: hipGraph-capturable, and the list may be rewritten on
+ * the device between replays.  MSIM_EINVAL: a negative size, a null or misaligned pointer (codes 16-byte, ids 8-byte, offsets and
+ * scores 4-byte aligned; scale bytes unaligned), ld_cand < m or ld_scores < m.  MSIM_EUNSUPPORTED: dim != 320 (width 128 is
+ * msim_f4_candidates', which refuses 320 in turn), max_q_tokens > 128, more workgroups than one launch holds
+ * (ceil(n_q m / 4) >= 2^31).  n_q == 0 or m == 0: MSIM_OK before a pointer is looked at, nothing launched.  All of it is decided
+ * before the device is touched.
+ */
+int msim_f4w_candidates_plan(int n_q, int max_q_tokens, int m, int32_t *plan /* [4]: NT, D, waves per workgroup, workgroups */);
+int msim_f4w_candidates(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                        const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                        int64_t d_rows, int dim, const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores,
+                        int64_t ld_scores, int64_t *out_ids /* or NULL */, void *stream);
+
+/*
  * CENTROID-CODE INDEX (centroid_index.hip; additions to ABI 22): every corpus row stored as the uint16 id of its nearest of K
  * centroids, pages scored by centroid interaction (PLAID's first stage) -- a first stage for two-stage search that reads 2 bytes
  * per row, reranked exactly by msim_fwd_candidates.  C: K centroid rows [K, 128] in the dtype of the rows they meet; K a multiple

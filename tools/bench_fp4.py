@@ -5,6 +5,7 @@
                               [--legs build,stage1,pooled,two_stage,recall]
     python tools/bench_fp4.py --legs refine --summary profiles/fp4_summary.md      (rewrites only its own section of the summary)
     python tools/bench_fp4.py --dim 320 [--out FILE] [--summary profiles/fp4_wide_summary.md] [--legs build,stage1,two_stage,recall]
+    python tools/bench_fp4.py --dim 320 --legs refine --summary profiles/fp4_wide_summary.md   (rewrites only its own section)
 
 --dim 320 measures the 320-wide index (msim_f4w_*, colpali_amd.Fp4WideIndex) on the shard of tools/bench_rerank.py --dim 320
 (50 000 x 1024 x 320 bf16 by default): see `main_wide`.
@@ -29,6 +30,11 @@ figure is the median with its range:
     beside the same FDE search without refine and search(prefilter=Fp4Index, n_candidates=100), all in one loop (m1 = 4000 is the deep
     top-k's range: the same prefilter= route).  Recall@10 of the
     same configurations on the planted set, with e2m1 and e2m3 query tokens.
+    With --dim 320: `fp4_wide_rerank_scores` at 1000 x 32 x m = 1000 and 4 x 32 x m = 4000 on uniform and clustered lists beside
+    `rerank_scores` on the same lists and `fp4_wide_scores` plus a gather; bounds = n_q m rows 161 B / 8 TB/s for the list form and
+    distinct pages x rows x 640 B / 8 TB/s for the exact rerank.  The cascade search(prefilter=<343-row pooled shard>,
+    n_candidates=m1, refine=Fp4WideIndex, n_refine=100) at m1 in {400, 1000} beside the same search without refine and
+    search(prefilter=Fp4WideIndex, n_candidates=100); recall@10 of the same variants on the planted set at width 320.
 """
 from __future__ import annotations
 
@@ -226,9 +232,9 @@ def refine_section(res):
     return L
 
 
-def splice_refine_section(text, section):
-    """`text` (an earlier summary) with its refine section replaced by `section` (appended when it has none)"""
-    at = text.find(REFINE_MARK)
+def splice_refine_section(text, section, mark=REFINE_MARK):
+    """`text` (an earlier summary) with its refine section (the one headed `mark`) replaced by `section` (appended when it has none)"""
+    at = text.find(mark)
     if at >= 0:
         nxt = text.find("\n## ", at + 1)
         text = text[:at] + (text[nxt + 1:] if nxt >= 0 else "")
@@ -347,6 +353,101 @@ def wide_recall_leg(amd, dev, n_docs, k=10):
             "bytes": {"fp4_wide_full": idx.nbytes, "pooled_corpus": pooled.nbytes, "shard": full.nbytes}}
 
 
+# ------------------------------------------------------------------------------------- width 320: the list form and the cascade
+WIDE_REFINE_M1 = (400, 1000)
+WIDE_REFINE_MARK = "## FP4 candidate rerank and three-stage search at width 320"
+WIDE_EXACT_ROW_BYTES = 640     # a bf16 row of the 320-wide shard
+
+
+def wide_rerank_legs(amd, corpus, idx, q_len, doc_len, dev, steps):
+    """the wide list form alone: per (n_q, m, list distribution) the three variants alternating in one loop"""
+    from tools.bench_rerank import clustered_candidates, make_queries_dim, uniform_candidates
+
+    n = len(corpus)
+    out = {}
+    for n_q, m in ((1000, 1000), (4, 4000)):
+        pq = amd.pack_queries(make_queries_dim(n_q, q_len, 320, dev, seed=99), dev, compact=False)
+        full = torch.empty((n_q, n), dtype=torch.float32, device=dev)
+        for dist_name, cand in (("uniform", uniform_candidates(n_q, n, m, dev, seed=7)),
+                                ("clustered", clustered_candidates(n_q, n, m, dev, seed=7, pool=min(2 * m, n)))):
+            s4 = torch.empty((n_q, m), dtype=torch.float32, device=dev)
+            leg = alternating({"fp4_wide_rerank": lambda: amd.fp4_wide_rerank_scores(pq, idx, cand, out=s4),
+                               "exact_rerank": lambda: amd.rerank(pq, corpus, cand),
+                               "fp4_wide_scan_gather": lambda: torch.gather(amd.fp4_wide_scores(pq, idx, out=full), 1, cand)},
+                              steps if n_q == 4 else max(3, steps // 2), 1)
+            leg["distinct_pages"] = int(torch.unique(cand).numel())
+            leg["bound_ms"] = n_q * m * doc_len * WIDE_ROW_BYTES / (HBM_PEAK_GBS * 1e9) * 1e3
+            leg["exact_bound_ms"] = leg["distinct_pages"] * doc_len * WIDE_EXACT_ROW_BYTES / (HBM_PEAK_GBS * 1e9) * 1e3
+            leg["share_of_bound"] = leg["bound_ms"] / leg["fp4_wide_rerank"]["median_ms"]
+            leg["exact_vs_fp4_wide"] = leg["exact_rerank"]["median_ms"] / leg["fp4_wide_rerank"]["median_ms"]
+            leg["faster_than_exact"] = leg["fp4_wide_rerank"]["max_ms"] < leg["exact_rerank"]["min_ms"]     # the ranges do not overlap
+            leg["bits_equal_scan_gather"] = bool(torch.equal(s4.view(torch.int32), torch.gather(full, 1, cand).view(torch.int32)))
+            out[f"{n_q}x{q_len}_m{m}_{dist_name}"] = leg
+        del full
+    return out
+
+
+def wide_cascade_leg(amd, corpus, idx, coarse, q_len, dev, steps):
+    from tools.bench_rerank import make_queries_dim
+
+    pq = amd.pack_queries(make_queries_dim(1000, q_len, 320, dev, seed=99), dev, compact=False)
+    r = amd.ShardedRetriever(corpus)
+    variants = {}
+    for m1 in WIDE_REFINE_M1:
+        variants[f"pooled_refine_m{m1}"] = lambda m1=m1: r.search(pq, k=10, prefilter=coarse, n_candidates=m1, refine=idx, n_refine=N_REFINE)
+        variants[f"pooled_only_m{m1}"] = lambda m1=m1: r.search(pq, k=10, prefilter=coarse, n_candidates=m1)
+    variants["fp4_wide_m100"] = lambda: r.search(pq, k=10, prefilter=idx, n_candidates=100)
+    out = alternating(variants, max(3, steps // 2), 1)
+    out["n_queries"], out["n_refine"], out["coarse_rows_per_doc"] = 1000, N_REFINE, POOLED_LEN
+    return out
+
+
+def wide_refine_recall_leg(amd, dev, n_docs, k=10):
+    full, pooled, pq = wide_planted(amd, dev, n_docs)
+    r = amd.ShardedRetriever(full)
+    exact = r.search(pq, k=k)[1].tolist()
+    idx = amd.Fp4WideIndex.build(full)
+
+    def hits(got):
+        return sum(len(set(a) & set(b)) for a, b in zip(exact, got[1].tolist())) / (len(pq) * k)
+
+    out = {"docs": n_docs, "queries": len(pq), "k": k, "n_refine": N_REFINE, "pooled_rows_per_doc": float(pooled.blob.shape[0]) / n_docs}
+    for m1 in WIDE_REFINE_M1:
+        out[f"pooled_refine_m{m1}"] = hits(r.search(pq, k=k, prefilter=pooled, n_candidates=m1, refine=idx, n_refine=N_REFINE))
+        out[f"pooled_only_m{m1}"] = hits(r.search(pq, k=k, prefilter=pooled, n_candidates=m1))
+    out["fp4_wide_m100"] = hits(r.search(pq, k=k, prefilter=idx, n_candidates=100))
+    return out
+
+
+def wide_refine_section(res):
+    """the wide summary's section of the refine leg: measured figures only"""
+    f = res["refine"]
+    L = [WIDE_REFINE_MARK, "",
+         f"`tools/bench_fp4.py --dim 320 --legs refine --steps {res['steps']}` on the 320-wide shard ({res['docs']} pages × {res['doc_len']} "
+         "rows).  The variants of a row alternate call by call in one timed loop; median, with the range in brackets.  The list form's "
+         "bound is n_q × m × rows × 161 B at 8 TB/s (every listed page read once per entry: no page shared between queries); the exact "
+         "rerank's is distinct pages × rows × 640 B at 8 TB/s (a page read once for all the queries that list it); a share is bound / "
+         "measured.  `faster` says whether the list form's whole range lies below the exact rerank's in this loop.", "",
+         "| shape, list | `fp4_wide_rerank_scores` (share) | `rerank_scores` (exact) | exact / list form | faster | `fp4_wide_scores` + gather | "
+         "bound, list form | bound, exact | distinct pages | bits = scan |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for name, leg in f["rerank"].items():
+        L += [f"| {name.replace('_', ' ')} | {_ms(leg['fp4_wide_rerank'])} ({leg['share_of_bound']:.2f}) | {_ms(leg['exact_rerank'])} | "
+              f"{leg['exact_vs_fp4_wide']:.2f} × | {'yes' if leg['faster_than_exact'] else 'NO'} | {_ms(leg['fp4_wide_scan_gather'])} | "
+              f"{leg['bound_ms']:.2f} ms | {leg['exact_bound_ms']:.2f} ms | {leg['distinct_pages']} | "
+              f"{'yes' if leg['bits_equal_scan_gather'] else 'NO'} |"]
+    c, rc = f["cascade"], f["recall"]
+    L += ["", f"Search at 1000 × 32, k = 10, n_refine = {c['n_refine']}, all alternating in one loop (the pooled shard of the timing has "
+          f"{c['coarse_rows_per_doc']} random rows per page); recall@10 against the exact search on the planted {rc['docs']}-page set at "
+          f"width 320 ({rc['queries']} queries, pooled pages of {rc['pooled_rows_per_doc']:.0f} rows):", "",
+          "| search | time | recall@10 |", "|---|---|---|"]
+    for m1 in WIDE_REFINE_M1:
+        L += [f"| `prefilter=pooled, n_candidates={m1}, refine=Fp4WideIndex, n_refine={c['n_refine']}` | {_ms(c[f'pooled_refine_m{m1}'])} | "
+              f"{rc[f'pooled_refine_m{m1}']:.3f} |",
+              f"| `prefilter=pooled, n_candidates={m1}` (no refine) | {_ms(c[f'pooled_only_m{m1}'])} | {rc[f'pooled_only_m{m1}']:.3f} |"]
+    L += [f"| `prefilter=Fp4WideIndex, n_candidates=100` | {_ms(c['fp4_wide_m100'])} | {rc['fp4_wide_m100']:.3f} |", ""]
+    return L
+
+
 def wide_summary(res):
     L = ["# FP4 index at width 320: measured on one MI355X", "",
          f"`tools/bench_fp4.py --dim 320 --steps {res['steps']} --warmup {res['warmup']}` on the 320-wide shard ({res['docs']} pages × "
@@ -386,12 +487,14 @@ def wide_summary(res):
         for key, name in (("fp4_wide_full", "`Fp4WideIndex`, full pages"),
                           ("pooled_corpus", f"pooled `PackedCorpus` ({r['pooled_rows_per_doc']:.0f} rows per page)")):
             L += [f"| {name} | {r['bytes'][key] / 1e6:.0f} MB | " + " | ".join(f"{r[key][str(m)]:.3f}" for m in MS) + " |"]
+    if "refine" in res:
+        L += [""] + wide_refine_section(res)
     return "\n".join(L) + "\n"
 
 
 def main_wide(args):
     """--dim 320: index bytes, build, stage 1 beside the exact 320-wide scan, two-stage search beside the exact search and the
-    pooled-prefilter two-stage search, recall@10 on the planted set."""
+    pooled-prefilter two-stage search, recall@10 on the planted set; --legs refine: the list form and the three-stage search."""
     import colpali_amd as amd
     from tools.bench_rerank import make_queries_dim, make_shard_dim
 
@@ -403,6 +506,19 @@ def main_wide(args):
     t0 = time.perf_counter()
     res = {"tool": "bench_fp4", "dim": 320, "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len, "steps": args.steps,
            "warmup": args.warmup, "hbm_peak_GBps": HBM_PEAK_GBS, "fp4_peak_TFLOPs": FP4_PEAK_TFLOPS}
+    if "refine" in legs:
+        corpus = make_shard_dim(docs, args.doc_len, 320, dev, seed=1234)
+        idx = amd.Fp4WideIndex.build(corpus)
+        _progress("shard and index", t0)
+        res["refine"] = {"rerank": wide_rerank_legs(amd, corpus, idx, args.q_len, args.doc_len, dev, args.steps)}
+        _progress("refine: list form", t0)
+        coarse = make_shard_dim(docs, POOLED_LEN, 320, dev, seed=4321)
+        res["refine"]["cascade"] = wide_cascade_leg(amd, corpus, idx, coarse, args.q_len, dev, args.steps)
+        _progress("refine: cascade", t0)
+        del corpus, idx, coarse
+        torch.cuda.empty_cache()
+        res["refine"]["recall"] = wide_refine_recall_leg(amd, dev, args.recall_docs)
+        _progress("refine: recall", t0)
     if legs & {"build", "stage1", "two_stage"}:
         corpus = make_shard_dim(docs, args.doc_len, 320, dev, seed=1234)
         idx = amd.Fp4WideIndex.build(corpus)
@@ -450,8 +566,12 @@ def main_wide(args):
         with open(args.out, "w") as f:
             f.write(line + "\n")
     if args.summary:
+        text = wide_summary(res)
+        if legs == {"refine"} and os.path.exists(args.summary):            # the other legs' recorded figures stay
+            with open(args.summary) as f:
+                text = splice_refine_section(f.read(), wide_refine_section(res), WIDE_REFINE_MARK)
         with open(args.summary, "w") as f:
-            f.write(wide_summary(res))
+            f.write(text)
     print(line)
 
 
