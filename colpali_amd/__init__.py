@@ -30,6 +30,9 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      per row, three chained block-scaled MFMAs per 16 rows x 16 tokens: a first stage for prefilter=
   * fp4_wide_rerank_scores        -- its list form: the FP4 score of the pages a candidate list names (161 bytes per row read, the
                                      scan's bits); search(prefilter=pooled, n_candidates=m1, refine=fp4_wide_index, n_refine=m2)
+  * FdeWideIndex / fde_wide_scores -- the fixed dimensional encodings of a 320-wide (ColQwen3) shard, by an encoder of its own and
+                                     the scorer of fde_scores: the one-GEMM first stage at width 320, and the front of
+                                     search(prefilter=fde_wide, n_candidates=m1, refine=fp4_wide_index, n_refine=m2)
   * LiveCorpus.fp4_index / drop_fp4_index -- the FP4 index of a shard that changes (width 128 and 320), kept in step: add encodes
                                      the new rows, compact moves code rows and scale bytes (msim_f4_live_compact); its stage-1
                                      scores, and those of any Fp4Index / Fp4WideIndex passed as prefilter=, are tombstone-masked
@@ -61,6 +64,7 @@ from .fp4_index import (Fp4Index, fp4_quantize_queries, fp4_rerank_scores, fp4_s
 from .fp4_wide_index import (Fp4WideIndex, fp4_wide_quantize_queries, fp4_wide_rerank_scores, fp4_wide_scores,
                              fp4_wide_scores_from_codes)
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
+from .fde_wide import FdeWideIndex, fde_wide_encode_queries, fde_wide_scores
 from .filter import PageFilter
 from .group import PageGroups, group_reduce, group_select
 from .int8_index import Int8Index, int8_scores, quantize_queries
@@ -90,6 +94,9 @@ __all__ = [
     "FdeIndex",
     "encode_queries",
     "fde_scores",
+    "FdeWideIndex",
+    "fde_wide_encode_queries",
+    "fde_wide_scores",
     "Int8Index",
     "int8_scores",
     "quantize_queries",

@@ -182,6 +182,10 @@ def lib() -> ctypes.CDLL:
     L.msim_fde_encode_queries.restype = i32
     L.msim_fde_scores.argtypes = [i32, vp, i32, vp, i32, i32, vp, i64, vp]
     L.msim_fde_scores.restype = i32
+    L.msim_fdew_encode_docs.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.msim_fdew_encode_docs.restype = i32
+    L.msim_fdew_encode_queries.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.msim_fdew_encode_queries.restype = i32
     L.msim_i8_encode_docs.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, vp]
     L.msim_i8_encode_docs.restype = i32
     L.msim_i8_encode_queries.argtypes = [i32, vp, i64, i32, vp, vp, vp]

@@ -22,6 +22,7 @@ from .corpus import PackedCorpus, _as_packed
 from .scoring import _require_gpu
 
 DIM = 128
+WIDE_DIM = 320                    # colpali_amd/fde_wide.py
 MAX_DIM = 65536
 
 
@@ -59,12 +60,15 @@ class FdeConfig:
         """F, the length of one encoding."""
         return self.reps * self.buckets * self.dproj
 
-    def params(self) -> Tuple[torch.Tensor, torch.Tensor]:
+    def params(self, width: int = DIM) -> Tuple[torch.Tensor, torch.Tensor]:
         """The random parameters, fp32 on the host, drawn in this fixed order from torch.Generator().manual_seed(seed):
-        G [reps, ksim, 128] standard normal (the bucket hyperplanes), S [reps, dproj, 128] +-1 (the projections)."""
+        G [reps, ksim, width] standard normal (the bucket hyperplanes), S [reps, dproj, width] +-1 (the projections).
+        width: 128 (the default: `FdeIndex`) or 320 (`FdeWideIndex`)."""
+        if isinstance(width, bool) or width not in (DIM, WIDE_DIM):
+            raise ValueError(f"FdeConfig.params(width={width!r}): the encoders take rows of width {DIM} or {WIDE_DIM}")
         g = torch.Generator().manual_seed(self.seed)
-        G = torch.randn((self.reps, self.ksim, DIM), generator=g, dtype=torch.float32)
-        S = torch.randint(0, 2, (self.reps, self.dproj, DIM), generator=g, dtype=torch.int64).to(torch.float32) * 2 - 1
+        G = torch.randn((self.reps, self.ksim, width), generator=g, dtype=torch.float32)
+        S = torch.randint(0, 2, (self.reps, self.dproj, width), generator=g, dtype=torch.int64).to(torch.float32) * 2 - 1
         return G, S
 
 

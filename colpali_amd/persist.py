@@ -30,6 +30,7 @@ from .binary_index import BinaryIndex
 from .centroid import CentroidIndex
 from .corpus import PackedCorpus, _staging
 from .fde import FdeConfig, FdeIndex
+from .fde_wide import FdeWideIndex
 from .fp4_index import Fp4Index
 from .fp4_wide_index import Fp4WideIndex
 from .int8_index import Int8Index
@@ -60,6 +61,7 @@ _FROZEN = {
     "CentroidIndex": (CentroidIndex, (("centroids", "whole"), ("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"),
                                       ("lengths", "pages"))),
     "FdeIndex": (FdeIndex, (("Fd", "rows"), ("G", "whole"), ("S", "whole"))),
+    "FdeWideIndex": (FdeWideIndex, (("Fd", "rows"), ("G", "whole"), ("S", "whole"))),
     "ResidualCorpus": (ResidualCorpus, (("centroids", "whole"), ("codes", "rows"), ("residuals", "rows"), ("cutoffs", "whole"),
                                         ("weights", "whole"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
 }
@@ -250,14 +252,14 @@ def _kind_of(obj) -> str:
 
 
 def save(obj, path, *, chunk_bytes: int = DEFAULT_CHUNK_BYTES) -> None:
-    """Write `obj` -- a `PackedCorpus`, `Int8Index`, `BinaryIndex`, `Fp4Index`, `Fp4WideIndex`, `CentroidIndex`, `FdeIndex`, `ResidualCorpus`, `LiveCorpus` or
+    """Write `obj` -- a `PackedCorpus`, `Int8Index`, `BinaryIndex`, `Fp4Index`, `Fp4WideIndex`, `CentroidIndex`, `FdeIndex`, `FdeWideIndex`, `ResidualCorpus`, `LiveCorpus` or
     `LiveResidualCorpus` -- to `path` (see the module docstring).  Written to `path + ".tmp"`, fsynced and renamed: a failed save
     leaves nothing under `path` and an older file there untouched.  Holds two pinned chunks of host memory at most, whatever the
     object's size.  Synchronises with the host; raises under stream capture."""
     kind = _kind_of(obj)
     if kind in _FROZEN:
         meta = dict(id_base=int(obj.id_base))
-        if kind == "FdeIndex":
+        if kind in ("FdeIndex", "FdeWideIndex"):
             G, S = obj.params
             meta["config"] = {f: getattr(obj.config, f) for f in _FDE_FIELDS}
             tensors = [("Fd", "rows", obj.Fd), ("G", "whole", G), ("S", "whole", S)]
@@ -514,8 +516,8 @@ def _load_frozen(rd: _Reader, kind: str, device, pages):
             return Fp4WideIndex(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind == "CentroidIndex":
             return CentroidIndex(got["centroids"], got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
-        if kind == "FdeIndex":
-            return FdeIndex(got["Fd"], id_base, FdeConfig(**{f: meta["config"][f] for f in _FDE_FIELDS}), params=(got["G"], got["S"]))
+        if kind in ("FdeIndex", "FdeWideIndex"):
+            return cls(got["Fd"], id_base, FdeConfig(**{f: meta["config"][f] for f in _FDE_FIELDS}), params=(got["G"], got["S"]))
         return ResidualCorpus(got["centroids"], got["codes"], got["residuals"], got["cutoffs"], got["weights"], got["offsets"],
                               got["clamp0"], got["lengths"], id_base, int(meta["bits"]))
     except (KeyError, AttributeError, TypeError) as exc:

@@ -23,6 +23,7 @@ from .fp4_index import Fp4Index, fp4_rerank_scores, fp4_scores, fp6_rerank_score
 from .fp4_wide_index import Fp4WideIndex, fp4_wide_rerank_scores, fp4_wide_scores
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .fde import FdeIndex, fde_scores
+from .fde_wide import FdeWideIndex, fde_wide_scores
 from . import filter as _filter
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
 from .group import SELECT_MAX_M, PageGroups, group_reduce, group_select
@@ -219,7 +220,7 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
             fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, fp4_wide_rerank_scores, align,
-            residual_align)
+            residual_align, fde_wide_scores)
 
 
 class ShardedRetriever:
@@ -240,7 +241,8 @@ class ShardedRetriever:
                  int8_score_fn: Callable = int8_scores, centroid_score_fn: Callable = centroid_scores, binary_score_fn: Callable = binary_scores, fp4_score_fn: Callable = fp4_scores, fp4_wide_score_fn: Callable = fp4_wide_scores, align_fn: Callable = align, mine_bounds_fn: Callable = mine_bounds,
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
                  filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select,
-                 fp4_rerank_fn: Callable = fp4_rerank_scores, fp4_wide_rerank_fn: Callable = fp4_wide_rerank_scores):
+                 fp4_rerank_fn: Callable = fp4_rerank_scores, fp4_wide_rerank_fn: Callable = fp4_wide_rerank_scores,
+                 fde_wide_score_fn: Callable = fde_wide_scores):
         if isinstance(shard, ResidualCorpus) and rerank_fn is rerank_scores:
             rerank_fn = residual_rerank_scores
         self.shard, self.world, self.rank = shard, world, rank
@@ -250,6 +252,7 @@ class ShardedRetriever:
         self._res_refuses = isinstance(shard, ResidualCorpus) and score_fn is maxsim_scores
         self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
         self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
+        self._fde_wide_score = fde_wide_score_fn  # (queries, FdeWideIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeWideIndex>
         self._int8_score = int8_score_fn  # (queries, Int8Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Int8Index>
         self._centroid_score = centroid_score_fn  # (queries, CentroidIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<CentroidIndex>
         self._binary_score = binary_score_fn  # (queries, BinaryIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<BinaryIndex>
@@ -291,7 +294,9 @@ class ShardedRetriever:
         `BinaryIndex` of the shard or of its pooled pages: stage 1 is then the 1-bit sign scan (`binary_scores`); it has no trained
         parameter, so its scores are comparable across shards as they stand.  Or an `Fp4Index` of the shard or of its pooled
         pages: stage 1 is then the FP4 scan (`fp4_scores`), comparable across shards in the same way.  Or, over a 320-wide shard,
-        an `Fp4WideIndex` of it: stage 1 is then `fp4_wide_scores`, under the same rules, and stage 2 the 320-wide rerank.
+        an `Fp4WideIndex` of it: stage 1 is then `fp4_wide_scores`, under the same rules, and stage 2 the 320-wide rerank; or an
+        `FdeWideIndex` of it: stage 1 is then the encoding GEMM at width 320 (`fde_wide_scores`).  An `FdeIndex` over a 320-wide
+        shard, or an `FdeWideIndex` over a 128-wide one, raises ValueError.
 
         Filtered search: `filter` -- a `PageFilter` over this shard (same count, same id_base, same device; ValueError otherwise, and
         for a per-query filter whose rows differ from the number of queries) -- restricts every query to its allowed pages.  For each
@@ -594,12 +599,20 @@ class ShardedRetriever:
             if m > SELECT_MAX_M:
                 raise NotImplementedError(f"group_by over a list of {m} pages: group_select takes at most {SELECT_MAX_M}")
         if prefilter is not None:
-            if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex, BinaryIndex, Fp4Index, Fp4WideIndex)):
-                raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index, a CentroidIndex or a BinaryIndex, or an Fp4Index or an Fp4WideIndex")
+            if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex, BinaryIndex, Fp4Index, Fp4WideIndex,
+                                          FdeWideIndex)):
+                raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index, a CentroidIndex or a BinaryIndex, or an Fp4Index or an Fp4WideIndex"
+                                 ", or an FdeWideIndex")
+            if isinstance(prefilter, (FdeIndex, FdeWideIndex)):
+                width = getattr(self.shard, "width", 128)                 # the two classes differ by the shard's 320 only
+                if (width == 320) != isinstance(prefilter, FdeWideIndex):
+                    raise ValueError(f"prefilter is an {type(prefilter).__name__}, the shard is {width} wide: a 320-wide shard takes "
+                                     "an FdeWideIndex, any other an FdeIndex")
             self._check_covers("prefilter holds", prefilter, "documents")
             if n_candidates is None or int(n_candidates) < 1:
                 raise ValueError("prefilter= needs n_candidates >= 1")
-        stage1 = (self._fde_score if isinstance(prefilter, FdeIndex) else self._int8_score if isinstance(prefilter, Int8Index)
+        stage1 = (self._fde_score if isinstance(prefilter, FdeIndex) else self._fde_wide_score if isinstance(prefilter, FdeWideIndex)
+                  else self._int8_score if isinstance(prefilter, Int8Index)
                   else self._centroid_score if isinstance(prefilter, CentroidIndex)
                   else self._binary_score if isinstance(prefilter, BinaryIndex)
                   else self._fp4_score if isinstance(prefilter, Fp4Index)

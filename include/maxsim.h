@@ -245,7 +245,8 @@ int msim_fwd_candidates(int dtype, const void *Qt, const int32_t *q_off, const i
  * derives is checked before it becomes an address; a broken invariant makes every score of the call NaN.
  * workspace: msim_fwd_candidates_wide_workspace_bytes(n_q, m, n_d, dim) bytes (0 when there is no entry), 16-byte aligned, contents
  * irrelevant; one per call in flight.  After the call its first int32 is 0, or the bits of the broken invariant.
- * NOT served at width 320: the int8 and FDE first stages (msim_i8_*, msim_fde_*: width 128 only), fp32.
+ * NOT served at width 320: the int8 first stage (msim_i8_*: width 128 only), fp32.  The FDE encoders msim_fde_encode_* are width
+ * 128 only; width 320 has encoders of its own (msim_fdew_encode_*), scored by msim_fde_scores.
  */
 size_t msim_fwd_candidates_wide_workspace_bytes(int n_q, int m, int n_d, int dim);
 int msim_fwd_candidates_wide(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q,
@@ -670,6 +671,23 @@ int msim_fde_encode_queries(int dtype, const void *Qt, const int32_t *q_off, int
  */
 int msim_fde_scores(int dtype, const void *Fq, int n_q, const void *Fd, int n_d, int F, float *scores, int64_t ld_scores,
                     void *stream);
+
+/*
+ * FIXED DIMENSIONAL ENCODINGS AT WIDTH 320 (ColQwen3; fde_wide.hip): the two encoders above for rows X [n_rows, 320], with
+ * G fp32 [R, k_sim, 320] and S fp32 [R, d_proj, 320].  The same arithmetic with 128 replaced by 320 -- sign dots in fp32 on the
+ * unrounded row values, SUM for queries, MEAN for pages, fill_empty by Hamming distance with the lowest row index on a tie,
+ * psi_r(v) = S[r] v / sqrt(d_proj) in fp32, rounded once on store --, the same argument lists, configuration space and refusals
+ * (all before any device work), with `dim` required to be 320 (MSIM_EUNSUPPORTED otherwise).  An item whose offsets fall outside
+ * 0 .. n_rows or run backwards is written as NaN.  No float atomics: an item's bits do not depend on the other items of the
+ * launch or on reruns.  The encodings are scored by msim_fde_scores, which depends on F alone.  Asynchronous on `stream`, no
+ * allocation, no host synchronisation: hipGraph-capturable.
+ */
+int msim_fdew_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim,
+                          const float *G, const float *S, int reps, int ksim, int dproj, int fill_empty,
+                          void *out, uint8_t *codes /* or NULL */, void *stream);
+int msim_fdew_encode_queries(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t n_rows, int dim,
+                             const float *G, const float *S, int reps, int ksim, int dproj,
+                             void *out, uint8_t *codes /* or NULL */, void *stream);
 
 /*
  * INT8 TOKEN-LEVEL INDEX (int8_index.hip): an int8 copy of a packed corpus, scored token by token on int8 MFMAs -- a first stage

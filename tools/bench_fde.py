@@ -13,6 +13,12 @@ Legs, each timed with device events after a warm-up:
   * recall: recall@10 against the exact search on the planted 10 000-page set of tools/bench_rerank.py:planted_recall, for each m,
     beside the pooled prefilter at m = 100 (reported, not gated; the encoding is not tuned on this set).
 Kernel times come from a separate `rocprofv3 --kernel-trace --stats` run of this script.
+
+    python tools/bench_fde.py --dim 320 [--out FILE] [--summary profiles/fde_wide_summary.md] [--legs build,stage1,search,recall]
+
+--dim 320 measures the 320-wide index (msim_fdew_*, colpali_amd.FdeWideIndex) on the shard of tools/bench_fp4.py --dim 320
+(50 000 x 1024 x 320 bf16 by default), the variants of a leg alternating call by call in one timed loop (median and range): see
+`main_wide`.
 """
 from __future__ import annotations
 
@@ -74,9 +80,143 @@ def recall_leg(amd, dev, n_docs, k=10):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------ width 320
+WIDE_M1 = (1000, 4000)
+N_REFINE = 100
+POOLED_LEN = 343
+
+
+def wide_recall_leg(amd, dev, n_docs, config, k=10):
+    """recall@10 against the exact search on the planted set at width 320 (tools/bench_fp4.py: wide_planted)"""
+    from tools.bench_fp4 import wide_planted
+
+    full, pooled, pq = wide_planted(amd, dev, n_docs)
+    r = amd.ShardedRetriever(full)
+    exact = r.search(pq, k=k)[1].tolist()
+    fde, f4 = amd.FdeWideIndex.build(full, config), amd.Fp4WideIndex.build(full)
+
+    def hits(**kw):
+        got = r.search(pq, k=k, **kw)[1].tolist()
+        return sum(len(set(a) & set(b)) for a, b in zip(exact, got)) / (len(pq) * k)
+
+    out = {"docs": n_docs, "queries": len(pq), "k": k, "n_refine": N_REFINE, "pooled_rows_per_doc": float(pooled.blob.shape[0]) / n_docs,
+           "fde_wide": {str(m): hits(prefilter=fde, n_candidates=m) for m in MS},
+           "pooled_corpus": {str(m): hits(prefilter=pooled, n_candidates=m) for m in MS},
+           "fp4_wide_m100": hits(prefilter=f4, n_candidates=100)}
+    for m1 in WIDE_M1:
+        out[f"fde_wide_refine_m{m1}"] = hits(prefilter=fde, n_candidates=m1, refine=f4, n_refine=N_REFINE)
+    return out
+
+
+def _rng(v):
+    return f"{v['median_ms']:.2f} ({v['min_ms']:.2f} – {v['max_ms']:.2f})"
+
+
+def wide_summary(res):
+    L = ["# FDE index at width 320: measured on one MI355X", "",
+         f"`tools/bench_fde.py --dim 320 --steps {res['steps']} --warmup {res['warmup']}` on the 320-wide shard ({res['docs']} pages × "
+         f"{res['doc_len']} rows, bf16), queries of {res['q_len']} tokens, configuration R = {res['config']['reps']}, k_sim = "
+         f"{res['config']['ksim']}, d_proj = {res['config']['dproj']} (F = {res['F']}).  The variants of a leg alternate call by call in "
+         "one timed loop; median ms, with the range in brackets.", ""]
+    if "build" in res:
+        b = res["build"]
+        L += ["## Build", "", f"`FdeWideIndex.build`: {_rng(b['fde_wide_build'])} ms; the bound (the shard's rows + the index at "
+              f"{res['hbm_peak_GBps'] / 1000:.0f} TB/s) is {b['bound_ms']:.1f} ms.  Beside it in the loop, `Fp4WideIndex.build`: "
+              f"{_rng(b['fp4_wide_build'])} ms.", ""]
+    if "stage1" in res:
+        L += ["## Stage 1: query encoder + scorer", "", "| queries | `fde_wide_scores` | scorer alone | query encoder alone | bound |",
+              "|---|---|---|---|---|"]
+        for n_q, leg in res["stage1"].items():
+            L.append(f"| {n_q} × {res['q_len']} | {_rng(leg['fde_wide_scores'])} | {_rng(leg['scorer_only'])} | "
+                     f"{_rng(leg['encode_queries'])} | {leg['bound_ms']:.2f} |")
+        L.append("")
+    if "search" in res:
+        L += [f"## Search at 1000 × {res['q_len']}, k = 10, all alternating in one loop", "", "| variant | ms |", "|---|---|"]
+        L += [f"| `{name}` | {_rng(v)} |" for name, v in res["search"].items() if isinstance(v, dict)]
+        L.append("")
+    if "recall" in res:
+        r = res["recall"]
+        L += [f"## Recall@10 against the exact search, planted {r['docs']}-page set at width 320 ({r['queries']} queries)", "",
+              "| first stage | " + " | ".join(f"m = {m}" for m in MS) + " |", "|---|" + "---|" * len(MS),
+              "| `FdeWideIndex` | " + " | ".join(f"{r['fde_wide'][str(m)]:.3f}" for m in MS) + " |",
+              f"| pooled pages ({r['pooled_rows_per_doc']:.0f} rows) | " + " | ".join(f"{r['pooled_corpus'][str(m)]:.3f}" for m in MS) + " |",
+              "", f"`Fp4WideIndex` at m = 100: {r['fp4_wide_m100']:.3f}.  The cascade `prefilter=<FdeWideIndex>, refine=<Fp4WideIndex>, "
+              f"n_refine={r['n_refine']}`: " + ", ".join(f"{r[f'fde_wide_refine_m{m1}']:.3f} at n_candidates = {m1}" for m1 in WIDE_M1) + ".", ""]
+    return "\n".join(L)
+
+
+def main_wide(args):
+    """--dim 320: build beside the FP4 build; encoder + scorer at 4 and 1000 queries; the two-stage search at m = 100 / 400 / 1000 and
+    the cascade through the FP4 rows at n_candidates = 1000 / 4000, beside the pooled prefilter and the FP4 first stage; recall."""
+    from tools.bench_binary import alternating
+    from tools.bench_rerank import make_queries_dim, make_shard_dim
+
+    import colpali_amd as amd
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    amd._lib.lib()
+    legs = set(args.legs.split(","))
+    docs = args.docs if args.docs is not None else 50_000
+    t0 = time.perf_counter()
+    config = amd.FdeConfig()
+    F = config.dim
+    res = {"tool": "bench_fde", "dim": 320, "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len, "F": F, "steps": args.steps,
+           "warmup": args.warmup, "config": {"reps": config.reps, "ksim": config.ksim, "dproj": config.dproj, "fill_empty": config.fill_empty},
+           "hbm_peak_GBps": HBM_PEAK_GBS, "mfma_peak_TFLOPs": MFMA_PEAK_TFLOPS}
+    if legs & {"build", "stage1", "search"}:
+        corpus = make_shard_dim(docs, args.doc_len, 320, dev, seed=1234)
+        index = amd.FdeWideIndex.build(corpus, config)
+        if "build" in legs:
+            b = alternating({"fde_wide_build": lambda: amd.FdeWideIndex.build(corpus, config),
+                             "fp4_wide_build": lambda: amd.Fp4WideIndex.build(corpus)}, max(3, args.steps // 3), 1)
+            b["bound_ms"] = (corpus.nbytes + index.Fd.numel() * 2) / (HBM_PEAK_GBS * 1e9) * 1e3
+            res["build"] = b
+        if "stage1" in legs:
+            res["stage1"] = {}
+            for n_q in (4, 1000):
+                pq = amd.pack_queries(make_queries_dim(n_q, args.q_len, 320, dev, seed=99), dev, compact=False)
+                out = torch.empty((n_q, len(index)), dtype=torch.float32, device=dev)
+                Fq = amd.fde_wide_encode_queries(pq, index)
+                leg = alternating({"fde_wide_scores": lambda: amd.fde_wide_scores(pq, index, out=out),
+                                   "scorer_only": lambda: amd.fde.scores_from_encodings(Fq, index.Fd, out=out),
+                                   "encode_queries": lambda: amd.fde_wide_encode_queries(pq, index)}, args.steps, args.warmup)
+                leg["bound_ms"] = stage1_bound_ms(n_q, len(index), F)
+                res["stage1"][str(n_q)] = leg
+                del out
+        if "search" in legs:
+            pq = amd.pack_queries(make_queries_dim(1000, args.q_len, 320, dev, seed=99), dev, compact=False)
+            coarse = make_shard_dim(docs, POOLED_LEN, 320, dev, seed=4321)
+            f4 = amd.Fp4WideIndex.build(corpus)
+            r = amd.ShardedRetriever(corpus)
+            variants = {f"fde_wide_m{m}": (lambda m=m: r.search(pq, k=10, prefilter=index, n_candidates=m)) for m in MS}
+            for m1 in WIDE_M1:
+                variants[f"fde_wide_m{m1}_refine_m{N_REFINE}"] = lambda m1=m1: r.search(pq, k=10, prefilter=index, n_candidates=m1, refine=f4,
+                                                                                        n_refine=N_REFINE)
+            variants["pooled_m100"] = lambda: r.search(pq, k=10, prefilter=coarse, n_candidates=100)
+            variants["fp4_wide_m100"] = lambda: r.search(pq, k=10, prefilter=f4, n_candidates=100)
+            res["search"] = alternating(variants, max(3, args.steps // 2), 1)
+            del coarse, f4
+        del corpus, index
+        torch.cuda.empty_cache()
+    if "recall" in legs:
+        res["recall"] = wide_recall_leg(amd, dev, args.recall_docs, config)
+    res["wall_s"] = time.perf_counter() - t0
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    if args.summary:
+        with open(args.summary, "w") as f:
+            f.write(wide_summary(res) + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--docs", type=int, default=125_000)
+    ap.add_argument("--dim", type=int, default=128, choices=(128, 320), help="320: the FdeWideIndex on the 320-wide shard")
+    ap.add_argument("--summary", default=None, help="--dim 320: write the markdown summary here")
+    ap.add_argument("--docs", type=int, default=None, help="default: 125 000 at width 128, 50 000 at width 320 (the same bytes)")
     ap.add_argument("--doc-len", type=int, default=1024)
     ap.add_argument("--coarse-len", type=int, default=343)
     ap.add_argument("--q-len", type=int, default=32)
@@ -88,6 +228,11 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_fde.py needs an MI355X (there is no CPU fallback)")
+    if args.dim == 320:
+        if args.legs == "build,stage1,two_stage,recall":
+            args.legs = "build,stage1,search,recall"
+        return main_wide(args)
+    args.docs = 125_000 if args.docs is None else args.docs
     import colpali_amd as amd
 
     dev = torch.device("cuda:0")
