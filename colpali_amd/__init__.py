@@ -49,7 +49,8 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
   * save / load / verify_file     -- every shard and index class as one flat, versioned file (no pickle), streamed through the pinned
                                      double buffer and verified chunk by chunk by a digest computed on the device (msim_digest)
   * embedding_head / CorpusWriter <- the projection / L2-norm / mask tail of every Col* forward
-                                     (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus
+                                     (models/paligemma/colpali/modeling_colpali.py:67-77), writing the packed corpus;
+                                     width 128, and width 320 (ColQwen3: the width is the weight's, CorpusWriter(width=320))
 The compute lives in hand-written HIP kernels behind a C ABI (include/maxsim.h,
 colpali_amd/csrc/); this package is the thin host-side mirror of the reference interface.
 """

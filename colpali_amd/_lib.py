@@ -156,6 +156,10 @@ def lib() -> ctypes.CDLL:
     L.msim_embed_head_writer_map.restype = i32
     L.msim_embed_head_bwd.argtypes = [i32, vp, vp, vp, i64, i32, vp, vp]
     L.msim_embed_head_bwd.restype = i32
+    L.msim_embed_head_wide.argtypes = [i32, vp, i64, i32, vp, vp, i32, vp, vp, i64, vp]
+    L.msim_embed_head_wide.restype = i32
+    L.msim_embed_head_wide_bwd.argtypes = [i32, vp, vp, vp, i64, i32, vp, vp]
+    L.msim_embed_head_wide_bwd.restype = i32
     L.msim_sim_matrix.argtypes = [i32, vp, i32, vp, i32, i32, vp, i64, u32, vp]
     L.msim_sim_matrix.restype = i32
     L.msim_pool_cluster.argtypes = [i32, vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]

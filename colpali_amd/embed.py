@@ -10,12 +10,14 @@ Reference lines (identical in every model family):
 and the road from there to the scorer (README.md:121-126: `torch.unbind(embeddings.to("cpu"))`, later
 `pad_sequence` + H2D per block inside score_multi_vector, processing_utils.py:172-178).
 
-`embedding_head`  -- dense drop-in for those lines: same [B, S, 128] tensor.
+`embedding_head`  -- dense drop-in for those lines: same [B, S, 128] tensor ([B, S, 320] for a ColQwen3 projection).
 `CorpusWriter`    -- the MI355X-native road: rows go straight from the model's hidden states into the resident
                      packed corpus the MaxSim kernels stream; masked positions are dropped and replaced by the
                      per-document clamp0 flag (a zero row and "similarity 0 takes part in the max" are the same
                      thing), so the corpus holds real patches only and never leaves the GPU.
 All arithmetic runs in colpali_amd/csrc/embed_head.hip behind msim_embed_head (include/maxsim.h); no torch fallback.
+Width 320 (ColQwen3, `self.dim = 320`) runs a kernel of its own, colpali_amd/csrc/embed_head_wide.hip behind
+msim_embed_head_wide; the width is read off the weight, the row maps are the same.
 """
 from __future__ import annotations
 
@@ -27,22 +29,33 @@ from . import _lib
 from .corpus import PackedCorpus, block_clamp0
 
 HEAD_DIM = 128
+HEAD_DIMS = (128, 320)          # 320: ColQwen3 (msim_embed_head_wide, hidden sizes up to 4096)
+_WIDE_DIM = 320
+_WIDE_MAX_HIDDEN = 4096
 _TILE = 256
 
 
 def _check(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], mask: torch.Tensor) -> None:
     if hidden.dim() != 3:
         raise ValueError("hidden_states must be [batch, sequence, hidden]")
+    wrong_weight = (f"weight must be [{HEAD_DIMS[0]}, hidden] or [{HEAD_DIMS[1]}, hidden] with the dtype/device of the hidden states "
+                    f"(got {tuple(weight.shape)})")
+    if weight.dim() == 2 and weight.shape[0] not in HEAD_DIMS:      # a width no kernel is built for: an error on any machine
+        raise ValueError(wrong_weight)
     if hidden.device.type != "cuda":
         raise RuntimeError("colpali_amd.embedding_head runs on an MI355X only (no CPU fallback)")
     if hidden.dtype not in (torch.bfloat16, torch.float16):
         raise NotImplementedError(f"embedding head: hidden states of dtype {hidden.dtype}; bf16 / fp16 only")
-    if weight.shape != (HEAD_DIM, hidden.shape[2]) or weight.dtype != hidden.dtype or weight.device != hidden.device:
-        raise ValueError(f"weight must be [{HEAD_DIM}, hidden] with the dtype/device of the hidden states")
-    if bias is not None and (bias.shape != (HEAD_DIM,) or bias.dtype != hidden.dtype or bias.device != hidden.device):
-        raise ValueError(f"bias must be [{HEAD_DIM}] with the dtype/device of the hidden states")
+    if (weight.dim() != 2 or weight.shape[0] not in HEAD_DIMS or weight.shape[1] != hidden.shape[2] or weight.dtype != hidden.dtype
+            or weight.device != hidden.device):
+        raise ValueError(wrong_weight)
+    width = weight.shape[0]
+    if bias is not None and (bias.shape != (width,) or bias.dtype != hidden.dtype or bias.device != hidden.device):
+        raise ValueError(f"bias must be [{width}] with the dtype/device of the hidden states")
     if hidden.shape[2] % 64 != 0:
         raise NotImplementedError(f"embedding head: hidden size {hidden.shape[2]} is not a multiple of 64")
+    if width == _WIDE_DIM and hidden.shape[2] > _WIDE_MAX_HIDDEN:
+        raise NotImplementedError(f"embedding head of width {_WIDE_DIM}: hidden size {hidden.shape[2]} is above {_WIDE_MAX_HIDDEN}")
     if mask.shape != hidden.shape[:2]:
         raise ValueError("attention_mask must be [batch, sequence]")
 
@@ -52,11 +65,13 @@ def _launch(hidden: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Ten
     L = _lib.lib()
     x = hidden.contiguous()
     M, H = x.shape[0] * x.shape[1], x.shape[2]
+    width = weight.shape[0]
+    entry, name = (L.msim_embed_head_wide, "msim_embed_head_wide") if width == _WIDE_DIM else (L.msim_embed_head, "msim_embed_head")
     with torch.cuda.device(x.device):
-        rc = L.msim_embed_head(_lib.dtype_code(x.dtype), _lib.ptr(x), M, H, _lib.ptr(weight.contiguous()),
-                               _lib.ptr(bias.contiguous() if bias is not None else None), HEAD_DIM, _lib.ptr(row_map),
-                               _lib.ptr(out), out.stride(0), _lib.current_stream_handle(x.device))
-    _lib.check(rc, "msim_embed_head")
+        rc = entry(_lib.dtype_code(x.dtype), _lib.ptr(x), M, H, _lib.ptr(weight.contiguous()),
+                   _lib.ptr(bias.contiguous() if bias is not None else None), width, _lib.ptr(row_map),
+                   _lib.ptr(out), out.stride(0), _lib.current_stream_handle(x.device))
+    _lib.check(rc, name)
 
 
 _MASK_KINDS = {torch.bool: 0, torch.uint8: 0, torch.int8: 0, torch.int16: 1, torch.int32: 2, torch.int64: 3, torch.float32: 4,
@@ -93,17 +108,18 @@ def _dense_row_map(attention_mask: torch.Tensor, extra_mask: Optional[torch.Tens
 class _EmbeddingHeadFn(torch.autograd.Function):
     """The fused head inside a training graph (modeling_colpali.py:65-78 is part of the graph the reference trainers
     back-propagate through, trainer/contrastive_trainer.py:135-162).  Forward = the fused kernel.  Backward: the Linear
-    output is recomputed by a library GEMM, the norm / mask Jacobian runs in `msim_embed_head_bwd` (fp32 inside, one
-    rounding), and dX = dproj W, dW = dproj^T X, db = sum dproj are library GEMMs / a reduction again -- the same three
+    output is recomputed by a library GEMM, the norm / mask Jacobian runs in `msim_embed_head_bwd` (`msim_embed_head_wide_bwd`
+    at width 320; fp32 inside, one rounding), and dX = dproj W, dW = dproj^T X, db = sum dproj are library GEMMs / a reduction again -- the same three
     products torch's own autograd runs for nn.Linear."""
 
     @staticmethod
     def forward(ctx, hidden, weight, bias, row_map):
         B, S, _ = hidden.shape
-        out = torch.empty((B * S, HEAD_DIM), dtype=hidden.dtype, device=hidden.device)
+        width = weight.shape[0]
+        out = torch.empty((B * S, width), dtype=hidden.dtype, device=hidden.device)
         _launch(hidden, weight, bias, row_map, out)
         ctx.save_for_backward(hidden, weight, bias, row_map)
-        return out.view(B, S, HEAD_DIM)
+        return out.view(B, S, width)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -111,16 +127,19 @@ class _EmbeddingHeadFn(torch.autograd.Function):
         hidden, weight, bias, row_map = ctx.saved_tensors
         B, S, H = hidden.shape
         M = B * S
+        width = weight.shape[0]
         x2 = hidden.reshape(M, H)
-        g = grad_out.reshape(M, HEAD_DIM).to(hidden.dtype).contiguous()
+        g = grad_out.reshape(M, width).to(hidden.dtype).contiguous()
         with torch.autocast("cuda", enabled=False):
             proj = torch.nn.functional.linear(x2, weight, bias)                  # :67 again: a plain library GEMM
             dproj = torch.empty_like(proj)
             L = _lib.lib()
+            entry, name = ((L.msim_embed_head_wide_bwd, "msim_embed_head_wide_bwd") if width == _WIDE_DIM
+                           else (L.msim_embed_head_bwd, "msim_embed_head_bwd"))
             with torch.cuda.device(hidden.device):
-                rc = L.msim_embed_head_bwd(_lib.dtype_code(hidden.dtype), _lib.ptr(proj), _lib.ptr(g), _lib.ptr(row_map), M,
-                                           HEAD_DIM, _lib.ptr(dproj), _lib.current_stream_handle(hidden.device))
-            _lib.check(rc, "msim_embed_head_bwd")
+                rc = entry(_lib.dtype_code(hidden.dtype), _lib.ptr(proj), _lib.ptr(g), _lib.ptr(row_map), M,
+                           width, _lib.ptr(dproj), _lib.current_stream_handle(hidden.device))
+            _lib.check(rc, name)
             d_hidden = (dproj @ weight).view(B, S, H) if ctx.needs_input_grad[0] else None
             d_weight = dproj.t() @ x2 if ctx.needs_input_grad[1] else None
             d_bias = dproj.sum(dim=0) if bias is not None and ctx.needs_input_grad[2] else None
@@ -130,6 +149,7 @@ class _EmbeddingHeadFn(torch.autograd.Function):
 def embedding_head(hidden_states: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                    attention_mask: torch.Tensor, extra_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Dense drop-in for modeling_colpali.py:67-77: [B, S, hidden] -> [B, S, 128] (unit rows, masked rows zero).
+    The width is the weight's: a [320, hidden] weight (ColQwen3) gives [B, S, 320]; any other width is a ValueError.
 
     `extra_mask` is the optional image-token mask of `mask_non_image_embeddings` ([B, S] or [B, S, 1]).
     Differentiable: when autograd is recording and the hidden states, the weight or the bias require a gradient, the
@@ -140,9 +160,10 @@ def embedding_head(hidden_states: torch.Tensor, weight: torch.Tensor, bias: Opti
     if torch.is_grad_enabled() and (hidden_states.requires_grad or weight.requires_grad
                                     or (bias is not None and bias.requires_grad)):
         return _EmbeddingHeadFn.apply(hidden_states, weight, bias, row_map)
-    out = torch.empty((B * S, HEAD_DIM), dtype=hidden_states.dtype, device=hidden_states.device)
+    width = weight.shape[0]
+    out = torch.empty((B * S, width), dtype=hidden_states.dtype, device=hidden_states.device)
     _launch(hidden_states, weight, bias, row_map, out)
-    return out.view(B, S, HEAD_DIM)
+    return out.view(B, S, width)
 
 
 class CorpusWriter:
@@ -153,11 +174,17 @@ class CorpusWriter:
     (README.md:121-126) with the same `batch_size` blocking: a page's masked positions are zero rows there, here they
     are dropped and the page carries the clamp0 flag; pages of different padded lengths sharing a scorer block get the
     flag through the same `block_clamp0` rule as pack_passages.
+
+    `width` is the embedding width of the corpus, 128 or 320 (ColQwen3): every appended weight must have that many rows.
     """
 
-    def __init__(self, capacity_rows: int, device, dtype: torch.dtype = torch.bfloat16, score_batch_size: Optional[int] = 128):
+    def __init__(self, capacity_rows: int, device, dtype: torch.dtype = torch.bfloat16, score_batch_size: Optional[int] = 128,
+                 width: int = HEAD_DIM):
+        if width not in HEAD_DIMS:
+            raise ValueError(f"CorpusWriter: width {width}; the embedding head writes rows of {HEAD_DIMS[0]} or {HEAD_DIMS[1]} elements")
         self.device = torch.device(device)
-        self.blob = torch.empty((max(capacity_rows, 1), HEAD_DIM), dtype=dtype, device=self.device)
+        self.width = width
+        self.blob = torch.empty((max(capacity_rows, 1), width), dtype=dtype, device=self.device)
         self.capacity = capacity_rows
         self.score_batch_size = score_batch_size
         self._rows_dev = torch.zeros((), dtype=torch.int64, device=self.device)   # exact count, stays on the device
@@ -171,6 +198,8 @@ class CorpusWriter:
         recorded for a gradient are refused instead of silently detached (call it under torch.no_grad(), as README.md:121
         does for inference, or use `embedding_head`, which is differentiable)."""
         _check(hidden_states, weight, bias, attention_mask)
+        if weight.shape[0] != self.width:
+            raise ValueError(f"CorpusWriter of width {self.width}: the projection weight has {weight.shape[0]} rows")
         if torch.is_grad_enabled() and (hidden_states.requires_grad or weight.requires_grad
                                         or (bias is not None and bias.requires_grad)):
             raise RuntimeError("CorpusWriter.append writes into the resident corpus and has no backward: call it under "

@@ -543,6 +543,21 @@ int msim_embed_head_bwd(int dtype, const void *proj, const void *grad_out, const
                         void *dproj, void *stream);
 
 /*
+ * The embedding head at width 320 (ColQwen3: nn.Linear(hidden, 320), the same three lines behind it): msim_embed_head with
+ * n_out = 320, a kernel of its own.  Same rounding chain, same row map (built by msim_embed_head_row_map / _writer_map, which do
+ * not depend on the width).
+ *   X [M, H] bf16|f16 (H a multiple of 64, <= 4096), W [320, H], bias [320] or NULL (same dtype); X, W and out 16-byte aligned
+ *   out [rows, ld_out] same dtype as X, ld_out >= 320 elements and a multiple of 8 (whole 8-byte stores: one store form only).
+ * msim_embed_head_wide_bwd: msim_embed_head_bwd for proj, grad_out, dproj of [M, 320] (dense rows, 16-byte aligned).
+ * MSIM_EUNSUPPORTED for n_out != 320 (msim_embed_head / msim_embed_head_bwd take 128), other dtypes, H % 64 != 0 or H > 4096, and
+ * more rows than an int32 row map addresses; MSIM_EINVAL for null pointers, negative sizes, misaligned buffers and a bad ld_out.
+ */
+int msim_embed_head_wide(int dtype, const void *X, int64_t M, int H, const void *W, const void *bias, int n_out,
+                         const int32_t *row_map, void *out, int64_t ld_out, void *stream);
+int msim_embed_head_wide_bwd(int dtype, const void *proj, const void *grad_out, const int32_t *row_map, int64_t M, int n_out,
+                             void *dproj, void *stream);
+
+/*
  * Plain similarity matrix, no reduction:   out[i, j] = <A[i, :], B[j, :]>   (fp32 accumulate)
  * Replaces colpali_engine/utils/processing_utils.py:126  torch.einsum("bd,cd->bc", qs, ps)   (score_single_vector, the
  * bi-encoder scorer of the same processor class) and the contraction of
