@@ -30,6 +30,9 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      per row, three chained block-scaled MFMAs per 16 rows x 16 tokens: a first stage for prefilter=
   * fp4_wide_rerank_scores        -- its list form: the FP4 score of the pages a candidate list names (161 bytes per row read, the
                                      scan's bits); search(prefilter=pooled, n_candidates=m1, refine=fp4_wide_index, n_refine=m2)
+  * fp6_wide_scores / fp6_wide_rerank_scores -- the same Fp4WideIndex scored with e2m3 (FP6) query tokens, scan and list form:
+                                     ShardedRetriever(..., fp4_wide_score_fn=fp6_wide_scores,
+                                     fp4_wide_rerank_fn=fp6_wide_rerank_scores)
   * FdeWideIndex / fde_wide_scores -- the fixed dimensional encodings of a 320-wide (ColQwen3) shard, by an encoder of its own and
                                      the scorer of fde_scores: the one-GEMM first stage at width 320, and the front of
                                      search(prefilter=fde_wide, n_candidates=m1, refine=fp4_wide_index, n_refine=m2)
@@ -63,7 +66,7 @@ from .embed import CorpusWriter, embedding_head
 from .fp4_index import (Fp4Index, fp4_quantize_queries, fp4_rerank_scores, fp4_scores, fp4_scores_from_codes, fp6_quantize_queries,
                         fp6_rerank_scores, fp6_scores)
 from .fp4_wide_index import (Fp4WideIndex, fp4_wide_quantize_queries, fp4_wide_rerank_scores, fp4_wide_scores,
-                             fp4_wide_scores_from_codes)
+                             fp4_wide_scores_from_codes, fp6_wide_quantize_queries, fp6_wide_rerank_scores, fp6_wide_scores)
 from .fde import FdeConfig, FdeIndex, encode_queries, fde_scores
 from .fde_wide import FdeWideIndex, fde_wide_encode_queries, fde_wide_scores
 from .filter import PageFilter
@@ -117,6 +120,9 @@ __all__ = [
     "fp4_wide_rerank_scores",
     "fp4_wide_scores_from_codes",
     "fp4_wide_quantize_queries",
+    "fp6_wide_scores",
+    "fp6_wide_quantize_queries",
+    "fp6_wide_rerank_scores",
     "CentroidIndex",
     "centroid_scores",
     "train_centroids",

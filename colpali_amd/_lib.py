@@ -218,11 +218,15 @@ def lib() -> ctypes.CDLL:
     L.msim_f6_encode_rows.restype = i32
     L.msim_f4_scores_q6.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp]
     L.msim_f4_scores_q6.restype = i32
+    L.msim_f6w_encode_rows.argtypes = [i32, vp, i64, i32, vp, vp, vp]
+    L.msim_f6w_encode_rows.restype = i32
+    L.msim_f4w_scores_q6.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i64, vp]
+    L.msim_f4w_scores_q6.restype = i32
     L.msim_f4_candidates_plan.argtypes = [i32, i32, i32, vp]
     L.msim_f4_candidates_plan.restype = i32
     L.msim_f4w_candidates_plan.argtypes = [i32, i32, i32, vp]
     L.msim_f4w_candidates_plan.restype = i32
-    for entry in (L.msim_f4_candidates, L.msim_f4_candidates_q6, L.msim_f4w_candidates):
+    for entry in (L.msim_f4_candidates, L.msim_f4_candidates_q6, L.msim_f4w_candidates, L.msim_f4w_candidates_q6):
         entry.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, i32, i64, i32, vp, i32, i64, i64, vp, i64, vp, vp]
         entry.restype = i32
     L.msim_cent_encode_docs.argtypes = [i32, vp, vp, i32, i64, i32, i32, vp, i32, vp, vp, vp]

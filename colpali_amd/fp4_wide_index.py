@@ -14,6 +14,12 @@ pages a candidate list names and of no other, bit for bit what the scan gives fo
 of a three-stage search on a 320-wide shard -- a cheap stage 1 makes a long list, the 161-byte FP4 rows cut it, the exact rerank
 orders the survivors: `ShardedRetriever.search(prefilter=pooled, n_candidates=m1, refine=index, n_refine=m2)`.
 
+`fp6_wide_scores` / `fp6_wide_rerank_scores` score the same index with the query tokens coded as OCP e2m3 (FP6: 240 code bytes
+and a scale byte per token, msim_f6w_encode_rows / msim_f4w_scores_q6 / msim_f4w_candidates_q6).  The pages stay FP4 and the index
+is untouched: the instruction takes a format per operand, so the first stage loses most of the query side's quantisation error for
+nothing stored.  They are the functions to hand to a retriever:
+`ShardedRetriever(shard, fp4_wide_score_fn=fp6_wide_scores, fp4_wide_rerank_fn=fp6_wide_rerank_scores)`.
+
 It is the sibling of `Fp4Index` (width 128), which keeps refusing width 320 as this class refuses width 128.
 """
 from __future__ import annotations
@@ -28,25 +34,37 @@ from .scoring import _require_gpu
 
 DIM = 320
 ROW_BYTES = DIM // 2
+Q6_ROW_BYTES = DIM * 6 // 8                       # an e2m3 query token: 320 6-bit fields
+QUERY_CODES = {"e2m1": ROW_BYTES, "e2m3": Q6_ROW_BYTES}   # query_code -> code bytes per token
 
 
-def _check_format(dtype: torch.dtype, width: int, what: str) -> None:
+def _check_format(dtype: torch.dtype, width: int, what: str, query_code: str = "e2m1") -> None:
     if dtype not in (torch.bfloat16, torch.float16) or width != DIM:
-        hint = "; a 128-wide corpus takes Fp4Index / fp4_scores" if width == 128 else ""
+        narrow = "fp6_scores" if query_code == "e2m3" else "fp4_scores"
+        hint = f"; a 128-wide corpus takes Fp4Index / {narrow}" if width == 128 else ""
         raise NotImplementedError(f"the wide fp4 index takes bfloat16 / float16 {what} of width {DIM} (got {dtype}, width {width})"
                                   f"{hint}")
 
 
-def _encode_rows(rows_t: torch.Tensor, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """codes uint8 [rows, 160] and scales uint8 [rows] of a [rows, 320] bf16 / f16 device tensor: one launch, asynchronous"""
+def _check_query_code(query_code: str) -> int:
+    """code bytes per token of a query code"""
+    if query_code not in QUERY_CODES:
+        raise ValueError(f"query_code must be 'e2m1' or 'e2m3' (got {query_code!r})")
+    return QUERY_CODES[query_code]
+
+
+def _encode_rows(rows_t: torch.Tensor, dev: torch.device, code: str = "e2m1") -> Tuple[torch.Tensor, torch.Tensor]:
+    """codes uint8 [rows, 160] (e2m1) or [rows, 240] (e2m3) and scales uint8 [rows] of a [rows, 320] bf16 / f16 device tensor: one
+    launch, asynchronous"""
     rows_t = rows_t if rows_t.is_contiguous() else rows_t.contiguous()
     rows = int(rows_t.shape[0])
-    codes = torch.empty((rows, ROW_BYTES), dtype=torch.uint8, device=dev)
+    name = "msim_f6w_encode_rows" if code == "e2m3" else "msim_f4w_encode_rows"
+    codes = torch.empty((rows, QUERY_CODES[code]), dtype=torch.uint8, device=dev)
     scales = torch.empty((rows,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = _lib.lib().msim_f4w_encode_rows(_lib.dtype_code(rows_t.dtype), _lib.ptr(rows_t), rows, DIM, _lib.ptr(codes),
-                                             _lib.ptr(scales), _lib.current_stream_handle(dev))
-    _lib.check(rc, "msim_f4w_encode_rows")
+        rc = getattr(_lib.lib(), name)(_lib.dtype_code(rows_t.dtype), _lib.ptr(rows_t), rows, DIM, _lib.ptr(codes), _lib.ptr(scales),
+                                       _lib.current_stream_handle(dev))
+    _lib.check(rc, name)
     return codes, scales
 
 
@@ -119,19 +137,32 @@ def fp4_wide_quantize_queries(queries, device: Optional[torch.device] = None) ->
     return _quantize_packed(queries)
 
 
-def _quantize_packed(q: PackedQueries) -> Tuple[torch.Tensor, torch.Tensor]:
+def fp6_wide_quantize_queries(queries, device: Optional[torch.device] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-token e2m3 codes uint8 [T, 240] and scales uint8 [T] of `queries` (as `fp4_wide_quantize_queries` takes them), in the
+    packed token order: dimension k is the 6-bit field (sign << 5 | code) at bit 6 k of the little-endian 240-byte row."""
+    if not isinstance(queries, PackedQueries):
+        if device is None:
+            device = queries.device if isinstance(queries, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        queries = _as_packed(queries, device, layout="flat")
+    return _quantize_packed(queries, "e2m3")
+
+
+def _quantize_packed(q: PackedQueries, code: str = "e2m1") -> Tuple[torch.Tensor, torch.Tensor]:
     dev = _require_gpu(q.device)
     _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
-    return _encode_rows(q.tokens, dev)
+    return _encode_rows(q.tokens, dev, code)
 
 
 def fp4_wide_scores_from_codes(q_codes: torch.Tensor, q_scales: torch.Tensor, q_offsets: torch.Tensor, max_q_tokens: int,
-                               index: Fp4WideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                               index: Fp4WideIndex, out: Optional[torch.Tensor] = None, *, query_code: str = "e2m1") -> torch.Tensor:
     """fp32 [n_q, len(index)] (msim_f4w_scores) from coded queries (`fp4_wide_quantize_queries`): codes uint8 [T, 160], scales
-    uint8 [T], offsets int32 [n_q + 1] on the device and a host bound on every query's token count."""
-    if q_codes.dtype != torch.uint8 or q_codes.dim() != 2 or q_codes.shape[1] != ROW_BYTES or not q_codes.is_contiguous():
-        raise ValueError(f"query codes must be a contiguous uint8 [tokens, {ROW_BYTES}] tensor (got {q_codes.dtype} "
+    uint8 [T], offsets int32 [n_q + 1] on the device and a host bound on every query's token count.  `query_code="e2m3"`: codes
+    uint8 [T, 240] from `fp6_wide_quantize_queries` (msim_f4w_scores_q6)."""
+    width = _check_query_code(query_code)
+    if q_codes.dtype != torch.uint8 or q_codes.dim() != 2 or q_codes.shape[1] != width or not q_codes.is_contiguous():
+        raise ValueError(f"{query_code} query codes must be a contiguous uint8 [tokens, {width}] tensor (got {q_codes.dtype} "
                          f"{list(q_codes.shape)})")
+    name = "msim_f4w_scores_q6" if query_code == "e2m3" else "msim_f4w_scores"
     dev = _require_gpu(index.device)
     for t in (q_codes, q_scales, q_offsets):
         if t.device != dev:
@@ -142,56 +173,68 @@ def fp4_wide_scores_from_codes(q_codes: torch.Tensor, q_scales: torch.Tensor, q_
     elif out.shape != (n_q, n) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"out must be a contiguous fp32 [{n_q}, {n}] tensor on {dev}")
     with torch.cuda.device(dev):
-        rc = _lib.lib().msim_f4w_scores(_lib.ptr(q_codes), _lib.ptr(q_scales), _lib.ptr(q_offsets), n_q, int(q_codes.shape[0]),
-                                        int(max_q_tokens), _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets),
-                                        _lib.ptr(index.clamp0), n, int(index.codes.shape[0]), DIM, _lib.ptr(out), max(n, 1),
-                                        _lib.current_stream_handle(dev))
-    _lib.check(rc, "msim_f4w_scores")
+        rc = getattr(_lib.lib(), name)(_lib.ptr(q_codes), _lib.ptr(q_scales), _lib.ptr(q_offsets), n_q, int(q_codes.shape[0]),
+                                       int(max_q_tokens), _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets),
+                                       _lib.ptr(index.clamp0), n, int(index.codes.shape[0]), DIM, _lib.ptr(out), max(n, 1),
+                                       _lib.current_stream_handle(dev))
+    _lib.check(rc, name)
     return out
 
 
-def fp4_wide_scores(queries, index: Fp4WideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def fp4_wide_scores(queries, index: Fp4WideIndex, out: Optional[torch.Tensor] = None, *, query_code: str = "e2m1") -> torch.Tensor:
     """Approximate MaxSim of every query against every page of the index: fp32 [n_q, len(index)], column j = page
     index.id_base + j.  A score's bits depend on its query and page only.  Asynchronous on torch's current stream.  Given a
     `PackedQueries` it never synchronises with the host and is hipGraph-capturable: its only allocations are torch tensors (the
-    query codes and scales, and `out` when it is None), made on the current stream before the library calls."""
+    query codes and scales, and `out` when it is None), made on the current stream before the library calls.  `query_code`: how the
+    query tokens are coded, "e2m1" (as the pages) or "e2m3" (`fp6_wide_scores`)."""
+    _check_query_code(query_code)
     if not isinstance(index, Fp4WideIndex):
-        raise TypeError(f"fp4_wide_scores takes an Fp4WideIndex (got {type(index).__name__})")
+        hint = "; an Fp4Index of a 128-wide shard takes fp6_scores" if type(index).__name__ == "Fp4Index" and query_code == "e2m3" else ""
+        raise TypeError(f"fp4_wide_scores takes an Fp4WideIndex (got {type(index).__name__}){hint}")
     dev = index.device
     q = _as_packed(queries, dev, layout="flat")
-    _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
+    _check_format(q.dtype, int(q.tokens.shape[1]), "queries", query_code)
     if q.device != dev:
         raise ValueError("queries and index live on different devices")
     lens = q.lengths
     max_q = int(lens.max()) if lens.numel() else 0
-    codes, scales = _quantize_packed(q)
-    return fp4_wide_scores_from_codes(codes, scales, q.offsets, max_q, index, out=out)
+    codes, scales = _quantize_packed(q, query_code)
+    return fp4_wide_scores_from_codes(codes, scales, q.offsets, max_q, index, out=out, query_code=query_code)
+
+
+def fp6_wide_scores(queries, index: Fp4WideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`fp4_wide_scores` with the query tokens coded as e2m3 (FP6) against the same FP4 pages: a first stage with less query-side
+    quantisation error from the same index, bit for bit reproducible in the same way.  The stage-1 hook of a retriever on a
+    320-wide shard: `ShardedRetriever(shard, fp4_wide_score_fn=fp6_wide_scores)`.  A 128-wide shard takes `fp6_scores`."""
+    return fp4_wide_scores(queries, index, out, query_code="e2m3")
 
 
 MAX_RERANK_TOKENS = 128                            # the longest query of the list form (eight 16-token tiles in registers)
 
 
-def fp4_wide_rerank_scores(queries, index: Fp4WideIndex, candidates: torch.Tensor, *, out: Optional[torch.Tensor] = None
-                           ) -> Tuple[torch.Tensor, torch.Tensor]:
-    """The FP4 score of listed candidates at width 320 (include/maxsim.h: msim_f4w_candidates): (scores fp32 [n_q, m], ids int64
-    [n_q, m]).
+def fp4_wide_rerank_scores(queries, index: Fp4WideIndex, candidates: torch.Tensor, *, query_code: str = "e2m1",
+                           out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The FP4 score of listed candidates at width 320 (include/maxsim.h: msim_f4w_candidates, msim_f4w_candidates_q6): (scores
+    fp32 [n_q, m], ids int64 [n_q, m]).
 
     Entry (q, j) is scored against page candidates[q, j] (a GLOBAL id, int64 [n_q, m] on the index's device) of `index`; its bits
-    are those of `fp4_wide_scores(queries, index)[q, candidates[q, j] - index.id_base]`, whatever else the list holds.  An id of
-    -1 or outside [id_base, id_base + len(index)) comes back as (-inf, -1) and reads nothing; a page of 0 rows scores -inf; an id
-    listed twice is scored twice.  Only the listed pages are read: 161 bytes per row.  Lists are taken as `rerank_scores` takes
-    them (a broadcast row is copied).  Queries are packed and coded as `fp4_wide_scores` does; more than 128 tokens in a query, or
-    an index that is not an `Fp4WideIndex` (an `Fp4Index` of a 128-wide shard goes to `fp4_rerank_scores`), raises
-    NotImplementedError.  `out`: the fp32 [n_q, m] score tensor.  Asynchronous on torch's current stream; given a `PackedQueries`
-    it never synchronises with the host, never reads the list on the host, and is hipGraph-capturable (its allocations are torch
-    tensors made before the library call; the list may be rewritten in place between replays).  It is the `fp4_wide_rerank_fn`
-    hook of `ShardedRetriever` (`search(refine=)`)."""
+    are those of `fp4_wide_scores(queries, index, query_code=query_code)[q, candidates[q, j] - index.id_base]`, whatever else the
+    list holds.  An id of -1 or outside [id_base, id_base + len(index)) comes back as (-inf, -1) and reads nothing; a page of 0
+    rows scores -inf; an id listed twice is scored twice.  Only the listed pages are read: 161 bytes per row.  Lists are taken as
+    `rerank_scores` takes them (a broadcast row is copied).  Queries are packed and coded as `fp4_wide_scores` does; more than 128
+    tokens in a query, or an index that is not an `Fp4WideIndex` (an `Fp4Index` of a 128-wide shard goes to `fp4_rerank_scores` /
+    `fp6_rerank_scores`), raises NotImplementedError.  `out`: the fp32 [n_q, m] score tensor.  Asynchronous on torch's current
+    stream; given a `PackedQueries` it never synchronises with the host, never reads the list on the host, and is
+    hipGraph-capturable (its allocations are torch tensors made before the library call; the list may be rewritten in place between
+    replays).  It is the `fp4_wide_rerank_fn` hook of `ShardedRetriever` (`search(refine=)`)."""
+    width = _check_query_code(query_code)
     if not isinstance(index, Fp4WideIndex):
-        hint = "; an Fp4Index of a 128-wide shard takes fp4_rerank_scores" if type(index).__name__ == "Fp4Index" else ""
+        other = "fp6_rerank_scores" if query_code == "e2m3" else "fp4_rerank_scores"
+        hint = f"; an Fp4Index of a 128-wide shard takes {other}" if type(index).__name__ == "Fp4Index" else ""
         raise NotImplementedError(f"the wide fp4 rerank takes an Fp4WideIndex of a 320-wide shard (got {type(index).__name__}){hint}")
     dev = _require_gpu(index.device)
     q = _as_packed(queries, dev, layout="flat")
-    _check_format(q.dtype, int(q.tokens.shape[1]), "queries")
+    _check_format(q.dtype, int(q.tokens.shape[1]), "queries", query_code)
     if q.device != dev:
         raise ValueError("queries and index live on different devices")
     lens = q.lengths
@@ -199,13 +242,23 @@ def fp4_wide_rerank_scores(queries, index: Fp4WideIndex, candidates: torch.Tenso
     if max_q > MAX_RERANK_TOKENS:
         raise NotImplementedError(f"the wide fp4 rerank takes queries of at most {MAX_RERANK_TOKENS} tokens (got {max_q})")
     n_q, n = len(q), len(index)
-    codes, scales = _quantize_packed(q)
+    codes, scales = _quantize_packed(q, query_code)
+    assert int(codes.shape[1]) == width
+    name = "msim_f4w_candidates_q6" if query_code == "e2m3" else "msim_f4w_candidates"
     with torch.cuda.device(dev):
         candidates, m, ld_cand, out, ids, _ = _rerank_args(n_q, dev, candidates, out, lambda m: 0)
-        rc = _lib.lib().msim_f4w_candidates(_lib.ptr(codes), _lib.ptr(scales), _lib.ptr(q.offsets), n_q, int(codes.shape[0]), max_q,
-                                            _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets),
-                                            _lib.ptr(index.clamp0), n, int(index.codes.shape[0]), DIM, _lib.ptr(candidates), m,
-                                            ld_cand, int(index.id_base), _lib.ptr(out), max(m, 1), _lib.ptr(ids),
-                                            _lib.current_stream_handle(dev))
-    _lib.check(rc, "msim_f4w_candidates")
+        rc = getattr(_lib.lib(), name)(_lib.ptr(codes), _lib.ptr(scales), _lib.ptr(q.offsets), n_q, int(codes.shape[0]), max_q,
+                                       _lib.ptr(index.codes), _lib.ptr(index.scales), _lib.ptr(index.offsets), _lib.ptr(index.clamp0),
+                                       n, int(index.codes.shape[0]), DIM, _lib.ptr(candidates), m, ld_cand, int(index.id_base),
+                                       _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.current_stream_handle(dev))
+    _lib.check(rc, name)
     return out, ids
+
+
+def fp6_wide_rerank_scores(queries, index: Fp4WideIndex, candidates: torch.Tensor, *, out: Optional[torch.Tensor] = None
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`fp4_wide_rerank_scores` with the query tokens coded as e2m3 (FP6): the bits of `fp6_wide_scores` at the listed pages.  The
+    refine hook to hand to a retriever beside `fp4_wide_score_fn=fp6_wide_scores`:
+    `ShardedRetriever(shard, fp4_wide_rerank_fn=fp6_wide_rerank_scores)`.  An `Fp4Index` of a 128-wide shard takes
+    `fp6_rerank_scores`."""
+    return fp4_wide_rerank_scores(queries, index, candidates, query_code="e2m3", out=out)

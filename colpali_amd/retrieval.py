@@ -20,7 +20,7 @@ from . import _lib
 from .align import Alignment, align
 from .binary_index import BinaryIndex, binary_scores
 from .fp4_index import Fp4Index, fp4_rerank_scores, fp4_scores, fp6_rerank_scores, fp6_scores
-from .fp4_wide_index import Fp4WideIndex, fp4_wide_rerank_scores, fp4_wide_scores
+from .fp4_wide_index import Fp4WideIndex, fp4_wide_rerank_scores, fp4_wide_scores, fp6_wide_rerank_scores, fp6_wide_scores
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .fde import FdeIndex, fde_scores
 from .fde_wide import FdeWideIndex, fde_wide_scores
@@ -220,7 +220,7 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
             fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, fp4_wide_rerank_scores, align,
-            residual_align, fde_wide_scores)
+            residual_align, fde_wide_scores, fp6_wide_scores, fp6_wide_rerank_scores)
 
 
 class ShardedRetriever:

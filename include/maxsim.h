@@ -888,6 +888,25 @@ int msim_f4_candidates_q6(const uint8_t *q6, const uint8_t *qs, const int32_t *q
  *     msim_f4w_scores_plan writes the launch form msim_f4w_scores takes for the same arguments on the current device: plan[0] = NT
  *     (16-token tiles a wave holds), plan[1] = GW (waves that share one page range: 1, 2 or 4), plan[2] = D (chunks read ahead),
  *     plan[3] = pages per wave range (1 .. 63).  A query longer than 16 NT tokens takes ceil(tokens / (16 NT)) passes over its range.
+ *     The plan describes both scorers: msim_f4w_scores_q6 takes the same launch form for the same arguments.
+ *   E2M3 QUERY TOKENS (fp6_wide_query.hip: msim_f6w_encode_rows, msim_f4w_scores_q6; additions to ABI 22): the pages stay FP4, the
+ *   query tokens are coded as OCP e2m3 (FP6), which the same instruction takes as its B operand.  The stored index is the same index.
+ *   Query row code (msim_f6w_encode_rows; bf16 / f16, width 320; NaN elements unspecified, as above): msim_f6_encode_rows' rule
+ *     over 320 dimensions.  a = max over all 320 |x_k|.  If a == 0 every field is 0 and the scale byte is 127.  Otherwise e = the
+ *     smallest integer with a <= 7.5 * 2^e, clamped to [-32, 32], read from a's exponent and mantissa fields: a = m * 2^E
+ *     (1 <= m < 2) gives e = E - 2 + (m > 1.875).  y_k = min(|x_k| * 2^-e, 7.5); the code is the nearest of the 32 e2m3 magnitudes
+ *     -- codes 0 .. 7 the subnormals i/8, code 8 (j + 1) + i the normal (1 + i/8) * 2^j for j = 0 .. 2, i = 0 .. 7 -- a tie going
+ *     to the even code.  The 6-bit field is sign << 5 | code, and 0 when the code is 0 (so -0.0 and everything that rounds to 0
+ *     store 0).  Scale byte = e + 127.  A token is 240 code bytes and 1 scale byte: dimension k is the 6-bit field at bit 6 k of the
+ *     little-endian row.  codes uint8 [n_rows, 240], scales uint8 [n_rows].
+ *     As operands, for lane group l4 = lane >> 4: K blocks 0 and 1 (b = 0, 1) take the lane's 24 bytes at byte 96 b + 24 l4,
+ *     dimensions 128 b + 32 l4 .. + 31, the partners of the 16 FP4 bytes the page side holds there; K block 2 takes the lane's 12
+ *     bytes at byte 192 + 12 l4, dimensions 256 + 16 l4 .. + 15, as fields 0 .. 15 of the operand with registers 3 .. 5 zero, the
+ *     partners of the page side's 8 bytes (nibbles 0 .. 15).
+ *   Score (msim_f4w_scores_q6): as msim_f4w_scores with v(q) a multiple of 1/8: I_ij is a multiple of 1/16 with
+ *     |I| <= 320 * 7.5 * 6 = 14 400 (230 400 sixteenths, below 2^24), and so is every partial sum through the chained C operand:
+ *     exact in fp32 in any order; Z, M, clamp0, the sequential sum in token order, the 0-row page (-inf), the 0-token query (0),
+ *     broken offsets (NaN), the range limit and every argument but q6 [q_rows, 240] as msim_f4w_scores.
  * Width 320 and bf16 / f16 only (MSIM_EUNSUPPORTED otherwise -- width 128 is msim_f4_*'s, which refuses 320 in turn); a null or
  * misaligned pointer or a negative size is MSIM_EINVAL; both are decided before the device is touched.  Rows and codes 16-byte
  * aligned; offsets and scores 4-byte aligned; scale bytes unaligned.  A call with nothing to do returns 0 before it looks at a
@@ -899,6 +918,11 @@ int msim_f4w_scores_plan(int n_q, int max_q_tokens, int n_d, int64_t d_rows, int
 int msim_f4w_scores(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
                     const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
                     int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
+int msim_f6w_encode_rows(int dtype, const void *X, int64_t n_rows, int dim, uint8_t *codes /* [n_rows, 240] */, uint8_t *scales,
+                         void *stream);
+int msim_f4w_scores_q6(const uint8_t *q6, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                       const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                       int64_t d_rows, int dim, float *scores, int64_t ld_scores, void *stream);
 
 /*
  * FP4 CANDIDATES AT WIDTH 320 (fp4_wide_candidates.hip; additions to ABI 22): the LIST form of msim_f4w_scores -- the FP4 score of
@@ -927,12 +951,20 @@ int msim_f4w_scores(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, 
  * msim_f4_candidates', which refuses 320 in turn), max_q_tokens > 128, more workgroups than one launch holds
  * (ceil(n_q m / 4) >= 2^31).  n_q == 0 or m == 0: MSIM_OK before a pointer is looked at, nothing launched.  All of it is decided
  * before the device is touched.
+ *   msim_f4w_candidates_q6 (fp6_wide_candidates.hip; an addition to ABI 22) is the list form of msim_f4w_scores_q6: q6
+ *     [q_rows, 240] e2m3 fields from msim_f6w_encode_rows, every other argument, every check, refusal and result as
+ *     msim_f4w_candidates, and out_scores[q, j] has EXACTLY the bits msim_f4w_scores_q6 writes at [q, cand[q, j] - id_base].  It takes
+ *     the same launch form for the same arguments: msim_f4w_candidates_plan describes both.
  */
 int msim_f4w_candidates_plan(int n_q, int max_q_tokens, int m, int32_t *plan /* [4]: NT, D, waves per workgroup, workgroups */);
 int msim_f4w_candidates(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
                         const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
                         int64_t d_rows, int dim, const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores,
                         int64_t ld_scores, int64_t *out_ids /* or NULL */, void *stream);
+int msim_f4w_candidates_q6(const uint8_t *q6, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                           const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0 /* or NULL */, int n_d,
+                           int64_t d_rows, int dim, const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores,
+                           int64_t ld_scores, int64_t *out_ids /* or NULL */, void *stream);
 
 /*
  * CENTROID-CODE INDEX (centroid_index.hip; additions to ABI 22): every corpus row stored as the uint16 id of its nearest of K

@@ -35,6 +35,9 @@ figure is the median with its range:
     distinct pages x rows x 640 B / 8 TB/s for the exact rerank.  The cascade search(prefilter=<343-row pooled shard>,
     n_candidates=m1, refine=Fp4WideIndex, n_refine=100) at m1 in {400, 1000} beside the same search without refine and
     search(prefilter=Fp4WideIndex, n_candidates=100); recall@10 of the same variants on the planted set at width 320.
+    Every --dim 320 leg carries its e2m3 variant in the same loop: `fp6_wide_scores` beside `fp4_wide_scores` (stage1),
+    fp4_wide_score_fn=fp6_wide_scores (two_stage, recall), `fp6_wide_rerank_scores` beside `fp4_wide_rerank_scores` and the e2m3
+    hooks in the cascade and its recall (refine).
 """
 from __future__ import annotations
 
@@ -309,6 +312,11 @@ def summary(res):
 WIDE_ROW_BYTES = 161           # 160 code bytes and one scale byte
 
 
+def _overlap(a, b):
+    """whether the (min, max) ranges of two timed variants overlap"""
+    return a["min_ms"] <= b["max_ms"] and b["min_ms"] <= a["max_ms"]
+
+
 def wide_bounds_ms(n_q, q_len, n_d, rows):
     """memory: the index read once and the scores written; matrix cores: three K = 128 instructions per 16 x 16 tile"""
     return {"memory_ms": (rows * WIDE_ROW_BYTES + n_q * n_d * 4) / (HBM_PEAK_GBS * 1e9) * 1e3,
@@ -344,13 +352,16 @@ def wide_recall_leg(amd, dev, n_docs, k=10):
     exact = r.search(pq, k=k)[1].tolist()
     idx = amd.Fp4WideIndex.build(full)
 
-    def recall(prefilter, m):
-        two = r.search(pq, k=k, prefilter=prefilter, n_candidates=m)[1].tolist()
+    r6 = amd.ShardedRetriever(full, fp4_wide_score_fn=amd.fp6_wide_scores)      # the same index, e2m3 query tokens
+
+    def recall(prefilter, m, retriever=r):
+        two = retriever.search(pq, k=k, prefilter=prefilter, n_candidates=m)[1].tolist()
         return sum(len(set(a) & set(b)) for a, b in zip(exact, two)) / (len(pq) * k)
 
     return {"docs": n_docs, "queries": len(pq), "k": k, "pooled_rows_per_doc": float(pooled.blob.shape[0]) / n_docs,
-            "fp4_wide_full": {str(m): recall(idx, m) for m in MS}, "pooled_corpus": {str(m): recall(pooled, m) for m in MS},
-            "bytes": {"fp4_wide_full": idx.nbytes, "pooled_corpus": pooled.nbytes, "shard": full.nbytes}}
+            "fp4_wide_full": {str(m): recall(idx, m) for m in MS}, "fp6_wide_full": {str(m): recall(idx, m, r6) for m in MS},
+            "pooled_corpus": {str(m): recall(pooled, m) for m in MS},
+            "bytes": {"fp4_wide_full": idx.nbytes, "fp6_wide_full": idx.nbytes, "pooled_corpus": pooled.nbytes, "shard": full.nbytes}}
 
 
 # ------------------------------------------------------------------------------------- width 320: the list form and the cascade
@@ -371,7 +382,9 @@ def wide_rerank_legs(amd, corpus, idx, q_len, doc_len, dev, steps):
         for dist_name, cand in (("uniform", uniform_candidates(n_q, n, m, dev, seed=7)),
                                 ("clustered", clustered_candidates(n_q, n, m, dev, seed=7, pool=min(2 * m, n)))):
             s4 = torch.empty((n_q, m), dtype=torch.float32, device=dev)
+            s6 = torch.empty((n_q, m), dtype=torch.float32, device=dev)
             leg = alternating({"fp4_wide_rerank": lambda: amd.fp4_wide_rerank_scores(pq, idx, cand, out=s4),
+                               "fp6_wide_rerank": lambda: amd.fp6_wide_rerank_scores(pq, idx, cand, out=s6),
                                "exact_rerank": lambda: amd.rerank(pq, corpus, cand),
                                "fp4_wide_scan_gather": lambda: torch.gather(amd.fp4_wide_scores(pq, idx, out=full), 1, cand)},
                               steps if n_q == 4 else max(3, steps // 2), 1)
@@ -382,6 +395,10 @@ def wide_rerank_legs(amd, corpus, idx, q_len, doc_len, dev, steps):
             leg["exact_vs_fp4_wide"] = leg["exact_rerank"]["median_ms"] / leg["fp4_wide_rerank"]["median_ms"]
             leg["faster_than_exact"] = leg["fp4_wide_rerank"]["max_ms"] < leg["exact_rerank"]["min_ms"]     # the ranges do not overlap
             leg["bits_equal_scan_gather"] = bool(torch.equal(s4.view(torch.int32), torch.gather(full, 1, cand).view(torch.int32)))
+            leg["fp6_vs_fp4_wide"] = leg["fp6_wide_rerank"]["median_ms"] / leg["fp4_wide_rerank"]["median_ms"]
+            leg["fp6_ranges_overlap"] = _overlap(leg["fp6_wide_rerank"], leg["fp4_wide_rerank"])
+            leg["fp6_bits_equal_scan_gather"] = bool(torch.equal(
+                s6.view(torch.int32), torch.gather(amd.fp6_wide_scores(pq, idx, out=full), 1, cand).view(torch.int32)))
             out[f"{n_q}x{q_len}_m{m}_{dist_name}"] = leg
         del full
     return out
@@ -392,11 +409,15 @@ def wide_cascade_leg(amd, corpus, idx, coarse, q_len, dev, steps):
 
     pq = amd.pack_queries(make_queries_dim(1000, q_len, 320, dev, seed=99), dev, compact=False)
     r = amd.ShardedRetriever(corpus)
+    r6 = amd.ShardedRetriever(corpus, fp4_wide_score_fn=amd.fp6_wide_scores, fp4_wide_rerank_fn=amd.fp6_wide_rerank_scores)
     variants = {}
     for m1 in WIDE_REFINE_M1:
         variants[f"pooled_refine_m{m1}"] = lambda m1=m1: r.search(pq, k=10, prefilter=coarse, n_candidates=m1, refine=idx, n_refine=N_REFINE)
+        variants[f"pooled_refine_m{m1}_e2m3"] = lambda m1=m1: r6.search(pq, k=10, prefilter=coarse, n_candidates=m1, refine=idx,
+                                                                         n_refine=N_REFINE)
         variants[f"pooled_only_m{m1}"] = lambda m1=m1: r.search(pq, k=10, prefilter=coarse, n_candidates=m1)
     variants["fp4_wide_m100"] = lambda: r.search(pq, k=10, prefilter=idx, n_candidates=100)
+    variants["fp4_wide_m100_e2m3"] = lambda: r6.search(pq, k=10, prefilter=idx, n_candidates=100)
     out = alternating(variants, max(3, steps // 2), 1)
     out["n_queries"], out["n_refine"], out["coarse_rows_per_doc"] = 1000, N_REFINE, POOLED_LEN
     return out
@@ -412,10 +433,13 @@ def wide_refine_recall_leg(amd, dev, n_docs, k=10):
         return sum(len(set(a) & set(b)) for a, b in zip(exact, got[1].tolist())) / (len(pq) * k)
 
     out = {"docs": n_docs, "queries": len(pq), "k": k, "n_refine": N_REFINE, "pooled_rows_per_doc": float(pooled.blob.shape[0]) / n_docs}
+    r6 = amd.ShardedRetriever(full, fp4_wide_score_fn=amd.fp6_wide_scores, fp4_wide_rerank_fn=amd.fp6_wide_rerank_scores)
     for m1 in WIDE_REFINE_M1:
         out[f"pooled_refine_m{m1}"] = hits(r.search(pq, k=k, prefilter=pooled, n_candidates=m1, refine=idx, n_refine=N_REFINE))
+        out[f"pooled_refine_m{m1}_e2m3"] = hits(r6.search(pq, k=k, prefilter=pooled, n_candidates=m1, refine=idx, n_refine=N_REFINE))
         out[f"pooled_only_m{m1}"] = hits(r.search(pq, k=k, prefilter=pooled, n_candidates=m1))
     out["fp4_wide_m100"] = hits(r.search(pq, k=k, prefilter=idx, n_candidates=100))
+    out["fp4_wide_m100_e2m3"] = hits(r6.search(pq, k=k, prefilter=idx, n_candidates=100))
     return out
 
 
@@ -435,6 +459,12 @@ def wide_refine_section(res):
               f"{leg['exact_vs_fp4_wide']:.2f} × | {'yes' if leg['faster_than_exact'] else 'NO'} | {_ms(leg['fp4_wide_scan_gather'])} | "
               f"{leg['bound_ms']:.2f} ms | {leg['exact_bound_ms']:.2f} ms | {leg['distinct_pages']} | "
               f"{'yes' if leg['bits_equal_scan_gather'] else 'NO'} |"]
+    L += ["", "The same lists with e2m3 query tokens (`fp6_wide_rerank_scores`, alternating with the rows above in the same loop); "
+          "`ranges` says whether the two list forms' ranges overlap:", "",
+          "| shape, list | `fp6_wide_rerank_scores` | `fp4_wide_rerank_scores` | e2m3 / e2m1 | ranges | bits = e2m3 scan |", "|---|---|---|---|---|---|"]
+    for name, leg in f["rerank"].items():
+        L += [f"| {name.replace('_', ' ')} | {_ms(leg['fp6_wide_rerank'])} | {_ms(leg['fp4_wide_rerank'])} | {leg['fp6_vs_fp4_wide']:.3f} | "
+              f"{'overlap' if leg['fp6_ranges_overlap'] else 'APART'} | {'yes' if leg['fp6_bits_equal_scan_gather'] else 'NO'} |"]
     c, rc = f["cascade"], f["recall"]
     L += ["", f"Search at 1000 × 32, k = 10, n_refine = {c['n_refine']}, all alternating in one loop (the pooled shard of the timing has "
           f"{c['coarse_rows_per_doc']} random rows per page); recall@10 against the exact search on the planted {rc['docs']}-page set at "
@@ -443,8 +473,11 @@ def wide_refine_section(res):
     for m1 in WIDE_REFINE_M1:
         L += [f"| `prefilter=pooled, n_candidates={m1}, refine=Fp4WideIndex, n_refine={c['n_refine']}` | {_ms(c[f'pooled_refine_m{m1}'])} | "
               f"{rc[f'pooled_refine_m{m1}']:.3f} |",
+              f"| the same with the e2m3 hooks (`fp6_wide_rerank_scores`) | {_ms(c[f'pooled_refine_m{m1}_e2m3'])} | "
+              f"{rc[f'pooled_refine_m{m1}_e2m3']:.3f} |",
               f"| `prefilter=pooled, n_candidates={m1}` (no refine) | {_ms(c[f'pooled_only_m{m1}'])} | {rc[f'pooled_only_m{m1}']:.3f} |"]
-    L += [f"| `prefilter=Fp4WideIndex, n_candidates=100` | {_ms(c['fp4_wide_m100'])} | {rc['fp4_wide_m100']:.3f} |", ""]
+    L += [f"| `prefilter=Fp4WideIndex, n_candidates=100` | {_ms(c['fp4_wide_m100'])} | {rc['fp4_wide_m100']:.3f} |",
+          f"| the same with `fp4_wide_score_fn=fp6_wide_scores` | {_ms(c['fp4_wide_m100_e2m3'])} | {rc['fp4_wide_m100_e2m3']:.3f} |", ""]
     return L
 
 
@@ -462,18 +495,24 @@ def wide_summary(res):
         L += [f"Build: `Fp4WideIndex.build` {_ms(b['fp4_wide_build'])} in one launch, {b['share_of_bound']:.2f} of its {b['bound_ms']:.2f} ms bound "
               "(the shard read once, codes and scales written).", ""]
     if "stage1" in res:
-        L += ["## Stage 1", "", "| | `fp4_wide_scores` | exact scan | ratio | memory bound (share) | matrix-core bound (share) |", "|---|---|---|---|---|---|"]
+        L += ["## Stage 1", "", "| | `fp4_wide_scores` | `fp6_wide_scores` | exact scan | ratio | memory bound (share) | matrix-core bound (share) |",
+              "|---|---|---|---|---|---|---|"]
         for n, leg in res["stage1"].items():
             bd = leg["bounds"]
-            L += [f"| {n} × 32 | {_ms(leg['fp4_wide_scores'])} | {_ms(leg['exact_scan'])} | {leg['exact_vs_fp4_wide']:.2f} × | "
+            L += [f"| {n} × 32 | {_ms(leg['fp4_wide_scores'])} | {_ms(leg['fp6_wide_scores'])} | {_ms(leg['exact_scan'])} | {leg['exact_vs_fp4_wide']:.2f} × | "
                   f"{bd['memory_ms']:.2f} ms ({bd['memory_ms'] / leg['fp4_wide_scores']['median_ms']:.2f}) | "
                   f"{bd['matrix_ms']:.2f} ms ({bd['matrix_ms'] / leg['fp4_wide_scores']['median_ms']:.2f}) |"]
+        L += ["", "Ratio, bounds and shares are `fp4_wide_scores`'.  e2m3 query tokens against the same index:"]
+        for n, leg in res["stage1"].items():
+            L += [f"{n} × 32: `fp6_wide_scores` / `fp4_wide_scores` = {leg['fp6_vs_fp4_wide']:.3f}; the two ranges "
+                  f"{'overlap' if leg['fp6_ranges_overlap'] else 'are APART'} in this loop."]
         L += [""]
     if "two_stage" in res:
         t = res["two_stage"]
         L += ["## Two-stage search at 1000 × 32, k = 10", "", "| | time | exact search / this |", "|---|---|---|"]
         ex = t["exact_search"]
         for key, name in [(f"fp4_wide_m{m}", f"`prefilter=<Fp4WideIndex>`, m = {m}") for m in MS] + \
+                         [(f"fp6_wide_m{m}", f"the same with `fp4_wide_score_fn=fp6_wide_scores`, m = {m}") for m in MS] + \
                          [("pooled_m100", f"`prefilter=<PackedCorpus of {t['coarse_rows_per_doc']}-row pages>`, m = 100"), ("exact_search", "exact search")]:
             L += [f"| {name} | {_ms(t[key])} | {ex['median_ms'] / t[key]['median_ms']:.2f} |"]
         a = t["fp4_wide_m100"]
@@ -485,6 +524,7 @@ def wide_summary(res):
         L += [f"## Recall@10 against the exact search, planted {r['docs']}-page set at width 320 ({r['queries']} queries)", "",
               "| first stage | bytes | m = 100 | m = 400 | m = 1000 |", "|---|---|---|---|---|"]
         for key, name in (("fp4_wide_full", "`Fp4WideIndex`, full pages"),
+                          ("fp6_wide_full", "`Fp4WideIndex`, full pages, e2m3 queries (`fp6_wide_scores`)"),
                           ("pooled_corpus", f"pooled `PackedCorpus` ({r['pooled_rows_per_doc']:.0f} rows per page)")):
             L += [f"| {name} | {r['bytes'][key] / 1e6:.0f} MB | " + " | ".join(f"{r[key][str(m)]:.3f}" for m in MS) + " |"]
     if "refine" in res:
@@ -536,19 +576,25 @@ def main_wide(args):
             for n in (4, 1000):
                 pq = amd.pack_queries(make_queries_dim(n, args.q_len, 320, dev, seed=99), dev, compact=False)
                 out = torch.empty((n, len(idx)), dtype=torch.float32, device=dev)
+                out6 = torch.empty((n, len(idx)), dtype=torch.float32, device=dev)
                 leg = alternating({"fp4_wide_scores": lambda: amd.fp4_wide_scores(pq, idx, out=out),
+                                   "fp6_wide_scores": lambda: amd.fp6_wide_scores(pq, idx, out=out6),
                                    "exact_scan": lambda: amd.maxsim_scores(pq, corpus)},
                                   args.steps if n == 4 else max(3, args.steps // 2), args.warmup if n == 4 else 1)
                 leg["bounds"] = wide_bounds_ms(n, args.q_len, len(idx), rows)
                 leg["exact_vs_fp4_wide"] = leg["exact_scan"]["median_ms"] / leg["fp4_wide_scores"]["median_ms"]
+                leg["fp6_vs_fp4_wide"] = leg["fp6_wide_scores"]["median_ms"] / leg["fp4_wide_scores"]["median_ms"]
+                leg["fp6_ranges_overlap"] = _overlap(leg["fp6_wide_scores"], leg["fp4_wide_scores"])
                 res["stage1"][str(n)] = leg
-                del out
+                del out, out6
             _progress("stage1", t0)
         if "two_stage" in legs:
             pq = amd.pack_queries(make_queries_dim(1000, args.q_len, 320, dev, seed=99), dev, compact=False)
             coarse = make_shard_dim(docs, POOLED_LEN, 320, dev, seed=4321)
             r = amd.ShardedRetriever(corpus)
+            r6 = amd.ShardedRetriever(corpus, fp4_wide_score_fn=amd.fp6_wide_scores)
             variants = {f"fp4_wide_m{m}": (lambda m=m: r.search(pq, k=10, prefilter=idx, n_candidates=m)) for m in MS}
+            variants.update({f"fp6_wide_m{m}": (lambda m=m: r6.search(pq, k=10, prefilter=idx, n_candidates=m)) for m in MS})
             variants["pooled_m100"] = lambda: r.search(pq, k=10, prefilter=coarse, n_candidates=100)
             variants["exact_search"] = lambda: r.search(pq, k=10)
             ts = alternating(variants, max(3, args.steps // 2), 1)
