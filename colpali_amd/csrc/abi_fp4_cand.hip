@@ -1,74 +1,48 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the list form of the FP4 index's scorers (msim_f4_candidates_plan,
-// msim_f4_candidates, msim_f4_candidates_q6).  Host-side dispatch only: argument validation, kernel selection and launch on the
-// caller's stream.  Nothing here allocates, frees or synchronises, and nothing reads the list, so every entry point is
-// hipGraph-capturable.  The kernels of fp4_candidates.hip are defined and launched in this translation unit and in no other
-// (DESIGN.md section 1); the FP4 / FP6 scan kernels it shares constants and helpers with are templates that this unit never
-// instantiates, so the units of abi_fp4.hip and abi_fp6.hip compile to the kernels they had.
+// msim_f4_candidates, msim_f4_candidates_q6).  Host-side dispatch only: argument validation (the family's checks and plans,
+// abi_fp4_family.hpp), kernel selection and launch on the caller's stream.  Nothing here allocates, frees or synchronises, and
+// nothing reads the list, so every entry point is hipGraph-capturable.  The kernels of fp4_candidates.hip are defined and launched
+// in this translation unit and in no other; the FP4 / FP6 scan kernels it shares constants and helpers with
+// are templates that this unit never instantiates, so the units of abi_fp4.hip and abi_fp6.hip compile to the kernels they had.
 #include <hip/hip_runtime.h>
 
 #include "../../include/maxsim.h"
 #include "abi_common.hpp"
 #include "fp4_candidates.hip"
+#include "abi_fp4_family.hpp"
 
 using namespace msim_abi;
 
 namespace {
 
-// the launch form: NT = the 16-token tiles a wave holds (the smallest of 1, 2, 4, 8 that covers max_q_tokens), one workgroup of
-// four waves per four entries
-struct F4CandPlan {
-    int NT;
-    long long wgs;
-};
-
-// MSIM_OK, or the refusal both the plan entry and the scorers give
-int f4_cand_plan(const char *who, int n_q, int max_q_tokens, int m, F4CandPlan *p) {
-    if (n_q < 0 || m < 0 || max_q_tokens < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d m=%d max_q_tokens=%d)", who, n_q, m, max_q_tokens);
-    if (max_q_tokens > msim::kF4CandMaxTokens)
-        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d above %d", who, max_q_tokens, msim::kF4CandMaxTokens);
-    const int tiles = (max_q_tokens + msim::kF4Tile - 1) / msim::kF4Tile;
-    p->NT = tiles <= 1 ? 1 : tiles <= 2 ? 2 : tiles <= 4 ? 4 : 8;
-    p->wgs = ((long long)n_q * m + msim::kF4CandWaves - 1) / msim::kF4CandWaves;
-    if (p->wgs > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: %lld workgroups exceed one launch", who, p->wgs);
-    return MSIM_OK;
-}
+constexpr F4CandLimits kLimits{msim::kF4CandMaxTokens, msim::kF4Tile, msim::kF4CandWaves};
+static_assert(kF4Narrow.dim == msim::kDim, "the family's refusals name the kernels' row width");
 
 template <bool Q6>
 int f4_candidates(const char *who, const uint8_t *qc, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
                   const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int dim,
                   const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids,
                   void *stream) {
-    if (n_q < 0 || n_d < 0 || m < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0)
-        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d m=%d q_rows=%lld d_rows=%lld max_q_tokens=%d)", who, n_q, n_d, m,
-                    (long long)q_rows, (long long)d_rows, max_q_tokens);
-    if (dim != msim::kDim) return fail(MSIM_EUNSUPPORTED, "%s: rows of width %d; the fp4 index takes width %d", who, dim, msim::kDim);
-    if (n_q == 0 || m == 0) return MSIM_OK;
-    if ((!qc && q_rows > 0) || (!qs && q_rows > 0) || !q_off || (!d4 && d_rows > 0) || (!ds && d_rows > 0) || (!d_off && n_d > 0) || !cand ||
-        !out_scores)
-        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
-    if (misaligned(qc, 16) || misaligned(d4, 16) || misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(out_scores, 4) ||
-        misaligned(cand, 8) || misaligned(out_ids, 8))
-        return fail(MSIM_EINVAL, "%s: codes must be 16-byte aligned; ids 8-byte aligned; offsets and scores 4-byte aligned", who);
-    if (ld_cand < m || ld_scores < m)
-        return fail(MSIM_EINVAL, "%s: ld_cand=%lld / ld_scores=%lld < m=%d", who, (long long)ld_cand, (long long)ld_scores, m);
+    const F4Queries qa{qc, qs, q_off, n_q, q_rows, max_q_tokens};
+    const F4Pages da{d4, ds, d_off, clamp0, n_d, d_rows, dim};
     F4CandPlan p;
-    if (int rc = f4_cand_plan(who, n_q, max_q_tokens, m, &p)) return rc;
+    if (int rc = f4_cand_check(who, kF4Narrow, kLimits, qa, da, cand, m, ld_cand, out_scores, ld_scores, out_ids, &p); rc != kF4Launch)
+        return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define MSIM_F4_CAND_LAUNCH(N)                                                                                                          \
+#define MSIM_CAND_LAUNCH(N)                                                                                                              \
     case N:                                                                                                                              \
         hipLaunchKernelGGL((msim::f4_candidates_kernel<N, Q6>), dim3((unsigned)p.wgs), dim3(256), 0, st, qc, qs, q_off, n_q,             \
                            (long long)q_rows, d4, ds, d_off, clamp0, n_d, (long long)d_rows, cand, m, (long long)ld_cand,                \
                            (long long)id_base, out_scores, (long long)ld_scores, out_ids);                                               \
         break;
     switch (p.NT) {
-        MSIM_F4_CAND_LAUNCH(1)
-        MSIM_F4_CAND_LAUNCH(2)
-        MSIM_F4_CAND_LAUNCH(4)
-        MSIM_F4_CAND_LAUNCH(8)
+        MSIM_CAND_LAUNCH(1)
+        MSIM_CAND_LAUNCH(2)
+        MSIM_CAND_LAUNCH(4)
+        MSIM_CAND_LAUNCH(8)
         default: break;
     }
-#undef MSIM_F4_CAND_LAUNCH
+#undef MSIM_CAND_LAUNCH
     return launch_failed("f4_candidates_kernel");
 }
 
@@ -77,31 +51,23 @@ int f4_candidates(const char *who, const uint8_t *qc, const uint8_t *qs, const i
 extern "C" {
 
 int msim_f4_candidates_plan(int n_q, int max_q_tokens, int m, int32_t *plan) {
-    const char *who = "msim_f4_candidates_plan";
-    if (!plan) return fail(MSIM_EINVAL, "%s: null plan", who);
-    F4CandPlan p;
-    if (int rc = f4_cand_plan(who, n_q, max_q_tokens, m, &p)) return rc;
-    plan[0] = p.NT;
-    plan[1] = msim::kF4CandD;
-    plan[2] = msim::kF4CandWaves;
-    plan[3] = (int32_t)p.wgs;
-    return MSIM_OK;
+    return f4_cand_plan_entry("msim_f4_candidates_plan", kLimits, [](int) { return msim::kF4CandD; }, n_q, max_q_tokens, m, plan);
 }
 
 int msim_f4_candidates(const uint8_t *q4, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
                        const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int dim,
-                       const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores,
-                       int64_t *out_ids, void *stream) {
-    return f4_candidates<false>("msim_f4_candidates", q4, qs, q_off, n_q, q_rows, max_q_tokens, d4, ds, d_off, clamp0, n_d, d_rows, dim,
-                                cand, m, ld_cand, id_base, out_scores, ld_scores, out_ids, stream);
+                       const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids,
+                       void *stream) {
+    return f4_candidates<false>("msim_f4_candidates", q4, qs, q_off, n_q, q_rows, max_q_tokens, d4, ds, d_off, clamp0, n_d, d_rows, dim, cand, m,
+                              ld_cand, id_base, out_scores, ld_scores, out_ids, stream);
 }
 
 int msim_f4_candidates_q6(const uint8_t *q6, const uint8_t *qs, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
-                          const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows,
-                          int dim, const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores,
-                          int64_t *out_ids, void *stream) {
-    return f4_candidates<true>("msim_f4_candidates_q6", q6, qs, q_off, n_q, q_rows, max_q_tokens, d4, ds, d_off, clamp0, n_d, d_rows, dim,
-                               cand, m, ld_cand, id_base, out_scores, ld_scores, out_ids, stream);
+                          const uint8_t *d4, const uint8_t *ds, const int32_t *d_off, const uint8_t *clamp0, int n_d, int64_t d_rows, int dim,
+                          const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores, int64_t *out_ids,
+                          void *stream) {
+    return f4_candidates<true>("msim_f4_candidates_q6", q6, qs, q_off, n_q, q_rows, max_q_tokens, d4, ds, d_off, clamp0, n_d, d_rows, dim, cand, m,
+                             ld_cand, id_base, out_scores, ld_scores, out_ids, stream);
 }
 
 }  // extern "C"

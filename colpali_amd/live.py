@@ -29,9 +29,8 @@ from . import _lib
 from .corpus import PackedCorpus, _as_packed, _staging, _widen, host_list_image
 from .int8_index import DIM as I8_DIM
 from .int8_index import Int8Index, int8_scores
-from .fp4_index import DIM as F4_DIM
+from ._fp4_family import FAMILIES as F4_FAMILIES
 from .fp4_index import Fp4Index, fp4_rerank_scores, fp4_scores
-from .fp4_wide_index import DIM as F4W_DIM
 from .fp4_wide_index import Fp4WideIndex, fp4_wide_rerank_scores, fp4_wide_scores
 from .align import Alignment, align
 from .filter import PageFilter, filter_ids, filter_list, filter_mask
@@ -519,7 +518,7 @@ class LiveCorpus(_LiveShard):
         """FP4 code rows and scale bytes of blob rows r0 .. r1 - 1, written where they belong (the scale pointer may be unaligned)"""
         if r1 <= r0:
             return
-        name = "msim_f4w_encode_rows" if self.width == F4W_DIM else "msim_f4_encode_rows"
+        name = F4_FAMILIES[self.width].encode["e2m1"]
         with torch.cuda.device(self.device):
             rc = getattr(_lib.lib(), name)(_lib.dtype_code(self.dtype), _lib.ptr(self.blob[r0:]), r1 - r0, self.width,
                                            _lib.ptr(self._f4_codes[r0:]), _lib.ptr(self._f4_scales[r0:]),
@@ -535,14 +534,14 @@ class LiveCorpus(_LiveShard):
         if self._f4_codes is None:
             if self.device.type != "cuda":
                 raise RuntimeError("the fp4 index is built by gfx950 kernels: this corpus lives on " + str(self.device))
-            if self.dtype not in (torch.bfloat16, torch.float16) or self.width not in (F4_DIM, F4W_DIM):
-                raise NotImplementedError(f"the fp4 index takes bfloat16 / float16 pages of width {F4_DIM} or {F4W_DIM} "
+            if self.dtype not in (torch.bfloat16, torch.float16) or self.width not in F4_FAMILIES:
+                raise NotImplementedError(f"the fp4 index takes bfloat16 / float16 pages of width {' or '.join(map(str, F4_FAMILIES))} "
                                           f"(got {self.dtype}, width {self.width})")
             self._f4_codes = torch.zeros((self.capacity_rows, self.width // 2), dtype=torch.uint8, device=self.device)
             self._f4_scales = torch.zeros((self.capacity_rows,), dtype=torch.uint8, device=self.device)
             self._encode_f4(0, self._rows_used)
         n, rows = self.n_slots, max(self._rows_used, 1)
-        cls = Fp4WideIndex if self.width == F4W_DIM else Fp4Index
+        cls = F4_FAMILIES[self.width].cls
         return cls(self._f4_codes[:rows], self._f4_scales[:rows], self.offsets[:n + 1], None, torch.from_numpy(self._lengths[:n].copy()),
                    self.id_base)
 

@@ -51,13 +51,13 @@ _DTYPE_NAMES = {v: k for k, v in _DTYPES.items()}
 
 # per kind: the tensors in file order, (attribute, role).  `rows` tensors are cut at offsets[lo] .. offsets[hi] by a range load
 # (at lo .. hi where the kind has no offsets), `pages` tensors at lo .. hi, `offsets` is rebased, `whole` is kept.
+_FP4_FIELDS = (("codes", "rows"), ("scales", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))
 _FROZEN = {
     "PackedCorpus": (PackedCorpus, (("blob", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
     "Int8Index": (Int8Index, (("codes", "rows"), ("scales", "pages"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
     "BinaryIndex": (BinaryIndex, (("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
-    "Fp4Index": (Fp4Index, (("codes", "rows"), ("scales", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
-    "Fp4WideIndex": (Fp4WideIndex, (("codes", "rows"), ("scales", "rows"), ("offsets", "offsets"), ("clamp0", "pages"),
-                                    ("lengths", "pages"))),
+    "Fp4Index": (Fp4Index, _FP4_FIELDS),
+    "Fp4WideIndex": (Fp4WideIndex, _FP4_FIELDS),
     "CentroidIndex": (CentroidIndex, (("centroids", "whole"), ("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"),
                                       ("lengths", "pages"))),
     "FdeIndex": (FdeIndex, (("Fd", "rows"), ("G", "whole"), ("S", "whole"))),
@@ -510,10 +510,8 @@ def _load_frozen(rd: _Reader, kind: str, device, pages):
             return Int8Index(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind == "BinaryIndex":
             return BinaryIndex(got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
-        if kind == "Fp4Index":
-            return Fp4Index(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
-        if kind == "Fp4WideIndex":
-            return Fp4WideIndex(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
+        if kind in ("Fp4Index", "Fp4WideIndex"):
+            return cls(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind == "CentroidIndex":
             return CentroidIndex(got["centroids"], got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind in ("FdeIndex", "FdeWideIndex"):

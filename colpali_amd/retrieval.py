@@ -19,6 +19,7 @@ import torch
 from . import _lib
 from .align import Alignment, align
 from .binary_index import BinaryIndex, binary_scores
+from ._fp4_family import Index as Fp4FamilyIndex
 from .fp4_index import Fp4Index, fp4_rerank_scores, fp4_scores, fp6_rerank_scores, fp6_scores
 from .fp4_wide_index import Fp4WideIndex, fp4_wide_rerank_scores, fp4_wide_scores, fp6_wide_rerank_scores, fp6_wide_scores
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
@@ -256,10 +257,9 @@ class ShardedRetriever:
         self._int8_score = int8_score_fn  # (queries, Int8Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Int8Index>
         self._centroid_score = centroid_score_fn  # (queries, CentroidIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<CentroidIndex>
         self._binary_score = binary_score_fn  # (queries, BinaryIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<BinaryIndex>
-        self._fp4_score = fp4_score_fn    # (queries, Fp4Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4Index>
-        self._fp4_wide_score = fp4_wide_score_fn  # (queries, Fp4WideIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Fp4WideIndex>
-        self._fp4_rerank = fp4_rerank_fn  # (queries, Fp4Index, candidates) -> (scores [n_q, m], ids [n_q, m]): the refine stage of refine=
-        self._fp4_wide_rerank = fp4_wide_rerank_fn  # the same for an Fp4WideIndex: the refine stage on a 320-wide shard
+        # the FP4 family's hooks by the index's width (Fp4Index: 128, Fp4WideIndex: 320): (stage 1 of prefilter=<index>: (queries,
+        # index) -> fp32 [n_q, len(index)]; the refine stage of refine=<index>: (queries, index, candidates) -> (scores, ids) [n_q, m])
+        self._fp4_hooks = {128: (fp4_score_fn, fp4_rerank_fn), 320: (fp4_wide_score_fn, fp4_wide_rerank_fn)}
         self._align = align_fn            # (queries, corpus, ids, maps=) -> Alignment, (-inf, -1) off the shard
         self._mine_bounds = mine_bounds_fn    # (scores, csr, id_base, local=, alive=) -> fp32 [n_q]: the best in-shard positive of each query
         self._mine_mask = mine_mask_fn        # (scores, csr, id_base, bounds, max_ratio, alive) -> scores, -inf where ineligible
@@ -615,9 +615,8 @@ class ShardedRetriever:
                   else self._int8_score if isinstance(prefilter, Int8Index)
                   else self._centroid_score if isinstance(prefilter, CentroidIndex)
                   else self._binary_score if isinstance(prefilter, BinaryIndex)
-                  else self._fp4_score if isinstance(prefilter, Fp4Index)
-                  else self._fp4_wide_score if isinstance(prefilter, Fp4WideIndex) else self._score)
-        fine = self._fp4_wide_rerank if isinstance(refine, Fp4WideIndex) else self._fp4_rerank
+                  else self._fp4_hooks[prefilter.family.dim][0] if isinstance(prefilter, Fp4FamilyIndex) else self._score)
+        fine = self._fp4_hooks[refine.family.dim][1] if refine is not None else None
         queries = self._pack(queries, compact, self._rerank, *((stage1,) if prefilter is not None else ()),
                              *((fine,) if refine is not None else ()))
         if flt is not None:
