@@ -248,6 +248,12 @@ def lib() -> ctypes.CDLL:
     L.msim_res_candidates.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, i32, i64, i32, vp, i32, i64, i64, vp, i64,
                                       vp, vp, vp]
     L.msim_res_candidates.restype = i32
+    # the compressed shard at width 320: the signatures of the 128 entries
+    for wide, narrow in ((L.msim_cent_wide_encode_docs, L.msim_cent_encode_docs), (L.msim_cent_wide_table, L.msim_cent_table),
+                         (L.msim_res_wide_encode_docs, L.msim_res_encode_docs), (L.msim_res_wide_decode_rows, L.msim_res_decode_rows),
+                         (L.msim_res_wide_candidates_workspace_bytes, L.msim_res_candidates_workspace_bytes),
+                         (L.msim_res_wide_candidates, L.msim_res_candidates)):
+        wide.argtypes, wide.restype = narrow.argtypes, narrow.restype
     L.msim_res_align_candidates.argtypes = [i32, vp, vp, i32, i64, i32, vp, vp, vp, i32, vp, i32, vp, vp, i32, i64, i32, vp, i32, i64,
                                             i64, vp, vp, vp, i32, vp]
     L.msim_res_align_candidates.restype = i32

@@ -37,7 +37,7 @@ from .fp4_index import fp4_rerank_scores
 from .group import group_reduce, group_select
 from .live import _LiveShard, mask_scores
 from .mine import mine_bounds, mine_mask
-from .residual import DIM, ResidualCorpus, _check_bits, _check_codec, residual_align, residual_rerank_scores
+from .residual import DIM, ResidualCorpus, _check_bits, _check_codec, _require_kind, residual_align, residual_rerank_scores
 from .retrieval import ShardedRetriever, topk
 from .scoring import maxsim_scores
 
@@ -125,16 +125,14 @@ class LiveResidualCorpus(_LiveShard):
     def like(cls, rc: ResidualCorpus, capacity_rows: int, capacity_docs: int, id_base: int = 0, **kw) -> "LiveResidualCorpus":
         """An empty shard with the codec of `rc` (its centroids, cutoffs, weights and bits; the tensors are shared, not copied):
         train on a sample that fits, then stream the corpus in."""
-        if not isinstance(rc, ResidualCorpus):
-            raise ValueError("rc must be a ResidualCorpus")
+        _require_kind(rc, ResidualCorpus, "the live form")             # a ResidualWideCorpus: NotImplementedError, no live form at 320
         return cls(rc.centroids, rc.cutoffs, rc.weights, rc.bits, capacity_rows, capacity_docs, id_base, **kw)
 
     @classmethod
     def from_residual(cls, rc: ResidualCorpus, spare_rows: int, spare_docs: int, **kw) -> "LiveResidualCorpus":
         """A live shard holding the pages of `rc` (one device copy of its codes and residuals) plus room for `spare_rows` rows and
         `spare_docs` pages."""
-        if not isinstance(rc, ResidualCorpus):
-            raise ValueError("rc must be a ResidualCorpus")
+        _require_kind(rc, ResidualCorpus, "the live form")             # a ResidualWideCorpus: NotImplementedError, no live form at 320
         lens = cls._source_lengths(rc)
         n, rows = int(lens.size), int(lens.sum())
         live = cls.like(rc, rows + int(spare_rows), n + int(spare_docs), rc.id_base, **kw)

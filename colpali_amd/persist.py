@@ -37,6 +37,7 @@ from .int8_index import Int8Index
 from .live import LiveCorpus
 from .live_residual import LiveResidualCorpus
 from .residual import ResidualCorpus
+from .residual_wide import CentroidWideIndex, ResidualWideCorpus
 
 MAGIC = b"MSIMSHRD"
 FORMAT_VERSION = 1
@@ -52,18 +53,21 @@ _DTYPE_NAMES = {v: k for k, v in _DTYPES.items()}
 # per kind: the tensors in file order, (attribute, role).  `rows` tensors are cut at offsets[lo] .. offsets[hi] by a range load
 # (at lo .. hi where the kind has no offsets), `pages` tensors at lo .. hi, `offsets` is rebased, `whole` is kept.
 _FP4_FIELDS = (("codes", "rows"), ("scales", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))
+_CENT_FIELDS = (("centroids", "whole"), ("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))
+_RES_FIELDS = (("centroids", "whole"), ("codes", "rows"), ("residuals", "rows"), ("cutoffs", "whole"), ("weights", "whole"),
+               ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))
 _FROZEN = {
     "PackedCorpus": (PackedCorpus, (("blob", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
     "Int8Index": (Int8Index, (("codes", "rows"), ("scales", "pages"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
     "BinaryIndex": (BinaryIndex, (("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
     "Fp4Index": (Fp4Index, _FP4_FIELDS),
     "Fp4WideIndex": (Fp4WideIndex, _FP4_FIELDS),
-    "CentroidIndex": (CentroidIndex, (("centroids", "whole"), ("codes", "rows"), ("offsets", "offsets"), ("clamp0", "pages"),
-                                      ("lengths", "pages"))),
+    "CentroidIndex": (CentroidIndex, _CENT_FIELDS),
+    "CentroidWideIndex": (CentroidWideIndex, _CENT_FIELDS),
     "FdeIndex": (FdeIndex, (("Fd", "rows"), ("G", "whole"), ("S", "whole"))),
     "FdeWideIndex": (FdeWideIndex, (("Fd", "rows"), ("G", "whole"), ("S", "whole"))),
-    "ResidualCorpus": (ResidualCorpus, (("centroids", "whole"), ("codes", "rows"), ("residuals", "rows"), ("cutoffs", "whole"),
-                                        ("weights", "whole"), ("offsets", "offsets"), ("clamp0", "pages"), ("lengths", "pages"))),
+    "ResidualCorpus": (ResidualCorpus, _RES_FIELDS),
+    "ResidualWideCorpus": (ResidualWideCorpus, _RES_FIELDS),
 }
 _LIVE = {"LiveCorpus": LiveCorpus, "LiveResidualCorpus": LiveResidualCorpus}
 _HOST_TENSORS = ("lengths",)          # host tensors by contract: loaded to the host whatever the device
@@ -252,7 +256,7 @@ def _kind_of(obj) -> str:
 
 
 def save(obj, path, *, chunk_bytes: int = DEFAULT_CHUNK_BYTES) -> None:
-    """Write `obj` -- a `PackedCorpus`, `Int8Index`, `BinaryIndex`, `Fp4Index`, `Fp4WideIndex`, `CentroidIndex`, `FdeIndex`, `FdeWideIndex`, `ResidualCorpus`, `LiveCorpus` or
+    """Write `obj` -- a `PackedCorpus`, `Int8Index`, `BinaryIndex`, `Fp4Index`, `Fp4WideIndex`, `CentroidIndex`, `CentroidWideIndex`, `FdeIndex`, `FdeWideIndex`, `ResidualCorpus`, `ResidualWideCorpus`, `LiveCorpus` or
     `LiveResidualCorpus` -- to `path` (see the module docstring).  Written to `path + ".tmp"`, fsynced and renamed: a failed save
     leaves nothing under `path` and an older file there untouched.  Holds two pinned chunks of host memory at most, whatever the
     object's size.  Synchronises with the host; raises under stream capture."""
@@ -264,7 +268,7 @@ def save(obj, path, *, chunk_bytes: int = DEFAULT_CHUNK_BYTES) -> None:
             meta["config"] = {f: getattr(obj.config, f) for f in _FDE_FIELDS}
             tensors = [("Fd", "rows", obj.Fd), ("G", "whole", G), ("S", "whole", S)]
         else:
-            if kind == "ResidualCorpus":
+            if kind in ("ResidualCorpus", "ResidualWideCorpus"):
                 meta["bits"] = int(obj.bits)
             tensors = [(name, role, getattr(obj, name)) for name, role in _FROZEN[kind][1]]
     else:
@@ -512,12 +516,12 @@ def _load_frozen(rd: _Reader, kind: str, device, pages):
             return BinaryIndex(got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind in ("Fp4Index", "Fp4WideIndex"):
             return cls(got["codes"], got["scales"], got["offsets"], got["clamp0"], got["lengths"], id_base)
-        if kind == "CentroidIndex":
-            return CentroidIndex(got["centroids"], got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
+        if kind in ("CentroidIndex", "CentroidWideIndex"):
+            return cls(got["centroids"], got["codes"], got["offsets"], got["clamp0"], got["lengths"], id_base)
         if kind in ("FdeIndex", "FdeWideIndex"):
             return cls(got["Fd"], id_base, FdeConfig(**{f: meta["config"][f] for f in _FDE_FIELDS}), params=(got["G"], got["S"]))
-        return ResidualCorpus(got["centroids"], got["codes"], got["residuals"], got["cutoffs"], got["weights"], got["offsets"],
-                              got["clamp0"], got["lengths"], id_base, int(meta["bits"]))
+        return cls(got["centroids"], got["codes"], got["residuals"], got["cutoffs"], got["weights"], got["offsets"], got["clamp0"],
+                   got["lengths"], id_base, int(meta["bits"]))
     except (KeyError, AttributeError, TypeError) as exc:
         raise ShardFileError(f"{rd.path}: the tensors of this {kind} are incomplete ({exc})") from None
 

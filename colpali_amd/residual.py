@@ -23,6 +23,11 @@ retriever only scans on request: `ShardedRetriever(rc, score_fn=residual_scores)
 listed pages decoded inside the kernel that consumes them (colpali_amd/csrc/residual_align.hip): the bits of the same call over
 `rc.decompress()`, no decoded copy in memory, no host read of the list.  `align(queries, rc, ids)` and `gather_pages(rc, ids)`
 dispatch to them; `ShardedRetriever(rc, align_fn=residual_align)` opens the retriever's `align`.
+
+The container, the build, `decompress` and the rerank are one host layer for both row widths (`_ResidualRows`: a public class binds
+the width, its centroid-index class and the library entries that read rows of that width).  `ResidualCorpus` is width 128;
+`ResidualWideCorpus` (colpali_amd/residual_wide.py) is width 320 -- a sibling, not a subclass, so the scan, align and gather above,
+which exist at width 128 only, refuse it by its type.
 """
 from __future__ import annotations
 
@@ -32,11 +37,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from .centroid import CentroidIndex
+from .centroid import CentroidIndex, _CentroidCodes
 from .corpus import PackedCorpus, PackedQueries, _as_packed, _dtype_width, _id_list, _rerank_args
 from .scoring import _require_gpu
 
 DIM = 128
+WIDE_DIM = 320
 BITS = (2, 4)
 
 
@@ -54,14 +60,17 @@ def _check_codec(cutoffs: torch.Tensor, weights: torch.Tensor, bits: int) -> Non
         raise ValueError(f"weights must be a contiguous fp32 [{nb}] tensor")
 
 
-def train_residual_codec(residual_sample: torch.Tensor, bits: int = 2) -> Tuple[torch.Tensor, torch.Tensor]:
+def train_residual_codec(residual_sample: torch.Tensor, bits: int = 2, *, width: int = DIM) -> Tuple[torch.Tensor, torch.Tensor]:
     """(cutoffs fp32 [2^bits - 1], weights fp32 [2^bits]) from sampled residuals fp32 [s, 128] (any device; plain torch: this is
-    build time, like `train_centroids`).  Cutoff j (1 .. 2^bits - 1) is the j / 2^bits quantile of ALL sampled values: element
+    build time, like `train_centroids`).  `width=320` takes the [s, 320] samples of a `ResidualWideCorpus` instead: the sample's
+    width must be the one named, 128 unless said otherwise.  Cutoff j (1 .. 2^bits - 1) is the j / 2^bits quantile of ALL sampled values: element
     floor(j * N / 2^bits) of the N sorted values.  Weight b is the mean of the values falling in bucket b (the number of cutoffs
     <= value); an empty bucket takes the midpoint of its cutoffs (an outer one, which has a single cutoff, that cutoff)."""
     bits = _check_bits(bits)
-    if residual_sample.dim() != 2 or residual_sample.shape[1] != DIM or residual_sample.dtype != torch.float32:
-        raise ValueError(f"residual_sample must be fp32 [s, {DIM}]")
+    if width not in (DIM, WIDE_DIM):
+        raise ValueError(f"width must be {DIM} or {WIDE_DIM} (got {width!r})")
+    if residual_sample.dim() != 2 or residual_sample.shape[1] != width or residual_sample.dtype != torch.float32:
+        raise ValueError(f"residual_sample must be fp32 [s, {width}]")
     if residual_sample.shape[0] < 1:
         raise ValueError("residual_sample is empty")
     nb = 1 << bits
@@ -87,21 +96,29 @@ def train_residual_codec(residual_sample: torch.Tensor, bits: int = 2) -> Tuple[
     return cutoffs, weights.contiguous()
 
 
-class ResidualCorpus:
-    """One resident shard in compressed form: `centroids` [K, 128] (bf16 / f16), `codes` uint16 [rows], `residuals` uint8
-    [rows, 16 * bits], `cutoffs` fp32 [2^bits - 1], `weights` fp32 [2^bits], the pages' `offsets` (int32 [n + 1], device), `clamp0`
-    (uint8 [n] or None), `lengths` (int64 [n], host), `id_base` and `bits`.  `.index` is a `CentroidIndex` over the SAME `codes` and
-    `centroids` tensors (no copy): the stage 1 that goes with this stage 2."""
+class _ResidualRows:
+    """What the compressed shards of both widths are: `centroids` [K, WIDTH] (bf16 / f16), `codes` uint16 [rows], `residuals` uint8
+    [rows, WIDTH / 8 * bits], `cutoffs` fp32 [2^bits - 1], `weights` fp32 [2^bits], the pages' `offsets` (int32 [n + 1], device),
+    `clamp0` (uint8 [n] or None), `lengths` (int64 [n], host), `id_base` and `bits`.  `.index` is the centroid index of the same
+    width over the SAME `codes` and `centroids` tensors (no copy).  A subclass sets WIDTH, its index class and the names of the
+    library entries that read rows of that width."""
+
+    WIDTH: int = 0
+    _INDEX = None
+    _ENCODE: str = ""
+    _DECODE: str = ""
+    _CANDIDATES: str = ""
 
     def __init__(self, centroids: torch.Tensor, codes: torch.Tensor, residuals: torch.Tensor, cutoffs: torch.Tensor,
                  weights: torch.Tensor, offsets: torch.Tensor, clamp0: Optional[torch.Tensor], lengths: torch.Tensor,
                  id_base: int = 0, bits: int = 2):
         bits = _check_bits(bits)
-        self.index = CentroidIndex(centroids, codes, offsets, clamp0, lengths, id_base)       # validates what the two share
+        self.index = self._INDEX(centroids, codes, offsets, clamp0, lengths, id_base)         # validates what the two share
         _check_codec(cutoffs, weights, bits)
-        if (residuals.dtype != torch.uint8 or residuals.dim() != 2 or residuals.shape != (codes.shape[0], 16 * bits)
+        row_bytes = self.WIDTH // 8 * bits
+        if (residuals.dtype != torch.uint8 or residuals.dim() != 2 or residuals.shape != (codes.shape[0], row_bytes)
                 or not residuals.is_contiguous()):
-            raise ValueError(f"residuals must be a contiguous uint8 [{codes.shape[0]}, {16 * bits}] tensor")
+            raise ValueError(f"residuals must be a contiguous uint8 [{codes.shape[0]}, {row_bytes}] tensor")
         for name, t in (("centroids", centroids), ("residuals", residuals), ("cutoffs", cutoffs), ("weights", weights),
                         ("offsets", offsets)):
             if t.device != codes.device:
@@ -124,7 +141,7 @@ class ResidualCorpus:
 
     @property
     def width(self) -> int:
-        return DIM
+        return self.WIDTH
 
     @property
     def n_centroids(self) -> int:
@@ -137,31 +154,33 @@ class ResidualCorpus:
         return n + (self.clamp0.numel() if self.clamp0 is not None else 0)
 
     @classmethod
-    def build(cls, corpus: PackedCorpus, index: Optional[CentroidIndex] = None, bits: int = 2,
+    def build(cls, corpus: PackedCorpus, index: Optional[_CentroidCodes] = None, bits: int = 2,
               cutoffs: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None, sample_rows: int = 1 << 18,
-              seed: int = 0, **centroid_kwargs) -> "ResidualCorpus":
-        """Compress `corpus` (bf16 / f16, width 128).  `index=None` builds a `CentroidIndex` first (`**centroid_kwargs` go to
-        `CentroidIndex.build`); a given one must cover the corpus's pages and rows.  With given `cutoffs` and `weights` the build is
+              seed: int = 0, **centroid_kwargs):
+        """Compress `corpus` (bf16 / f16, the class's width: 128 for `ResidualCorpus`, 320 for `ResidualWideCorpus`).  `index=None`
+        builds the centroid index of that width first (`CentroidIndex` / `CentroidWideIndex`; `**centroid_kwargs` go to its
+        `build`); a given one must be of that class and cover the corpus's pages and rows.  With given `cutoffs` and `weights` the build is
         bit-reproducible; otherwise they are trained (`train_residual_codec`) on the residuals of a seeded sample of `sample_rows`
         rows.  The corpus is not kept: the caller may free it.  Asynchronous on torch's current stream (training reads a few
         numbers back)."""
         bits = _check_bits(bits)
         dev = _require_gpu(corpus.device)
-        if corpus.blob.dtype not in (torch.bfloat16, torch.float16) or int(corpus.blob.shape[1]) != DIM:
-            raise NotImplementedError(f"the residual codec takes bfloat16 / float16 pages of width {DIM} (got {corpus.blob.dtype}, "
+        W, kind = cls.WIDTH, cls._INDEX
+        if corpus.blob.dtype not in (torch.bfloat16, torch.float16) or int(corpus.blob.shape[1]) != W:
+            raise NotImplementedError(f"the residual codec takes bfloat16 / float16 pages of width {W} (got {corpus.blob.dtype}, "
                                       f"width {int(corpus.blob.shape[1])})")
         if (cutoffs is None) != (weights is None):
             raise ValueError("pass both cutoffs and weights, or neither")
         if sample_rows < 1:
             raise ValueError("sample_rows must be >= 1")
         if index is None:
-            index = CentroidIndex.build(corpus, **centroid_kwargs)
+            index = kind.build(corpus, **centroid_kwargs)
         elif centroid_kwargs:
-            raise ValueError(f"{sorted(centroid_kwargs)} go to CentroidIndex.build: they do not go with index=")
+            raise ValueError(f"{sorted(centroid_kwargs)} go to {kind.__name__}.build: they do not go with index=")
         rows = int(corpus.blob.shape[0])
-        if (len(index) != len(corpus) or index.id_base != corpus.id_base or int(index.codes.shape[0]) != rows
+        if (not isinstance(index, kind) or len(index) != len(corpus) or index.id_base != corpus.id_base or int(index.codes.shape[0]) != rows
                 or index.device != dev or index.centroids.dtype != corpus.blob.dtype):
-            raise ValueError("index must be a CentroidIndex of this corpus (same pages, rows, id_base, dtype and device)")
+            raise ValueError(f"index must be a {kind.__name__} of this corpus (same pages, rows, id_base, dtype and device)")
         blob = corpus.blob if corpus.blob.is_contiguous() else corpus.blob.contiguous()
         if cutoffs is None:
             g = torch.Generator().manual_seed(int(seed))
@@ -169,33 +188,34 @@ class ResidualCorpus:
             pick = (torch.randperm(rows, generator=g)[:n_s] if rows <= 1 << 24 else torch.randint(0, rows, (n_s,), generator=g)).to(dev)
             c_of = (index.codes.view(torch.int16)[pick].to(torch.int64) & 0xFFFF).clamp(max=index.n_centroids - 1)
             sample = blob.index_select(0, pick).float() - index.centroids.index_select(0, c_of).float()
-            cutoffs, weights = train_residual_codec(sample, bits)
+            cutoffs, weights = train_residual_codec(sample, bits, width=W)
         cutoffs, weights = cutoffs.to(dev), weights.to(dev)
         _check_codec(cutoffs, weights, bits)
-        residuals = torch.empty((rows, 16 * bits), dtype=torch.uint8, device=dev)
+        residuals = torch.empty((rows, W // 8 * bits), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.lib().msim_res_encode_docs(_lib.dtype_code(blob.dtype), _lib.ptr(blob), rows, DIM, _lib.ptr(index.codes),
-                                                 _lib.ptr(index.centroids), index.n_centroids, _lib.ptr(cutoffs), bits,
-                                                 _lib.ptr(residuals), _lib.current_stream_handle(dev))
-        _lib.check(rc, "msim_res_encode_docs")
+            rc = getattr(_lib.lib(), cls._ENCODE)(_lib.dtype_code(blob.dtype), _lib.ptr(blob), rows, W, _lib.ptr(index.codes),
+                                                  _lib.ptr(index.centroids), index.n_centroids, _lib.ptr(cutoffs), bits,
+                                                  _lib.ptr(residuals), _lib.current_stream_handle(dev))
+        _lib.check(rc, cls._ENCODE)
         return cls(index.centroids, index.codes, residuals, cutoffs, weights, index.offsets, index.clamp0, index.lengths,
                    index.id_base, bits)
 
     def _decode(self, row0: int, row1: int, out: torch.Tensor) -> None:
         dev = self.device
         with torch.cuda.device(dev):
-            rc = _lib.lib().msim_res_decode_rows(_lib.dtype_code(self.dtype), _lib.ptr(self.codes), _lib.ptr(self.residuals),
-                                                 int(self.codes.shape[0]), row0, row1, _lib.ptr(self.centroids), self.n_centroids,
-                                                 _lib.ptr(self.weights), self.bits, DIM, out.data_ptr(), _lib.current_stream_handle(dev))
-        _lib.check(rc, "msim_res_decode_rows")
+            rc = getattr(_lib.lib(), self._DECODE)(_lib.dtype_code(self.dtype), _lib.ptr(self.codes), _lib.ptr(self.residuals),
+                                                   int(self.codes.shape[0]), row0, row1, _lib.ptr(self.centroids), self.n_centroids,
+                                                   _lib.ptr(self.weights), self.bits, self.WIDTH, out.data_ptr(),
+                                                   _lib.current_stream_handle(dev))
+        _lib.check(rc, self._DECODE)
 
     def decompress(self, ids: Union[None, Sequence[int], torch.Tensor] = None) -> PackedCorpus:
-        """The decoded pages as a `PackedCorpus` (msim_res_decode_rows): all of them (same offsets, clamp0 and id_base), or the
+        """The decoded pages as a `PackedCorpus` (msim_res_decode_rows / msim_res_wide_decode_rows): all of them (same offsets, clamp0 and id_base), or the
         listed LOCAL pages in the order given (id_base 0; only their rows are read)."""
         dev = _require_gpu(self.device)
         if ids is None:
             rows = int(self.lengths.sum()) if len(self) else 0
-            blob = torch.zeros((max(rows, 1), DIM), dtype=self.dtype, device=dev)
+            blob = torch.zeros((max(rows, 1), self.WIDTH), dtype=self.dtype, device=dev)
             self._decode(0, rows, blob)
             clamp0 = self.clamp0.clone() if self.clamp0 is not None else None
             return PackedCorpus(blob=blob, offsets=self.offsets.clone(), clamp0=clamp0, lengths=self.lengths.clone(),
@@ -210,7 +230,7 @@ class ResidualCorpus:
         sel = ln[pages]
         off = np.zeros(pages.size + 1, dtype=np.int64)
         np.cumsum(sel, out=off[1:])
-        blob = torch.zeros((max(int(off[-1]), 1), DIM), dtype=self.dtype, device=dev)
+        blob = torch.zeros((max(int(off[-1]), 1), self.WIDTH), dtype=self.dtype, device=dev)
         for i, p in enumerate(pages):
             if sel[i]:
                 self._decode(int(start[p]), int(start[p + 1]), blob[int(off[i]):])
@@ -225,7 +245,7 @@ class ResidualCorpus:
         persist.save(self, path, chunk_bytes=chunk_bytes)
 
     @classmethod
-    def load(cls, path, device, *, verify: bool = True, pages=None) -> "ResidualCorpus":
+    def load(cls, path, device, *, verify: bool = True, pages=None):
         """The compressed corpus saved at `path`, on `device`, every chunk verified where it landed; `pages=(lo, hi)`: those pages only
         (`persist.load`)."""
         from . import persist
@@ -233,19 +253,43 @@ class ResidualCorpus:
         return persist.load(path, device, verify=verify, pages=pages, expect=cls)
 
 
-def _check_query_format(queries, rc: ResidualCorpus, what: str) -> None:
+class ResidualCorpus(_ResidualRows):
+    """One resident shard in compressed form: `centroids` [K, 128] (bf16 / f16), `codes` uint16 [rows], `residuals` uint8
+    [rows, 16 * bits], `cutoffs` fp32 [2^bits - 1], `weights` fp32 [2^bits], the pages' `offsets` (int32 [n + 1], device), `clamp0`
+    (uint8 [n] or None), `lengths` (int64 [n], host), `id_base` and `bits`.  `.index` is a `CentroidIndex` over the SAME `codes` and
+    `centroids` tensors (no copy): the stage 1 that goes with this stage 2."""
+
+    WIDTH = DIM
+    _INDEX = CentroidIndex
+    _ENCODE = "msim_res_encode_docs"
+    _DECODE = "msim_res_decode_rows"
+    _CANDIDATES = "msim_res_candidates"
+
+
+def _check_query_format(queries, rc: _ResidualRows, what: str) -> None:
     """the formats the residual kernels take, in whatever form the queries came (no device work)"""
     q_dtype, dim = _dtype_width(queries)
     if q_dtype != rc.dtype:
         raise RuntimeError(f"expected queries and passages of one dtype, got {q_dtype} and {rc.dtype}")
-    if q_dtype not in (torch.bfloat16, torch.float16) or dim != DIM:
-        raise NotImplementedError(f"the residual {what} takes bfloat16 / float16 embeddings of width {DIM} (got {q_dtype}, width {dim})")
+    if q_dtype not in (torch.bfloat16, torch.float16) or dim != rc.WIDTH:
+        raise NotImplementedError(f"the residual {what} takes bfloat16 / float16 embeddings of width {rc.WIDTH} (got {q_dtype}, width "
+                                  f"{dim})")
 
 
-def _flat_queries(queries, rc: ResidualCorpus, what: str) -> Tuple[torch.device, PackedQueries]:
-    """the query forms and checks the residual kernels share: a `PackedQueries`, a host list, or a dense device box"""
-    if not isinstance(rc, ResidualCorpus):
-        raise ValueError("rc must be a ResidualCorpus")
+def _require_kind(rc, kind, who: str) -> None:
+    """the sibling classes refuse each other by type, naming the width: no kernel of one width ever sees rows of the other"""
+    if isinstance(rc, _ResidualRows) and not isinstance(rc, kind):
+        raise NotImplementedError(f"{who} of a {kind.__name__} exists at width {kind.WIDTH} only (got a {type(rc).__name__} of width "
+                                  f"{rc.WIDTH})")
+    if not isinstance(rc, kind):
+        raise ValueError(f"rc must be a {kind.__name__}")
+
+
+def _flat_queries(queries, rc, what: str, kind=None) -> Tuple[torch.device, PackedQueries]:
+    """the query forms and checks the residual kernels share: a `PackedQueries`, a host list, or a dense device box.  `kind`: the
+    class the caller's kernels take (the siblings refuse each other by type)"""
+    kind = kind or ResidualCorpus
+    _require_kind(rc, kind, f"the residual {what}")
     dev = _require_gpu(rc.device)
     _check_query_format(queries, rc, what)
     queries = _as_packed(queries, dev, layout="flat")
@@ -289,20 +333,23 @@ def residual_rerank_scores(queries, rc: ResidualCorpus, candidates: torch.Tensor
     `rerank_scores(queries, rc.decompress(), candidates)` gives; an id of -1 or outside [id_base, id_base + len(rc)) comes back as
     (-inf, -1).  bfloat16 / float16, width 128, queries of at most 128 tokens (NotImplementedError otherwise).  Given a
     `PackedQueries` it never synchronises with the host and is hipGraph-capturable."""
-    dev, queries = _flat_queries(queries, rc, "rerank")
+    return _rerank_scores(queries, rc, candidates, out, ResidualCorpus)
+
+
+def _rerank_scores(queries, rc, candidates: torch.Tensor, out: Optional[torch.Tensor], kind) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the candidate rerank of both widths: the entry of `kind` over a shard of that class"""
+    dev, queries = _flat_queries(queries, rc, "rerank", kind)
     n_q, n = len(queries), len(rc)
     L = _lib.lib()
+    entry, ws_bytes = getattr(L, kind._CANDIDATES), getattr(L, kind._CANDIDATES + "_workspace_bytes")
     tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
     with torch.cuda.device(dev):
-        candidates, m, ld_cand, out, ids, ws = _rerank_args(n_q, dev, candidates, out,
-                                                            lambda m: L.msim_res_candidates_workspace_bytes(n_q, m, n))
-        rcode = L.msim_res_candidates(_lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets),
-                                      queries.offsets_host.data_ptr(), n_q, _lib.ptr(rc.codes), _lib.ptr(rc.residuals),
-                                      _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets),
-                                      _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM, _lib.ptr(candidates), m, ld_cand,
-                                      int(rc.id_base), _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.ptr(ws),
-                                      _lib.current_stream_handle(dev))
-    _lib.check(rcode, "msim_res_candidates")
+        candidates, m, ld_cand, out, ids, ws = _rerank_args(n_q, dev, candidates, out, lambda m: ws_bytes(n_q, m, n))
+        rcode = entry(_lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets), queries.offsets_host.data_ptr(), n_q,
+                      _lib.ptr(rc.codes), _lib.ptr(rc.residuals), _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits,
+                      _lib.ptr(rc.offsets), _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), kind.WIDTH, _lib.ptr(candidates), m, ld_cand,
+                      int(rc.id_base), _lib.ptr(out), max(m, 1), _lib.ptr(ids), _lib.ptr(ws), _lib.current_stream_handle(dev))
+    _lib.check(rcode, kind._CANDIDATES)
     return out, ids
 
 
@@ -319,8 +366,7 @@ def residual_align(queries, rc: ResidualCorpus, ids: torch.Tensor, *, maps: bool
     and `ids` for queries that come packed."""
     from .align import MAX_QUERY_TOKENS, Alignment, resolve_ids          # align dispatches here
 
-    if not isinstance(rc, ResidualCorpus):
-        raise ValueError("rc must be a ResidualCorpus")
+    _require_kind(rc, ResidualCorpus, "residual_align")
     _check_query_format(queries, rc, "align")
     n = len(rc)
     if max_rows is None:
@@ -364,8 +410,7 @@ def residual_gather_pages(rc: ResidualCorpus, ids: torch.Tensor, pad_to: Optiona
     for such a slot.  A page longer than `pad_to`: host ids raise ValueError, device ids TRUNCATE (`lengths` reports the truncated
     count), as `gather_pages`.  out: a contiguous [*ids.shape, L_pad, 128] tensor to write into (every byte of it is written).
     Asynchronous on torch's current stream; with device ids there is no host synchronisation and the call is hipGraph-capturable."""
-    if not isinstance(rc, ResidualCorpus):
-        raise ValueError("rc must be a ResidualCorpus")
+    _require_kind(rc, ResidualCorpus, "residual_gather_pages")
     if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
         raise ValueError("ids must be an int64 tensor")
     n = len(rc)

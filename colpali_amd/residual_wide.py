@@ -1,0 +1,79 @@
+"""The residual-compressed shard at width 320 (ColQwen3): the centroid-code first stage and PLAID's second half over 640-byte rows.
+
+`CentroidWideIndex` is to `CentroidIndex`, and `ResidualWideCorpus` to `ResidualCorpus`, what `Fp4WideIndex` is to `Fp4Index`: the
+same contracts with 128 replaced by 320, on kernels of their own (include/maxsim.h: msim_cent_wide_*, msim_res_wide_*;
+colpali_amd/csrc/residual_wide.hip).  A row costs 2 bytes of centroid code plus 40 * bits bytes of residual -- 82 bytes at 2 bits,
+162 at 4, instead of 640 -- and no full-precision row is kept.
+
+    encode   code[r] = argmax_k <row_r, C_k> (one fp32 MFMA chain over the ten 32-wide k-steps; the lowest k wins equal values)
+             e_k = fl32(float(x_k) - float(C[c]_k));  bucket b_k = #{cutoffs t : t <= e_k}
+    pack     dimension k = bits [k * bits, k * bits + bits) of the row's 40 * bits bytes, a little-endian bit string
+    decode   xhat_k = round_to_dtype(float(C[c]_k) + weights[b_k])   -- one rounding, NO renormalisation
+
+`centroid_wide_scores` is the wide query table followed by the scan of `centroid_scores` (the scan reads the table and the codes
+alone, so it is the same kernel for both widths).  `residual_wide_rerank_scores` reranks candidate lists straight from the
+compressed rows: every score has the bits `rerank_scores` gives the same query against `rc.decompress()`.  Stage 1 is `rc.index`:
+`ShardedRetriever(rc).search(q, k, prefilter=rc.index, n_candidates=m)`; `refine=<Fp4WideIndex>` (built from the corpus before it
+is freed) puts the FP4 rows between the two.
+
+The host layer is the one of widths 128 (colpali_amd/centroid.py: `_CentroidCodes`, colpali_amd/residual.py: `_ResidualRows`); the
+classes here bind the width and the wide entries.  They are siblings of the 128 classes, not subclasses: everything that exists
+at width 128 only -- the full scan (`residual_scores`), `residual_align`, `residual_gather_pages`, `LiveResidualCorpus` -- refuses
+them by their type, and no 128 kernel ever sees a 320-wide row.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from .centroid import _CentroidCodes, _require_kind, _scores
+from .residual import WIDE_DIM as DIM
+from .residual import _rerank_scores, _ResidualRows
+
+
+class CentroidWideIndex(_CentroidCodes):
+    """The centroid-code copy of one resident 320-wide shard: `centroids` [K, 320] (bf16 / f16, K a multiple of 256 in 256 .. 2048),
+    `codes` uint16 [rows] in the corpus's row order, the corpus's page `offsets` (int32 [n + 1], device) and `clamp0` (uint8 [n] or
+    None), copied; `lengths` (int64 [n], host) and `id_base` as the corpus's.  `build(corpus, centroids=None, n_centroids=1024,
+    iters=8, sample_rows=2^18, seed=0, chunk_docs=65536)` trains by spherical k-means with the wide encode kernel when no centroids
+    are given; `nbytes`, `save` and `load` as `CentroidIndex`.  With world > 1 every rank must build its index from the SAME
+    centroids, as for a `CentroidIndex`: stage-1 scores of different centroid sets do not compare."""
+
+    WIDTH = DIM
+    _ENCODE = "msim_cent_wide_encode_docs"
+    _TABLE = "msim_cent_wide_table"
+
+
+class ResidualWideCorpus(_ResidualRows):
+    """One resident 320-wide shard in compressed form: `centroids` [K, 320] (bf16 / f16), `codes` uint16 [rows], `residuals` uint8
+    [rows, 40 * bits], `cutoffs` fp32 [2^bits - 1], `weights` fp32 [2^bits], the pages' `offsets` (int32 [n + 1], device), `clamp0`
+    (uint8 [n] or None), `lengths` (int64 [n], host), `id_base` and `bits`.  `.index` is a `CentroidWideIndex` over the SAME `codes`
+    and `centroids` tensors (no copy): the stage 1 that goes with this stage 2.  `build`, `decompress`, `save` and `load` as
+    `ResidualCorpus`; `width` is 320."""
+
+    WIDTH = DIM
+    _INDEX = CentroidWideIndex
+    _ENCODE = "msim_res_wide_encode_docs"
+    _DECODE = "msim_res_wide_decode_rows"
+    _CANDIDATES = "msim_res_wide_candidates"
+
+
+def centroid_wide_scores(queries, index: CentroidWideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Centroid-interaction scores of every 320-wide query against every page of the index (msim_cent_wide_table, then
+    msim_cent_scores): fp32 [n_q, len(index)], column j = page index.id_base + j, with the forms, checks and guarantees of
+    `centroid_scores` -- bf16 / f16, queries of up to 128 tokens; given a `PackedQueries` no host synchronisation, hipGraph-capturable."""
+    if not isinstance(index, _CentroidCodes):
+        raise ValueError("index must be a CentroidWideIndex")
+    _require_kind(index, CentroidWideIndex, "centroid_wide_scores")
+    return _scores(queries, index, out)
+
+
+def residual_wide_rerank_scores(queries, rc: ResidualWideCorpus, candidates: torch.Tensor, *,
+                                out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MaxSim of listed candidates against the compressed 320-wide pages (include/maxsim.h: msim_res_wide_candidates): (scores fp32
+    [n_q, m], ids int64 [n_q, m]) with the signature, the query forms and the checks of `rerank_scores`.  Entry (q, j) has the bits
+    `rerank_scores(queries, rc.decompress(), candidates)` gives; an id of -1 or outside [id_base, id_base + len(rc)) comes back as
+    (-inf, -1).  bfloat16 / float16, width 320, queries of at most 128 tokens (NotImplementedError otherwise).  Given a
+    `PackedQueries` it never synchronises with the host and is hipGraph-capturable."""
+    return _rerank_scores(queries, rc, candidates, out, ResidualWideCorpus)

@@ -32,6 +32,7 @@ from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
 from .residual import ResidualCorpus, residual_align, residual_rerank_scores, residual_scores
+from .residual_wide import CentroidWideIndex, ResidualWideCorpus, centroid_wide_scores, residual_wide_rerank_scores
 from .scoring import _require_gpu, maxsim_scores
 
 
@@ -206,12 +207,13 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
     Asynchronous on torch's current stream; with a `PackedQueries` the call is hipGraph-capturable (no host synchronisation, no
     allocation inside the library call).
     `corpus` may be a `ResidualCorpus`: the listed pages are then scored straight from their compressed rows
-    (`residual_rerank_scores`; width 128, no `ref_rounding`), with the bits `rerank` gives over `corpus.decompress()`."""
+    (`residual_rerank_scores`; width 128, no `ref_rounding`), with the bits `rerank` gives over `corpus.decompress()`; or a
+    `ResidualWideCorpus` (`residual_wide_rerank_scores`; width 320, no `ref_rounding`), under the same rule."""
     scorer = partial(rerank_scores, ref_rounding=ref_rounding)
-    if isinstance(corpus, ResidualCorpus):
+    if isinstance(corpus, (ResidualCorpus, ResidualWideCorpus)):
         if ref_rounding:
-            raise NotImplementedError("ref_rounding over a ResidualCorpus: the residual rerank has no reference-rounding form")
-        scorer = residual_rerank_scores
+            raise NotImplementedError(f"ref_rounding over a {type(corpus).__name__}: the residual rerank has no reference-rounding form")
+        scorer = residual_wide_rerank_scores if isinstance(corpus, ResidualWideCorpus) else residual_rerank_scores
     if k is None:
         return scorer(queries, corpus, candidates, out=out)[0]
     scores, ids = scorer(queries, corpus, candidates)
@@ -221,7 +223,7 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
             fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, fp4_wide_rerank_scores, align,
-            residual_align, fde_wide_scores, fp6_wide_scores, fp6_wide_rerank_scores)
+            residual_align, fde_wide_scores, fp6_wide_scores, fp6_wide_rerank_scores, centroid_wide_scores, residual_wide_rerank_scores)
 
 
 class ShardedRetriever:
@@ -234,7 +236,10 @@ class ShardedRetriever:
     on the mask, list and auto routes (the list route runs the residual rerank), `group_by=` on every route, `filter=` with
     `candidates=` / `prefilter=`, and `mine` -- each with the bits of the same call over `shard.decompress()`.  `align` is opened
     the same way, by its own hook: `align_fn=residual_align` decodes the listed pages inside the alignment kernel; with the default
-    `align_fn` it keeps raising."""
+    `align_fn` it keeps raising.  A `ResidualWideCorpus` (width 320) works the same way on the candidate routes -- the default
+    `rerank_fn` is `residual_wide_rerank_scores`, `prefilter=shard.index` is its `CentroidWideIndex`, `refine=` takes an
+    `Fp4WideIndex` -- and refuses the scanning routes and `align`: the scan and the alignment of a compressed shard exist at width
+    128 only, so there is no scorer to opt in with."""
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
@@ -243,19 +248,22 @@ class ShardedRetriever:
                  mine_mask_fn: Callable = mine_mask, filter_mask_fn: Callable = filter_mask, filter_list_fn: Callable = filter_list,
                  filter_ids_fn: Callable = filter_ids, group_reduce_fn: Callable = group_reduce, group_select_fn: Callable = group_select,
                  fp4_rerank_fn: Callable = fp4_rerank_scores, fp4_wide_rerank_fn: Callable = fp4_wide_rerank_scores,
-                 fde_wide_score_fn: Callable = fde_wide_scores):
+                 fde_wide_score_fn: Callable = fde_wide_scores, centroid_wide_score_fn: Callable = centroid_wide_scores):
         if isinstance(shard, ResidualCorpus) and rerank_fn is rerank_scores:
             rerank_fn = residual_rerank_scores
+        if isinstance(shard, ResidualWideCorpus) and rerank_fn is rerank_scores:
+            rerank_fn = residual_wide_rerank_scores
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = (_dist(dist) if world > 1 else dist), group
         self._score, self._select = score_fn, select
         # a compressed shard is scanned on request only: a scorer of its own must be handed in (residual_scores)
-        self._res_refuses = isinstance(shard, ResidualCorpus) and score_fn is maxsim_scores
+        self._res_refuses = isinstance(shard, (ResidualCorpus, ResidualWideCorpus)) and score_fn is maxsim_scores
         self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
         self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
         self._fde_wide_score = fde_wide_score_fn  # (queries, FdeWideIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeWideIndex>
         self._int8_score = int8_score_fn  # (queries, Int8Index) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<Int8Index>
         self._centroid_score = centroid_score_fn  # (queries, CentroidIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<CentroidIndex>
+        self._centroid_wide_score = centroid_wide_score_fn  # (queries, CentroidWideIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<CentroidWideIndex>
         self._binary_score = binary_score_fn  # (queries, BinaryIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<BinaryIndex>
         # the FP4 family's hooks by the index's width (Fp4Index: 128, Fp4WideIndex: 320): (stage 1 of prefilter=<index>: (queries,
         # index) -> fp32 [n_q, len(index)]; the refine stage of refine=<index>: (queries, index, candidates) -> (scores, ids) [n_q, m])
@@ -295,8 +303,10 @@ class ShardedRetriever:
         parameter, so its scores are comparable across shards as they stand.  Or an `Fp4Index` of the shard or of its pooled
         pages: stage 1 is then the FP4 scan (`fp4_scores`), comparable across shards in the same way.  Or, over a 320-wide shard,
         an `Fp4WideIndex` of it: stage 1 is then `fp4_wide_scores`, under the same rules, and stage 2 the 320-wide rerank; or an
-        `FdeWideIndex` of it: stage 1 is then the encoding GEMM at width 320 (`fde_wide_scores`).  An `FdeIndex` over a 320-wide
-        shard, or an `FdeWideIndex` over a 128-wide one, raises ValueError.
+        `FdeWideIndex` of it: stage 1 is then the encoding GEMM at width 320 (`fde_wide_scores`); or a `CentroidWideIndex` of it:
+        stage 1 is then the centroid-code scan behind the 320-wide query table (`centroid_wide_scores`), under the rules of a
+        `CentroidIndex` -- with world > 1 every rank must build it from the SAME centroids.  An `FdeIndex` or a `CentroidIndex` over
+        a 320-wide shard, or an `FdeWideIndex` or a `CentroidWideIndex` over a 128-wide one, raises ValueError.
 
         Filtered search: `filter` -- a `PageFilter` over this shard (same count, same id_base, same device; ValueError otherwise, and
         for a per-query filter whose rows differ from the number of queries) -- restricts every query to its allowed pages.  For each
@@ -356,7 +366,8 @@ class ShardedRetriever:
         not depend on the number of shards.  An entry the refine stage scored -inf (no page, an empty page) becomes -1 and is not
         reranked.  The exact rerank then runs on the `n_refine` survivors, unchanged, so every returned score is still the exact
         one.  With `group_by=`, `n_refine` counts PAGES and the 4096-entry limit applies to `n_refine`, not to `n_candidates`.  A
-        `ResidualCorpus` shard works as it does with `prefilter=`: the last stage is its own rerank.  An index of the other width
+        `ResidualCorpus` shard (or, with an `Fp4WideIndex`, a `ResidualWideCorpus` one) works as it does with `prefilter=`: the last
+        stage is its own rerank.  An index of the other width
         -- an `Fp4WideIndex` on a 128-wide shard, an `Fp4Index` on a 320-wide one -- raises NotImplementedError.  With
         `refine=None` every route runs exactly as it did.
 
@@ -433,6 +444,12 @@ class ShardedRetriever:
         return int(n_refine)
 
     def _no_rows(self, what: str):
+        if isinstance(self.shard, ResidualWideCorpus):
+            raise NotImplementedError(f"{what} over a ResidualWideCorpus: the shard keeps no full-precision rows and only candidate "
+                                      "lists are scored from the compressed ones -- use search(candidates=) or "
+                                      "search(prefilter=shard.index, n_candidates=), or shard.decompress() for a PackedCorpus.  The "
+                                      "scan and the alignment of a compressed shard exist at width 128 only: there is no score_fn / "
+                                      "align_fn that opens this route at width 320")
         raise NotImplementedError(f"{what} over a ResidualCorpus: the shard keeps no full-precision rows and only candidate lists are "
                                   "scored from the compressed ones -- use search(candidates=) or search(prefilter=shard.index, "
                                   "n_candidates=), or shard.decompress() for a PackedCorpus; ShardedRetriever(shard, "
@@ -493,7 +510,7 @@ class ShardedRetriever:
         `maps=True` is for a single shard: the maps of a sharded corpus stay on the rank that holds the page (ValueError).
         Over a `ResidualCorpus` the default `align_fn` refuses (NotImplementedError); `align_fn=residual_align` decodes the listed
         pages inside the kernel and gives the bits of the same call over `shard.decompress()`."""
-        if isinstance(self.shard, ResidualCorpus) and self._align is align:        # opt-in, as the scan: align_fn=residual_align
+        if isinstance(self.shard, (ResidualCorpus, ResidualWideCorpus)) and self._align is align:  # opt-in, as the scan: align_fn=residual_align
             self._no_rows("align")
         if maps and self.world > 1:
             raise ValueError("maps=True with world > 1: similarity maps are made by the rank that holds the page; call align() on "
@@ -600,20 +617,26 @@ class ShardedRetriever:
                 raise NotImplementedError(f"group_by over a list of {m} pages: group_select takes at most {SELECT_MAX_M}")
         if prefilter is not None:
             if not isinstance(prefilter, (PackedCorpus, FdeIndex, Int8Index, CentroidIndex, BinaryIndex, Fp4Index, Fp4WideIndex,
-                                          FdeWideIndex)):
+                                          FdeWideIndex, CentroidWideIndex)):
                 raise ValueError("prefilter must be a PackedCorpus, an FdeIndex, an Int8Index, a CentroidIndex or a BinaryIndex, or an Fp4Index or an Fp4WideIndex"
-                                 ", or an FdeWideIndex")
+                                 ", or an FdeWideIndex, or a CentroidWideIndex")
             if isinstance(prefilter, (FdeIndex, FdeWideIndex)):
                 width = getattr(self.shard, "width", 128)                 # the two classes differ by the shard's 320 only
                 if (width == 320) != isinstance(prefilter, FdeWideIndex):
                     raise ValueError(f"prefilter is an {type(prefilter).__name__}, the shard is {width} wide: a 320-wide shard takes "
                                      "an FdeWideIndex, any other an FdeIndex")
+            if isinstance(prefilter, (CentroidIndex, CentroidWideIndex)):
+                width = getattr(self.shard, "width", 128)
+                if (width == 320) != isinstance(prefilter, CentroidWideIndex):
+                    raise ValueError(f"prefilter is a {type(prefilter).__name__}, the shard is {width} wide: a 320-wide shard takes "
+                                     "a CentroidWideIndex, any other a CentroidIndex")
             self._check_covers("prefilter holds", prefilter, "documents")
             if n_candidates is None or int(n_candidates) < 1:
                 raise ValueError("prefilter= needs n_candidates >= 1")
         stage1 = (self._fde_score if isinstance(prefilter, FdeIndex) else self._fde_wide_score if isinstance(prefilter, FdeWideIndex)
                   else self._int8_score if isinstance(prefilter, Int8Index)
                   else self._centroid_score if isinstance(prefilter, CentroidIndex)
+                  else self._centroid_wide_score if isinstance(prefilter, CentroidWideIndex)
                   else self._binary_score if isinstance(prefilter, BinaryIndex)
                   else self._fp4_hooks[prefilter.family.dim][0] if isinstance(prefilter, Fp4FamilyIndex) else self._score)
         fine = self._fp4_hooks[refine.family.dim][1] if refine is not None else None
@@ -673,7 +696,7 @@ class ExactMaxSimIndex:
 
 
 class ResidualMaxSimIndex:
-    """What `create_plaid_index(nbits=2 | 4)` returns: a `ResidualCorpus` -- centroid codes plus a few residual bits per dimension,
+    """What `create_plaid_index(nbits=2 | 4)` returns: a `ResidualCorpus` (a `ResidualWideCorpus` for 320-wide pages) -- centroid codes plus a few residual bits per dimension,
     no full-precision embedding, as in the FastPlaid index the reference builds -- behind the same `search(queries_embeddings,
     top_k)` interface and result shape as `ExactMaxSimIndex`.  A search is approximate in the way PLAID is: centroid stage 1
     (`centroid_scores`) keeps the top `min(n_candidates, n)` pages, the residual rerank scores them from the compressed rows, the
@@ -699,7 +722,8 @@ def create_plaid_index(ps, device=None, *, nbits: Optional[int] = None, n_centro
     FastPlaid the unpadded pages -- no block zero-padding semantics apply here (`batch_size=None`).
     `nbits=None` (the default) is that exact index.  `nbits` = 2 or 4 builds what FastPlaid builds instead, a compressed index:
     the pages are packed, `n_centroids` centroids and the residual codec are trained on them, a `ResidualCorpus` is built, the
-    full-precision pack is dropped, and a `ResidualMaxSimIndex` (stage 1 keeps `n_candidates` pages) comes back."""
+    full-precision pack is dropped, and a `ResidualMaxSimIndex` (stage 1 keeps `n_candidates` pages) comes back.  320-wide
+    (ColQwen3) pages give the same index over a `ResidualWideCorpus`."""
     from .corpus import pack_passages
     from .scoring import _require_gpu, get_torch_device
 
@@ -711,7 +735,8 @@ def create_plaid_index(ps, device=None, *, nbits: Optional[int] = None, n_centro
     corpus = pack_passages(list(ps) if not isinstance(ps, torch.Tensor) else ps, dev, batch_size=None)
     if nbits is None:
         return ExactMaxSimIndex(corpus)
-    rc = ResidualCorpus.build(corpus, bits=int(nbits), n_centroids=n_centroids)
+    kind = ResidualWideCorpus if corpus.width == 320 else ResidualCorpus
+    rc = kind.build(corpus, bits=int(nbits), n_centroids=n_centroids)
     del corpus                                    # the compressed shard is all that stays resident
     return ResidualMaxSimIndex(rc, n_candidates)
 

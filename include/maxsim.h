@@ -1074,6 +1074,57 @@ int msim_res_scores(int dtype, const void *Qt, const int32_t *q_off, const int32
                     void *workspace, void *stream);
 
 /*
+ * THE COMPRESSED SHARD AT WIDTH 320 (ColQwen3; residual_wide.hip; additions to ABI 22): the centroid-code first stage and the
+ * residual codec over rows of 320 dimensions.  The entries above keep refusing dim == 320 (MSIM_EUNSUPPORTED); these take
+ * dim == 320 ONLY (anything else, and a dtype other than bf16 / f16: MSIM_EUNSUPPORTED).  K a multiple of 256 in 256 .. 2048
+ * (MSIM_EINVAL otherwise), bits 2 or 4 (MSIM_EUNSUPPORTED otherwise), queries of 0 .. 128 tokens (MSIM_EUNSUPPORTED beyond).  A row
+ * costs 2 + 80 = 82 bytes at 2 bits and 2 + 160 = 162 at 4, instead of 640.
+ * msim_cent_wide_encode_docs: the contract of msim_cent_encode_docs over D [n_rows, 320] and C [K, 320] -- code[r] = argmax_k
+ *   <row_r, C_k>, each dot product ONE fp32-accumulated MFMA chain (v_mfma_f32_16x16x32) from zero over the ten 32-wide k steps in
+ *   ascending order; the lowest k wins equal values.  max_doc_rows and status (int32 [n_d] or NULL) as there: a page whose offsets
+ *   fall outside 0 .. n_rows, or that is longer than max_doc_rows, is skipped and reported 1, nothing of it becomes an address.
+ * msim_cent_wide_table: msim_cent_table over Qt [q_rows, 320] -- S[i, k] = fp16(fl32 <q_i, C_k>), the same chain, rounded to nearest
+ *   even once -- into the SAME table[n_q * nb][K][32] fp16 layout, msim_cent_table_bytes(n_q, max_q_tokens, K) bytes.  The scan reads
+ *   the table and the codes only, so msim_cent_scores, msim_cent_scores_plan and msim_cent_table_bytes serve the wide index unchanged.
+ * msim_res_wide_encode_docs / msim_res_wide_decode_rows: the codec above on the 40 chunks of 8 dimensions of a row.
+ *   Code.  e_k = fl32(float(x_k) - float(C[c]_k)); the bucket b_k is the number of cutoffs t with t <= e_k.
+ *   Packing.  residuals: uint8 [rows, 40 * bits]; dimension k occupies bits [k * bits, k * bits + bits) of its row read as a
+ *     little-endian bit string: 80 bytes per row at 2 bits, 160 at 4, 16-byte aligned.
+ *   Decode.  xhat_k = round_to_dtype(float(C[c]_k) + weights[b_k]): one fp32 addition, ONE rounding, no renormalisation.
+ *   A row whose code is >= K is encoded as all-zero buckets and decodes to the NaN row; such a code never becomes an address.
+ *   msim_res_wide_decode_rows writes rows row0 .. row1 - 1 (0 <= row0 <= row1 <= n_rows) -> out [row1 - row0, 320].
+ * msim_res_wide_candidates: msim_res_candidates' contract over the wide rows.  out_scores[q, j] has exactly the bits
+ *   msim_fwd_candidates_wide (flags 0) gives the same query against the page decoded by msim_res_wide_decode_rows: per (32-row slab,
+ *   16-token unit) one fp32 accumulator from zero chained across the panels p = 0, 1, 2 (128 + 128 + 64 dimensions) with the k steps
+ *   ascending inside each; rows past the page's end in the last slab are masked to -inf behind the MFMAs, never zero-filled; an exact
+ *   maximum over the page's rows; the same token sum.  The page is decoded slab by slab in registers into LDS and never written to
+ *   memory.  An id of -1 or outside [id_base, id_base + n_d) is (-inf, -1) and reads nothing; a query of 0 tokens scores 0; a page of
+ *   0 rows scores -inf (0 when flagged in d_clamp0); a duplicate id is scored once per occurrence.  A page with a code >= K, or whose
+ *   offsets fall outside 0 <= d_off[c] <= d_off[c + 1] <= d_rows, scores NaN (checked before anything becomes an address; other pages
+ *   are not affected); a device q_off that disagrees with q_off_host makes every score of the call NaN.  One wave scores one entry.
+ *   workspace: msim_res_wide_candidates_workspace_bytes(n_q, m, n_d) bytes (0 when there is no entry), 16-byte aligned, initialised
+ *   by the call (by a kernel); it does not depend on the number of rows.  After the call its first int32 is 0, or 1 for a broken q_off.
+ * MSIM_EINVAL for a negative size, a null or misaligned pointer (rows, centroids, residuals, out, table, workspace: 16 bytes),
+ * ld < m, a q_off_host that does not start at 0 or decreases; MSIM_EUNSUPPORTED for d_rows >= 2^31 in msim_res_wide_candidates.  A
+ * call with nothing to do returns 0 before it looks at a pointer.  Every refusal happens before the device is touched.
+ * Asynchronous on `stream`, no allocation, no host synchronisation, no float atomics: hipGraph-capturable.
+ */
+int msim_cent_wide_encode_docs(int dtype, const void *D, const int32_t *d_off, int n_d, int64_t n_rows, int dim, int max_doc_rows,
+                               const void *C, int K, uint16_t *codes, int32_t *status /* or NULL */, void *stream);
+int msim_cent_wide_table(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens, int dim,
+                         const void *C, int K, void *table, void *stream);
+int msim_res_wide_encode_docs(int dtype, const void *D, int64_t n_rows, int dim, const uint16_t *codes, const void *C, int K,
+                              const float *cutoffs, int bits, uint8_t *residuals, void *stream);
+int msim_res_wide_decode_rows(int dtype, const uint16_t *codes, const uint8_t *residuals, int64_t n_rows, int64_t row0, int64_t row1,
+                              const void *C, int K, const float *weights, int bits, int dim, void *out, void *stream);
+size_t msim_res_wide_candidates_workspace_bytes(int n_q, int m, int n_d);
+int msim_res_wide_candidates(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q,
+                             const uint16_t *codes, const uint8_t *residuals, const void *C, int K, const float *weights, int bits,
+                             const int32_t *d_off, const uint8_t *d_clamp0 /* or NULL */, int n_d, int64_t d_rows, int dim,
+                             const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores,
+                             int64_t *out_ids /* or NULL */, void *workspace, void *stream);
+
+/*
  * ROWS OUT OF THE COMPRESSED SHARD (residual_align.hip; additions to ABI 22): the two operations that return rows, decoded inside
  * the kernel that consumes them.  No decoded copy of a listed page is written to memory, and nothing reads the list on the host.
  * Formats as msim_res_candidates: bf16 / f16, width 128, bits 2 or 4, K a multiple of 256 in 256 .. 2048 -- MSIM_EUNSUPPORTED for

@@ -27,6 +27,16 @@ Legs, each timed with device events after a warm-up, for 2 and 4 residual bits (
   * gather (not in the default legs): `residual_gather_pages` (msim_res_gather_pages) on `[1000, 8]` ids beside `gather_pages` over a
     RESIDENT `rc.decompress()` (whose 256 bytes per row are what the compressed shard exists to avoid), alternating, with the bytes
     compared.
+
+    python tools/bench_residual.py --dim 320 [--out FILE] [--summary profiles/residual_wide_summary.md] [--docs 50000]
+
+--dim 320 measures the 320-wide compressed shard (msim_cent_wide_*, msim_res_wide_*, colpali_amd.ResidualWideCorpus) on the shard of
+tools/bench_rerank.py --dim 320 (50 000 x 1024 x 320 bf16, 32.8 GB), for 2 and 4 residual bits: the encode (centroid codes, then
+residuals), `decompress()`, `residual_wide_rerank_scores` beside `rerank_scores` over a resident `decompress()` on the same uniform
+and clustered lists (1000 x 32 x m = 100 and 4 x 32 x m = 1000) with their bit-equality, the two-stage search
+`prefilter=rc.index` at m = 100 / 400 / 1000 beside the same search over the bf16 shard, and recall@10 and the mean score error on
+the planted 320-wide set of tools/bench_fp4.py --dim 320.  One run; the variants of a comparison alternate step by step inside
+one timing loop and every figure is a median (min - max).
 """
 from __future__ import annotations
 
@@ -200,8 +210,126 @@ def recall_leg(amd, dev, n_docs, k=10):
     return out
 
 
+def _fmt(t):
+    return f"{t['median_ms']:.2f} ({t['min_ms']:.2f} - {t['max_ms']:.2f})"
+
+
+def wide_summary(res) -> str:
+    """profiles/residual_wide_summary.md from one --dim 320 result"""
+    L = ["# The residual-compressed shard at width 320 (ColQwen3)", "",
+         f"`tools/bench_residual.py --dim 320 --steps {res['steps']} --warmup {res['warmup']}` on the 320-wide shard ({res['docs']} pages x "
+         f"{res['doc_len']} rows x 320 bf16, {res['corpus_bytes'] / 1e9:.1f} GB), K = {res['n_centroids']} centroids.  One run; the variants of "
+         "a comparison alternate step by step inside one timing loop; every time is a median (min - max) in ms.", ""]
+    L += ["## Size and build", "", "| bits | shard bytes | bytes per row | share of bf16 | centroid encode | residual encode | decompress() |",
+          "|---|---|---|---|---|---|---|"]
+    for bits in BITS:
+        b = res[f"bits{bits}"]
+        L.append(f"| {bits} | {b['nbytes'] / 1e9:.2f} GB | {b['bytes_per_row']:.1f} | {b['nbytes'] / res['corpus_bytes']:.3f} | "
+                 f"{_fmt(res['centroid_encode'])} | {_fmt(b['encode'])} | {_fmt(b['decompress'])} |")
+    L += ["", "## Candidate rerank: from the compressed rows beside a resident decompressed copy", "",
+          "| bits | queries x m | lists | residual_wide_rerank_scores | rerank_scores over decompress() | ratio | same bits |", "|---|---|---|---|---|---|---|"]
+    for bits in BITS:
+        for shape, by_list in res[f"bits{bits}"]["rerank"].items():
+            for name, leg in by_list.items():
+                L.append(f"| {bits} | {shape} | {name} | {_fmt(leg['residual'])} | {_fmt(leg['bf16_decompressed'])} | "
+                         f"{leg['residual_over_bf16']:.2f} | {leg['bit_identical']} |")
+    L += ["", "## Two-stage search, 1000 x 32 queries, k = 10: prefilter=rc.index over the compressed shard beside the bf16 shard", "",
+          "| bits | n_candidates | compressed shard | bf16 shard |", "|---|---|---|---|"]
+    for bits in BITS:
+        for m, leg in res[f"bits{bits}"]["two_stage"].items():
+            L.append(f"| {bits} | {m} | {_fmt(leg['residual'])} | {_fmt(leg['bf16'])} |")
+    r = res["recall"]
+    L += ["", f"## Recall@10 against the exact search, planted {r['docs']}-page set at width 320 ({r['queries']} queries)", "",
+          "| bits | m = 100 | m = 400 | m = 1000 | mean abs score error | mean exact score |", "|---|---|---|---|---|---|"]
+    for bits in BITS:
+        b = r[f"bits{bits}"]
+        L.append(f"| {bits} | {b['100']:.3f} | {b['400']:.3f} | {b['1000']:.3f} | {b['mean_abs_score_error']:.4f} | {b['mean_exact_score']:.3f} |")
+    return "\n".join(L) + "\n"
+
+
+def main_wide(args):
+    """--dim 320: see the module docstring"""
+    import colpali_amd as amd
+    from tools.bench_fp4 import wide_planted
+    from tools.bench_rerank import make_queries_dim, make_shard_dim
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    amd._lib.lib()
+    docs = args.docs if args.docs != 125_000 else 50_000
+    t0 = time.perf_counter()
+    res = {"tool": "bench_residual", "dim": 320, "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len, "n_centroids": K,
+           "steps": args.steps, "warmup": args.warmup}
+    corpus = make_shard_dim(docs, args.doc_len, 320, dev, seed=1234)
+    index = amd.CentroidWideIndex.build(corpus, n_centroids=K)
+    res["corpus_bytes"], res["index_bytes"] = corpus.nbytes, index.nbytes
+    res["centroid_encode"] = timed_alternating({"encode": lambda: amd.CentroidWideIndex.build(corpus, centroids=index.centroids)}, 3, 1)["encode"]
+    pq1000 = amd.pack_queries(make_queries_dim(1000, args.q_len, 320, dev, seed=99), dev, compact=False)
+    for bits in BITS:
+        rc = amd.ResidualWideCorpus.build(corpus, index=index, bits=bits)
+        leg = {"nbytes": rc.nbytes, "bytes_per_row": rc.nbytes / max(int(rc.codes.shape[0]), 1)}
+        leg["encode"] = timed_alternating({"encode": lambda: amd.ResidualWideCorpus.build(corpus, index=index, bits=bits, cutoffs=rc.cutoffs,
+                                                                                         weights=rc.weights)}, 3, 1)["encode"]
+        leg["decompress"] = timed_alternating({"decompress": lambda: rc.decompress()}, 3, 1)["decompress"]
+        dec = rc.decompress()
+        leg["rerank"] = {}
+        for n_q, m in SHAPES:
+            pq = amd.pack_queries(make_queries_dim(n_q, args.q_len, 320, dev, seed=99), dev, compact=False)
+            by_list = {}
+            for name, cand in (("uniform", uniform_candidates(n_q, len(rc), m, dev, 7)),
+                               ("clustered", clustered_candidates(n_q, len(rc), m, dev, 8, pool=max(200, 2 * m)))):
+                a = torch.empty((n_q, m), dtype=torch.float32, device=dev)
+                b = torch.empty((n_q, m), dtype=torch.float32, device=dev)
+                t = timed_alternating({"residual": lambda: amd.residual_wide_rerank_scores(pq, rc, cand, out=a),
+                                       "bf16_decompressed": lambda: amd.retrieval.rerank_scores(pq, dec, cand, out=b)}, args.steps, args.warmup)
+                t["residual_over_bf16"] = t["residual"]["median_ms"] / t["bf16_decompressed"]["median_ms"]
+                t["bit_identical"] = bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
+                by_list[name] = t
+            leg["rerank"][f"{n_q}x{m}"] = by_list
+        del dec
+        torch.cuda.empty_cache()
+        r_c, r_b = amd.ShardedRetriever(rc), amd.ShardedRetriever(corpus)
+        leg["two_stage"] = {str(m): timed_alternating({"residual": lambda: r_c.search(pq1000, k=10, prefilter=rc.index, n_candidates=m),
+                                                       "bf16": lambda: r_b.search(pq1000, k=10, prefilter=index, n_candidates=m)},
+                                                      args.steps, args.warmup) for m in MS}
+        res[f"bits{bits}"] = leg
+        del rc, r_c, r_b
+        torch.cuda.empty_cache()
+    del corpus, index
+    torch.cuda.empty_cache()
+    full, _, pq = wide_planted(amd, dev, args.recall_docs)
+    exact_s, exact_i = amd.ShardedRetriever(full).search(pq, k=10)
+    index = amd.CentroidWideIndex.build(full, n_centroids=K)
+    rec = {"docs": args.recall_docs, "queries": len(pq), "k": 10, "n_centroids": K}
+    for bits in BITS:
+        rc = amd.ResidualWideCorpus.build(full, index=index, bits=bits)
+        r = amd.ShardedRetriever(rc)
+        leg = {}
+        for m in MS:
+            _, i = r.search(pq, k=10, prefilter=rc.index, n_candidates=m)
+            leg[str(m)] = sum(len(set(a) & set(b)) for a, b in zip(exact_i.tolist(), i.tolist())) / (len(pq) * 10)
+        approx = amd.rerank(pq, rc, exact_i)                        # the codec's own error: the exact top-k rescored from the compressed rows
+        ok = exact_i >= 0
+        leg["mean_abs_score_error"] = float((approx - exact_s)[ok].abs().mean())
+        leg["mean_exact_score"] = float(exact_s[ok].mean())
+        rec[f"bits{bits}"] = leg
+        del rc, r
+    res["recall"] = rec
+    res["wall_s"] = time.perf_counter() - t0
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    if args.summary:
+        with open(args.summary, "w") as f:
+            f.write(wide_summary(res))
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dim", type=int, default=128, choices=(128, 320), help="320: the ResidualWideCorpus on the 320-wide shard")
+    ap.add_argument("--summary", default=None, help="--dim 320: write the markdown summary here")
     ap.add_argument("--docs", type=int, default=125_000)
     ap.add_argument("--doc-len", type=int, default=1024)
     ap.add_argument("--q-len", type=int, default=32)
@@ -214,6 +342,8 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_residual.py needs an MI355X (there is no CPU fallback)")
+    if args.dim == 320:
+        return main_wide(args)
     import colpali_amd as amd
 
     dev = torch.device("cuda:0")
