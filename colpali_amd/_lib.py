@@ -263,6 +263,9 @@ def lib() -> ctypes.CDLL:
     L.msim_res_scores_workspace_bytes.restype = sz
     L.msim_res_scores.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, i32, i64, i32, vp, i64, vp, vp]
     L.msim_res_scores.restype = i32
+    for wide, narrow in ((L.msim_res_wide_scores_workspace_bytes, L.msim_res_scores_workspace_bytes),
+                         (L.msim_res_wide_scores, L.msim_res_scores)):      # the full scan at width 320: the same two signatures
+        wide.argtypes, wide.restype = narrow.argtypes, narrow.restype
     L.msim_live_compact_workspace_bytes.argtypes = [i32, i64]
     L.msim_live_compact_workspace_bytes.restype = sz
     L.msim_live_compact.argtypes = [vp, i64, i64, vp, vp, i32, vp, vp, vp, i64, vp]

@@ -1,16 +1,18 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the residual-compressed shard at width 320 (msim_cent_wide_*, msim_res_wide_*)
-// -- the centroid-code encoder and query table, the residual codec and the candidate rerank over the compressed rows.
+// -- the centroid-code encoder and query table, the residual codec, the candidate rerank and the full scan over the compressed rows.
 // Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates, frees or
-// synchronises, so every entry point is hipGraph-capturable.  The kernels of residual_wide.hip are defined and launched in this
-// translation unit and in no other.  The table msim_cent_wide_table writes is scanned by msim_cent_scores
+// synchronises, so every entry point is hipGraph-capturable.  The kernels of residual_wide.hip and residual_wide_scan.hip are defined
+// and launched in this translation unit and in no other.  The table msim_cent_wide_table writes is scanned by msim_cent_scores
 // (abi_index.hip), which depends on the table and the codes alone.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 
 #include "../../include/maxsim.h"
 #include "abi_common.hpp"
 #include "residual_wide.hip"
+#include "residual_wide_scan.hip"
 
 using namespace msim_abi;
 
@@ -183,6 +185,70 @@ int msim_res_wide_candidates(int dtype, const void *Qt, const int32_t *q_off, co
                        (long long)id_base, out_scores, (long long)ld_scores, out_ids, status);
     hipLaunchKernelGGL(msim::res_wide_poison_kernel, dim3(eblocks), dim3(256), 0, st, status, n_q, m, out_scores, (long long)ld_scores);
     return launch_failed("res_wide_candidates_kernel");
+}
+
+// the full scan: the status words plus one 16-byte group per query at most -- a function of n_q alone, never of the row count
+size_t msim_res_wide_scores_workspace_bytes(int n_q, int n_d) {
+    if (n_q <= 0 || n_d <= 0) return 0;
+    return align16(msim::kResScanStatusBytes + (size_t)n_q * sizeof(msim::ResScanGroup));
+}
+
+int msim_res_wide_scores(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const uint16_t *codes,
+                         const uint8_t *residuals, const void *C, int K, const float *weights, int bits, const int32_t *d_off,
+                         const uint8_t *d_clamp0, int n_d, int64_t d_rows, int dim, float *out_scores, int64_t ld_scores, void *workspace,
+                         void *stream) {
+    const char *who = "msim_res_wide_scores";
+    if (n_q < 0 || n_d < 0 || d_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d n_d=%d d_rows=%lld)", who, n_q, n_d, (long long)d_rows);
+    if (n_q == 0 || n_d == 0) return MSIM_OK;
+    if (int rc = rw_check_format(who, dtype, dim, K, bits)) return rc;
+    if (!Qt || !q_off || !q_off_host || ((!codes || !residuals) && d_rows > 0) || !C || !weights || !d_off || !out_scores || !workspace)
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(C, 16) || misaligned(residuals, 16) || misaligned(workspace, 16) || misaligned(codes, 2) ||
+        misaligned(weights, 4) || misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(out_scores, 4))
+        return fail(MSIM_EINVAL, "%s: Qt, centroids, residuals and workspace must be 16-byte aligned; the rest by their element size", who);
+    if (ld_scores < n_d) return fail(MSIM_EINVAL, "%s: ld_scores=%lld < n_d=%d", who, (long long)ld_scores, n_d);
+    if (d_rows > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld exceeds 32-bit page offsets", who, (long long)d_rows);
+    if (q_off_host[0] != 0) return fail(MSIM_EINVAL, "%s: q_off[0] must be 0", who);
+    // the checks of the offsets and, by the rule the device applies to its own copy (residual_scan_groups.hpp), the number of query groups
+    const int cap_units = std::min(std::max(ab_env("MSIM_RES_SCAN_UNITS", msim::kRwScanGroupUnits), 1), msim::kStreamMaxUnits);
+    int n_groups = 0, cur_nq = 0, cur_tok0 = 0;
+    for (int i = 0; i < n_q; ++i) {
+        const int len = q_off_host[i + 1] - q_off_host[i];
+        if (len < 0) return fail(MSIM_EINVAL, "%s: q_off must be non-decreasing (query %d)", who, i);
+        if (len > msim::kStreamMaxUnits * msim::kUnitTok)
+            return fail(MSIM_EUNSUPPORTED, "query %d has %d tokens: %s takes queries of at most %d", i, len, who,
+                        msim::kStreamMaxUnits * msim::kUnitTok);
+        if (msim::res_scan_new_group(cur_nq, cur_tok0, q_off_host[i + 1], cap_units)) {
+            ++n_groups;
+            cur_nq = 0;
+            cur_tok0 = q_off_host[i];
+        }
+        ++cur_nq;
+    }
+    ++n_groups;
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t *status = static_cast<int32_t *>(workspace);
+    auto *groups = reinterpret_cast<msim::ResScanGroup *>(static_cast<char *>(workspace) + msim::kResScanStatusBytes);
+    const long long q_rows = q_off_host[n_q];
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = bits == 2 ? (f16 ? msim::res_wide_scan_kernel<true, 2> : msim::res_wide_scan_kernel<false, 2>)
+                          : (f16 ? msim::res_wide_scan_kernel<true, 4> : msim::res_wide_scan_kernel<false, 4>);
+    static std::atomic<int> configured[2][2][kMaxDevices];
+    if (int rc = allow_lds(kern, msim::kRwLdsBytes, configured[bits == 4][f16])) return rc;
+    hipLaunchKernelGGL(msim::res_wide_scan_groups_kernel, dim3(1), dim3(64), 0, st, q_off, n_q, q_rows, cap_units, n_groups, groups, status);
+    // a persistent grid: every wave walks pages of its own, one workgroup per CU (its LDS holds one, and a wave runs alone on its SIMD)
+    const long long wg_needed = ((long long)n_d + 3) / 4;
+    const long long wg_cap = (long long)di->cus;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(wg_needed < wg_cap ? wg_needed : wg_cap)), dim3(256), msim::kRwLdsBytes, st,
+                       static_cast<const uint16_t *>(Qt), q_off, n_q, q_rows, codes, residuals, static_cast<const uint16_t *>(C), K, weights,
+                       d_off, d_clamp0, n_d, (long long)d_rows, out_scores, (long long)ld_scores, groups, n_groups, status);
+    const long long pblocks = ((long long)n_q * n_d + 255) / 256;
+    hipLaunchKernelGGL(msim::res_wide_scan_poison_kernel, dim3((unsigned)(pblocks < wg_cap * 8 ? pblocks : wg_cap * 8)), dim3(256), 0, st,
+                       status, n_q, n_d, out_scores, (long long)ld_scores);
+    return launch_failed("res_wide_scan_kernel");
 }
 
 }  // extern "C"

@@ -25,23 +25,14 @@
 // NaN, no other column changes), query offsets in the prologue, the group table again where it is read.
 #pragma once
 #include "residual_codec.hip"
+#include "residual_scan_groups.hpp"
 
 namespace msim {
 
-constexpr int kResScanGroupQueries = 8;                   // 8 reduction lanes per query: at most 8 queries share a wave
 constexpr int kResScanGroupUnits = kStreamMaxUnits;       // token cap of a group, in 16-token units (above kResPrefetchUnits the slab
                                                           // loads are issued at the top of the slab: DESIGN.md section 3.18)
-constexpr int kResScanStatusBytes = 16;                   // status word, device group count, two spare words
-struct ResScanGroup {                                     // 16 bytes of the workspace per group
-    int q0, nq;                                           // queries q0 .. q0 + nq - 1
-    int tok0, tok1;                                       // their tokens: rows tok0 .. tok1 - 1 of the flat token matrix
-};
 
-// the greedy rule, one query at a time: does query (tokens prev .. e - 1) open a new group?
-__host__ __device__ inline bool res_scan_new_group(int cur_nq, int cur_tok0, int e, int cap_units) {
-    return cur_nq > 0 && (cur_nq + 1 > kResScanGroupQueries || e - cur_tok0 > cap_units * kUnitTok);
-}
-
+// the group table and the greedy rule: residual_scan_groups.hpp (shared with the scan at width 320)
 __global__ __launch_bounds__(64) void res_scan_groups_kernel(const int32_t *__restrict__ q_off, int n_q, long long q_rows, int cap_units,
                                                              int n_groups_host, ResScanGroup *__restrict__ groups,
                                                              int32_t *__restrict__ status) {

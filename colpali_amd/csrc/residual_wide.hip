@@ -24,7 +24,8 @@
 //                             (slab, unit) ONE fp32 accumulator from zero runs across the panels p = 0, 1, 2 with ks ascending in each
 //                             (4 + 4 + 2 k-steps of 32), then the tail mask (rows past the page's end re-read the page's last row and
 //                             are set to -inf behind the MFMAs, never zero-filled), the exact max over rows and reduce_query_tokens:
-//                             entry (q, j) has the bits msim_fwd_candidates_wide gives the query against the decoded page.
+//                             entry (q, j) has the bits msim_fwd_candidates_wide gives the query against the decoded page.  The
+//                             page loop is rw_page_max, shared with the full scan (residual_wide_scan.hip).
 //   LDS per wave: 3 x 8 KiB panel-slabs + the per-token max table (kStreamTokBytes) + 64 B of weights = 26 752 B; 107 008 B per
 //   workgroup of four waves, one workgroup per CU.  Registers: up to 8 units x 40 query VGPRs = 320, so a wave runs alone on its SIMD
 //   with the unified 512-register file (__launch_bounds__(256) and no second bound), as K1cP.  hipcc reports 256 + 256 registers and
@@ -287,30 +288,14 @@ __device__ __forceinline__ void rw_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// the score of one entry: the query's NU units against the page rows r0 .. r0 + len - 1.  Returns in lanes 0 .. 7; lane 0 stores.
+// one page (rows r0 .. r0 + len - 1) against NU resident query units, decoded slab by slab into the wave's three panel-slabs: mx[u] =
+// the running maxima of unit u over this lane's rows (-inf for a page without rows).  Shared by the rerank (rw_entry) and the scan
+// (residual_wide_scan.hip: rw_scan_group).
 template <int NU, bool F16, int BITS>
-__device__ __forceinline__ float rw_entry(const uint16_t *__restrict__ Qt, int qs, int qe, const uint16_t *__restrict__ codes,
-                                          const uint8_t *__restrict__ res, const uint16_t *__restrict__ C, int K, long long r0, int len,
-                                          bool clamp, bool &bad, char *slabs, int lane) {
+__device__ __forceinline__ void rw_page_max(float (&mx)[NU], const bf16x8 (&qf)[NU][kRwKSteps], const uint16_t *__restrict__ codes,
+                                            const uint8_t *__restrict__ res, const uint16_t *__restrict__ C, int K, long long r0, int len,
+                                            bool &bad, char *slabs, const float *wtab, const int (&rd_off)[2][kKSteps16], int lane) {
     const int l16 = lane & 15, l4 = lane >> 4;
-    char *tokmax = slabs + kRwPanels * kSlabBytes;
-    const float *wtab = reinterpret_cast<const float *>(tokmax + kStreamTokBytes);
-    int rd_off[2][kKSteps16];                                   // per entry, not per kernel: nothing of it lives across the unit switch
-    slab_rd_offsets16(lane, rd_off);
-    // the query's units: K1cP's B operands, [unit][k-step of 32]
-    bf16x8 qf[NU][kRwKSteps];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        const int row = qs + u * kUnitTok + l16;
-        const bool valid = row < qe;
-        const uint16_t *p = Qt + (size_t)(valid ? row : 0) * kRwDim + l4 * 8;
-#pragma unroll
-        for (int ks = 0; ks < kRwKSteps; ++ks) {
-            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(p + ks * 32);
-            qf[u][ks] = valid ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    }
-    float mx[NU];
 #pragma unroll
     for (int u = 0; u < NU; ++u) mx[u] = -INFINITY;
 
@@ -386,6 +371,33 @@ __device__ __forceinline__ float rw_entry(const uint16_t *__restrict__ Qt, int q
     const int n_full = len / kSlabRows, rem = len - n_full * kSlabRows;
     for (int s = 0; s < n_full; ++s) slab(std::false_type{}, s, kSlabRows);
     if (rem > 0) slab(std::true_type{}, n_full, rem);
+}
+
+// the score of one entry: the query's NU units against the page rows r0 .. r0 + len - 1.  Returns in lanes 0 .. 7; lane 0 stores.
+template <int NU, bool F16, int BITS>
+__device__ __forceinline__ float rw_entry(const uint16_t *__restrict__ Qt, int qs, int qe, const uint16_t *__restrict__ codes,
+                                          const uint8_t *__restrict__ res, const uint16_t *__restrict__ C, int K, long long r0, int len,
+                                          bool clamp, bool &bad, char *slabs, int lane) {
+    const int l16 = lane & 15, l4 = lane >> 4;
+    char *tokmax = slabs + kRwPanels * kSlabBytes;
+    const float *wtab = reinterpret_cast<const float *>(tokmax + kStreamTokBytes);
+    int rd_off[2][kKSteps16];                                   // per entry, not per kernel: nothing of it lives across the unit switch
+    slab_rd_offsets16(lane, rd_off);
+    // the query's units: K1cP's B operands, [unit][k-step of 32]
+    bf16x8 qf[NU][kRwKSteps];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        const int row = qs + u * kUnitTok + l16;
+        const bool valid = row < qe;
+        const uint16_t *p = Qt + (size_t)(valid ? row : 0) * kRwDim + l4 * 8;
+#pragma unroll
+        for (int ks = 0; ks < kRwKSteps; ++ks) {
+            const bf16x8 v = *reinterpret_cast<const bf16x8 *>(p + ks * 32);
+            qf[u][ks] = valid ? v : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    }
+    float mx[NU];
+    rw_page_max<NU, F16, BITS>(mx, qf, codes, res, C, K, r0, len, bad, slabs, wtab, rd_off, lane);
 
 #pragma unroll
     for (int u = 0; u < NU; ++u) store_token_max(tokmax, u, mx[u], lane);

@@ -173,7 +173,8 @@ def mine_hard_negatives(queries, corpus: PackedCorpus, positives: Positives, n_n
 
     queries: anything `maxsim_scores` takes (a `PackedQueries` or a contiguous [n_q, Lq, width] device tensor); corpus: a GPU
     `PackedCorpus` of any dtype and width the full scan takes (RuntimeError for a CPU corpus: the kernels are gfx950 only), or a
-    `ResidualCorpus`: the scan is then `residual_scores` over its compressed rows (its query forms and formats).
+    `ResidualCorpus` or a `ResidualWideCorpus`: the scan is then `residual_scores` / `residual_wide_scores` over its compressed rows
+    (its query forms and formats).
     positives: GLOBAL ids (`corpus.id_base + column`) as an int64 [n_q] tensor (-1 = none), an int64 [n_q, P] tensor padded with
     -1, or a CSR pair (ids int64 [nnz], offsets int32 [n_q + 1]); an id outside the shard is ignored on the device -- no error, no
     synchronisation; duplicates are allowed.  ValueError for another dtype or shape.
@@ -191,8 +192,10 @@ def mine_hard_negatives(queries, corpus: PackedCorpus, positives: Positives, n_n
     n = len(corpus)
     if scores is None:
         from .residual import ResidualCorpus, residual_scores
+        from .residual_wide import ResidualWideCorpus, residual_wide_scores
 
-        s = residual_scores(queries, corpus) if isinstance(corpus, ResidualCorpus) else maxsim_scores(queries, corpus)
+        s = (residual_scores(queries, corpus) if isinstance(corpus, ResidualCorpus)
+             else residual_wide_scores(queries, corpus) if isinstance(corpus, ResidualWideCorpus) else maxsim_scores(queries, corpus))
     else:
         if not isinstance(scores, torch.Tensor) or scores.dtype != torch.float32 or scores.dim() != 2 or scores.shape[1] != n:
             raise ValueError(f"scores must be the fp32 [n_q, n = {n}] matrix of maxsim_scores(queries, corpus)")

@@ -26,8 +26,9 @@ dispatch to them; `ShardedRetriever(rc, align_fn=residual_align)` opens the retr
 
 The container, the build, `decompress` and the rerank are one host layer for both row widths (`_ResidualRows`: a public class binds
 the width, its centroid-index class and the library entries that read rows of that width).  `ResidualCorpus` is width 128;
-`ResidualWideCorpus` (colpali_amd/residual_wide.py) is width 320 -- a sibling, not a subclass, so the scan, align and gather above,
-which exist at width 128 only, refuse it by its type.
+`ResidualWideCorpus` (colpali_amd/residual_wide.py) is width 320 -- a sibling, not a subclass, so the scan above (its own is
+`residual_wide_scores`, over the same host body: `_scan_scores`) and align and gather, which exist at width 128 only, refuse it by
+its type.
 """
 from __future__ import annotations
 
@@ -264,6 +265,7 @@ class ResidualCorpus(_ResidualRows):
     _ENCODE = "msim_res_encode_docs"
     _DECODE = "msim_res_decode_rows"
     _CANDIDATES = "msim_res_candidates"
+    _SCORES = "msim_res_scores"
 
 
 def _check_query_format(queries, rc: _ResidualRows, what: str) -> None:
@@ -306,7 +308,12 @@ def residual_scores(queries, rc: ResidualCorpus, *, out: Optional[torch.Tensor] 
     NotImplementedError for fp32, a width other than 128 or a query over 128 tokens.  `out`: fp32 [n_q, n] with unit inner stride on
     the corpus' device -- it may be a column slice of a wider matrix, whose other columns are not touched.  Given a `PackedQueries`
     it never synchronises with the host and is hipGraph-capturable."""
-    dev, queries = _flat_queries(queries, rc, "scan")
+    return _scan_scores(queries, rc, out, ResidualCorpus)
+
+
+def _scan_scores(queries, rc, out: Optional[torch.Tensor], kind) -> torch.Tensor:
+    """the full scan of both widths: the entry of `kind` over a shard of that class"""
+    dev, queries = _flat_queries(queries, rc, "scan", kind)
     n_q, n = len(queries), len(rc)
     if out is None:
         out = torch.empty((n_q, n), dtype=torch.float32, device=dev)
@@ -315,14 +322,15 @@ def residual_scores(queries, rc: ResidualCorpus, *, out: Optional[torch.Tensor] 
         raise ValueError(f"out must be an fp32 [n_q={n_q}, n={n}] tensor with unit inner stride on the corpus' device")
     ld = out.stride(0) if n_q > 1 else max(n, 1)
     L = _lib.lib()
+    entry, ws_bytes = getattr(L, kind._SCORES), getattr(L, kind._SCORES + "_workspace_bytes")
     tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
     with torch.cuda.device(dev):
-        ws = _lib.workspace(int(L.msim_res_scores_workspace_bytes(n_q, n)), dev)
-        rcode = L.msim_res_scores(_lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets), queries.offsets_host.data_ptr(),
-                                  n_q, _lib.ptr(rc.codes), _lib.ptr(rc.residuals), _lib.ptr(rc.centroids), rc.n_centroids,
-                                  _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets), _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM,
-                                  _lib.ptr(out), max(ld, 1), _lib.ptr(ws), _lib.current_stream_handle(dev))
-    _lib.check(rcode, "msim_res_scores")
+        ws = _lib.workspace(int(ws_bytes(n_q, n)), dev)
+        rcode = entry(_lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets), queries.offsets_host.data_ptr(), n_q,
+                      _lib.ptr(rc.codes), _lib.ptr(rc.residuals), _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits,
+                      _lib.ptr(rc.offsets), _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), kind.WIDTH, _lib.ptr(out), max(ld, 1),
+                      _lib.ptr(ws), _lib.current_stream_handle(dev))
+    _lib.check(rcode, kind._SCORES)
     return out
 
 

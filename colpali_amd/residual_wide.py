@@ -14,12 +14,17 @@ colpali_amd/csrc/residual_wide.hip).  A row costs 2 bytes of centroid code plus 
 alone, so it is the same kernel for both widths).  `residual_wide_rerank_scores` reranks candidate lists straight from the
 compressed rows: every score has the bits `rerank_scores` gives the same query against `rc.decompress()`.  Stage 1 is `rc.index`:
 `ShardedRetriever(rc).search(q, k, prefilter=rc.index, n_candidates=m)`; `refine=<Fp4WideIndex>` (built from the corpus before it
-is freed) puts the FP4 rows between the two.
+is freed) puts the FP4 rows between the two.  `residual_wide_scores` is the full scan of such a shard (include/maxsim.h:
+msim_res_wide_scores; colpali_amd/csrc/residual_wide_scan.hip): a page is decoded once per group of up to 8 queries, never written
+to memory, and entry (q, c) has the rerank's bits.  The default retriever only scans on request:
+`ShardedRetriever(rc, score_fn=residual_wide_scores)` opens the full scan, `filter=`, `group_by=` and `mine`, as
+`score_fn=residual_scores` does at width 128; `mine_hard_negatives(q, rc, ...)` dispatches to it.
 
 The host layer is the one of widths 128 (colpali_amd/centroid.py: `_CentroidCodes`, colpali_amd/residual.py: `_ResidualRows`); the
-classes here bind the width and the wide entries.  They are siblings of the 128 classes, not subclasses: everything that exists
-at width 128 only -- the full scan (`residual_scores`), `residual_align`, `residual_gather_pages`, `LiveResidualCorpus` -- refuses
-them by their type, and no 128 kernel ever sees a 320-wide row.
+classes here bind the width and the wide entries.  They are siblings of the 128 classes, not subclasses: the 128 scan
+(`residual_scores`) and everything that exists at width 128 only -- `residual_align`, `residual_gather_pages`,
+`LiveResidualCorpus` -- refuse them by their type, as `residual_wide_scores` refuses a `ResidualCorpus`, and no kernel of one width
+ever sees a row of the other.
 """
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ import torch
 
 from .centroid import _CentroidCodes, _require_kind, _scores
 from .residual import WIDE_DIM as DIM
-from .residual import _rerank_scores, _ResidualRows
+from .residual import _rerank_scores, _ResidualRows, _scan_scores
 
 
 class CentroidWideIndex(_CentroidCodes):
@@ -57,6 +62,7 @@ class ResidualWideCorpus(_ResidualRows):
     _ENCODE = "msim_res_wide_encode_docs"
     _DECODE = "msim_res_wide_decode_rows"
     _CANDIDATES = "msim_res_wide_candidates"
+    _SCORES = "msim_res_wide_scores"
 
 
 def centroid_wide_scores(queries, index: CentroidWideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -77,3 +83,18 @@ def residual_wide_rerank_scores(queries, rc: ResidualWideCorpus, candidates: tor
     (-inf, -1).  bfloat16 / float16, width 320, queries of at most 128 tokens (NotImplementedError otherwise).  Given a
     `PackedQueries` it never synchronises with the host and is hipGraph-capturable."""
     return _rerank_scores(queries, rc, candidates, out, ResidualWideCorpus)
+
+
+def residual_wide_scores(queries, rc: ResidualWideCorpus, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaxSim of every query against every page of the compressed 320-wide shard (include/maxsim.h: msim_res_wide_scores): fp32
+    [n_q, len(rc)], `residual_scores` at width 320 and the counterpart of `maxsim_scores` over a `PackedCorpus`.  Entry (q, c) has the
+    bits `residual_wide_rerank_scores` gives the query against page c, which are the bits of `maxsim_scores(queries, rc.decompress())`
+    whenever that scan runs the flat kernel every ragged batch runs; a scan of ONE query length and at most four 32-token tiles runs
+    another kernel, whose token sum is a butterfly, and agrees to the bound include/maxsim.h states, not bit for bit.  Every row of the
+    shard is decoded, once per group of up to 8 queries (128 tokens), and never written to memory.  The query forms and checks of
+    `residual_wide_rerank_scores`: a `PackedQueries`, a host list or a dense device box; RuntimeError on a dtype mismatch;
+    NotImplementedError for fp32, a width other than 320, a query over 128 tokens or a `ResidualCorpus` (width 128:
+    `residual_scores`).  `out`: fp32 [n_q, n] with unit inner stride on the corpus' device -- it may be a column slice of a wider
+    matrix, whose other columns are not touched.  Given a `PackedQueries` it never synchronises with the host and is
+    hipGraph-capturable."""
+    return _scan_scores(queries, rc, out, ResidualWideCorpus)

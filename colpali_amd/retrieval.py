@@ -32,7 +32,8 @@ from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
 from .residual import ResidualCorpus, residual_align, residual_rerank_scores, residual_scores
-from .residual_wide import CentroidWideIndex, ResidualWideCorpus, centroid_wide_scores, residual_wide_rerank_scores
+from .residual_wide import (CentroidWideIndex, ResidualWideCorpus, centroid_wide_scores, residual_wide_rerank_scores,
+                            residual_wide_scores)
 from .scoring import _require_gpu, maxsim_scores
 
 
@@ -223,7 +224,8 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 # the hooks' defaults: what `ShardedRetriever._pack` packs the queries for
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
             fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, fp4_wide_rerank_scores, align,
-            residual_align, fde_wide_scores, fp6_wide_scores, fp6_wide_rerank_scores, centroid_wide_scores, residual_wide_rerank_scores)
+            residual_align, fde_wide_scores, fp6_wide_scores, fp6_wide_rerank_scores, centroid_wide_scores, residual_wide_rerank_scores,
+            residual_wide_scores)
 
 
 class ShardedRetriever:
@@ -236,10 +238,13 @@ class ShardedRetriever:
     on the mask, list and auto routes (the list route runs the residual rerank), `group_by=` on every route, `filter=` with
     `candidates=` / `prefilter=`, and `mine` -- each with the bits of the same call over `shard.decompress()`.  `align` is opened
     the same way, by its own hook: `align_fn=residual_align` decodes the listed pages inside the alignment kernel; with the default
-    `align_fn` it keeps raising.  A `ResidualWideCorpus` (width 320) works the same way on the candidate routes -- the default
-    `rerank_fn` is `residual_wide_rerank_scores`, `prefilter=shard.index` is its `CentroidWideIndex`, `refine=` takes an
-    `Fp4WideIndex` -- and refuses the scanning routes and `align`: the scan and the alignment of a compressed shard exist at width
-    128 only, so there is no scorer to opt in with."""
+    `align_fn` it keeps raising.  A `ResidualWideCorpus` (width 320) works the same way: the default `rerank_fn` is
+    `residual_wide_rerank_scores`, `prefilter=shard.index` is its `CentroidWideIndex`, `refine=` takes an `Fp4WideIndex`, and
+    `score_fn=residual_wide_scores` opens the same scanning routes -- the full scan, `filter=` on the mask, list and auto routes,
+    `group_by=` on every route, `filter=` with `candidates=` / `prefilter=`, and `mine` -- each with the bits of the same call over
+    `shard.decompress()` scored by the flat kernel every ragged batch runs (`search`'s note on width 320 says where a scan of the
+    decompressed pages runs another kernel).  `align` keeps raising whatever the hooks: the alignment of a compressed shard exists
+    at width 128 only."""
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
@@ -256,7 +261,7 @@ class ShardedRetriever:
         self.shard, self.world, self.rank = shard, world, rank
         self.dist, self.group = (_dist(dist) if world > 1 else dist), group
         self._score, self._select = score_fn, select
-        # a compressed shard is scanned on request only: a scorer of its own must be handed in (residual_scores)
+        # a compressed shard is scanned on request only: a scorer of its own must be handed in (residual_scores / residual_wide_scores)
         self._res_refuses = isinstance(shard, (ResidualCorpus, ResidualWideCorpus)) and score_fn is maxsim_scores
         self._rerank = rerank_fn          # (queries, corpus, candidates) -> (scores [n_q, m], ids [n_q, m]), (-inf, -1) off the shard
         self._fde_score = fde_score_fn    # (queries, FdeIndex) -> fp32 [n_q, len(index)]: stage 1 of prefilter=<FdeIndex>
@@ -447,9 +452,10 @@ class ShardedRetriever:
         if isinstance(self.shard, ResidualWideCorpus):
             raise NotImplementedError(f"{what} over a ResidualWideCorpus: the shard keeps no full-precision rows and only candidate "
                                       "lists are scored from the compressed ones -- use search(candidates=) or "
-                                      "search(prefilter=shard.index, n_candidates=), or shard.decompress() for a PackedCorpus.  The "
-                                      "scan and the alignment of a compressed shard exist at width 128 only: there is no score_fn / "
-                                      "align_fn that opens this route at width 320")
+                                      "search(prefilter=shard.index, n_candidates=), or shard.decompress() for a PackedCorpus; "
+                                      "ShardedRetriever(shard, score_fn=residual_wide_scores) opts in to scanning the compressed rows "
+                                      "(the full scan, filter=, group_by= and mine).  align needs rows either way, and the alignment "
+                                      "of a compressed shard exists at width 128 only: there is no align_fn that opens it at width 320")
         raise NotImplementedError(f"{what} over a ResidualCorpus: the shard keeps no full-precision rows and only candidate lists are "
                                   "scored from the compressed ones -- use search(candidates=) or search(prefilter=shard.index, "
                                   "n_candidates=), or shard.decompress() for a PackedCorpus; ShardedRetriever(shard, "

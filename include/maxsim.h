@@ -1074,8 +1074,8 @@ int msim_res_scores(int dtype, const void *Qt, const int32_t *q_off, const int32
                     void *workspace, void *stream);
 
 /*
- * THE COMPRESSED SHARD AT WIDTH 320 (ColQwen3; residual_wide.hip; additions to ABI 22): the centroid-code first stage and the
- * residual codec over rows of 320 dimensions.  The entries above keep refusing dim == 320 (MSIM_EUNSUPPORTED); these take
+ * THE COMPRESSED SHARD AT WIDTH 320 (ColQwen3; residual_wide.hip, residual_wide_scan.hip; additions to ABI 22): the centroid-code
+ * first stage, the residual codec, the candidate rerank and the full scan over rows of 320 dimensions.  The entries above keep refusing dim == 320 (MSIM_EUNSUPPORTED); these take
  * dim == 320 ONLY (anything else, and a dtype other than bf16 / f16: MSIM_EUNSUPPORTED).  K a multiple of 256 in 256 .. 2048
  * (MSIM_EINVAL otherwise), bits 2 or 4 (MSIM_EUNSUPPORTED otherwise), queries of 0 .. 128 tokens (MSIM_EUNSUPPORTED beyond).  A row
  * costs 2 + 80 = 82 bytes at 2 bits and 2 + 160 = 162 at 4, instead of 640.
@@ -1104,6 +1104,23 @@ int msim_res_scores(int dtype, const void *Qt, const int32_t *q_off, const int32
  *   are not affected); a device q_off that disagrees with q_off_host makes every score of the call NaN.  One wave scores one entry.
  *   workspace: msim_res_wide_candidates_workspace_bytes(n_q, m, n_d) bytes (0 when there is no entry), 16-byte aligned, initialised
  *   by the call (by a kernel); it does not depend on the number of rows.  After the call its first int32 is 0, or 1 for a broken q_off.
+ * msim_res_wide_scores: the FULL SCAN of the wide compressed shard (residual_wide_scan.hip), msim_res_scores' contract and argument
+ *   list over the wide rows -- out_scores[q, c] for every query q and every page c, row stride ld_scores >= n_d (columns >= n_d of a
+ *   wider matrix are not written).  Bit identity: entry (q, c) has exactly the bits msim_res_wide_candidates gives the same query
+ *   against page c -- that is, the bits msim_fwd_candidates_wide (flags 0), and the flat panel kernel behind msim_fwd_ragged at width
+ *   320 (K1bPF), give against the page decoded by msim_res_wide_decode_rows: the same chain, tail mask and exact maximum, and the same
+ *   token sum (a pure function of the token values and the query's length, so the bits do not depend on which queries share a wave).
+ *   A scan of the decoded pages that the few-query panel kernel serves (ONE query length and at most four 32-token tiles: K1sP) adds
+ *   the tokens in another fp32 order: the bound stated for msim_fwd_candidates_wide, |delta| <= 2 gamma(L - 1) sum_i |M_i|, covers
+ *   it.  A wave holds a group of consecutive queries (at most 8 queries and 8 units of 16 tokens) in registers and decodes a page
+ *   once per group, not once per query.  A query of 0 tokens scores 0; a page of 0 rows scores -inf (0 when flagged in d_clamp0).  A
+ *   page with a code >= K, or whose offsets fall outside 0 <= d_off[c] <= d_off[c + 1] <= d_rows, scores NaN in its column for every
+ *   query with at least one token (checked before anything becomes an address; no other column changes); a device q_off that
+ *   disagrees with q_off_host makes every score of the call NaN.
+ *   workspace: msim_res_wide_scores_workspace_bytes(n_q, n_d) bytes (0 when n_q <= 0 or n_d <= 0), 16-byte aligned, initialised by
+ *   the call (by a kernel, not a memset node); a function of n_q alone (status words plus the query-group table), never of the row
+ *   count.  After the call its first int32 is 0, or 1 for a broken q_off.  MSIM_EINVAL also for ld_scores < n_d; MSIM_EUNSUPPORTED
+ *   for d_rows >= 2^31.  n_q == 0 or n_d == 0 is nothing to do.
  * MSIM_EINVAL for a negative size, a null or misaligned pointer (rows, centroids, residuals, out, table, workspace: 16 bytes),
  * ld < m, a q_off_host that does not start at 0 or decreases; MSIM_EUNSUPPORTED for d_rows >= 2^31 in msim_res_wide_candidates.  A
  * call with nothing to do returns 0 before it looks at a pointer.  Every refusal happens before the device is touched.
@@ -1123,6 +1140,11 @@ int msim_res_wide_candidates(int dtype, const void *Qt, const int32_t *q_off, co
                              const int32_t *d_off, const uint8_t *d_clamp0 /* or NULL */, int n_d, int64_t d_rows, int dim,
                              const int64_t *cand, int m, int64_t ld_cand, int64_t id_base, float *out_scores, int64_t ld_scores,
                              int64_t *out_ids /* or NULL */, void *workspace, void *stream);
+size_t msim_res_wide_scores_workspace_bytes(int n_q, int n_d);
+int msim_res_wide_scores(int dtype, const void *Qt, const int32_t *q_off, const int32_t *q_off_host, int n_q, const uint16_t *codes,
+                         const uint8_t *residuals, const void *C, int K, const float *weights, int bits, const int32_t *d_off,
+                         const uint8_t *d_clamp0 /* or NULL */, int n_d, int64_t d_rows, int dim, float *out_scores, int64_t ld_scores,
+                         void *workspace, void *stream);
 
 /*
  * ROWS OUT OF THE COMPRESSED SHARD (residual_align.hip; additions to ABI 22): the two operations that return rows, decoded inside

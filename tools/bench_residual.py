@@ -35,7 +35,9 @@ tools/bench_rerank.py --dim 320 (50 000 x 1024 x 320 bf16, 32.8 GB), for 2 and 4
 residuals), `decompress()`, `residual_wide_rerank_scores` beside `rerank_scores` over a resident `decompress()` on the same uniform
 and clustered lists (1000 x 32 x m = 100 and 4 x 32 x m = 1000) with their bit-equality, the two-stage search
 `prefilter=rc.index` at m = 100 / 400 / 1000 beside the same search over the bf16 shard, and recall@10 and the mean score error on
-the planted 320-wide set of tools/bench_fp4.py --dim 320.  One run; the variants of a comparison alternate step by step inside
+the planted 320-wide set of tools/bench_fp4.py --dim 320.  `--dim 320 --legs scan` times the full scan alone -- `residual_wide_scores`
+(msim_res_wide_scores) at 4 x 32, 32 x 32 and 1000 x 32 queries beside `maxsim_scores` over a resident `rc.decompress()` and, at 4 x 32,
+`residual_wide_rerank_scores` over all ids, checks the bit identity with that rerank, and APPENDS its table to --summary.  One run; the variants of a comparison alternate step by step inside
 one timing loop and every figure is a median (min - max).
 """
 from __future__ import annotations
@@ -105,24 +107,34 @@ SCAN_BATCHES = (4, 32, 1000)
 
 
 def scan_leg(amd, rc, dec, q_len, dev, steps, warmup):
-    """dec=None: residual_scores alone"""
+    """dec=None: the scan alone.  A `ResidualWideCorpus` is scanned by `residual_wide_scores` beside `residual_wide_rerank_scores`."""
     n = len(rc)
+    wide = isinstance(rc, amd.ResidualWideCorpus)
+    scan_fn, rerank_fn = (amd.residual_wide_scores, amd.residual_wide_rerank_scores) if wide else (amd.residual_scores, amd.residual_rerank_scores)
     out = {}
     for n_q in SCAN_BATCHES:
-        pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
+        if wide:
+            from tools.bench_rerank import make_queries_dim
+
+            pq = amd.pack_queries(make_queries_dim(n_q, q_len, rc.width, dev, seed=99), dev, compact=False)
+        else:
+            pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
         scores = torch.empty((n_q, n), dtype=torch.float32, device=dev)
-        fns = {"residual_scan": lambda: amd.residual_scores(pq, rc, out=scores)}
+        fns = {"residual_scan": lambda: scan_fn(pq, rc, out=scores)}
         if dec is not None:
             ref = torch.empty((n_q, n), dtype=torch.float32, device=dev)
             fns["bf16_decompressed_scan"] = lambda: amd.maxsim_scores(pq, dec, out=ref)
             if n_q == SCAN_BATCHES[0]:
                 ids = (torch.arange(n, device=dev) + rc.id_base).expand(n_q, n).contiguous()
                 listed = torch.empty((n_q, n), dtype=torch.float32, device=dev)
-                fns["residual_rerank_all_ids"] = lambda: amd.residual_rerank_scores(pq, rc, ids, out=listed)
+                fns["residual_rerank_all_ids"] = lambda: rerank_fn(pq, rc, ids, out=listed)
         leg = timed_alternating(fns, steps, warmup)
         if dec is not None:
             leg["residual_over_bf16"] = leg["residual_scan"]["median_ms"] / leg["bf16_decompressed_scan"]["median_ms"]
+            # (width 320: queries of one length in at most four 32-token tiles send the decompressed scan to another kernel, whose token
+            # sum has another fp32 order -- the bit identity that is claimed there is the one with the rerank)
             leg["bit_identical_to_bf16_scan"] = bool(torch.equal(scores.view(torch.int32), ref.view(torch.int32)))
+            leg["max_abs_diff_to_bf16_scan"] = float((scores - ref).abs().nan_to_num(0.0).max())
             if "residual_rerank_all_ids" in fns:
                 leg["scan_over_rerank_all_ids"] = leg["residual_scan"]["median_ms"] / leg["residual_rerank_all_ids"]["median_ms"]
                 leg["bit_identical_to_rerank_all_ids"] = bool(torch.equal(scores.view(torch.int32), listed.view(torch.int32)))
@@ -130,7 +142,7 @@ def scan_leg(amd, rc, dec, q_len, dev, steps, warmup):
             del ref
         passes = (n_q * q_len + 127) // 128
         leg["passes_over_the_shard"] = passes
-        leg["row_bytes_per_s"] = int(rc.codes.shape[0]) * (2 + 16 * rc.bits) * passes / (leg["residual_scan"]["median_ms"] * 1e-3)
+        leg["row_bytes_per_s"] = int(rc.codes.shape[0]) * (2 + rc.width // 8 * rc.bits) * passes / (leg["residual_scan"]["median_ms"] * 1e-3)
         out[f"{n_q}x{q_len}"] = leg
         del scores, pq
     return out
@@ -247,6 +259,56 @@ def wide_summary(res) -> str:
     return "\n".join(L) + "\n"
 
 
+def wide_scan_summary(res) -> str:
+    """the section `--dim 320 --legs scan` appends to profiles/residual_wide_summary.md"""
+    L = ["", "## Full scan: residual_wide_scores beside maxsim_scores over a resident decompress()", "",
+         f"`tools/bench_residual.py --dim 320 --legs scan --steps {res['steps']} --warmup {res['warmup']}` on {res['docs']} pages x "
+         f"{res['doc_len']} rows x 320 bf16 ({res['corpus_bytes'] / 1e9:.1f} GB), K = {res['n_centroids']}; the variants alternate step by step "
+         "inside one timing loop; median (min - max) in ms.  The rerank over all ids is timed at the smallest batch only.", "",
+         "| bits | queries | residual_wide_scores | maxsim_scores over decompress() | ratio | rerank over all ids | scan / rerank | "
+         "same bits as the rerank | max abs diff to the decompressed scan | compressed row bytes read per s |", "|---|---|---|---|---|---|---|---|---|---|"]
+    for bits in BITS:
+        for shape, leg in res[f"bits{bits}"]["scan"].items():
+            rr = "residual_rerank_all_ids" in leg
+            L.append(f"| {bits} | {shape} | {_fmt(leg['residual_scan'])} | {_fmt(leg['bf16_decompressed_scan'])} | {leg['residual_over_bf16']:.2f} | "
+                     f"{_fmt(leg['residual_rerank_all_ids']) if rr else '-'} | {leg['scan_over_rerank_all_ids']:.2f} | " if rr else
+                     f"| {bits} | {shape} | {_fmt(leg['residual_scan'])} | {_fmt(leg['bf16_decompressed_scan'])} | {leg['residual_over_bf16']:.2f} | - | - | ")
+            L[-1] += (f"{leg['bit_identical_to_rerank_all_ids'] if rr else '-'} | {leg['max_abs_diff_to_bf16_scan']:.2e} | "
+                      f"{leg['row_bytes_per_s'] / 1e9:.1f} GB |")
+    return "\n".join(L) + "\n"
+
+
+def main_wide_scan(args, amd, dev):
+    """--dim 320 --legs scan: the full scan of the compressed shard alone; the section is APPENDED to --summary"""
+    from tools.bench_rerank import make_shard_dim
+
+    docs = args.docs if args.docs != 125_000 else 50_000
+    t0 = time.perf_counter()
+    res = {"tool": "bench_residual", "dim": 320, "legs": "scan", "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len,
+           "n_centroids": K, "steps": args.steps, "warmup": args.warmup}
+    corpus = make_shard_dim(docs, args.doc_len, 320, dev, seed=1234)
+    index = amd.CentroidWideIndex.build(corpus, n_centroids=K)
+    res["corpus_bytes"] = corpus.nbytes
+    shards = {bits: amd.ResidualWideCorpus.build(corpus, index=index, bits=bits) for bits in BITS}
+    del corpus
+    torch.cuda.empty_cache()
+    for bits, rc in shards.items():
+        dec = rc.decompress() if args.scan_ref else None
+        res[f"bits{bits}"] = {"nbytes": rc.nbytes, "scan": scan_leg(amd, rc, dec, args.q_len, dev, args.steps, args.warmup)}
+        del dec
+        torch.cuda.empty_cache()
+    res["wall_s"] = time.perf_counter() - t0
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    if args.summary and args.scan_ref:
+        fresh = not os.path.exists(args.summary)
+        with open(args.summary, "a") as f:
+            f.write(("# The residual-compressed shard at width 320 (ColQwen3)\n" if fresh else "") + wide_scan_summary(res))
+    print(line)
+
+
 def main_wide(args):
     """--dim 320: see the module docstring"""
     import colpali_amd as amd
@@ -256,6 +318,8 @@ def main_wide(args):
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     amd._lib.lib()
+    if set(args.legs.split(",")) == {"scan"}:
+        return main_wide_scan(args, amd, dev)
     docs = args.docs if args.docs != 125_000 else 50_000
     t0 = time.perf_counter()
     res = {"tool": "bench_residual", "dim": 320, "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len, "n_centroids": K,
