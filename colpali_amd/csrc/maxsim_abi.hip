@@ -168,11 +168,11 @@ int launch_stream(const FwdCall &c) {
 
 // K1s over the 13-bit image (maxsim_stream13.hip): the same ring depths and grid rule as launch_stream -- 2 slabs of 6.5 KiB for 5-8
 // units (60.25 KiB per workgroup: two per CU; the next slab's requests pinned one per NU / 2 MFMAs: maxsim_stream.hip, ORDER, paced
-// half), 4 slabs below.  The documents the encoder flagged are skipped there and scored
+// half; the two waves of a SIMD swap s_setprio every 32 slabs: maxsim_stream13.hip, PRIO), 4 slabs below.  The documents the encoder flagged are skipped there and scored
 // from the blob by the raw K1s over their id list, into the same score columns; that launch exists only when the list is not empty.
-template <int NU, int RING, int ORDER>
+template <int NU, int RING, int ORDER, int DECODE = msim::stream13_decode(), int PRIO = msim::stream13_prio(RING)>
 int launch_stream13_order(const FwdCall &c) {
-    auto kern = msim::maxsim_stream13_kernel<NU, RING, 2, ORDER>;
+    auto kern = msim::maxsim_stream13_kernel<NU, RING, 2, ORDER, DECODE, PRIO>;
     constexpr int lds = 4 * (RING * msim::kSlab13Bytes + msim::kStreamTokBytes);
     static std::atomic<int> configured[kMaxDevices];
     if (int rc = allow_lds(kern, lds, configured)) return rc;
@@ -187,11 +187,37 @@ int launch_stream13_order(const FwdCall &c) {
     }
     return MSIM_OK;
 }
+// MSIM_STREAM13_DECODE=0|1 / MSIM_STREAM13_PRIO=0..3 (measurement builds): how the high bytes are decoded (maxsim_stream13.hip: or3, bfi)
+// and how the two waves of a SIMD share its vector issue (none, doc, slabs, static; 2-slot forms only), at the shipped request order
+template <int NU, int RING, int ORDER>
+int launch_stream13_issue(const FwdCall &c) {
+#if defined(MSIM_AB) || defined(MSIM_TRACE)
+    static const int decode = ab_env("MSIM_STREAM13_DECODE", msim::stream13_decode());
+    static const int prio = RING == 2 ? ab_env("MSIM_STREAM13_PRIO", msim::stream13_prio(RING)) : msim::kPrioNone;
+    if constexpr (ORDER == msim::stream13_order(RING)) {
+        auto with_prio = [&](auto dec) {
+            constexpr int D = decltype(dec)::value;
+            if constexpr (RING == 2) {
+                switch (prio) {
+                    case msim::kPrioDoc: return launch_stream13_order<NU, RING, ORDER, D, msim::kPrioDoc>(c);
+                    case msim::kPrioSlabs: return launch_stream13_order<NU, RING, ORDER, D, msim::kPrioSlabs>(c);
+                    case msim::kPrioStatic: return launch_stream13_order<NU, RING, ORDER, D, msim::kPrioStatic>(c);
+                    default: break;
+                }
+            }
+            return launch_stream13_order<NU, RING, ORDER, D, msim::kPrioNone>(c);
+        };
+        return decode == msim::kDecodeOr3 ? with_prio(std::integral_constant<int, msim::kDecodeOr3>{})
+                                          : with_prio(std::integral_constant<int, msim::kDecodeBfi>{});
+    }
+#endif
+    return launch_stream13_order<NU, RING, ORDER>(c);
+}
 template <int NU>
 int launch_stream13(const FwdCall &c) {
     constexpr int RING = NU >= 5 ? 2 : kStreamRing;
     static const int forced = ab_env("MSIM_STREAM_ORDER", -1);
-    return dispatch_order<RING, msim::stream13_order(RING)>(forced, [&](auto order) { return launch_stream13_order<NU, RING, decltype(order)::value>(c); });
+    return dispatch_order<RING, msim::stream13_order(RING)>(forced, [&](auto order) { return launch_stream13_issue<NU, RING, decltype(order)::value>(c); });
 }
 
 // K1s holds 1..8 units: launch(std::integral_constant<int, NU>) for the plan's count

@@ -38,7 +38,7 @@ struct StreamArgs {
     int n_d;
     unsigned flags;
 #ifdef MSIM_TRACE
-    unsigned long long *trace;   // tools/trace_stream.py: per wave of the first kStreamTraceWgs workgroups {s_memtime ticks in the wait, in the rest of the body, slabs, s_memrealtime ticks of the wave}; or null
+    unsigned long long *trace;   // tools/trace_stream.py: per wave of the first and the last kStreamTraceWgs workgroups {s_memtime ticks in the wait, in the rest of the body, slabs, s_memrealtime ticks of the wave, HW_ID | XCC_ID << 32 | workgroup << 40, s_memrealtime at its start}; or null
 #endif
 };
 
@@ -63,11 +63,20 @@ constexpr int stream_order_stride(int order, int nu) {                          
     return order == kOrderPaced ? nu : order == kOrderPacedHalf ? (nu >= 2 ? nu / 2 : 1) : 0;
 }
 
-// MSIM_TRACE builds only: s_memtime stamps around the wait of every slab body (wave-uniform, SGPRs only)
+// s_getreg_b32 operands: where a wave sits (K1s13's priority phase; the trace)
+constexpr int kHwRegHwId = 4 | (31 << 11);        // hwreg(HW_REG_HW_ID, 0, 32): wave slot [3:0], SIMD [5:4], pipe [7:6], CU [11:8], SH [12], SE [15:13]
+constexpr int kHwRegXccId = 20 | (3 << 11);       // hwreg(HW_REG_XCC_ID, 0, 4): the XCD
+
+// MSIM_TRACE builds only: s_memtime stamps around the wait of every slab body (wave-uniform, SGPRs only), for the waves of the first
+// and of the last kStreamTraceWgs workgroups of the grid (the oldest and the youngest): kStreamTraceWords words per wave, the first
+// workgroups' waves in rows 0 .. 4 * kStreamTraceWgs - 1, the last ones' behind them
 #ifdef MSIM_TRACE
 constexpr int kStreamTraceWgs = 64;
+constexpr int kStreamTraceWords = 6;
 #define MSIM_STREAM_TRACE_BEGIN() \
-    const bool tracing = a.trace != nullptr && blockIdx.x < kStreamTraceWgs; \
+    const int tr_last0 = (int)gridDim.x - kStreamTraceWgs < kStreamTraceWgs ? kStreamTraceWgs : (int)gridDim.x - kStreamTraceWgs; \
+    const int tr_wg = (int)blockIdx.x < kStreamTraceWgs ? (int)blockIdx.x : (int)blockIdx.x - tr_last0 + kStreamTraceWgs; \
+    const bool tracing = a.trace != nullptr && ((int)blockIdx.x < kStreamTraceWgs || (int)blockIdx.x >= tr_last0); \
     unsigned long long tr_wait = 0, tr_body = 0, tr_n = 0, tr_t0 = 0, tr_t1 = 0; \
     const unsigned long long tr_r0 = tracing ? __builtin_amdgcn_s_memrealtime() : 0
 #define MSIM_STREAM_TRACE_TOP() do { if (tracing) tr_t0 = __builtin_amdgcn_s_memtime(); } while (0)
@@ -75,7 +84,8 @@ constexpr int kStreamTraceWgs = 64;
 #define MSIM_STREAM_TRACE_END() \
     do { if (tracing) { const unsigned long long t2 = __builtin_amdgcn_s_memtime(); tr_wait += tr_t1 - tr_t0; tr_body += t2 - tr_t1; ++tr_n; } } while (0)
 #define MSIM_STREAM_TRACE_WRITE() \
-    do { if (tracing && lane == 0) { unsigned long long *t = a.trace + (size_t)gw * 4; t[0] = tr_wait; t[1] = tr_body; t[2] = tr_n; t[3] = __builtin_amdgcn_s_memrealtime() - tr_r0; } } while (0)
+    do { if (tracing && lane == 0) { unsigned long long *t = a.trace + (size_t)(tr_wg * 4 + wave) * kStreamTraceWords; t[0] = tr_wait; t[1] = tr_body; t[2] = tr_n; t[3] = __builtin_amdgcn_s_memrealtime() - tr_r0; \
+        t[4] = (unsigned long long)__builtin_amdgcn_s_getreg(kHwRegHwId) | ((unsigned long long)__builtin_amdgcn_s_getreg(kHwRegXccId) << 32) | ((unsigned long long)blockIdx.x << 40); t[5] = tr_r0; } } while (0)
 #else
 #define MSIM_STREAM_TRACE_BEGIN() do {} while (0)
 #define MSIM_STREAM_TRACE_TOP() do {} while (0)

@@ -23,9 +23,26 @@ __device__ __forceinline__ void pack13_interleave(uint32_t H, uint32_t L, int &o
     o1 = (int)__builtin_amdgcn_perm(H, L, 0x07030602u);     // L2 H2 L3 H3
 }
 
-// the four A fragments of one 16-row group from the lane's raw 52 bytes
+// how the high bytes are put together (DECODE of the kernel).  High byte = 0 0 1 1 nibble under the sign:
+//   or3: H = ((nib >> 4h) & 0x0f0f0f0f) | 0x30303030 | ((sign << q) & 0x80808080)      v_and, v_and, v_or3 + the shifts: 6.5 VALU per four values
+//   bfi: X = ((sign << q) & 0x80808080) | k30;  H = (nib >> 4h) under 0x0f0f0f0f, X elsewhere    v_and_or, v_bfi + the shifts: 5.5
+// (with the two v_perm of the interleave; a shift by 0 is not there).  The same bits either way.  hipcc turns every C++ spelling of
+// the second form back into the first as long as it can see through X (the bits under the mask are known), so X and the constant
+// k30 = 0x30303030 pass through EMPTY asm statements that only hide their values: no instruction is written by hand, the selector
+// emits v_and_or_b32 (one scalar operand per VOP3 on gfx9: k30 lives in a register) and v_bfi_b32 itself, and the hazard recognizer
+// sees every instruction next to the MFMAs.  (The two instructions written out as asm text were measured and dropped: hipcc does not
+// look into asm text for the MFMA hazards -- profiles/stream13_issue.md.)
+constexpr int kDecodeOr3 = 0, kDecodeBfi = 1;
+constexpr int stream13_decode() { return kDecodeBfi; }
+__device__ __forceinline__ uint32_t pack13_hidden(uint32_t x) {
+    asm("" : "+v"(x));
+    return x;
+}
+
+// the four A fragments of one 16-row group from the lane's raw 52 bytes; k30: pack13_hidden(0x30303030), made once per kernel (bfi)
+template <int DECODE>
 __device__ __forceinline__ void pack13_decode_group(bf16x8 (&af)[kKSteps16], const i32x4 &lo01, const i32x4 &lo23, const i32x4 &nib,
-                                                    uint32_t sign) {
+                                                    uint32_t sign, uint32_t k30) {
 #pragma unroll
     for (int ks = 0; ks < kKSteps16; ++ks) {
         i32x4 o;
@@ -33,8 +50,14 @@ __device__ __forceinline__ void pack13_decode_group(bf16x8 (&af)[kKSteps16], con
         for (int h = 0; h < 2; ++h) {
             const int q = 2 * ks + h;
             const uint32_t L = (uint32_t)(ks < 2 ? lo01[2 * ks + h] : lo23[2 * (ks - 2) + h]);
-            uint32_t H = (((uint32_t)nib[ks] >> (4 * h)) & 0x0f0f0f0fu) | 0x30303030u;
-            H |= (sign << q) & 0x80808080u;
+            uint32_t H;
+            if constexpr (DECODE == kDecodeBfi) {
+                const uint32_t X = pack13_hidden(((q ? sign << q : sign) & 0x80808080u) | k30);
+                H = ((h ? (uint32_t)nib[ks] >> 4 : (uint32_t)nib[ks]) & 0x0f0f0f0fu) | (X & 0xf0f0f0f0u);
+            } else {
+                H = (((uint32_t)nib[ks] >> (4 * h)) & 0x0f0f0f0fu) | 0x30303030u;
+                H |= (sign << q) & 0x80808080u;
+            }
             int o0, o1;
             pack13_interleave(H, L, o0, o1);
             o[2 * h] = o0;
@@ -44,7 +67,27 @@ __device__ __forceinline__ void pack13_decode_group(bf16x8 (&af)[kKSteps16], con
     }
 }
 
-template <int NU, int RING, int AUX = 2, int ORDER = stream13_order(RING)>
+// ---- PRIO of the kernel, 2-slot forms only (two workgroups on a CU, so two waves on a SIMD): how the two partners share the SIMD's
+// vector issue, which goes to the higher s_setprio and then to the OLDER wave -- left alone, the older workgroup of a CU runs nearly
+// unimpeded, finishes early, and the younger one ends the scan alone at one wave per SIMD.  The phase is the parity of the wave's
+// slot on its SIMD (HW_ID, read once into an SGPR): on MI355X the traced waves report slots 0 and 1 only, the first workgroup of a
+// CU on 0 and the second on 1 (tools/trace_stream.py prints the slots per generation).
+//   none   : both at priority 0
+//   doc    : priority (documents scored ^ phase) & 1, set at every document's start: the partners take turns
+//   slabs  : the same per kPrioSlabCount consumed slabs, so that ragged shards keep the partners out of step (shipped)
+//   static : the wave of odd phase at priority 1 for the whole kernel (cdna_hip_programming.md T5, static form): no gain here
+// Every form is back at priority 0 before the wave ends.  Measured in profiles/stream13_issue.md; the forms not shipped exist in
+// measurement builds only (MSIM_STREAM13_PRIO).
+constexpr int kPrioNone = 0, kPrioDoc = 1, kPrioSlabs = 2, kPrioStatic = 3;
+constexpr int kPrioSlabCount = 32;
+constexpr int stream13_prio(int ring) { return ring == 2 ? kPrioSlabs : kPrioNone; }      // what the shipped library runs
+// s_setprio takes an immediate and ignores EXEC: the choice is a scalar branch on a value made wave-uniform by construction
+__device__ __forceinline__ void stream13_setprio(unsigned odd) {
+    if (__builtin_amdgcn_readfirstlane(odd & 1u)) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+}
+
+template <int NU, int RING, int AUX = 2, int ORDER = stream13_order(RING), int DECODE = stream13_decode(), int PRIO = stream13_prio(RING)>
 __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t *__restrict__ Qt,      // [T, 128] flat query tokens
                                                                  const int32_t *__restrict__ d_off,    // [n_d + 1]
                                                                  const uint8_t *__restrict__ clamp0,   // [n_d] or null
@@ -82,6 +125,8 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
         for (int ks = 0; ks < kKSteps16; ++ks) asm volatile("" : "+v"(qu[u].f[ks]));
 
     const int off16 = lane * 16, off4 = lane * 4;
+    uint32_t k30 = 0x30303030u;
+    if constexpr (DECODE == kDecodeBfi) asm volatile("" : "+v"(k30));      // hidden once, in front of the loops: stays in its register
 
     // ---- producer cursor (wave-uniform): next slab to request
     int p_idx = gw, p_s = 0, p_n = 0;
@@ -141,7 +186,14 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
     constexpr int kOrd = ORDER;
     constexpr int kEarly = stream_order_early(kOrd);     // pieces of the next request issued in front of the wait
     static_assert(7 * stream_order_stride(kOrd, NU) < 8 * NU, "the eighth pinned piece must stand in front of an MFMA of the body");
+    static_assert(PRIO == kPrioNone || RING == 2, "one workgroup per CU is one wave per SIMD: nobody to take turns with");
     MSIM_STREAM_TRACE_BEGIN();
+    unsigned prio_turn = 0;            // wave-uniform: the phase, plus the documents (doc) or the blocks of slabs (slabs) behind the wave
+    int prio_slabs = 0;
+    if constexpr (PRIO != kPrioNone) {
+        prio_turn = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_s_getreg(kHwRegHwId)) & 1u;
+        if constexpr (PRIO != kPrioDoc) stream13_setprio(prio_turn);
+    }
     const bool ref_bf16 = (a.flags & kFlagRefBf16) != 0;
     int c_slot = 0;
     for (int c_idx = gw; c_idx < a.n_d; c_idx += GW) {
@@ -150,6 +202,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
         float m[NU];
 #pragma unroll
         for (int u = 0; u < NU; ++u) m[u] = -INFINITY;
+        if constexpr (PRIO == kPrioDoc) stream13_setprio(prio_turn++);
 
         auto slab = [&](auto tail_c, int rows_left) {
             constexpr bool kTail = decltype(tail_c)::value;
@@ -180,7 +233,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
                 const i32x4 lo23 = *reinterpret_cast<const i32x4 *>(src + (2 * g + 1) * 1024 + off16);
                 const i32x4 nib = *reinterpret_cast<const i32x4 *>(src + kSlab13Nib + g * 1024 + off16);
                 const uint32_t sign = *reinterpret_cast<const uint32_t *>(src + kSlab13Sign + g * 256 + off4);
-                pack13_decode_group(af[g], lo01, lo23, nib, sign);
+                pack13_decode_group<DECODE>(af[g], lo01, lo23, nib, sign, k30);
                 if constexpr (kOrd == kOrderSplit) {
                     if (g == 0) {
                         __builtin_amdgcn_sched_barrier(0);
@@ -203,6 +256,12 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
                 }
             });
             advance(nx_live);
+            if constexpr (PRIO == kPrioSlabs) {
+                if (++prio_slabs == kPrioSlabCount) {
+                    prio_slabs = 0;
+                    stream13_setprio(++prio_turn);
+                }
+            }
             MSIM_STREAM_TRACE_END();
         };
         const int n_full = len / kSlabRows, rem = len - n_full * kSlabRows;
@@ -222,6 +281,7 @@ __global__ __launch_bounds__(256, 2) void maxsim_stream13_kernel(const uint16_t 
             if (ri == 0) scores[(size_t)rq * a.ld + c_idx] = tot;
         }
     }
+    if constexpr (PRIO != kPrioNone) __builtin_amdgcn_s_setprio(0);
     MSIM_STREAM_TRACE_WRITE();
 }
 
