@@ -49,10 +49,11 @@ Drop-in for the MaxSim hot path of illuin-tech/colpali:
                                      (align and gather_pages dispatch to them on a ResidualCorpus)
   * CentroidWideIndex / centroid_wide_scores, ResidualWideCorpus / residual_wide_rerank_scores -- the same two at width 320
                                      (ColQwen3): 82 / 162 bytes per row instead of 640, stage 1 by prefilter=rc.index, candidate
-                                     lists reranked straight from the compressed rows (align / gather and the live form exist at
-                                     width 128 only)
+                                     lists reranked straight from the compressed rows (the live form exists at width 128 only)
   * residual_wide_scores          -- the full scan of a ResidualWideCorpus, residual_scores at width 320: the score matrix behind
                                      ShardedRetriever(rc, score_fn=residual_wide_scores) -- search, filter=, group_by=, mine
+  * residual_wide_align / residual_wide_gather_pages -- align and gather_pages over a ResidualWideCorpus, the listed pages decoded
+                                     inside the kernel (align and gather_pages dispatch to them on a ResidualWideCorpus)
   * LiveResidualCorpus           -- such a shard filled incrementally from pages that are never kept: add (one fused encode pass),
                                      delete, compact in place; the lifecycle LiveCorpus gives the bf16 shard
   * save / load / verify_file     -- every shard and index class as one flat, versioned file (no pickle), streamed through the pinned
@@ -88,8 +89,8 @@ from .pooling import HierarchicalTokenPooler, TokenPoolingOutput
 from .patch import patch_colpali_engine, unpatch_colpali_engine
 from .residual import (ResidualCorpus, residual_align, residual_gather_pages, residual_rerank_scores, residual_scores,
                        train_residual_codec)
-from .residual_wide import (CentroidWideIndex, ResidualWideCorpus, centroid_wide_scores, residual_wide_rerank_scores,
-                            residual_wide_scores)
+from .residual_wide import (CentroidWideIndex, ResidualWideCorpus, centroid_wide_scores, residual_wide_align,
+                            residual_wide_gather_pages, residual_wide_rerank_scores, residual_wide_scores)
 from .retrieval import (TOPK_MAX_K, ExactMaxSimIndex, ResidualMaxSimIndex, ShardedRetriever, create_plaid_index, get_topk_plaid, merge_gathered,
                         rerank, shard_range, shard_topk, topk)
 from .scoring import (get_similarity_maps_from_embeddings, get_torch_device, maxsim_scores, score_multi_vector,
@@ -144,6 +145,8 @@ __all__ = [
     "CentroidWideIndex",
     "centroid_wide_scores",
     "ResidualWideCorpus",
+    "residual_wide_align",
+    "residual_wide_gather_pages",
     "residual_wide_rerank_scores",
     "residual_wide_scores",
     "LiveCorpus",

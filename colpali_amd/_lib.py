@@ -259,6 +259,9 @@ def lib() -> ctypes.CDLL:
     L.msim_res_align_candidates.restype = i32
     L.msim_res_gather_pages.argtypes = [i32, vp, vp, vp, i32, vp, i32, i32, i64, vp, i32, i64, vp, i64, i64, vp, vp, vp]
     L.msim_res_gather_pages.restype = i32
+    for wide, narrow in ((L.msim_res_wide_align_candidates, L.msim_res_align_candidates),
+                         (L.msim_res_wide_gather_pages, L.msim_res_gather_pages)):      # rows out of the 320-wide shard: the same two
+        wide.argtypes, wide.restype = narrow.argtypes, narrow.restype
     L.msim_res_scores_workspace_bytes.argtypes = [i32, i32]
     L.msim_res_scores_workspace_bytes.restype = sz
     L.msim_res_scores.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, i32, i64, i32, vp, i64, vp, vp]

@@ -91,11 +91,14 @@ def align(queries, corpus: PackedCorpus, ids: torch.Tensor, *, maps: bool = Fals
     position, in any batch and under any m.  Asynchronous on torch's current stream; with a `PackedQueries` there is no host
     synchronisation and the call is hipGraph-capturable.
     A `ResidualCorpus` goes to `residual_align` (width 128; the bits of this call over `corpus.decompress()`, the pages decoded
-    inside the kernel)."""
+    inside the kernel), a `ResidualWideCorpus` to `residual_wide_align` (width 320, under the same rule)."""
     from .residual import ResidualCorpus, residual_align      # residual imports this module's Alignment
+    from .residual_wide import ResidualWideCorpus, residual_wide_align
 
     if isinstance(corpus, ResidualCorpus):
         return residual_align(queries, corpus, ids, maps=maps, max_rows=max_rows)
+    if isinstance(corpus, ResidualWideCorpus):
+        return residual_wide_align(queries, corpus, ids, maps=maps, max_rows=max_rows)
     dev = _require_gpu(corpus.device)
     q_dtype, dim = _dtype_width(queries)
     if q_dtype != corpus.blob.dtype:

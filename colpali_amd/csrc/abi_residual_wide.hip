@@ -1,8 +1,9 @@
 // C ABI of libmaxsim_gfx950.so (see include/maxsim.h): the residual-compressed shard at width 320 (msim_cent_wide_*, msim_res_wide_*)
-// -- the centroid-code encoder and query table, the residual codec, the candidate rerank and the full scan over the compressed rows.
+// -- the centroid-code encoder and query table, the residual codec, the candidate rerank, the full scan, and align / gather_pages over
+// the compressed rows.
 // Host-side dispatch only: argument validation, kernel selection and launch on the caller's stream.  Nothing here allocates, frees or
-// synchronises, so every entry point is hipGraph-capturable.  The kernels of residual_wide.hip and residual_wide_scan.hip are defined
-// and launched in this translation unit and in no other.  The table msim_cent_wide_table writes is scanned by msim_cent_scores
+// synchronises, so every entry point is hipGraph-capturable.  The kernels of residual_wide.hip, residual_wide_scan.hip and
+// residual_wide_align.hip are defined and launched in this translation unit and in no other.  The table msim_cent_wide_table writes is scanned by msim_cent_scores
 // (abi_index.hip), which depends on the table and the codes alone.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 #include "../../include/maxsim.h"
 #include "abi_common.hpp"
 #include "residual_wide.hip"
+#include "residual_wide_align.hip"
 #include "residual_wide_scan.hip"
 
 using namespace msim_abi;
@@ -249,6 +251,84 @@ int msim_res_wide_scores(int dtype, const void *Qt, const int32_t *q_off, const 
     hipLaunchKernelGGL(msim::res_wide_scan_poison_kernel, dim3((unsigned)(pblocks < wg_cap * 8 ? pblocks : wg_cap * 8)), dim3(256), 0, st,
                        status, n_q, n_d, out_scores, (long long)ld_scores);
     return launch_failed("res_wide_scan_kernel");
+}
+
+// K1a's contract at width 320 over the compressed rows: every wave decodes the chunks it multiplies, nothing is staged or allocated
+int msim_res_wide_align_candidates(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                                   const uint16_t *codes, const uint8_t *residuals, const void *C, int K, const float *weights, int bits,
+                                   const int32_t *d_off, const uint8_t *d_clamp0, int n_d, int64_t d_rows, int dim, const int64_t *cand,
+                                   int m, int64_t ld_cand, int64_t id_base, float *best_sim, int32_t *best_row, float *sims, int max_rows,
+                                   void *stream) {
+    const char *who = "msim_res_wide_align_candidates";
+    if (n_q < 0 || m < 0 || n_d < 0 || q_rows < 0 || d_rows < 0 || max_q_tokens < 0 || max_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_q=%d m=%d n_d=%d q_rows=%lld d_rows=%lld max_q_tokens=%d max_rows=%d)", who, n_q,
+                    m, n_d, (long long)q_rows, (long long)d_rows, max_q_tokens, max_rows);
+    if (n_q == 0 || m == 0) return MSIM_OK;
+    if (int rc = rw_check_format(who, dtype, dim, K, bits)) return rc;
+    if (max_q_tokens > msim::kAlignMaxTokens)
+        return fail(MSIM_EUNSUPPORTED, "%s: max_q_tokens=%d: queries of at most %d tokens", who, max_q_tokens, msim::kAlignMaxTokens);
+    if ((!Qt && q_rows > 0) || !q_off || ((!codes || !residuals) && d_rows > 0) || !C || !weights || !d_off || !cand ||
+        ((!best_sim || !best_row) && max_q_tokens > 0))
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(Qt, 16) || misaligned(C, 16) || misaligned(residuals, 16))
+        return fail(MSIM_EINVAL, "%s: Qt, centroids and residuals must be 16-byte aligned", who);
+    if (misaligned(codes, 2) || misaligned(weights, 4) || misaligned(q_off, 4) || misaligned(d_off, 4) || misaligned(cand, 8) ||
+        misaligned(best_sim, 4) || misaligned(best_row, 4) || misaligned(sims, 4))
+        return fail(MSIM_EINVAL, "%s: codes must be 2-byte aligned; weights, offsets and outputs 4-byte aligned, cand 8-byte aligned", who);
+    if (ld_cand < m) return fail(MSIM_EINVAL, "%s: ld_cand=%lld < m=%d", who, (long long)ld_cand, m);
+    if ((long long)n_q * m > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: more than 2^31 - 1 entries (n_q=%d x m=%d)", who, n_q, m);
+    if (d_rows > 0x7fffffffLL) return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld exceeds 32-bit page offsets", who, (long long)d_rows);
+    if (max_q_tokens == 0) return MSIM_OK;                       // no token slot: nothing to write
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    msim::AlignArgs a;
+    a.ld_cand = ld_cand;
+    a.id_base = id_base;
+    a.q_rows = q_rows;
+    a.d_rows = d_rows;
+    a.n_q = n_q;
+    a.m = m;
+    a.n_d = n_d;
+    a.T = max_q_tokens;
+    a.R = max_rows;
+    a.vec = sims && !misaligned(sims, 16) && max_rows % 4 == 0;
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = bits == 2 ? (f16 ? msim::res_wide_align_kernel<true, 2> : msim::res_wide_align_kernel<false, 2>)
+                          : (f16 ? msim::res_wide_align_kernel<true, 4> : msim::res_wide_align_kernel<false, 4>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)n_q * m)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint16_t *>(Qt), q_off, codes, residuals, static_cast<const uint16_t *>(C), K, weights, d_off,
+                       d_clamp0, cand, best_sim, best_row, sims, a);
+    return launch_failed("res_wide_align_kernel");
+}
+
+// msim_gather_pages' contract (row_bytes 640) over the compressed rows: the box is decoded into, never copied from a decoded page
+int msim_res_wide_gather_pages(int dtype, const uint16_t *codes, const uint8_t *residuals, const void *C, int K, const float *weights,
+                               int bits, int dim, int64_t d_rows, const int32_t *d_off, int n_d, int64_t id_base, const int64_t *ids,
+                               int64_t n_slots, int64_t pad_rows, void *out, int32_t *lengths, void *stream) {
+    const char *who = "msim_res_wide_gather_pages";
+    if (n_slots < 0 || n_d < 0 || d_rows < 0 || pad_rows < 0)
+        return fail(MSIM_EINVAL, "%s: negative size (n_slots=%lld n_d=%d d_rows=%lld pad_rows=%lld)", who, (long long)n_slots, n_d,
+                    (long long)d_rows, (long long)pad_rows);
+    if (n_slots == 0) return MSIM_OK;
+    if (int rc = rw_check_format(who, dtype, dim, K, bits)) return rc;
+    if (d_rows > 0x7fffffffLL || pad_rows > 0x7fffffffLL || n_slots > 0x7fffffffLL)
+        return fail(MSIM_EUNSUPPORTED, "%s: d_rows=%lld, pad_rows=%lld or n_slots=%lld above 2^31 - 1", who, (long long)d_rows,
+                    (long long)pad_rows, (long long)n_slots);
+    if (!ids || !lengths || !d_off || ((!codes || !residuals) && d_rows > 0) || !C || !weights || (!out && pad_rows > 0))
+        return fail(MSIM_EINVAL, "%s: null pointer argument", who);
+    if (misaligned(out, 16) || misaligned(C, 16) || misaligned(residuals, 16) || misaligned(codes, 2) || misaligned(weights, 4) ||
+        misaligned(ids, 8) || misaligned(d_off, 4) || misaligned(lengths, 4))
+        return fail(MSIM_EINVAL, "%s: out, centroids and residuals must be 16-byte aligned, ids 8-byte, codes 2-byte, weights, d_off and "
+                    "lengths 4-byte aligned", who);
+    const DeviceInfo *di = nullptr;
+    if (int rc = device_info(&di)) return rc;
+    const bool f16 = dtype == MSIM_DTYPE_F16;
+    auto kern = bits == 2 ? (f16 ? msim::res_wide_gather_pages_kernel<true, 2> : msim::res_wide_gather_pages_kernel<false, 2>)
+                          : (f16 ? msim::res_wide_gather_pages_kernel<true, 4> : msim::res_wide_gather_pages_kernel<false, 4>);
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_slots), dim3(256), 0, static_cast<hipStream_t>(stream), codes, residuals,
+                       static_cast<const uint16_t *>(C), K, weights, (long long)d_rows, d_off, n_d, (long long)id_base, ids,
+                       (long long)pad_rows, static_cast<uint16_t *>(out), lengths);
+    return launch_failed("res_wide_gather_pages_kernel");
 }
 
 }  // extern "C"

@@ -222,11 +222,15 @@ def gather_pages(corpus: PackedCorpus, ids: torch.Tensor, pad_to: Optional[int] 
     the truncated count.
     out: a contiguous [*ids.shape, L_pad, width] tensor to write into (every byte of it is written).
     Asynchronous on torch's current stream; with device ids there is no host synchronisation and the call is hipGraph-capturable.
-    A `ResidualCorpus` goes to `residual_gather_pages`: the bytes of this call over `corpus.decompress()`, decoded into the box."""
+    A `ResidualCorpus` goes to `residual_gather_pages`, a `ResidualWideCorpus` (width 320) to `residual_wide_gather_pages`: the bytes
+    of this call over `corpus.decompress()`, decoded into the box."""
     from .residual import ResidualCorpus, residual_gather_pages
+    from .residual_wide import ResidualWideCorpus, residual_wide_gather_pages
 
     if isinstance(corpus, ResidualCorpus):
         return residual_gather_pages(corpus, ids, pad_to, out)
+    if isinstance(corpus, ResidualWideCorpus):
+        return residual_wide_gather_pages(corpus, ids, pad_to, out)
     dev = _require_gpu(corpus.device)
     if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
         raise ValueError("ids must be an int64 tensor")

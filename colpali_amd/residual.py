@@ -27,8 +27,8 @@ dispatch to them; `ShardedRetriever(rc, align_fn=residual_align)` opens the retr
 The container, the build, `decompress` and the rerank are one host layer for both row widths (`_ResidualRows`: a public class binds
 the width, its centroid-index class and the library entries that read rows of that width).  `ResidualCorpus` is width 128;
 `ResidualWideCorpus` (colpali_amd/residual_wide.py) is width 320 -- a sibling, not a subclass, so the scan above (its own is
-`residual_wide_scores`, over the same host body: `_scan_scores`) and align and gather, which exist at width 128 only, refuse it by
-its type.
+`residual_wide_scores`, over the same host body: `_scan_scores`) and `residual_align` / `residual_gather_pages` (its own are
+`residual_wide_align` / `residual_wide_gather_pages`, over the same host bodies: `_align_rows`, `_gather_rows`) refuse it by its type.
 """
 from __future__ import annotations
 
@@ -109,6 +109,9 @@ class _ResidualRows:
     _ENCODE: str = ""
     _DECODE: str = ""
     _CANDIDATES: str = ""
+    _SCORES: str = ""
+    _ALIGN: str = ""
+    _GATHER: str = ""
 
     def __init__(self, centroids: torch.Tensor, codes: torch.Tensor, residuals: torch.Tensor, cutoffs: torch.Tensor,
                  weights: torch.Tensor, offsets: torch.Tensor, clamp0: Optional[torch.Tensor], lengths: torch.Tensor,
@@ -266,6 +269,8 @@ class ResidualCorpus(_ResidualRows):
     _DECODE = "msim_res_decode_rows"
     _CANDIDATES = "msim_res_candidates"
     _SCORES = "msim_res_scores"
+    _ALIGN = "msim_res_align_candidates"
+    _GATHER = "msim_res_gather_pages"
 
 
 def _check_query_format(queries, rc: _ResidualRows, what: str) -> None:
@@ -372,9 +377,14 @@ def residual_align(queries, rc: ResidualCorpus, ids: torch.Tensor, *, maps: bool
     stream; with a `PackedQueries` there is no host synchronisation and the call is hipGraph-capturable.
     What can be refused without the device is refused before it is asked for: the formats and `max_rows` always, the token count
     and `ids` for queries that come packed."""
+    return _align_rows(queries, rc, ids, maps, max_rows, ResidualCorpus, "residual_align")
+
+
+def _align_rows(queries, rc, ids: torch.Tensor, maps: bool, max_rows: Optional[int], kind, who: str):
+    """`align` over the compressed shard of both widths: the entry of `kind` over a shard of that class"""
     from .align import MAX_QUERY_TOKENS, Alignment, resolve_ids          # align dispatches here
 
-    _require_kind(rc, ResidualCorpus, "residual_align")
+    _require_kind(rc, kind, who)
     _check_query_format(queries, rc, "align")
     n = len(rc)
     if max_rows is None:
@@ -398,12 +408,12 @@ def residual_align(queries, rc: ResidualCorpus, ids: torch.Tensor, *, maps: bool
     sims = torch.empty((n_q, m, T, max_rows), dtype=torch.float32, device=dev) if maps else None
     tokens = queries.tokens if queries.tokens.is_contiguous() else queries.tokens.contiguous()
     with torch.cuda.device(dev):
-        rcode = _lib.lib().msim_res_align_candidates(
+        rcode = getattr(_lib.lib(), kind._ALIGN)(
             _lib.dtype_code(rc.dtype), _lib.ptr(tokens), _lib.ptr(queries.offsets), n_q, int(tokens.shape[0]), T, _lib.ptr(rc.codes),
             _lib.ptr(rc.residuals), _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, _lib.ptr(rc.offsets),
-            _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), DIM, _lib.ptr(ids), m, ld, int(rc.id_base), _lib.ptr(best_sim),
+            _lib.ptr(rc.clamp0), n, int(rc.codes.shape[0]), kind.WIDTH, _lib.ptr(ids), m, ld, int(rc.id_base), _lib.ptr(best_sim),
             _lib.ptr(best_row), _lib.ptr(sims), max_rows, _lib.current_stream_handle(dev))
-    _lib.check(rcode, "msim_res_align_candidates")
+    _lib.check(rcode, kind._ALIGN)
     return Alignment(best_sim, best_row, resolve_ids(ids, int(rc.id_base), n), sims, q_lens, page_lengths=rc.lengths,
                      id_base=int(rc.id_base))
 
@@ -418,7 +428,13 @@ def residual_gather_pages(rc: ResidualCorpus, ids: torch.Tensor, pad_to: Optiona
     for such a slot.  A page longer than `pad_to`: host ids raise ValueError, device ids TRUNCATE (`lengths` reports the truncated
     count), as `gather_pages`.  out: a contiguous [*ids.shape, L_pad, 128] tensor to write into (every byte of it is written).
     Asynchronous on torch's current stream; with device ids there is no host synchronisation and the call is hipGraph-capturable."""
-    _require_kind(rc, ResidualCorpus, "residual_gather_pages")
+    return _gather_rows(rc, ids, pad_to, out, ResidualCorpus, "residual_gather_pages")
+
+
+def _gather_rows(rc, ids: torch.Tensor, pad_to: Optional[int], out: Optional[torch.Tensor], kind,
+                 who: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`gather_pages` over the compressed shard of both widths: the entry of `kind` over a shard of that class"""
+    _require_kind(rc, kind, who)
     if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64:
         raise ValueError("ids must be an int64 tensor")
     n = len(rc)
@@ -438,17 +454,17 @@ def residual_gather_pages(rc: ResidualCorpus, ids: torch.Tensor, pad_to: Optiona
         raise ValueError("ids and corpus live on different devices")
     dev = _require_gpu(rc.device)
     flat = ids.to(dev).reshape(-1).contiguous()
-    shape = tuple(ids.shape) + (pad_to, DIM)
+    shape = tuple(ids.shape) + (pad_to, kind.WIDTH)
     if out is None:
         out = torch.empty(shape, dtype=rc.dtype, device=dev)
     elif out.shape != shape or out.dtype != rc.dtype or out.device != dev or not out.is_contiguous():
         raise ValueError(f"out must be a contiguous {rc.dtype} tensor of shape {shape} on {dev}")
     lengths = torch.empty(tuple(ids.shape), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rcode = _lib.lib().msim_res_gather_pages(_lib.dtype_code(rc.dtype), _lib.ptr(rc.codes), _lib.ptr(rc.residuals),
-                                                 _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, DIM,
-                                                 int(rc.codes.shape[0]), _lib.ptr(rc.offsets), n, int(rc.id_base), _lib.ptr(flat),
-                                                 flat.numel(), pad_to, _lib.ptr(out), _lib.ptr(lengths),
-                                                 _lib.current_stream_handle(dev))
-    _lib.check(rcode, "msim_res_gather_pages")
+        rcode = getattr(_lib.lib(), kind._GATHER)(_lib.dtype_code(rc.dtype), _lib.ptr(rc.codes), _lib.ptr(rc.residuals),
+                                                  _lib.ptr(rc.centroids), rc.n_centroids, _lib.ptr(rc.weights), rc.bits, kind.WIDTH,
+                                                  int(rc.codes.shape[0]), _lib.ptr(rc.offsets), n, int(rc.id_base), _lib.ptr(flat),
+                                                  flat.numel(), pad_to, _lib.ptr(out), _lib.ptr(lengths),
+                                                  _lib.current_stream_handle(dev))
+    _lib.check(rcode, kind._GATHER)
     return out, lengths

@@ -20,11 +20,17 @@ to memory, and entry (q, c) has the rerank's bits.  The default retriever only s
 `ShardedRetriever(rc, score_fn=residual_wide_scores)` opens the full scan, `filter=`, `group_by=` and `mine`, as
 `score_fn=residual_scores` does at width 128; `mine_hard_negatives(q, rc, ...)` dispatches to it.
 
+`residual_wide_align` and `residual_wide_gather_pages` are `align` and `gather_pages` over such a shard, the listed pages decoded
+inside the kernel that consumes them (include/maxsim.h: msim_res_wide_align_candidates, msim_res_wide_gather_pages;
+colpali_amd/csrc/residual_wide_align.hip): the bits of the same call over `rc.decompress()`, no decoded copy in memory, no host read
+of the list.  `align(queries, rc, ids)` and `gather_pages(rc, ids)` dispatch to them;
+`ShardedRetriever(rc, align_fn=residual_wide_align)` opens the retriever's `align`.
+
 The host layer is the one of widths 128 (colpali_amd/centroid.py: `_CentroidCodes`, colpali_amd/residual.py: `_ResidualRows`); the
 classes here bind the width and the wide entries.  They are siblings of the 128 classes, not subclasses: the 128 scan
-(`residual_scores`) and everything that exists at width 128 only -- `residual_align`, `residual_gather_pages`,
-`LiveResidualCorpus` -- refuse them by their type, as `residual_wide_scores` refuses a `ResidualCorpus`, and no kernel of one width
-ever sees a row of the other.
+(`residual_scores`), the 128 `residual_align` / `residual_gather_pages` and what exists at width 128 only -- `LiveResidualCorpus` --
+refuse them by their type, as `residual_wide_scores`, `residual_wide_align` and `residual_wide_gather_pages` refuse a
+`ResidualCorpus`, and no kernel of one width ever sees a row of the other.
 """
 from __future__ import annotations
 
@@ -34,7 +40,7 @@ import torch
 
 from .centroid import _CentroidCodes, _require_kind, _scores
 from .residual import WIDE_DIM as DIM
-from .residual import _rerank_scores, _ResidualRows, _scan_scores
+from .residual import _align_rows, _gather_rows, _rerank_scores, _ResidualRows, _scan_scores
 
 
 class CentroidWideIndex(_CentroidCodes):
@@ -63,6 +69,8 @@ class ResidualWideCorpus(_ResidualRows):
     _DECODE = "msim_res_wide_decode_rows"
     _CANDIDATES = "msim_res_wide_candidates"
     _SCORES = "msim_res_wide_scores"
+    _ALIGN = "msim_res_wide_align_candidates"
+    _GATHER = "msim_res_wide_gather_pages"
 
 
 def centroid_wide_scores(queries, index: CentroidWideIndex, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -98,3 +106,33 @@ def residual_wide_scores(queries, rc: ResidualWideCorpus, *, out: Optional[torch
     matrix, whose other columns are not touched.  Given a `PackedQueries` it never synchronises with the host and is
     hipGraph-capturable."""
     return _scan_scores(queries, rc, out, ResidualWideCorpus)
+
+
+def residual_wide_align(queries, rc: ResidualWideCorpus, ids: torch.Tensor, *, maps: bool = False, max_rows: Optional[int] = None):
+    """`align` over the compressed 320-wide shard (include/maxsim.h: msim_res_wide_align_candidates): `residual_align` at width 320.
+    The `Alignment` of every entry (q, j) of `ids` (int64 [n_q, m] GLOBAL ids on the shard's device, -1 = none), with the signature,
+    the query forms and the checks of `align`.  best_sim, best_row, ids and sims have the bits
+    `align(queries, rc.decompress(), ids, maps=, max_rows=)` gives: every listed page is decoded chunk by chunk in the registers of
+    the kernel that multiplies it, and no decoded row is written to memory.  bfloat16 / float16, width 320, queries of at most 128
+    tokens (NotImplementedError otherwise, and for a `ResidualCorpus` -- width 128: `residual_align`; RuntimeError when queries and
+    shard differ in dtype; ValueError for ids of the wrong shape, dtype or device).  `max_rows` bounds the rows of a listed page
+    (default: the shard's longest page, known on the host); a longer page comes back NaN / -1.  Asynchronous on torch's current
+    stream; with a `PackedQueries` there is no host synchronisation and the call is hipGraph-capturable.  What can be refused
+    without the device is refused before it is asked for: the formats and `max_rows` always, the token count and `ids` for queries
+    that come packed."""
+    return _align_rows(queries, rc, ids, maps, max_rows, ResidualWideCorpus, "residual_wide_align")
+
+
+def residual_wide_gather_pages(rc: ResidualWideCorpus, ids: torch.Tensor, pad_to: Optional[int] = None,
+                               out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`gather_pages` over the compressed 320-wide shard (include/maxsim.h: msim_res_wide_gather_pages): `residual_gather_pages` at
+    width 320.  (box [*ids.shape, L_pad, 320] of the shard's dtype, lengths int32 [*ids.shape]) with the bytes
+    `gather_pages(rc.decompress(), ids, pad_to)` gives -- the listed pages are decoded straight into the box, so
+    `mine_hard_negatives(q, rc, ...)` -> `gather_pages(rc, neg_ids)` feeds the explicit-negative losses without a decoded shard.
+    ids: int64 GLOBAL ids of any shape; L_pad = `pad_to`, or the shard's longest page.  Rows past a page's length, and the whole
+    page for id -1 or an id outside the shard, are exactly zero and `lengths` is 0 for such a slot.  A page longer than `pad_to`:
+    host ids raise ValueError, device ids TRUNCATE (`lengths` reports the truncated count), as `gather_pages`.  out: a contiguous
+    [*ids.shape, L_pad, 320] tensor to write into (every byte of it is written).  NotImplementedError for a `ResidualCorpus` (width
+    128: `residual_gather_pages`).  Asynchronous on torch's current stream; with device ids there is no host synchronisation and the
+    call is hipGraph-capturable."""
+    return _gather_rows(rc, ids, pad_to, out, ResidualWideCorpus, "residual_wide_gather_pages")

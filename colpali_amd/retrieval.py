@@ -32,7 +32,7 @@ from .centroid import CentroidIndex, centroid_scores
 from .int8_index import Int8Index, int8_scores
 from .mine import check_mine_args, mine_bounds, mine_mask, mine_masked, select_window
 from .residual import ResidualCorpus, residual_align, residual_rerank_scores, residual_scores
-from .residual_wide import (CentroidWideIndex, ResidualWideCorpus, centroid_wide_scores, residual_wide_rerank_scores,
+from .residual_wide import (CentroidWideIndex, ResidualWideCorpus, centroid_wide_scores, residual_wide_align, residual_wide_rerank_scores,
                             residual_wide_scores)
 from .scoring import _require_gpu, maxsim_scores
 
@@ -225,7 +225,7 @@ def rerank(queries, corpus: PackedCorpus, candidates: torch.Tensor, k: Optional[
 _KERNELS = (maxsim_scores, residual_scores, rerank_scores, residual_rerank_scores, fde_scores, int8_scores, centroid_scores, binary_scores,
             fp4_scores, fp6_scores, fp4_wide_scores, fp4_rerank_scores, fp6_rerank_scores, fp4_wide_rerank_scores, align,
             residual_align, fde_wide_scores, fp6_wide_scores, fp6_wide_rerank_scores, centroid_wide_scores, residual_wide_rerank_scores,
-            residual_wide_scores)
+            residual_wide_scores, residual_wide_align)
 
 
 class ShardedRetriever:
@@ -243,8 +243,8 @@ class ShardedRetriever:
     `score_fn=residual_wide_scores` opens the same scanning routes -- the full scan, `filter=` on the mask, list and auto routes,
     `group_by=` on every route, `filter=` with `candidates=` / `prefilter=`, and `mine` -- each with the bits of the same call over
     `shard.decompress()` scored by the flat kernel every ragged batch runs (`search`'s note on width 320 says where a scan of the
-    decompressed pages runs another kernel).  `align` keeps raising whatever the hooks: the alignment of a compressed shard exists
-    at width 128 only."""
+    decompressed pages runs another kernel).  `align` is opened by `align_fn=residual_wide_align` (`residual_align` exists at width
+    128 only and refuses such a shard); with the default `align_fn` it keeps raising, whatever `score_fn`."""
 
     def __init__(self, shard: PackedCorpus, world: int = 1, rank: int = 0, dist=None, group=None,
                  score_fn: Callable = maxsim_scores, select: Callable = topk, force_collective: bool = False,
@@ -454,8 +454,9 @@ class ShardedRetriever:
                                       "lists are scored from the compressed ones -- use search(candidates=) or "
                                       "search(prefilter=shard.index, n_candidates=), or shard.decompress() for a PackedCorpus; "
                                       "ShardedRetriever(shard, score_fn=residual_wide_scores) opts in to scanning the compressed rows "
-                                      "(the full scan, filter=, group_by= and mine).  align needs rows either way, and the alignment "
-                                      "of a compressed shard exists at width 128 only: there is no align_fn that opens it at width 320")
+                                      "(the full scan, filter=, group_by= and mine).  align needs rows either way; `residual_align` "
+                                      "exists at width 128 only: at width 320 pass align_fn=residual_wide_align, which decodes the "
+                                      "listed pages inside the alignment kernel")
         raise NotImplementedError(f"{what} over a ResidualCorpus: the shard keeps no full-precision rows and only candidate lists are "
                                   "scored from the compressed ones -- use search(candidates=) or search(prefilter=shard.index, "
                                   "n_candidates=), or shard.decompress() for a PackedCorpus; ShardedRetriever(shard, "
@@ -515,8 +516,9 @@ class ShardedRetriever:
         (-inf, -1, -1), so every rank ends up with the holder's result (best_row is relative to the page, whichever rank holds it).
         `maps=True` is for a single shard: the maps of a sharded corpus stay on the rank that holds the page (ValueError).
         Over a `ResidualCorpus` the default `align_fn` refuses (NotImplementedError); `align_fn=residual_align` decodes the listed
-        pages inside the kernel and gives the bits of the same call over `shard.decompress()`."""
-        if isinstance(self.shard, (ResidualCorpus, ResidualWideCorpus)) and self._align is align:  # opt-in, as the scan: align_fn=residual_align
+        pages inside the kernel and gives the bits of the same call over `shard.decompress()`.  Over a `ResidualWideCorpus` the
+        hook is `align_fn=residual_wide_align`, under the same rule."""
+        if isinstance(self.shard, (ResidualCorpus, ResidualWideCorpus)) and self._align is align:  # opt-in, as the scan: align_fn=residual_align / residual_wide_align
             self._no_rows("align")
         if maps and self.world > 1:
             raise ValueError("maps=True with world > 1: similarity maps are made by the rank that holds the page; call align() on "

@@ -1180,6 +1180,38 @@ int msim_res_gather_pages(int dtype, const uint16_t *codes, const uint8_t *resid
                           const int64_t *ids, int64_t n_slots, int64_t pad_rows, void *out, int32_t *lengths, void *stream);
 
 /*
+ * ROWS OUT OF THE COMPRESSED SHARD AT WIDTH 320 (residual_wide_align.hip; additions to ABI 22): msim_res_align_candidates and
+ * msim_res_gather_pages over the rows of a 320-wide compressed shard, with their argument lists.  Formats as
+ * msim_res_wide_candidates: bf16 / f16, dim == 320, bits 2 or 4 -- MSIM_EUNSUPPORTED for anything else (the two 128-wide entries
+ * above keep refusing dim 320) -- and K a multiple of 256 in 256 .. 2048: a K outside that range is MSIM_EINVAL, the code every
+ * msim_res_wide_* entry gives it (the 128-wide pair above answers MSIM_EUNSUPPORTED there).  max_q_tokens > 128: MSIM_EUNSUPPORTED.
+ * msim_res_wide_align_candidates: msim_align_candidates' contract (dim 320), conventions, output shapes and return codes over the
+ *   compressed rows.  ARITHMETIC: for every entry, best_sim, best_row and sims hold exactly the bits msim_align_candidates (dim 320)
+ *   gives the same queries and list over the output of msim_res_wide_decode_rows for the whole shard (rows 0 .. d_rows), every -inf
+ *   / 0.0 / NaN / -1 convention included: the operand of the chain of ten MFMAs is built by the decode helper
+ *   msim_res_wide_decode_rows uses, in the lane layout of K1a, and everything behind the operand is K1a.  A row whose code is >= K
+ *   is the NaN row msim_res_wide_decode_rows writes (the code never becomes an address; no other row or entry changes).  An entry
+ *   whose page is longer than max_rows, or whose offsets fall outside 0 <= d_off[c] <= d_off[c + 1] <= d_rows, is NaN / -1 in full
+ *   and reads nothing.
+ * msim_res_wide_gather_pages: out [n_slots, pad_rows, 320] in the corpus dtype holds exactly the bytes msim_gather_pages (row_bytes
+ *   640) gives the same ids over that decoded output -- the first min(rows, pad_rows) rows of page ids[s] - id_base decoded, exact
+ *   zeros behind them, all zeros for an id of -1, an id outside [id_base, id_base + n_d) or broken offsets; lengths[s] = the rows
+ *   decoded.  A row whose code is >= K is written as the NaN row.  Every byte of out is written.
+ * MSIM_EINVAL for a negative size, a null or misaligned pointer (Qt, centroids, residuals, out: 16 bytes; cand / ids: 8; codes: 2;
+ * the rest: 4), ld_cand < m; MSIM_EUNSUPPORTED above the 2^31 - 1 limits (n_q x m, d_rows, pad_rows, n_slots) -- all before the
+ * device is touched.  n_q == 0, m == 0 or n_slots == 0 returns 0 before any pointer is looked at.  No workspace, no allocation, no
+ * host synchronisation: asynchronous on `stream` and hipGraph-capturable.
+ */
+int msim_res_wide_align_candidates(int dtype, const void *Qt, const int32_t *q_off, int n_q, int64_t q_rows, int max_q_tokens,
+                                   const uint16_t *codes, const uint8_t *residuals, const void *C, int K, const float *weights,
+                                   int bits, const int32_t *d_off, const uint8_t *d_clamp0 /* or NULL */, int n_d, int64_t d_rows,
+                                   int dim, const int64_t *cand, int m, int64_t ld_cand, int64_t id_base,
+                                   float *best_sim, int32_t *best_row, float *sims /* or NULL */, int max_rows, void *stream);
+int msim_res_wide_gather_pages(int dtype, const uint16_t *codes, const uint8_t *residuals, const void *C, int K, const float *weights,
+                               int bits, int dim, int64_t d_rows, const int32_t *d_off, int n_d, int64_t id_base,
+                               const int64_t *ids, int64_t n_slots, int64_t pad_rows, void *out, int32_t *lengths, void *stream);
+
+/*
  * LIVE CORPUS (live_corpus.hip; additions to ABI 22): a packed corpus whose pages can be deleted and whose rows can be handed
  * back, without a change to any scorer.  A page's slot c never moves (its id stays id_base + c); `alive` uint8 [n_slots] is the
  * tombstone mask (0 = deleted).

@@ -38,7 +38,11 @@ and clustered lists (1000 x 32 x m = 100 and 4 x 32 x m = 1000) with their bit-e
 the planted 320-wide set of tools/bench_fp4.py --dim 320.  `--dim 320 --legs scan` times the full scan alone -- `residual_wide_scores`
 (msim_res_wide_scores) at 4 x 32, 32 x 32 and 1000 x 32 queries beside `maxsim_scores` over a resident `rc.decompress()` and, at 4 x 32,
 `residual_wide_rerank_scores` over all ids, checks the bit identity with that rerank, and APPENDS its table to --summary.  One run; the variants of a comparison alternate step by step inside
-one timing loop and every figure is a median (min - max).
+one timing loop and every figure is a median (min - max).  `--dim 320 --legs align,gather` (either or both) runs the align and gather
+legs above on the wide classes -- `residual_wide_align` / `residual_wide_gather_pages` (msim_res_wide_align_candidates,
+msim_res_wide_gather_pages) beside the decompress-then-call detour (ids read back, `rc.decompress(local ids)`, then `align` /
+`gather_pages` over that copy) and beside the call over a resident `rc.decompress()`, the three alternating in one loop -- and
+APPENDS its table to --summary.
 """
 from __future__ import annotations
 
@@ -152,9 +156,26 @@ ALIGN_SHAPE = (1000, 10)                    # (queries, hits per query)
 GATHER_SHAPE = (1000, 8)                    # the ids of a mined batch
 
 
+def _rows_fns(amd, rc):
+    """(fused align, fused gather, width) of the shard's class"""
+    if isinstance(rc, amd.ResidualWideCorpus):
+        return amd.residual_wide_align, amd.residual_wide_gather_pages, rc.width
+    return amd.residual_align, amd.residual_gather_pages, 128
+
+
+def _queries(amd, rc, n_q, q_len, dev):
+    if isinstance(rc, amd.ResidualWideCorpus):
+        from tools.bench_rerank import make_queries_dim
+
+        return amd.pack_queries(make_queries_dim(n_q, q_len, rc.width, dev, seed=99), dev, compact=False)
+    return amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
+
+
 def align_leg(amd, rc, dec, q_len, dev, steps, warmup):
+    """the keys keep their names at both widths: `residual_align` is the fused call of the shard's class"""
     n_q, k = ALIGN_SHAPE
-    pq = amd.pack_queries(make_queries(n_q, q_len, dev, seed=99), dev, compact=False)
+    fused = _rows_fns(amd, rc)[0]
+    pq = _queries(amd, rc, n_q, q_len, dev)
     ids = uniform_candidates(n_q, len(rc), k, dev, 7) + rc.id_base
     listed = torch.arange(n_q * k, device=dev).reshape(n_q, k)
     R = int(rc.lengths.max())
@@ -164,7 +185,7 @@ def align_leg(amd, rc, dec, q_len, dev, steps, warmup):
             part = rc.decompress((ids - rc.id_base).reshape(-1))       # reads the ids back: one synchronisation per call
             return amd.align(pq, part, listed, maps=maps, max_rows=R)
 
-        fns = {"residual_align": lambda: amd.residual_align(pq, rc, ids, maps=maps, max_rows=R), "decompress_then_align": via_decompress,
+        fns = {"residual_align": lambda: fused(pq, rc, ids, maps=maps, max_rows=R), "decompress_then_align": via_decompress,
                "align_resident_bf16": lambda: amd.align(pq, dec, ids, maps=maps, max_rows=R)}       # K1a itself: what the decode costs
         leg = timed_alternating(fns, steps, warmup)
         leg["residual_over_resident_bf16"] = leg["residual_align"]["median_ms"] / leg["align_resident_bf16"]["median_ms"]
@@ -183,16 +204,31 @@ def align_leg(amd, rc, dec, q_len, dev, steps, warmup):
     return out
 
 
-def gather_leg(amd, rc, dec, dev, steps, warmup):
+def gather_leg(amd, rc, dec, dev, steps, warmup, detour=False):
+    """detour=True adds the way round there was before the fused call: ids read back, `rc.decompress(local ids)`, `gather_pages`"""
     n_q, n_neg = GATHER_SHAPE
+    _, fused, width = _rows_fns(amd, rc)
     ids = uniform_candidates(n_q, len(rc), n_neg, dev, 11) + rc.id_base
     pad = int(rc.lengths.max())
-    box = torch.empty((n_q, n_neg, pad, 128), dtype=rc.dtype, device=dev)
+    box = torch.empty((n_q, n_neg, pad, width), dtype=rc.dtype, device=dev)
     ref = torch.empty_like(box)
-    leg = timed_alternating({"residual_gather_pages": lambda: amd.residual_gather_pages(rc, ids, pad, out=box),
-                             "gather_pages_resident_bf16": lambda: amd.gather_pages(dec, ids, pad, out=ref)}, steps, warmup)
+    fns = {"residual_gather_pages": lambda: fused(rc, ids, pad, out=box),
+           "gather_pages_resident_bf16": lambda: amd.gather_pages(dec, ids, pad, out=ref)}
+    if detour:
+        listed = torch.arange(n_q * n_neg, device=dev).reshape(n_q, n_neg)
+        via = torch.empty_like(box)
+
+        def via_decompress():
+            part = rc.decompress((ids - rc.id_base).reshape(-1))       # reads the ids back: one synchronisation per call
+            return amd.gather_pages(part, listed, pad, out=via)
+
+        fns["decompress_then_gather"] = via_decompress
+    leg = timed_alternating(fns, steps, warmup)
     leg["residual_over_bf16"] = leg["residual_gather_pages"]["median_ms"] / leg["gather_pages_resident_bf16"]["median_ms"]
     leg["bit_identical"] = bool(torch.equal(box.view(torch.int16), ref.view(torch.int16)))
+    if detour:
+        leg["residual_over_decompress"] = leg["residual_gather_pages"]["median_ms"] / leg["decompress_then_gather"]["median_ms"]
+        leg["bit_identical"] = leg["bit_identical"] and bool(torch.equal(box.view(torch.int16), via.view(torch.int16)))
     leg["bytes_written_per_s"] = box.numel() * 2 / (leg["residual_gather_pages"]["median_ms"] * 1e-3)
     return leg
 
@@ -309,6 +345,65 @@ def main_wide_scan(args, amd, dev):
     print(line)
 
 
+def wide_rows_summary(res) -> str:
+    """the section `--dim 320 --legs align,gather` appends to profiles/residual_wide_summary.md"""
+    L = ["", "## Rows out of the compressed shard: residual_wide_align / residual_wide_gather_pages", "",
+         f"`tools/bench_residual.py --dim 320 --legs {res['legs']} --steps {res['steps']} --warmup {res['warmup']}` on {res['docs']} pages x "
+         f"{res['doc_len']} rows x 320 bf16 ({res['corpus_bytes'] / 1e9:.1f} GB), K = {res['n_centroids']}; the three variants of a row alternate "
+         "step by step inside one timing loop; median (min - max) in ms.  The detour reads the ids back, decodes the listed pages with "
+         "`rc.decompress(ids)` and calls `align` / `gather_pages` over that copy.", "",
+         "| bits | leg | fused | decompress-then-call | over a resident decompress() | fused / detour | fused / resident | same bits |",
+         "|---|---|---|---|---|---|---|---|"]
+    for bits in BITS:
+        b = res[f"bits{bits}"]
+        for name, leg in b.get("align", {}).items():
+            L.append(f"| {bits} | align {ALIGN_SHAPE[0]} x {res['q_len']} x k = {ALIGN_SHAPE[1]}, {name} | {_fmt(leg['residual_align'])} | "
+                     f"{_fmt(leg['decompress_then_align'])} | {_fmt(leg['align_resident_bf16'])} | {leg['residual_over_decompress']:.3f} | "
+                     f"{leg['residual_over_resident_bf16']:.2f} | {leg['bit_identical']} |")
+        if "gather" in b:
+            leg = b["gather"]
+            L.append(f"| {bits} | gather ids [{GATHER_SHAPE[0]}, {GATHER_SHAPE[1]}] | {_fmt(leg['residual_gather_pages'])} | "
+                     f"{_fmt(leg['decompress_then_gather'])} | {_fmt(leg['gather_pages_resident_bf16'])} | {leg['residual_over_decompress']:.3f} | "
+                     f"{leg['residual_over_bf16']:.2f} | {leg['bit_identical']} |")
+    return "\n".join(L) + "\n"
+
+
+def main_wide_rows(args, amd, dev, legs):
+    """--dim 320 --legs align,gather: the two row-returning calls over the wide compressed shard; the section is APPENDED to --summary"""
+    from tools.bench_rerank import make_shard_dim
+
+    docs = args.docs if args.docs != 125_000 else 50_000
+    t0 = time.perf_counter()
+    res = {"tool": "bench_residual", "dim": 320, "legs": ",".join(sorted(legs)), "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len,
+           "n_centroids": K, "steps": args.steps, "warmup": args.warmup}
+    corpus = make_shard_dim(docs, args.doc_len, 320, dev, seed=1234)
+    index = amd.CentroidWideIndex.build(corpus, n_centroids=K)
+    res["corpus_bytes"] = corpus.nbytes
+    shards = {bits: amd.ResidualWideCorpus.build(corpus, index=index, bits=bits) for bits in BITS}
+    del corpus
+    torch.cuda.empty_cache()
+    for bits, rc in shards.items():
+        dec = rc.decompress()
+        leg = {"nbytes": rc.nbytes}
+        if "align" in legs:
+            leg["align"] = align_leg(amd, rc, dec, args.q_len, dev, args.steps, args.warmup)
+        if "gather" in legs:
+            leg["gather"] = gather_leg(amd, rc, dec, dev, args.steps, args.warmup, detour=True)
+        res[f"bits{bits}"] = leg
+        del dec
+        torch.cuda.empty_cache()
+    res["wall_s"] = time.perf_counter() - t0
+    line = json.dumps(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    if args.summary:
+        fresh = not os.path.exists(args.summary)
+        with open(args.summary, "a") as f:
+            f.write(("# The residual-compressed shard at width 320 (ColQwen3)\n" if fresh else "") + wide_rows_summary(res))
+    print(line)
+
+
 def main_wide(args):
     """--dim 320: see the module docstring"""
     import colpali_amd as amd
@@ -320,6 +415,8 @@ def main_wide(args):
     amd._lib.lib()
     if set(args.legs.split(",")) == {"scan"}:
         return main_wide_scan(args, amd, dev)
+    if set(args.legs.split(",")) <= {"align", "gather"}:
+        return main_wide_rows(args, amd, dev, set(args.legs.split(",")))
     docs = args.docs if args.docs != 125_000 else 50_000
     t0 = time.perf_counter()
     res = {"tool": "bench_residual", "dim": 320, "docs": docs, "doc_len": args.doc_len, "q_len": args.q_len, "n_centroids": K,
